@@ -9,13 +9,21 @@ MOI coefficient buffer from the Parameter values resident in HBM:
 (the literal objective the reference would emit is 1.65 TB at this size; the canonical form = canonicalize!(literal)).
 `value` is the DEVICE-RESIDENT rate: inputs in HBM when the timed region starts, outputs left in HBM, nothing crosses PCIe.
 
-    python bench.py --gpus N --steps K --warmup W        (N > 1: one rank per GPU under torch.distributed.run; started here if RANK is unset)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+                                                         (N > 1: one rank per GPU under torch.distributed.run; started here if RANK is unset)
 
-Prints ONE JSON line of at most 4 KB on stdout (rank 0): the contract's fields, `roofline` of the dominant kernel (HIP events in this run;
-`traffic` from rocprofv3 --pmc children of this run, tools/bench_pmc.py), `cpu_baseline` (oracle/ on one host core, bounded sample) and
-`summary`: one number per other BASELINE config (C1, C3, C4, C5: tools/bench_configs.py) and `C4_sharded` — config 4 sharded by instance
-over the N ranks with the slab exchange behind the C ABI, with `ranks_seen`.  Full objects: bench_detail.json (--detail PATH); the longer
-studies: tools/bench_study.py.  N > 1 runs N independent config-2 instances (replicas, weak scaling); --workload batch runs config 4 alone."""
+A plain run sets up, runs W warm-up and K timed steps and prints ONE JSON line on stdout (rank 0) with the contract's fields only: `value`
+(re-evaluations/s), `ms_per_step` (milliseconds of one timed step), `metric`, `unit`, `higher_is_better`, `dtype`, `n_gpus`, `config`, ...
+
+--full adds everything else to the same line (at most 4 KB): `roofline` of the dominant kernel (HIP events in this run; `traffic` from
+rocprofv3 --pmc children of this run, tools/bench_pmc.py), `cpu_baseline` (oracle/ on one host core, bounded sample) and `summary`: one
+number per other BASELINE config (C1, C3, C4, C5: tools/bench_configs.py) and `C4_sharded` — config 4 sharded by instance over the N ranks
+with the slab exchange behind the C ABI, with `ranks_seen`.  Full objects: bench_detail.json (--detail PATH); the longer studies:
+tools/bench_study.py.  N > 1 runs N independent config-2 instances (replicas, weak scaling); --workload batch runs config 4 alone.
+
+--dump-outputs DIR writes the MOI buffers the last timed step left in HBM as DIR/<name>.npy (float64; rank 0's instance; see
+C2Workload.outputs).  The inputs of that step depend only on the seeds, K and W: two builds run with the same arguments compare output for
+output."""
 import argparse
 import ctypes as C
 import json
@@ -33,6 +41,7 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 
 F64_MFMA_PEAK_TFLOPS = 78.6
 LINE_LIMIT = 4096              # bytes of the stdout line (the driver stopped parsing a 20.8 KB line in round 5)
 DOMINANT = "gram_mid_kernel"
+DUMP_LIMIT = 64 << 20          # bytes of --dump-outputs in all
 
 
 def parse_args():
@@ -43,13 +52,19 @@ def parse_args():
     p.add_argument("--workload", default="c2", choices=["c2", "batch", "launch-check"],
                    help="launch-check: no GPU work at all — the launcher / rank accounting alone over gloo (the CPU test of --gpus N)")
     p.add_argument("--dry-launch", action="store_true", help="print the torch.distributed.run command --gpus N would start (JSON) and exit")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-configs", action="store_true", help="skip the C1 / C3 / C4 / C5 sections and the sharded config 4")
-    p.add_argument("--no-pmc", action="store_true", help="do not run the rocprofv3 --pmc children (roofline.traffic is then the committed replay)")
+    p.add_argument("--full", action="store_true", help="also the roofline, per-kernel times, PMC children, the other configurations and the CPU "
+                                                       "baselines (the plain run times the K steps and prints the headline only)")
+    p.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (float64, c2 workload)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    p.add_argument("--no-configs", action="store_true", help="with --full: skip the C1 / C3 / C4 / C5 sections and the sharded config 4")
+    p.add_argument("--no-pmc", action="store_true", help="with --full: do not run the rocprofv3 --pmc children (roofline.traffic is then the committed replay)")
     p.add_argument("--timed-loop-only", action="store_true", help="spin-up, W warm-up and K timed steps, then exit without a line (the rocprofv3 children)")
     p.add_argument("--graph", action="store_true", help="replay the step as one hipGraph (no per-kernel events)")
-    p.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"), help="where the full objects go (the line carries one number each)")
-    return p.parse_args()
+    p.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"), help="with --full: where the full objects go (the line carries one number each)")
+    a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def dptr(t):
@@ -152,6 +167,23 @@ class C2Workload:
         self.refresh()
         self._lib.call("pmt_plan_update", self.plan)
 
+    DUMP_SAMPLE = 1 << 20          # terms kept of Q's n(n+1)/2 = 8.4 M and of C's m*n = 2.1 M: 6 fields x 8 MiB, within DUMP_LIMIT
+
+    def outputs(self):
+        """what the last step handed a caller: the MOI buffers (src/moi_interop.jl), one float64 array per field (indices are exact in
+        float64).  q, the constant and the constraint constants in full; of the quadratic and the constraint terms the same fixed
+        sample of DUMP_SAMPLE positions (seed 0) in every run — (row, col) and (out, var) name each sampled term"""
+        import numpy as np
+        from parametron_jl_amd._lib import LT, QT, VAT
+        self.torch.cuda.synchronize()
+        Q, q, Ct = self.Q.cpu().numpy().view(QT), self.q.cpu().numpy().view(LT), self.Ct.cpu().numpy().view(VAT)
+        rng = np.random.default_rng(0)
+        iq = np.sort(rng.choice(len(Q), min(len(Q), self.DUMP_SAMPLE), replace=False))
+        ic = np.sort(rng.choice(len(Ct), min(len(Ct), self.DUMP_SAMPLE), replace=False))
+        return {"quad_coeff": Q["coeff"][iq], "quad_row": Q["row"][iq], "quad_col": Q["col"][iq],
+                "lin_coeff": q["coeff"], "lin_var": q["var"], "constant": self.const.cpu().numpy(),
+                "con_out": Ct["out"][ic], "con_coeff": Ct["coeff"][ic], "con_var": Ct["var"][ic], "con_constant": self.Cc.cpu().numpy()}
+
     def close(self):
         if self.plan:
             self.torch.cuda.synchronize()
@@ -168,6 +200,18 @@ class C2Workload:
     def step_bytes(self):
         n, r, m = self.n, self.r, self.m
         return 8.0 * (r * n + r + m * n + m) + 24.0 * self.nq + 16.0 * n + 8 + 24.0 * m * n + 8.0 * m
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy in float64, at most DUMP_LIMIT bytes in all"""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise ValueError("--dump-outputs: %d bytes > the %d-byte limit" % (total, DUMP_LIMIT))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def timed_loop(torch, fn, steps):
@@ -430,6 +474,7 @@ def main():
     args = parse_args()
     claim_stdout()
     args.gpus >= 1 or fail("--gpus must be >= 1")
+    args.dump_outputs is None or args.workload == "c2" or fail("--dump-outputs: the c2 workload only")
     if "RANK" not in os.environ and (args.gpus > 1 or args.dry_launch):
         return self_launch(args, sys.argv[1:])
     rank, world, local_rank = (int(os.environ.get(k, d)) for k, d in (("RANK", "0"), ("WORLD_SIZE", "1"), ("LOCAL_RANK", "0")))
@@ -504,8 +549,31 @@ def main():
         if dist:
             dist.destroy_process_group()
         return 0
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, wl.outputs())
     ms_per_step = elapsed / args.steps * 1e3
     value = world * wl.units_per_step * args.steps / elapsed
+    out = None
+    if rank == 0:
+        out = {
+            "metric": "QP re-evaluations/sec (Q,q,C,d rebuild) at n=4096",
+            "value": value, "unit": "re-evaluations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": wl.name, "n": wl.n, "r": wl.r, "m": wl.m, "objective_mode": "canonical", "instances_per_gpu": 1,
+                       "parallelism": "replicas (independent QP instances, no collective)" if world > 1 else "single GPU",
+                       "replay": "hipGraph" if args.graph else "tape",
+                       "step": "update!(model): setdirty! + 4 device-side Parameter callbacks (rand! of A,b,C,d) + rebuild of Q,q,const,C,d; all in HBM"},
+            "step_algorithmic_bytes": wl.step_bytes(), "step_flops": wl.gram_flops(), "ranks_seen": ranks_seen,
+        }
+    if not args.full:
+        if rank == 0:
+            emit_line(_short(out))
+        wl.close()
+        if dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return 0
+
     elapsed_resident = bracketed(wl.step, args.steps)          # the rebuild alone (callbacks outside): the same K steps, bracketed the same way
     kernels = {}
     if not args.graph:
@@ -529,23 +597,13 @@ def main():
             kernels.setdefault(k, dict(v, measured="HIP events around every kernel, separate 20-step pass"))
         _lib.call("pmt_profile_enable", 0)
 
-    out = None
     if rank == 0:
-        out = {
-            "metric": "QP re-evaluations/sec (Q,q,C,d rebuild) at n=4096",
-            "value": value, "unit": "re-evaluations/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": wl.name, "n": wl.n, "r": wl.r, "m": wl.m, "objective_mode": "canonical", "instances_per_gpu": 1,
-                       "parallelism": "replicas (independent QP instances, no collective)" if world > 1 else "single GPU",
-                       "replay": "hipGraph" if args.graph else "tape",
-                       "step": "update!(model): setdirty! + 4 device-side Parameter callbacks (rand! of A,b,C,d) + rebuild of Q,q,const,C,d; all in HBM"},
-            "config_detail": {"setup_spinup_steps": wl.SPINUP_STEPS, "device_lda": [wl.lda, wl.ldc],
-                              "value_inputs_resident": world * wl.units_per_step * args.steps / elapsed_resident,
-                              "ms_per_step_inputs_resident": elapsed_resident / args.steps * 1e3,
-                              "boundary": "device-resident hand-off: the Parameter callbacks write HBM, MOI buffers left in HBM; nothing crosses "
-                                          "PCIe (PCIe-inclusive rates: tools/bench_study.py host_api).  value_inputs_resident = the rebuild alone"},
-            "step_algorithmic_bytes": wl.step_bytes(), "step_flops": wl.gram_flops(), "ranks_seen": ranks_seen, "kernels": kernels,
-        }
+        out["config_detail"] = {"setup_spinup_steps": wl.SPINUP_STEPS, "device_lda": [wl.lda, wl.ldc],
+                                "value_inputs_resident": world * wl.units_per_step * args.steps / elapsed_resident,
+                                "ms_per_step_inputs_resident": elapsed_resident / args.steps * 1e3,
+                                "boundary": "device-resident hand-off: the Parameter callbacks write HBM, MOI buffers left in HBM; nothing crosses "
+                                            "PCIe (PCIe-inclusive rates: tools/bench_study.py host_api).  value_inputs_resident = the rebuild alone"}
+        out["kernels"] = kernels
         g = kernels.get(DOMINANT)
         out["roofline"] = mfma_roofline(DOMINANT, g["avg_ms"], wl.gram_flops(), launches=g["launches"], algorithmic_bytes=wl.gram_bytes()) if g else None
     if world == 1 and not args.graph:

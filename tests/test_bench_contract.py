@@ -12,9 +12,29 @@ def test_command_line_contract_defaults(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py"])
     a = bench.parse_args()
     assert a.gpus == 1 and a.steps >= 20 and a.warmup >= 1 and a.workload == "c2"
+    assert a.full is False and a.dump_outputs is None                       # the plain run: headline only, nothing written
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "20", "--warmup", "5"])
     a = bench.parse_args()
     assert (a.gpus, a.steps, a.warmup) == (8, 20, 5)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse_args()
+    assert a.full is True and a.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + bad)
+        with pytest.raises(SystemExit):
+            bench.parse_args()
+
+
+def test_write_outputs_is_float64_and_bounded(tmp_path):
+    import numpy as np
+    bench.write_outputs(str(tmp_path / "d"), {"idx": np.arange(5, dtype=np.int64), "x": np.array([0.25])})
+    idx, x = np.load(tmp_path / "d" / "idx.npy"), np.load(tmp_path / "d" / "x.npy")
+    assert idx.dtype == np.float64 and list(idx) == [0, 1, 2, 3, 4] and x.dtype == np.float64 and x[0] == 0.25
+    with pytest.raises(ValueError):
+        bench.write_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_LIMIT // 8 + 1)})
+    assert not (tmp_path / "big").exists()
+    W = bench.C2Workload                    # config 2's dump: 6 sampled term fields + q (2 fields of n) + the constant + m constants
+    assert 8 * (6 * W.DUMP_SAMPLE + 2 * W.n + 1 + W.m) <= bench.DUMP_LIMIT
 
 
 def test_roofline_helpers_follow_the_contract():
@@ -221,6 +241,46 @@ def test_gpus_n_launches_n_ranks_by_itself():
     assert r.returncode == 0, r.stderr[-3000:]
     line = _only_line(r)
     assert line == {"launch_check": True, "n_gpus": 2, "ranks_seen": 2, "gpus_requested": 2}
+
+
+def test_dump_outputs_refused_for_other_workloads(tmp_path):
+    r = _run_bench("--workload", "launch-check", "--dump-outputs", str(tmp_path / "d"))
+    assert r.returncode != 0 and "error" in _only_line(r) and not (tmp_path / "d").exists()
+
+
+@pytest.mark.gpu
+def test_plain_run_times_k_steps_and_dumps_the_last_one(tmp_path):
+    """The plain command prints the contract's fields alone (the rest is --full) with `steps` as asked; --dump-outputs holds the MOI
+    buffers of the LAST timed step: the same in two runs with the same arguments, and the oracle's on that step's inputs (the seeds of
+    epoch W + K, C2Workload.refresh)."""
+    import numpy as np
+    from oracle import oracle as O
+    lines, dumps = [], []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        r = _run_bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d), timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(_only_line(r))
+        dumps.append({p.stem: np.load(p) for p in d.glob("*.npy")})
+    line = lines[0]
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["dtype"] == "f64" and line["higher_is_better"] is True
+    assert line["unit"] == "re-evaluations/s" and line["value"] == pytest.approx(1e3 / line["ms_per_step"], rel=1e-4)
+    assert "roofline" not in line and "summary" not in line and "cpu_baseline" not in line
+    a, b = dumps
+    assert sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k]) for k in a)
+    assert all(v.dtype == np.float64 for v in a.values()) and sum(v.nbytes for v in a.values()) <= bench.DUMP_LIMIT
+    W = bench.C2Workload
+    n, r, m, e = W.n, W.r, W.m, 1000 * (1 + 3)
+    Ah, bh, Ch, dh = O.fill_uniform(r * n, 1 + e), O.fill_uniform(r, 2 + e), O.fill_uniform(m * n, 3 + e), O.fill_uniform(m, 4 + e, 2.0)
+    assert len(a["quad_coeff"]) == W.DUMP_SAMPLE and np.all(a["quad_row"] <= a["quad_col"])
+    pick = np.linspace(0, W.DUMP_SAMPLE - 1, 64).astype(np.int64)
+    _, want = O.canonical_quad_samples(Ah, r, r, n, a["quad_row"][pick].astype(np.int64), a["quad_col"][pick].astype(np.int64))
+    np.testing.assert_allclose(a["quad_coeff"][pick], want, rtol=1e-12, atol=0)
+    _, want = O.canonical_lin_samples(Ah, r, r, n, bh, -1, a["lin_var"].astype(np.int64))
+    np.testing.assert_allclose(a["lin_coeff"], want, rtol=1e-12, atol=0)
+    np.testing.assert_allclose(a["constant"][0], float(np.sum(bh * bh)), rtol=1e-13, atol=0)
+    out, var = a["con_out"].astype(np.int64), a["con_var"].astype(np.int64)
+    assert np.array_equal(a["con_coeff"], Ch.reshape(n, m).T[out - 1, var - 1]) and np.array_equal(a["con_constant"], -dh)
 
 
 def test_world_size_must_match_gpus():

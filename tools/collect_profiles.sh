@@ -9,9 +9,9 @@ TAG=${1:-rXX}
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-timeout 600 python bench.py --detail "$OUT/bench_detail.json" > "$OUT/bench.json" 2> "$OUT/bench.err"
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --detail "$OUT/bench_driver_detail.json" > "$OUT/bench_driver.json" 2> "$OUT/bench_driver.err"
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python bench.py --no-cpu-baseline --no-pmc --detail "$OUT/bench_under_rocprof_detail.json" > "$OUT/bench_under_rocprof.json" 2> /dev/null
+timeout 600 python bench.py --full --detail "$OUT/bench_detail.json" > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full --detail "$OUT/bench_driver_detail.json" > "$OUT/bench_driver.json" 2> "$OUT/bench_driver.err"
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python bench.py --full --no-cpu-baseline --no-pmc --detail "$OUT/bench_under_rocprof_detail.json" > "$OUT/bench_under_rocprof.json" 2> /dev/null
 timeout 300 python bench.py --workload batch > "$OUT/bench_batch.json" 2> /dev/null
 # PMC traffic per (kernel, shape): the step's kernels from a short timed loop of bench.py; every other kernel from its own shape process
 pmc() {  # pmc <name> <cmd...>
@@ -57,7 +57,7 @@ tr = sorted(csv.DictReader(open(glob.glob(out + "/stats/*/*kernel_trace.csv")[0]
 bu = json.load(open(out + "/bench_under_rocprof.json"))
 det = json.load(open(out + "/bench_under_rocprof_detail.json"))
 first = det["config_detail"]["setup_spinup_steps"] + bu["warmup"]
-lines = ["rocprofv3 --kernel-trace of `python bench.py --no-cpu-baseline --no-pmc`, per-launch durations of the TIMED REGION (launches %d..%d of each kernel):"
+lines = ["rocprofv3 --kernel-trace of `python bench.py --full --no-cpu-baseline --no-pmc`, per-launch durations of the TIMED REGION (launches %d..%d of each kernel):"
          % (first, first + bu["steps"] - 1)]
 for name in ("gram_mid_kernel", "gram_sk_kernel", "gram_sk_fixup_kernel", "affine_tile_kernel<1"):
     d = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in tr if name in r["Kernel_Name"]]

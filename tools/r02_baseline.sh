@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 python -m pytest tests -m gpu -x -q > "$OUT/pytest_gpu.txt" 2>&1; tail -3 "$OUT/pytest_gpu.txt"
 ./tools/f64_coissue > "$OUT/f64_coissue.txt" 2>&1; cat "$OUT/f64_coissue.txt"
-python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 python bench.py --workload batch > "$OUT/bench_batch.json" 2> "$OUT/bench_batch.err"
 prof() {  # prof <name> <cmd...>: stats + FETCH/WRITE + SQ passes
   local name=$1; shift
