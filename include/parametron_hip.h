@@ -241,6 +241,45 @@ int pmt_quad_gram_csc_deliver_f64(const double *A, int64_t lda, int64_t rows, in
 int pmt_quad_gram_deliver_f64(const double *A, int64_t lda, int64_t rows, int64_t cols, const int64_t *xvar, const double *b, int sign,
                               int moi, const int64_t *varmap, pmt_quadratic_term *out_quad, pmt_quadratic_term *host_quad, int nstages,
                               pmt_linear_term *out_lin, double *out_const, void *workspace, void *stream);
+/* A WEIGHTED SUM of least-squares blocks and simple terms over one Variable vector x (n = cols variables) as one canonical MOI function:
+ * add! / mul! of quadratic functions (src/functions.jl:452-461 append the term lists, :578 scales them), canonicalize! (:381-386), then the
+ * MOI copy (src/moi_interop.jl:45-62).  `terms` is a HOST array of `nterms` (1 .. PMT_LSQ_MAX_TERMS) descriptors in expression order:
+ *   PMT_LSQ_BLOCK     dot(r_k, r_k), r_k = A_k*x (+|-) b_k.  The FIRST block is the function already in out_quad / out_lin / out_const
+ *                     (pmt_quad_gram_f64, moi = 1, with the model's varmap); every later one gives `values` (its CSC values,
+ *                     pmt_quad_gram_csc_f64 with alpha = 1), `lin` (its out_lin) and `constant` (its out_const).  1 .. 8 blocks.
+ *   PMT_LSQ_DIAG      dot(x, x) (vec NULL) or dot(x (+|-) v, x (+|-) v) (vec = v, sign = +1 | -1)
+ *   PMT_LSQ_LINEAR    dot(c, x) (vec = c)
+ *   PMT_LSQ_CONSTANT  a scalar: *vec (a scalar Parameter), or 1.0 when vec is NULL (a number folded into `scale`)
+ * Every term is weighted by W = scale * (*weight), or scale when weight is NULL (a scalar Parameter read on the device at run time).
+ * In place, with every operation in the order written (no contraction into fma):
+ *   quad[(j,k)].coeff = (((W_1*Q_1[j,k] + W_2*V_2[k(k+1)/2 + j]) + ..) + W_K*V_K[..]) + D*[j == k],   D = ((2*W_d1) + (2*W_d2)) + ..
+ *                       over the diagonal terms (no D term without one); row / col stay as block 1 wrote them
+ *   lin[j].coeff      = W_k*q_k[j] for each block, then W_d*(2*(0.0 (+|-) v_j)) for each diagonal term with v, then W_c*c_j for each
+ *                       linear term
+ *   const             = W_k*cc_k for each block, then W_d*S_d for each diagonal term with v, then W_s*(*vec or 1.0) for each constant;
+ *                       S_d = sum_j v_j^2: 256 chains (chain t adds j = t, t + 256, .. in order), then a halving tree (t += t + 128, t + 64, ..)
+ * Block 1 alone with the constant weight +1 (no weight pointer, scale 1.0) touches only the n diagonal terms, lin and the constant;
+ * otherwise one 64 x 64 tile of the upper triangle per workgroup rewrites every term (csrc/gram_sum.hip).  Recorded into a plan behind
+ * stream-K Gram nodes (whose constant is written at the end of the replay), the constant step is queued behind those constants. */
+#define PMT_LSQ_BLOCK 1
+#define PMT_LSQ_DIAG 2
+#define PMT_LSQ_LINEAR 3
+#define PMT_LSQ_CONSTANT 4
+#define PMT_LSQ_MAX_TERMS 32
+#define PMT_LSQ_MAX_BLOCKS 8
+typedef struct {
+    int32_t kind;                     /* PMT_LSQ_* */
+    int32_t sign;                     /* PMT_LSQ_DIAG with vec: +1 for x + v, -1 for x - v */
+    double scale;                     /* host factor of the weight */
+    const double *weight;             /* device scalar factor of the weight, or NULL */
+    const double *values;             /* PMT_LSQ_BLOCK after the first: CSC values of the block (cols*(cols+1)/2) */
+    const pmt_linear_term *lin;       /* PMT_LSQ_BLOCK after the first: the block's linear terms (cols) */
+    const double *constant;           /* PMT_LSQ_BLOCK after the first: the block's constant */
+    const double *vec;                /* PMT_LSQ_DIAG: v or NULL; PMT_LSQ_LINEAR: c (cols); PMT_LSQ_CONSTANT: the scalar or NULL */
+} pmt_lsq_term;
+int pmt_quad_gram_sum_f64(int64_t cols, const pmt_lsq_term *terms, int nterms, pmt_quadratic_term *out_quad,
+                          pmt_linear_term *out_lin, double *out_const, void *stream);
+
 /* host: block until every copy on the fetch stream of `stream` (a HIP stream, not a recording handle) has landed.  PMT_HIP_ERROR when a
  * delivery failed on the device: a transfer that never started, a courier without progress, or a split tile of a staged contraction whose
  * first half never arrived (the tile is then NaN in out_P_values / out_quad — never a plausible half sum — and this call says so). */

@@ -125,6 +125,24 @@ quad_gram_csc!(out_P_values, out_quad, out_lin, out_const, A, lda, rows, cols, x
                 (DevPtr, Int64, Int64, Int64, DevPtr, DevPtr, Cint, DevPtr, Cdouble, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
                 A, lda, rows, cols, xvar, b, sign, varmap, alpha, out_P_values, out_quad, out_lin, out_const, workspace, stream))
 
+"pmt_lsq_term (include/parametron_hip.h): one term of a weighted least-squares sum; kind PMT_LSQ_BLOCK = 1, DIAG = 2, LINEAR = 3, CONSTANT = 4"
+struct LsqTerm
+    kind::Int32
+    sign::Int32
+    scale::Float64
+    weight::DevPtr
+    values::DevPtr
+    lin::DevPtr
+    constant::DevPtr
+    vec::DevPtr
+end
+
+"weighted sum of least-squares blocks (the first one already in out_quad / out_lin / out_const) and simple terms, combined in place —
+ add! / mul! of quadratic functions and canonicalize!, src/functions.jl:452-461, 578, 381-386; src/moi_interop.jl:45-62"
+quad_gram_sum!(out_quad, out_lin, out_const, cols, terms::Vector{LsqTerm}, stream) =
+    check(ccall((:pmt_quad_gram_sum_f64, lib), Cint, (Int64, Ptr{LsqTerm}, Cint, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
+                cols, terms, length(terms), out_quad, out_lin, out_const, stream))
+
 "structure of a solver matrix from 1-based (row, col) indices (host, once): perm, seg_ptr, colptr, rowval (0-based), nnz"
 function csc_order(rows::Vector{Int64}, cols::Vector{Int64}, nrows, ncols; upper::Bool=false)
     n = length(rows)

@@ -17,6 +17,25 @@ QT = np.dtype([("coeff", "<f8"), ("row", "<i8"), ("col", "<i8")])
 VAT = np.dtype([("out", "<i8"), ("coeff", "<f8"), ("var", "<i8")])
 
 PMT_OK, PMT_DIMENSION_MISMATCH, PMT_INVALID_ARGUMENT, PMT_HIP_ERROR, PMT_STATE_ERROR, PMT_OUT_OF_MEMORY = range(6)
+PMT_LSQ_BLOCK, PMT_LSQ_DIAG, PMT_LSQ_LINEAR, PMT_LSQ_CONSTANT = 1, 2, 3, 4
+PMT_LSQ_MAX_TERMS, PMT_LSQ_MAX_BLOCKS = 32, 8
+
+
+class LsqTerm(C.Structure):
+    """pmt_lsq_term: one term of the weighted sum pmt_quad_gram_sum_f64 combines (pointers are device addresses, or None)."""
+    _fields_ = [("kind", C.c_int32), ("sign", C.c_int32), ("scale", C.c_double), ("weight", C.c_void_p), ("values", C.c_void_p),
+                ("lin", C.c_void_p), ("constant", C.c_void_p), ("vec", C.c_void_p)]
+
+
+def lsq_terms(terms):
+    """host array of pmt_lsq_term from dicts {kind, sign, scale, weight, values, lin, constant, vec} (missing fields: 0 / None)"""
+    arr = (LsqTerm * max(len(terms), 1))()
+    for i, t in enumerate(terms):
+        for k, v in t.items():
+            setattr(arr[i], k, v)
+        if "scale" not in t:
+            arr[i].scale = 1.0
+    return arr
 
 
 class DimensionMismatch(Exception):
@@ -64,6 +83,7 @@ SIGNATURES = {
     "pmt_quad_gram_csc_f64": (_ci, [_vp, _i64, _i64, _i64, _vp, _vp, _ci, _vp, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pmt_quad_gram_csc_deliver_f64": (_ci, [_vp, _i64, _i64, _i64, _vp, _vp, _ci, _vp, _f64, _vp, _vp, _ci, _vp, _vp, _vp, _vp]),
     "pmt_quad_gram_deliver_f64": (_ci, [_vp, _i64, _i64, _i64, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp]),
+    "pmt_quad_gram_sum_f64": (_ci, [_i64, _vp, _ci, _vp, _vp, _vp, _vp]),
     "pmt_fetch_synchronize": (_ci, [_vp]),
     "pmt_set_host_delivery": (_ci, [_ci]),
     "pmt_get_host_delivery": (_ci, [_ci, C.POINTER(_ci), C.POINTER(_ci)]),

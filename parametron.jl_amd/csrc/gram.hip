@@ -460,6 +460,20 @@ int replay_end(hipStream_t s) {
     return rc;
 }
 
+// `f` (launches on `s`) behind what a plan's replay has queued at its end for `s` so far — the stream-K node's c'c (const_part above):
+// appended to that queue inside a replay that has one, run now otherwise.  A consumer of a Gram node's constant (gram_sum.hip) goes
+// through this, so that it reads the constant after it has been written.
+int gram_after_deferred(hipStream_t s, std::function<int()> f) {
+    std::unique_lock<std::mutex> lock(g_side_mu);
+    auto it = g_side.find(s);
+    if (it != g_side.end() && it->second.in_replay && !it->second.deferred.empty()) {
+        it->second.deferred.push_back(std::move(f));
+        return PMT_OK;
+    }
+    lock.unlock();
+    return f();
+}
+
 // host: block until every copy enqueued on the fetch stream of `s` has landed
 int fetch_synchronize(hipStream_t s) {
     std::unique_lock<std::mutex> lock(g_side_mu);

@@ -551,6 +551,7 @@ class DQuad(DV):
         self.ctx = ctx
         self.nq, self.nl = int(nq), int(nl)
         self.quad = self.lin = self.const = None
+        self.inputs = ()                  # deferred DQuad operands: materialised with this one (their literal terms are read then)
         if alloc:
             self.materialize()
 
@@ -560,6 +561,8 @@ class DQuad(DV):
             if need > (200 << 30):
                 raise MemoryError("the literal (uncombined) expansion needs %.1f GB of QuadraticTerms; use the canonical "
                                   "objective mode (Model(..., quadratic_mode='canonical'))" % (need / 1e9))
+            for d in self.inputs:
+                d.materialize()
             self.quad = self.ctx.alloc(24 * max(self.nq, 1))
             self.lin = self.ctx.alloc(16 * max(self.nl, 1))
             self.const = self.ctx.alloc(8)

@@ -314,6 +314,7 @@ class DeviceNode(LazyExpression):
         self._emit = emit
         self._prepare = prepare           # run for every scheduled node before any emit (materialisation requests)
         self.gram_candidate = gram_candidate
+        self.lsq_sum = None               # the node as a weighted sum of least-squares terms (LsqTerm list), or None
 
     def prepare(self):
         if self._prepare is not None:
@@ -573,7 +574,7 @@ def _rule_dot(model, ctx, x, y):                                                
 
             def emit(c):
                 c.call("pmt_vecdot_numbers_vars_f64", P(v.buf), P(o.buf), n, P(out.terms), P(out.const))
-            return DeviceNode(model, "vecdot!", ins, out, emit)
+            return _with_lsq(DeviceNode(model, "vecdot!", ins, out, emit), [LsqTerm("linear", xvars=o, vec=v)])
         X = o.materialized()                                                     # :665-674
         if not X.uniform():
             raise ArgumentError("dot(numbers, Vector{AffineFunction}) needs rows of equal length on the device")
@@ -587,7 +588,8 @@ def _rule_dot(model, ctx, x, y):                                                
 
         def emit(c):
             c.call("pmt_vecdot_terms_f64", n, None, P(dx.buf), None, P(dy.buf), 0, None, P(out.quad))
-        return DeviceNode(model, "vecdot!", ins, out, emit)
+        node = DeviceNode(model, "vecdot!", ins, out, emit)
+        return _with_lsq(node, [LsqTerm("diag", xvars=dx)] if np.array_equal(dx.vars, dy.vars) else None)
     if isinstance(dx, DVars) or isinstance(dy, DVars):                           # :702-709 over :537-546
         o, v = (dx, dy) if isinstance(dy, DVars) else (dy, dx)
         X = o.materialized()
@@ -614,7 +616,13 @@ def _rule_dot(model, ctx, x, y):                                                
             c.call("pmt_quad_expand_f64", n, P(dx.terms), nx, P(dx.consts), P(dy.terms), ny, P(dy.consts), 0, None,
                    P(out.quad), P(out.lin), P(out.const))
         gram = dx if (dx is dy and isinstance(dx, DDenseAff)) else None
-        return DeviceNode(model, "vecdot!", ins, out, emit, gram_candidate=gram, prepare=prepare)
+        node = DeviceNode(model, "vecdot!", ins, out, emit, gram_candidate=gram, prepare=prepare)
+        if gram is not None:
+            return _with_lsq(node, [LsqTerm("block", r=gram)])
+        if isinstance(dx, DVarsAff) and isinstance(dy, DVarsAff) and np.array_equal(dx.xvars.vars, dy.xvars.vars) and dx.sign == dy.sign and \
+                dx.vec is not None and dy.vec is not None and dx.vec.buf == dy.vec.buf:
+            return _with_lsq(node, [LsqTerm("diag", xvars=dx.xvars, vec=dx.vec, sign=dx.sign)])          # dot(x (+|-) v, x (+|-) v)
+        return node
     raise ArgumentError("dot(%s, %s) is not supported on the device" % (kind_of(dx), kind_of(dy)))
 
 
@@ -643,6 +651,66 @@ def _rule_bilinear(model, ctx, x, Q, y):                                        
     return DeviceNode(model, "bilinearmul!", _inputs(x, Q, y), out, emit)
 
 
+# ---- weighted sums of least-squares terms -------------------------------------------------------------------------
+class LsqTerm:
+    """One term of a scalar node read as a weighted sum (DeviceNode.lsq_sum; combined by the canonical-sum objective, moi.py):
+      'block'     dot(r, r) / transpose(r)*r, r = A*x (+|-) b a Gram candidate (r: its DDenseAff)
+      'diag'      dot(x, x), or dot(x (+|-) v, x (+|-) v) with v a vector Parameter (xvars, vec, sign)
+      'linear'    dot(c, x) / dot(x, c) with c a vector Parameter (xvars, vec)
+      'constant'  a number (folded into scale) or a scalar Parameter (value)
+    weighted by scale (+-1 times Python numbers) times at most one scalar Parameter (param: its DNum, read on the device at run time)."""
+    __slots__ = ("kind", "scale", "param", "r", "xvars", "vec", "sign", "value")
+
+    def __init__(self, kind, scale=1.0, param=None, r=None, xvars=None, vec=None, sign=0, value=None):
+        self.kind, self.scale, self.param = kind, float(scale), param
+        self.r, self.xvars, self.vec, self.sign, self.value = r, xvars, vec, sign, value
+
+    def scaled(self, s, param=None):
+        t = LsqTerm(self.kind, self.scale * s, param or self.param, self.r, self.xvars, self.vec, self.sign, self.value)
+        return t
+
+    def __repr__(self):
+        return "LsqTerm(%s, scale=%r%s)" % (self.kind, self.scale, ", param" if self.param is not None else "")
+
+
+class _IndexVars:
+    """the variable indices of a host-built term (only compared with those of the blocks: no device buffer)"""
+
+    def __init__(self, indices):
+        self.vars = np.asarray(indices, dtype=np.int64)
+
+
+def _with_lsq(node, terms):
+    node.lsq_sum = terms
+    return node
+
+
+def _lsq_of(arg, dv):
+    """the weighted-sum description of a scalar operand, or None"""
+    if isinstance(arg, DeviceNode):
+        return getattr(arg, "lsq_sum", None)
+    if isinstance(arg, QuadraticFunction):
+        # dot(x, x) of plain Variables is evaluated on the host when the expression is built (no Parameter in it): sum_i 1.0 * x_i * x_i
+        q = arg.quadratic
+        if q and not arg.affine.linear and arg.affine.constant == 0 and all(t.coeff == 1.0 and t.rowvar.index == t.colvar.index for t in q):
+            return [LsqTerm("diag", xvars=_IndexVars([t.rowvar.index for t in q]))]
+        return None
+    if isinstance(dv, DNum):
+        return [LsqTerm("constant", scale=float(arg))] if _isnum(arg) else [LsqTerm("constant", value=dv)]
+    return None
+
+
+def _lsq_scaled(terms, sarg, sdv):
+    """terms * s: a number scales every term; a scalar Parameter becomes the terms' Parameter factor (a second one: not a sum we combine)"""
+    if terms is None:
+        return None
+    if _isnum(sarg):
+        return [t.scaled(float(sarg)) for t in terms]
+    if any(t.param is not None for t in terms):
+        return None
+    return [t.scaled(1.0, sdv) for t in terms]
+
+
 # ---- scalar add!/subtract! ------------------------------------------------------------------------------------
 def _scalar_affine_part(ctx, dv):
     """(terms, nterms, const) of the affine part of a scalar operand."""
@@ -662,22 +730,37 @@ def _rule_scalar_addsub(model, ctx, a, b, sign):                                
     da, db = _dv(ctx, a), _dv(ctx, b)
     name = "add!" if sign > 0 else "subtract!"
     sb = 1 if sign > 0 else -1
-    ta, na, ca = _scalar_affine_part(ctx, da)
-    tb, nb, cb = _scalar_affine_part(ctx, db)
+    la, lb = _lsq_of(a, da), _lsq_of(b, db)
+    lsq = None if la is None or lb is None else la + ([t.scaled(-1.0) for t in lb] if sb < 0 else lb)
     if isinstance(da, DQuad) or isinstance(db, DQuad):
-        qa, nqa = (da.quad, da.nq) if isinstance(da, DQuad) else (None, 0)
-        qb, nqb = (db.quad, db.nq) if isinstance(db, DQuad) else (None, 0)
-        out = DQuad(ctx, nqa + nqb, na + nb)
+        # the literal buffers (and those of the quadratic operands) exist only once a literal consumer asks for them: a weighted sum of
+        # least-squares terms is combined by the canonical objective instead (moi.py), and its literal expansion may not fit in memory
+        nqa = da.nq if isinstance(da, DQuad) else 0
+        nqb = db.nq if isinstance(db, DQuad) else 0
+        pa = None if isinstance(da, DQuad) else _scalar_affine_part(ctx, da)
+        pb = None if isinstance(db, DQuad) else _scalar_affine_part(ctx, db)
+        na = da.nl if isinstance(da, DQuad) else pa[1]
+        nb = db.nl if isinstance(db, DQuad) else pb[1]
+        out = DQuad(ctx, nqa + nqb, na + nb, alloc=False)
+        out.inputs = tuple(d for d in (da, db) if isinstance(d, DQuad))
 
         def emit(c):
+            if out.quad is None:
+                return
+            qa = da.quad if isinstance(da, DQuad) else None
+            qb = db.quad if isinstance(db, DQuad) else None
+            ta, _, ca = pa or _scalar_affine_part(ctx, da)
+            tb, _, cb = pb or _scalar_affine_part(ctx, db)
             c.call("pmt_quad_combine_f64", P(qa), nqa, P(qb), nqb, sb, P(out.quad))
             c.call("pmt_affvec_combine_f64", 1, P(ta), None, na, P(ca), P(tb), None, nb, P(cb), sb, P(out.lin), None, na + nb, P(out.const))
-        return DeviceNode(model, name, _inputs(a, b), out, emit)
+        return _with_lsq(DeviceNode(model, name, _inputs(a, b), out, emit), lsq)
+    ta, na, ca = _scalar_affine_part(ctx, da)
+    tb, nb, cb = _scalar_affine_part(ctx, db)
     out = DAff(ctx, na + nb)
 
     def emit(c):
         c.call("pmt_affvec_combine_f64", 1, P(ta), None, na, P(ca), P(tb), None, nb, P(cb), sb, P(out.terms), None, na + nb, P(out.const))
-    return DeviceNode(model, name, _inputs(a, b), out, emit)
+    return _with_lsq(DeviceNode(model, name, _inputs(a, b), out, emit), lsq)
 
 
 # ---- scalar mul! and vector scale! ----------------------------------------------------------------------------------
@@ -696,20 +779,23 @@ def _rule_mul_scalar(model, ctx, a, b):                                         
             return DeviceNode(model, "*", ins, out, emit)
         if isinstance(f, DNum):
             raise ArgumentError("number * number is plain data: compute it inside a Parameter callback")
+        sa, fa = (a, b) if s is da else (b, a)
         if isinstance(f, DAff):
             out = DAff(ctx, f.nterms)
 
             def emit(c):
                 c.call("pmt_affvec_scale_f64", 1, f.nterms, P(f.terms), P(f.const), P(s.buf), 0.0, P(out.terms), P(out.const))
-            return DeviceNode(model, "mul!", ins, out, emit)
+            return _with_lsq(DeviceNode(model, "mul!", ins, out, emit), _lsq_scaled(_lsq_of(fa, f), sa, s))
         if isinstance(f, DQuad):
-            f.materialize()
-            out = DQuad(ctx, f.nq, f.nl)
+            out = DQuad(ctx, f.nq, f.nl, alloc=False)                           # literal buffers on demand (as in add! above)
+            out.inputs = (f,)
 
             def emit(c):
+                if out.quad is None:
+                    return
                 c.call("pmt_quad_scale_f64", P(f.quad), f.nq, P(s.buf), 0.0, P(out.quad))
                 c.call("pmt_affvec_scale_f64", 1, f.nl, P(f.lin), P(f.const), P(s.buf), 0.0, P(out.lin), P(out.const))
-            return DeviceNode(model, "mul!", ins, out, emit)
+            return _with_lsq(DeviceNode(model, "mul!", ins, out, emit), _lsq_scaled(_lsq_of(fa, f), sa, s))
     if isinstance(da, DAff) and isinstance(db, DAff):                            # aff * aff (:548-576)
         out = DQuad(ctx, da.nterms * db.nterms, da.nterms + db.nterms)
 

@@ -164,6 +164,12 @@ def _write_mailbox(x, val):
         mb[0] = float(val)
 
 
+def _is_gram_record(r):
+    """a record whose MOI copy is the canonical least-squares node (bare, or the weighted sum of such nodes)"""
+    return getattr(r, "mode", "").startswith("canonical") and r.kind == "quad" and \
+        (getattr(r.expr, "gram_candidate", None) is not None or r.mode == "canonical-sum")
+
+
 class _Backend:
     """What MOI.copy_to sees of the ParametronMOIModel backend (src/moi_interop.jl:2-11)."""
 
@@ -343,10 +349,14 @@ class Model:
             ident = np.arange(1, self.nvars + 1, dtype=np.int64)     # IdentityVarMap until mapindices! (src/moi_interop.jl:32-33)
             ctx.upload(self._varmap_buf, self.model_var_to_optimizer if early else ident)
             if self.quadratic_mode == "canonical":
+                # a weighted sum of least-squares blocks over one x (the objective's lsq_sum): combined from the blocks' Gram nodes
+                # (moi.py, mode "canonical-sum") — the MOI boundary of a model beyond the small plan only
+                if not self._small and self.handoff == "moi" and self.objective in records:
+                    self.objective.lsq_terms = moi.lsq_sum_terms(self.objective.expr)
                 # any other quadratic objective: generic device canonicalize! (sorted, duplicates combined) before the MOI copy
                 for r in records:
                     gram = getattr(r.expr, "gram_candidate", None)
-                    if r.kind == "quad" and not (gram is not None and gram.xvars.strictly_increasing()):
+                    if r.kind == "quad" and not (gram is not None and gram.xvars.strictly_increasing()) and getattr(r, "lsq_terms", None) is None:
                         r.expr = r.expr.canonicalize()
             emitters = [r.compile(ctx, self._varmap_buf, self.quadratic_mode, self.model_var_to_optimizer if early else None) for r in records]
             self._order = schedule([r.expr for r in records])
@@ -363,8 +373,7 @@ class Model:
                 # Constraint, src/moi_interop.jl:168-175).  Beside a canonical least-squares objective they go to the plan's side lane:
                 # queued behind the contraction's small reductions, they run while its workgroups drain and its fix-up pass runs,
                 # instead of adding their kernels and in-stream gaps behind it.
-                gram = any(getattr(r, "mode", "").startswith("canonical") and r.kind == "quad" and getattr(r.expr, "gram_candidate", None) is not None
-                           for r in records)
+                gram = any(_is_gram_record(r) for r in records)
                 self._lane_records = []
                 # one small kernel on the lane does not pay (config 2: the co-resident pack slows the contraction by what it saves); several
                 # do (config 3: -0.15 ms), and so does the device hand-off, whose launches join them on the lane
@@ -379,9 +388,7 @@ class Model:
                     # a SMALL model: the records are independent of each other, so the one whose MOI copy is not an interpreter node — the
                     # canonical least-squares objective beyond tiny shapes (gram_tall.hip: two launches) — goes last; the constraints' packs
                     # then join the run of small entries at the front of the tape (callbacks, residual) in its ONE launch
-                    def is_gram(r):
-                        return getattr(r, "mode", "").startswith("canonical") and r.kind == "quad" and getattr(r.expr, "gram_candidate", None) is not None
-                    emit_order = [re for re in emit_order if not is_gram(re[0])] + [re for re in emit_order if is_gram(re[0])]
+                    emit_order = [re for re in emit_order if not _is_gram_record(re[0])] + [re for re in emit_order if _is_gram_record(re[0])]
                 elif use_lane:
                     # round 6c: the side lane's records go in FRONT of the objective — its one-launch node (gram_mid.hip) holds every CU
                     # with persistent workgroups and lane entries recorded behind it wait for it; recorded first they take CUs first and

@@ -268,6 +268,9 @@ class _Record:
                         c.call("pmt_quad_gram_f64", P(gram.mat.buf), gram.mat.lda, _gram_rows(gram), n, P(gram.xvars.buf), P(vec), gram.sign if vec else 0,
                                1, P(varmap_buf), P(dq), P(dl), P(dc), P(ws))
                 return emit
+            terms = getattr(self, "lsq_terms", None)
+            if terms is not None:
+                return self._compile_lsq_sum(ctx, varmap_buf, terms)
             self.mode = "literal"
             out.materialize()
             self.f = ScalarQuadraticFunction(out.nl, out.nq, alloc=ctx.pinned_array)
@@ -378,6 +381,52 @@ class _Record:
             c.call("pmt_pack_vector_affine_f64", P(m.terms), P(m.row_ptr_buf), m.rows, m.row_len, P(varmap_buf), 0, P(dt))
         return emit
 
+    def _compile_lsq_sum(self, ctx, varmap_buf, terms):
+        """The objective as a weighted sum of least-squares blocks over one x (lsq_sum_terms): block 1 by pmt_quad_gram_f64 straight into the
+        MOI buffers, blocks 2..K as CSC values (pmt_quad_gram_csc_f64, bit for bit the same coefficients), then pmt_quad_gram_sum_f64 weights
+        and adds everything in place.  The terms are final only after the combine: no overlapped delivery of the quadratic terms."""
+        from . import _lib
+        blocks = [t.r for t in terms if t.kind == "block"]
+        g1 = blocks[0]
+        n = g1.mat.cols
+        nq = n * (n + 1) // 2
+        self.f = ScalarQuadraticFunction(n, nq, alloc=ctx.pinned_array)
+        dq, dl, dc = ctx.alloc(24 * max(nq, 1)), ctx.alloc(16 * max(n, 1)), ctx.alloc(8)
+        self.dev = {"quad": dq, "lin": dl, "const": dc}
+        self.mode = "canonical-sum"
+        self._quad_delivered = False
+        ws = [ctx.alloc(max(16, int(ctx.lib.pmt_quad_gram_workspace_bytes(_gram_rows(g), n)))) for g in blocks]
+        # per block 2..K: its CSC values, linear terms and constant
+        parts = [(ctx.alloc(8 * max(nq, 1)), ctx.alloc(16 * max(n, 1)), ctx.alloc(8)) for _ in blocks[1:]]
+        desc, k = [], 0
+        for t in terms:
+            d = {"kind": {"block": _lib.PMT_LSQ_BLOCK, "diag": _lib.PMT_LSQ_DIAG, "linear": _lib.PMT_LSQ_LINEAR, "constant": _lib.PMT_LSQ_CONSTANT}[t.kind],
+                 "scale": t.scale, "weight": t.param.buf if t.param is not None else None}
+            if t.kind == "block":
+                if k > 0:
+                    d["values"], d["lin"], d["constant"] = parts[k - 1]
+                k += 1
+            elif t.kind == "diag":
+                d["vec"] = t.vec.buf if t.vec is not None else None
+                d["sign"] = t.sign if t.vec is not None else 0
+            elif t.kind == "linear":
+                d["vec"] = t.vec.buf
+            elif t.value is not None:
+                d["vec"] = t.value.buf
+            desc.append(d)
+        arr = _lib.lsq_terms(desc)
+
+        def gram_args(g):
+            vec = g.vec.buf if g.vec is not None else None
+            return (P(g.mat.buf), g.mat.lda, _gram_rows(g), n, P(g.xvars.buf), P(vec), g.sign if vec else 0)
+
+        def emit(c):
+            c.call("pmt_quad_gram_f64", *gram_args(g1), 1, P(varmap_buf), P(dq), P(dl), P(dc), P(ws[0]))
+            for g, w, (dv, dlk, dck) in zip(blocks[1:], ws[1:], parts):
+                c.call("pmt_quad_gram_csc_f64", *gram_args(g), P(varmap_buf), 1.0, P(dv), None, P(dlk), P(dck), P(w))
+            c.call("pmt_quad_gram_sum_f64", n, C.addressof(arr), len(desc), P(dq), P(dl), P(dc))
+        return emit
+
     def record_fetch(self, ctx):
         """while recording (Model._overlap_moi): the same copies as fetch(), as tape entries behind this record's launches on their lane —
         they leave while the rest of the tape is still running (pmt_plan_record_fetch); the objective's quadratic terms are delivered by
@@ -435,6 +484,26 @@ class _Record:
     def finish_fetch(self):
         if self.kind in ("aff", "quad"):
             self.f.constant = float(self._c[0])
+
+
+def lsq_sum_terms(expr):
+    """The LsqTerm list of an objective the canonical-sum path takes (Model.initialize checks the model-level conditions), or None:
+    1 .. 8 least-squares blocks, at most PMT_LSQ_MAX_TERMS terms, every block / diagonal / linear term over the same strictly increasing x."""
+    from . import _lib
+    terms = getattr(expr, "lsq_sum", None) if isinstance(expr, DeviceNode) else None
+    if not terms or len(terms) > _lib.PMT_LSQ_MAX_TERMS or getattr(expr, "gram_candidate", None) is not None:
+        return None
+    blocks = [t for t in terms if t.kind == "block"]
+    if not 1 <= len(blocks) <= _lib.PMT_LSQ_MAX_BLOCKS:
+        return None
+    x = blocks[0].r.xvars
+    if not x.strictly_increasing():
+        return None
+    for t in terms:
+        xv = t.r.xvars if t.kind == "block" else t.xvars
+        if xv is not None and not np.array_equal(xv.vars, x.vars):
+            return None
+    return terms
 
 
 class Objective(_Record):                                                 # src/moi_interop.jl:113-137
