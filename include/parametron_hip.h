@@ -66,6 +66,19 @@ int pmt_affine_assemble_f64(const double *A, int64_t lda, int64_t rows, int64_t 
                             const int64_t *xvar, const double *b, int sign,
                             pmt_linear_term *out_terms, double *out_consts, void *stream);
 
+/* A residual over SEVERAL Variable vectors, r = (+|-)A_1*x_1 (+|-) A_2*x_2 .. (vecadd! / vecsubtract! src/functions.jl:751-764, rules
+ * src/lazyexpression.jl:238-258), as one dense block over the union z of the variables:
+ *   out[i + c*ldo] = cols[c].sign * cols[c].src[i]   for i < rows, c < ncols  (the product exact: sign is +1 or -1, -1 flips the sign bit)
+ * `cols` is a DEVICE table of ncols entries built once by the host: entry c is the c-th variable of z, `src` the start of its column in
+ * the block's matrix (A_k + j*lda_k), `sign` that of the block.  Rows rows .. ldo-1 of `out` are never written (a zero-padded workspace
+ * stays zero-padded), so the Gram family reads `out` exactly as it reads a Parameter holding the stacked matrix (csrc/stack.hip).  The
+ * table's signs are not read on the host: _lib.stack_table (parametron.jl_amd/_lib.py) builds it and checks them. */
+typedef struct {
+    const double *src;                /* column start */
+    int64_t sign;                     /* +1 or -1 */
+} pmt_stack_column;                   /* 16 bytes, no padding (static_assert in csrc/stack.hip) */
+int pmt_affine_stack_columns_f64(const pmt_stack_column *cols, int64_t ncols, int64_t rows, double *out, int64_t ldo, void *stream);
+
 /* Same node written straight into MOI.VectorAffineFunction buffers:
  * out_terms[row*cols + col] = (row_offset + row + 1, A[row,col], varmap[xvar[col]]), out_consts as above.
  * Replaces the chain above + update!(::MOI.VectorAffineFunction, fs, varmap) src/moi_interop.jl:64-81. */
@@ -279,6 +292,18 @@ typedef struct {
 } pmt_lsq_term;
 int pmt_quad_gram_sum_f64(int64_t cols, const pmt_lsq_term *terms, int nterms, pmt_quadratic_term *out_quad,
                           pmt_linear_term *out_lin, double *out_const, void *stream);
+/* The same sum when PMT_LSQ_DIAG / PMT_LSQ_LINEAR terms cover only PART of the columns (dot(r, r) + lam*dot(u, u) with r stacked over
+ * z = [x; u], pmt_affine_stack_columns_f64).  term_cols[t] (a HOST array of nterms pointers, or NULL for all terms) lists the device
+ * positions term t covers: term_ncols[t] strictly increasing positions in 0 .. cols-1, read on the host at call time; NULL (the pointer
+ * array or its entry t) means every column.  Blocks and constants cover every column (a list for them is an error).  The vec of a subset
+ * term has one entry per listed position (term_ncols[t] entries).  A position a term does not list gets nothing from it (no + 0.0);
+ * otherwise the order is the one fixed above for pmt_quad_gram_sum_f64, restricted to the listed positions:
+ *   D_j = ((2*W_d1) + (2*W_d2)) + .. over the diagonal terms listing j (added only when one does); lin[j] takes the terms listing j in
+ *   the order above; S_d is the chain-then-tree sum over the term's own vector.
+ * The lists are held in the launch's arguments as runs of consecutive positions: at most PMT_LSQ_MAX_RUNS runs over all terms. */
+#define PMT_LSQ_MAX_RUNS 64
+int pmt_quad_gram_sum_sub_f64(int64_t cols, const pmt_lsq_term *terms, int nterms, const int64_t *const *term_cols, const int64_t *term_ncols,
+                              pmt_quadratic_term *out_quad, pmt_linear_term *out_lin, double *out_const, void *stream);
 
 /* host: block until every copy on the fetch stream of `stream` (a HIP stream, not a recording handle) has landed.  PMT_HIP_ERROR when a
  * delivery failed on the device: a transfer that never started, a courier without progress, or a split tile of a staged contraction whose

@@ -143,6 +143,29 @@ quad_gram_sum!(out_quad, out_lin, out_const, cols, terms::Vector{LsqTerm}, strea
     check(ccall((:pmt_quad_gram_sum_f64, lib), Cint, (Int64, Ptr{LsqTerm}, Cint, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
                 cols, terms, length(terms), out_quad, out_lin, out_const, stream))
 
+"weighted least-squares sum whose diagonal / linear terms cover only the positions listed in term_cols[t] (host vectors, strictly
+ increasing 0-based positions; `nothing` = every column) — the same combine as quad_gram_sum!, restricted to the listed columns"
+function quad_gram_sum_sub!(out_quad, out_lin, out_const, cols, terms::Vector{LsqTerm}, term_cols::Vector{Union{Nothing,Vector{Int64}}}, stream)
+    length(term_cols) == length(terms) || throw(DimensionMismatch("one column list (or nothing) per term"))
+    ptrs = Ptr{Int64}[c === nothing ? Ptr{Int64}(C_NULL) : pointer(c) for c in term_cols]
+    counts = Int64[c === nothing ? 0 : length(c) for c in term_cols]
+    GC.@preserve term_cols check(ccall((:pmt_quad_gram_sum_sub_f64, lib), Cint,
+                                       (Int64, Ptr{LsqTerm}, Cint, Ptr{Ptr{Int64}}, Ptr{Int64}, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
+                                       cols, terms, length(terms), ptrs, counts, out_quad, out_lin, out_const, stream))
+end
+
+"pmt_stack_column (include/parametron_hip.h): the device address of a column and its sign (+1 or -1)"
+struct StackColumn
+    src::DevPtr
+    sign::Int64
+end
+
+"out[:, c] = table[c].sign * column table[c].src (rows of each; out's rows rows+1 .. ldo untouched) — the blocks of a residual over several
+ Variable vectors as one matrix (vecadd!/vecsubtract! src/functions.jl:751-764, rules src/lazyexpression.jl:238-258); `table` on the device"
+affine_stack_columns!(out, ldo, table, ncols, rows, stream) =
+    check(ccall((:pmt_affine_stack_columns_f64, lib), Cint, (DevPtr, Int64, Int64, DevPtr, Int64, Ptr{Cvoid}),
+                table, ncols, rows, out, ldo, stream))
+
 "structure of a solver matrix from 1-based (row, col) indices (host, once): perm, seg_ptr, colptr, rowval (0-based), nnz"
 function csc_order(rows::Vector{Int64}, cols::Vector{Int64}, nrows, ncols; upper::Bool=false)
     n = length(rows)

@@ -18,7 +18,8 @@ VAT = np.dtype([("out", "<i8"), ("coeff", "<f8"), ("var", "<i8")])
 
 PMT_OK, PMT_DIMENSION_MISMATCH, PMT_INVALID_ARGUMENT, PMT_HIP_ERROR, PMT_STATE_ERROR, PMT_OUT_OF_MEMORY = range(6)
 PMT_LSQ_BLOCK, PMT_LSQ_DIAG, PMT_LSQ_LINEAR, PMT_LSQ_CONSTANT = 1, 2, 3, 4
-PMT_LSQ_MAX_TERMS, PMT_LSQ_MAX_BLOCKS = 32, 8
+PMT_LSQ_MAX_TERMS, PMT_LSQ_MAX_BLOCKS, PMT_LSQ_MAX_RUNS = 32, 8, 64
+STACK_COLUMN = np.dtype([("src", "<u8"), ("sign", "<i8")])       # pmt_stack_column
 
 
 class LsqTerm(C.Structure):
@@ -36,6 +37,28 @@ def lsq_terms(terms):
         if "scale" not in t:
             arr[i].scale = 1.0
     return arr
+
+
+def stack_table(srcs, signs):
+    """host image of the pmt_stack_column table of pmt_affine_stack_columns_f64: column c is signs[c] * (the column at device address
+    srcs[c]).  The entry point reads the table on the device only, so the signs are checked here."""
+    srcs = np.asarray(srcs, dtype=np.uint64).reshape(-1)
+    signs = np.asarray(signs, dtype=np.int64).reshape(-1)
+    if srcs.shape != signs.shape:
+        raise DimensionMismatch("stack_table: %d sources, %d signs" % (len(srcs), len(signs)))
+    if not np.all((signs == 1) | (signs == -1)):
+        raise ArgumentError("stack_table: every sign must be +1 or -1")
+    if np.any(srcs == 0):
+        raise ArgumentError("stack_table: null column source")
+    t = np.empty(len(srcs), dtype=STACK_COLUMN)
+    t["src"], t["sign"] = srcs, signs
+    return t
+
+
+def column_runs(positions):
+    """the number of runs of consecutive positions in a strictly increasing list (pmt_quad_gram_sum_sub_f64 holds PMT_LSQ_MAX_RUNS)"""
+    p = np.asarray(positions, dtype=np.int64)
+    return int(len(p) and 1 + np.count_nonzero(np.diff(p) != 1))
 
 
 class DimensionMismatch(Exception):
@@ -84,6 +107,8 @@ SIGNATURES = {
     "pmt_quad_gram_csc_deliver_f64": (_ci, [_vp, _i64, _i64, _i64, _vp, _vp, _ci, _vp, _f64, _vp, _vp, _ci, _vp, _vp, _vp, _vp]),
     "pmt_quad_gram_deliver_f64": (_ci, [_vp, _i64, _i64, _i64, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp]),
     "pmt_quad_gram_sum_f64": (_ci, [_i64, _vp, _ci, _vp, _vp, _vp, _vp]),
+    "pmt_quad_gram_sum_sub_f64": (_ci, [_i64, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pmt_affine_stack_columns_f64": (_ci, [_vp, _i64, _i64, _vp, _i64, _vp]),
     "pmt_fetch_synchronize": (_ci, [_vp]),
     "pmt_set_host_delivery": (_ci, [_ci]),
     "pmt_get_host_delivery": (_ci, [_ci, C.POINTER(_ci), C.POINTER(_ci)]),

@@ -356,6 +356,17 @@ class DVars(DV):
     def strictly_increasing(self):
         return bool(np.all(np.diff(self.vars) > 0))
 
+    @classmethod
+    def of_indices(cls, ctx, indices):
+        """the Variable vector of these model indices"""
+        self = cls.__new__(cls)
+        self.vars = np.ascontiguousarray(indices, dtype=np.int64)
+        self.n = len(self.vars)
+        self.buf = ctx.upload_new(self.vars) if self.n else ctx.alloc(8)
+        self._lt = None
+        self.ctx = ctx
+        return self
+
 
 class DLinVec(DV):
     """Vector{LinearTerm{Float64}}: LT[n]."""
@@ -437,6 +448,51 @@ class DVarsAff(DAffVec):
 
     def materialized(self):
         return self.require_terms()
+
+
+class DStackedAff(DAffVec):
+    """(+|-)A_1*x_1 (+|-) A_2*x_2 .. with at most one (+|-)b, the x_k pairwise disjoint Variable vectors, kept implicit as the dense blocks
+    it is made of (vecadd! / vecsubtract! of DDenseAff operands, src/functions.jl:751-764).  Two forms exist only on demand:
+      * the LinearTerms (`require_terms`, a literal consumer): today's pmt_affvec_combine_f64 of the two operands, in expression order;
+      * the stacked matrix (`require_stack`, a canonical Gram consumer): `mat`, rows x len(z) over the sorted union z of the variables
+        (`xvars`), written from the blocks' Parameter matrices by pmt_affine_stack_columns_f64, with the layout of a Parameter matrix of that
+        shape, so that r = mat*z (+|-) b reads like a DDenseAff (mat, xvars, vec, sign) to the Gram family."""
+
+    def __init__(self, ctx, rows, row_ptr, operands, blocks, vec, sign):
+        super().__init__(ctx, rows, row_ptr=row_ptr, alloc=False)
+        self.operands = operands          # (a, b, sb): the two operands' device values and the sign of b (the combine's arguments)
+        self.blocks = blocks              # [(DMat, DVars, +1 | -1)] in expression order
+        self.vec, self.sign = vec, sign
+        self.xvars = DVars.of_indices(ctx, np.sort(np.concatenate([x.vars for _, x, _ in blocks])))
+        self.mat = self.table = None
+        self.need_terms = False
+
+    def require_terms(self):
+        if not self.need_terms:
+            self.need_terms = True
+            for d in self.operands[:2]:
+                if isinstance(d, DAffVec):
+                    d.materialized()
+            self.terms = self.ctx.alloc(16 * max(self.nterms, 1))
+            self.consts = self.ctx.alloc(8 * max(self.rows, 1))
+        return self
+
+    def materialized(self):
+        return self.require_terms()
+
+    def require_stack(self):
+        """allocate the stacked matrix and its column table (once); the node writes it at every re-evaluation from then on"""
+        if self.mat is None:
+            z = self.xvars.vars
+            srcs, signs = np.zeros(len(z), dtype=np.uint64), np.zeros(len(z), dtype=np.int64)
+            for m, x, sgn in self.blocks:
+                pos = np.searchsorted(z, x.vars)
+                srcs[pos] = np.uint64(m.buf) + np.uint64(8 * m.lda) * np.arange(len(x.vars), dtype=np.uint64)
+                signs[pos] = sgn
+            self.ncols = len(z)
+            self.table = self.ctx.upload_new(_lib.stack_table(srcs, signs)) if len(z) else None
+            self.mat = DMat(self.ctx, self.rows, self.ncols)
+        return self
 
 
 class DSpMat(DV):
@@ -581,5 +637,5 @@ def fetch_f64(ctx, ptr, n):
     return out
 
 
-__all__ = ["DeviceContext", "DV", "DNum", "DVec", "DMat", "DVars", "DLinVec", "DAffVec", "DDenseAff", "DVarsAff", "DSpMat", "DSparseAff", "DAff", "DQuad",
+__all__ = ["DeviceContext", "DV", "DNum", "DVec", "DMat", "DVars", "DLinVec", "DAffVec", "DDenseAff", "DStackedAff", "DVarsAff", "DSpMat", "DSparseAff", "DAff", "DQuad",
            "fetch_terms", "fetch_f64", "P", "LT", "QT", "VAT", "ArgumentError"]

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import hostops
 from ._lib import LT, QT, ArgumentError, DimensionMismatch
-from .device import (DAff, DAffVec, DDenseAff, DLinVec, DMat, DNum, DQuad, DSparseAff, DSpMat, DV, DVars, DVarsAff, DVec, P,
+from .device import (DAff, DAffVec, DDenseAff, DLinVec, DStackedAff, DMat, DNum, DQuad, DSparseAff, DSpMat, DV, DVars, DVarsAff, DVec, P,
                      fetch_f64, fetch_terms)
 
 
@@ -315,6 +315,7 @@ class DeviceNode(LazyExpression):
         self._prepare = prepare           # run for every scheduled node before any emit (materialisation requests)
         self.gram_candidate = gram_candidate
         self.lsq_sum = None               # the node as a weighted sum of least-squares terms (LsqTerm list), or None
+        self.stacked_gram = None          # dot(r, r) of a stacked residual r (DStackedAff): its Gram candidate on demand
 
     def prepare(self):
         if self._prepare is not None:
@@ -545,17 +546,67 @@ def _rule_vec_addsub(model, ctx, a, b, sign):                                   
         return DeviceNode(model, name, _inputs(a, b), out, emit)
     if isinstance(da, DVec) and isinstance(db, DVec):
         raise ArgumentError("number vector (+|-) number vector is plain data: compute it inside a Parameter callback")
-    ta, pa, la, ca = _affvec_parts(da)
-    tb, pb, lb, cb = _affvec_parts(db)
     lens = _row_lens(da) + _row_lens(db)
     row_ptr = np.zeros(len(lens) + 1, dtype=np.int64)
     np.cumsum(lens, out=row_ptr[1:])
+    stacked = _stacked_form(da, db, sign)
+    if stacked is not None:
+        # dense blocks over disjoint Variable vectors: kept implicit (DStackedAff); the combine below runs only for a literal consumer, the
+        # stacking node only for a canonical Gram consumer (Model.initialize)
+        blocks, vec, vsign = stacked
+        sb = 1 if sign > 0 else -1
+        out = DStackedAff(ctx, len(lens), row_ptr, (da, db, sb), blocks, vec, vsign)
+
+        def emit(c):
+            if out.need_terms:
+                ta, pa, la, ca = _affvec_parts(da)
+                tb, pb, lb, cb = _affvec_parts(db)
+                c.call("pmt_affvec_combine_f64", out.rows, P(ta), P(pa), la, P(ca), P(tb), P(pb), lb, P(cb), sb,
+                       P(out.terms), P(out.row_ptr_buf), out.row_len, P(out.consts))
+            if out.mat is not None:
+                c.call("pmt_affine_stack_columns_f64", P(out.table), out.ncols, out.rows, P(out.mat.buf), out.mat.lda)
+        return DeviceNode(model, name, _inputs(a, b), out, emit)
+    ta, pa, la, ca = _affvec_parts(da)
+    tb, pb, lb, cb = _affvec_parts(db)
     out = DAffVec(ctx, len(lens), row_ptr=row_ptr)
 
     def emit(c):
         c.call("pmt_affvec_combine_f64", out.rows, P(ta), P(pa), la, P(ca), P(tb), P(pb), lb, P(cb), 1 if sign > 0 else -1,
                P(out.terms), P(out.row_ptr_buf), out.row_len, P(out.consts))
     return DeviceNode(model, name, _inputs(a, b), out, emit)
+
+
+def _stack_parts(dv):
+    """(blocks, vec, vsign) of an operand of a stacked residual: a dense block A*x (+|-) b, a stacked residual, or a number vector"""
+    if isinstance(dv, DDenseAff) and isinstance(dv.mat, DMat) and (dv.vec is None or isinstance(dv.vec, DVec)):
+        return [(dv.mat, dv.xvars, 1)], dv.vec, dv.sign
+    if isinstance(dv, DStackedAff):
+        return dv.blocks, dv.vec, dv.sign
+    if isinstance(dv, DVec):
+        return [], dv, 1
+    return None
+
+
+def _stacked_form(da, db, sign):
+    """(blocks, vec, vsign) of da (+|-) db as a stacked residual — two or more dense blocks over pairwise disjoint Variable vectors, at
+    most one number vector — or None"""
+    pa, pb = _stack_parts(da), _stack_parts(db)
+    if pa is None or pb is None:
+        return None
+    s = 1 if sign > 0 else -1
+    blocks = pa[0] + [(m, x, s * k) for m, x, k in pb[0]]
+    if len(blocks) < 2 or (pa[1] is not None and pb[1] is not None):
+        return None
+    if any(m.rows != blocks[0][0].rows for m, _, _ in blocks):
+        return None
+    allvars = np.concatenate([x.vars for _, x, _ in blocks])
+    if len(np.unique(allvars)) != len(allvars):                 # a variable in two blocks (or twice in one): not a stacking
+        return None
+    if pa[1] is not None:
+        return blocks, pa[1], pa[2]
+    if pb[1] is not None:
+        return blocks, pb[1], s * pb[2]
+    return blocks, None, 0
 
 
 # ---- dot(x, y) ------------------------------------------------------------------------------------------------
@@ -619,6 +670,10 @@ def _rule_dot(model, ctx, x, y):                                                
         node = DeviceNode(model, "vecdot!", ins, out, emit, gram_candidate=gram, prepare=prepare)
         if gram is not None:
             return _with_lsq(node, [LsqTerm("block", r=gram)])
+        if dx is dy and isinstance(dx, DStackedAff):
+            # a Gram candidate once the model asks for its stacked matrix (canonical mode beyond the small plan: Model.initialize)
+            node.stacked_gram = dx
+            return _with_lsq(node, [LsqTerm("block", r=dx)])
         if isinstance(dx, DVarsAff) and isinstance(dy, DVarsAff) and np.array_equal(dx.xvars.vars, dy.xvars.vars) and dx.sign == dy.sign and \
                 dx.vec is not None and dy.vec is not None and dx.vec.buf == dy.vec.buf:
             return _with_lsq(node, [LsqTerm("diag", xvars=dx.xvars, vec=dx.vec, sign=dx.sign)])          # dot(x (+|-) v, x (+|-) v)

@@ -349,10 +349,20 @@ class Model:
             ident = np.arange(1, self.nvars + 1, dtype=np.int64)     # IdentityVarMap until mapindices! (src/moi_interop.jl:32-33)
             ctx.upload(self._varmap_buf, self.model_var_to_optimizer if early else ident)
             if self.quadratic_mode == "canonical":
+                # dot(r, r) of a residual over several Variable vectors (a stacked residual, lazyexpression._stacked_form): the Gram candidate
+                # of its stacked matrix over the union z — beyond the small plan only
+                if not self._small:
+                    for r in records:
+                        st = getattr(r.expr, "stacked_gram", None)
+                        if r.kind == "quad" and st is not None and r.expr.gram_candidate is None:
+                            r.expr.gram_candidate = st.require_stack()
                 # a weighted sum of least-squares blocks over one x (the objective's lsq_sum): combined from the blocks' Gram nodes
                 # (moi.py, mode "canonical-sum") — the MOI boundary of a model beyond the small plan only
                 if not self._small and self.handoff == "moi" and self.objective in records:
                     self.objective.lsq_terms = moi.lsq_sum_terms(self.objective.expr)
+                    for t in self.objective.lsq_terms or ():
+                        if t.kind == "block" and hasattr(t.r, "require_stack"):
+                            t.r.require_stack()
                 # any other quadratic objective: generic device canonicalize! (sorted, duplicates combined) before the MOI copy
                 for r in records:
                     gram = getattr(r.expr, "gram_candidate", None)

@@ -415,6 +415,16 @@ class _Record:
                 d["vec"] = t.value.buf
             desc.append(d)
         arr = _lib.lsq_terms(desc)
+        # diagonal / linear terms over part of x: their positions in x (pmt_quad_gram_sum_sub_f64); over all of x: the plain combine
+        x = g1.xvars.vars
+        lists = [np.searchsorted(x, t.xvars.vars).astype(np.int64) if t.kind in ("diag", "linear") and not np.array_equal(t.xvars.vars, x) else None
+                 for t in terms]
+        sub = any(p is not None for p in lists)
+        if sub:
+            self._sub_lists = lists                                      # (the entry reads them when the call is recorded)
+            ptrs = (C.c_void_p * len(lists))(*[p.ctypes.data if p is not None else None for p in lists])
+            counts = np.array([len(p) if p is not None else 0 for p in lists], dtype=np.int64)
+            self._sub_args = (ptrs, counts)
 
         def gram_args(g):
             vec = g.vec.buf if g.vec is not None else None
@@ -424,7 +434,11 @@ class _Record:
             c.call("pmt_quad_gram_f64", *gram_args(g1), 1, P(varmap_buf), P(dq), P(dl), P(dc), P(ws[0]))
             for g, w, (dv, dlk, dck) in zip(blocks[1:], ws[1:], parts):
                 c.call("pmt_quad_gram_csc_f64", *gram_args(g), P(varmap_buf), 1.0, P(dv), None, P(dlk), P(dck), P(w))
-            c.call("pmt_quad_gram_sum_f64", n, C.addressof(arr), len(desc), P(dq), P(dl), P(dc))
+            if sub:
+                c.call("pmt_quad_gram_sum_sub_f64", n, C.addressof(arr), len(desc), C.cast(ptrs, C.c_void_p), counts.ctypes.data_as(C.c_void_p),
+                       P(dq), P(dl), P(dc))
+            else:
+                c.call("pmt_quad_gram_sum_f64", n, C.addressof(arr), len(desc), P(dq), P(dl), P(dc))
         return emit
 
     def record_fetch(self, ctx):
@@ -488,7 +502,9 @@ class _Record:
 
 def lsq_sum_terms(expr):
     """The LsqTerm list of an objective the canonical-sum path takes (Model.initialize checks the model-level conditions), or None:
-    1 .. 8 least-squares blocks, at most PMT_LSQ_MAX_TERMS terms, every block / diagonal / linear term over the same strictly increasing x."""
+    1 .. 8 least-squares blocks, at most PMT_LSQ_MAX_TERMS terms, every block over the same strictly increasing x (a stacked block over its
+    sorted union z), every diagonal / linear term over x or a strictly increasing part of it (pmt_quad_gram_sum_sub_f64, whose launch holds
+    at most PMT_LSQ_MAX_RUNS runs of positions)."""
     from . import _lib
     terms = getattr(expr, "lsq_sum", None) if isinstance(expr, DeviceNode) else None
     if not terms or len(terms) > _lib.PMT_LSQ_MAX_TERMS or getattr(expr, "gram_candidate", None) is not None:
@@ -499,10 +515,19 @@ def lsq_sum_terms(expr):
     x = blocks[0].r.xvars
     if not x.strictly_increasing():
         return None
+    runs = 0
     for t in terms:
-        xv = t.r.xvars if t.kind == "block" else t.xvars
-        if xv is not None and not np.array_equal(xv.vars, x.vars):
-            return None
+        if t.kind == "block":
+            if not np.array_equal(t.r.xvars.vars, x.vars):
+                return None
+        elif t.xvars is not None and not np.array_equal(t.xvars.vars, x.vars):
+            v = t.xvars.vars
+            pos = np.searchsorted(x.vars, v)
+            if not (len(v) and np.all(np.diff(v) > 0) and np.all(pos < len(x.vars)) and np.array_equal(x.vars[np.minimum(pos, len(x.vars) - 1)], v)):
+                return None
+            runs += _lib.column_runs(pos)
+    if runs > _lib.PMT_LSQ_MAX_RUNS:
+        return None
     return terms
 
 
