@@ -183,16 +183,18 @@ int pmt_quad_expand_f64(int64_t rows,
  *   out_const          = sum_i c_i^2 in a FIXED order that (rows, cols) alone determine (pmt_quad_gram_constant_order below): the
  *                        reference's left-to-right sum (src/functions.jl:574, bit for bit), 2048 interleaved chains, or the fused
  *                        forms' per-workgroup order — every one within (rows / 2048 + 2048) * eps / 2 of the exact sum.
- * Shapes of up to 2048 columns take the fused forms of csrc/gram_tall.hip whatever the row count (the triangle of every diagonal
- * 128-column tile, out_lin and out_const from ONE pass over A; the strictly upper tiles from one stream-K launch); tiny shapes recorded
- * into a plan are nodes of its one-launch interpreter (csrc/small.hip); 2049 .. 4096 columns below 2^29 elements (config 2) the one-launch
- * form of csrc/gram_mid.hip (round 6c; the staged `_deliver_` entry points keep the stream-K kernel there, with out_lin within 1e-13 of the
- * plain call's and out_const in the same order); wider or larger shapes the stream-K node with the two reductions on a side stream.
+ * The node takes one of five forms, which (rows, cols) and the kind of call fix (csrc/gram.hip: gram_form): tiny shapes of a plain call
+ * are nodes of the small-plan interpreter (csrc/small.hip); wide shapes of 129 .. 2048 columns by measured element counts, and 2049 .. 4096
+ * columns below 2^29 elements (config 2) unless delivered, the one-launch form of csrc/gram_mid.hip; the rest of up to 2048 columns the
+ * fused form of csrc/gram_tall.hip (the triangle of every diagonal 128-column tile, out_lin and out_const from ONE pass over A; the
+ * strictly upper tiles from one stream-K launch); every other shape the stream-K node with the two reductions on a side stream, staged
+ * for the `_deliver_` entry points (there, at 2049 .. 4096 columns, out_lin within 1e-13 of the plain call's and out_const in its order).
  * A is read as lda x cols doubles: a kernel may read (and ignore) the padding rows rows .. lda - 1 of a column, the last one included.
  * Requires xvar strictly increasing (distinct variables in sorted order — what Variable(model) yields);
  * moi == 0 keeps native indices (no varmap) but the same coefficients as the MOI form are NOT produced:
  *   native canonical form has diagonal coefficient (A'A)[j,j] and off-diagonal 2*(A'A)[j,k].
- * f64 MFMA contraction; `workspace` (device, pmt_quad_gram_workspace_bytes) holds split-K partial tiles and the chunk / chain sums. */
+ * f64 MFMA contraction; `workspace` (device, pmt_quad_gram_workspace_bytes) holds split-K partial tiles and the chunk / chain sums.  It is
+ * required: NULL is an ArgumentError (PMT_INVALID_ARGUMENT) wherever the fused or the one-launch form is taken, before anything runs. */
 size_t pmt_quad_gram_workspace_bytes(int64_t rows, int64_t cols);
 /* The summation order of the node's constant c'c for an r x n problem — fixed by (rows, cols) alone, reported so that a caller (and the
  * parity tests) can restate it:

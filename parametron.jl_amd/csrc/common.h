@@ -34,8 +34,6 @@ int fail(int code, const std::string &msg);
 // appended to that plan's tape (plan.cpp).
 using Launch = std::function<int(hipStream_t)>;
 int dispatch(void *stream, Launch launch);
-// at replay time: run `f` on `s` behind the work a plan's replay has deferred to its end on `s` (gram.hip), or now
-int gram_after_deferred(hipStream_t s, std::function<int()> f);
 
 // Small plans (small.hip): the reference walks a tiny model's DAG in nanoseconds per hop (src/lazyexpression.jl:50-61); on the device every
 // hop is a kernel launch of ~5 us.  An entry point whose work can also be described by a SmallNode records the description beside its

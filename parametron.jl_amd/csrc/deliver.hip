@@ -26,7 +26,7 @@ struct CourierArgs {
     double *dst;                          // device address of the page-locked host array
     long long *ready;                     // per band group: 1 = in the making, 0 = complete (cleared by the one-thread kernel behind the group's stage)
     unsigned *done;                       // workgroups that have finished; the last one re-arms the flags for the next launch
-    int *error;                           // set to 1 on timeout (page-locked host word, gram.hip SideStream::err_host)
+    int *error;                           // set to 1 on timeout (page-locked host word, streams.h SideStream::err_host)
     int ngroups;
     long long gbeg[MAXGROUPS], gend[MAXGROUPS];      // the groups' ranges of the array (doubles)
 };

@@ -38,7 +38,7 @@ struct FetchState {
     dma::Signal dep, done;
     bool tried = false, created = false, pending = false;
     int pinned = -1;                       // host_dst is page-locked and device-mapped (the engine must not be given pageable memory); -1: not looked up yet
-    ~FetchState();
+    ~FetchState() { if (eng && created) { dma::signal_destroy(eng, dep); dma::signal_destroy(eng, done); } }
 };
 
 }  // namespace pmt

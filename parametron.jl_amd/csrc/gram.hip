@@ -8,19 +8,13 @@
 // QuickSort order; here the contraction index runs in row order inside v_mfma_f64_4x4x4_4b_f64 — coefficients
 // agree to rounding (tests: <= 1e-12 relative), indices exactly.
 //
-// The contraction itself is the persistent stream-K kernel of gram_sk.hip; this file holds the node: validation, the two small
-// reductions of the node (q = 2 A'c, c'c) on a side stream, and the C-ABI entry points.
+// This file holds the node: validation, the choice of its form (gram_form: the contraction itself is gram_tall.hip's, gram_mid.hip's or
+// gram_sk.hip's), the stream-K form's two small reductions (q = 2 A'c, c'c) on a side stream, the host delivery, the C-ABI entry points.
 #include <algorithm>
-#include <cstring>
-#include <mutex>
-#include <unordered_map>
-
-#include <functional>
 #include <memory>
 #include <vector>
 
-#include "dma.h"
-#include "gram_common.h"
+#include "streams.h"
 
 #ifndef PMT_GRAM_ABL_NO_LINEAR
 #define PMT_GRAM_ABL_NO_LINEAR 0   // ablation (wrong q): the stream-K form without its affine part on the side stream — what folding q into the contraction could gain at most
@@ -28,36 +22,6 @@
 
 namespace pmt {
 
-int check_strictly_increasing(const int64_t *xvar_dev, int64_t n, void *stream);
-void mark_no_graph(void *stream);
-int launch_blocked_dot(const double *a, int sign_a, const double *b, int sign_b, int64_t n, double *scratch, double *out, hipStream_t s, int chained);
-int gram_tall_groups(int64_t rows, int64_t cols);
-int gram_tall_stage_rows(int64_t rows, int64_t cols);
-int gram_tall_run_lanes(int64_t rows, int64_t cols);
-size_t blocked_dot_scratch_doubles();
-size_t gram_sk_workspace_bytes(int64_t rows, int64_t cols);
-int launch_courier(const double *src, double *dst_dev, long long *ready, unsigned *done, int *error, int ngroups, const int64_t *gbeg, const int64_t *gend, hipStream_t s);
-int launch_to_host(const void *src, void *dst_dev, size_t bytes, hipStream_t s);
-int launch_to_host_2d(const void *src, size_t src_pitch, void *dst_dev, size_t dst_pitch, size_t width_bytes, size_t height, hipStream_t s);
-void *host_device_pointer(void *host);
-int launch_gram_sk(const double *A, int64_t lda, int64_t rows, int64_t cols, const int64_t *xvar, const int64_t *varmap, int moi,
-                   pmt_quadratic_term *out_quad, double *out_csc, double alpha, void *workspace, int order_w, int64_t seq_begin, int64_t seq_count,
-                   unsigned *pair_flags, unsigned epoch, int *error_word, hipStream_t s, int strict = 0);
-bool gram_tall_applies(int64_t rows, int64_t cols);
-bool gram_tiny(int64_t rows, int64_t cols);
-int launch_small_one(const SmallNode &nd, hipStream_t s);
-bool gram_tall_diag_applies(int64_t rows, int64_t cols);
-size_t gram_tall_workspace_bytes(int64_t rows, int64_t cols);
-int launch_gram_tall(const double *A, int64_t lda, int64_t rows, int64_t cols, const int64_t *xvar, const double *b, int sign, int moi,
-                     const int64_t *varmap, pmt_quadratic_term *out_quad, double *out_csc, double alpha, pmt_linear_term *out_lin,
-                     double *out_const, void *workspace, hipStream_t s);
-size_t gram_mid_workspace_bytes(int64_t rows, int64_t cols);
-int gram_mid_counters(int64_t cols);
-int launch_gram_mid(const double *A, int64_t lda, int64_t rows, int64_t cols, const int64_t *xvar, const double *b, int sign, int moi,
-                    const int64_t *varmap, pmt_quadratic_term *out_quad, double *out_csc, double alpha, pmt_linear_term *out_lin,
-                    double *out_const, void *workspace, unsigned *counters, hipStream_t s);
-int launch_gram_mid_constant(const double *b, int sign, int64_t rows, double *out_const, hipStream_t s);
-constexpr int GT = 128;          // output tile edge of the contraction (gram_sk.hip)
 constexpr size_t PAIR_FLAG_BYTES = 4096;      // 4 bytes per tile of a stage (at most 512 workgroups / 2 tiles)
 // a CSC delivery computes the tiles column band by column band (super-columns of ONE tile column: a band's completion is never held back by
 // its neighbour's, so the stages complete nearly equal byte counts — 1.73 vs 1.77 ms per solve with super-columns of two at n = 4096,
@@ -131,7 +95,7 @@ constexpr int64_t LIN_WAVES = 8192;          // waves that fill the chip (256 CU
 static bool constant_chained(int64_t rows, int64_t cols) {
     if (rows > 8192) return true;
     if (rows < 2048) return false;
-    const double nt = (double)cdiv(std::max<int64_t>(cols, 1), GT);
+    const double nt = (double)cdiv(std::max<int64_t>(cols, 1), ST);
     const double contraction_ms = (0.096 + 0.276 * (double)rows / 1024.0) * (nt * (nt + 1) / 2) / 528.0;
     return 0.07e-3 * (double)rows > 0.5 * contraction_ms;
 }
@@ -158,13 +122,13 @@ static bool constant_chained(int64_t rows, int64_t cols) {
 // 4616 -> 4405, 32768 x 3072 5338 -> 4863, 131072 x 2560 17877 -> 15256, 20000 x 3500 4878 -> 3859; 65536 x 4096 18287 -> 18444 is a tie.  A
 // STAGED host delivery of such a shape (config 2's host_csc hand-off: column bands leave while the contraction runs) keeps the stream-K
 // kernel — run_quad_gram — with the constant in this form's order, so that pmt_quad_gram_constant_order holds for every call form.
-bool gram_mid_big(int64_t rows, int64_t cols) {
+static bool gram_mid_big(int64_t rows, int64_t cols) {
 #ifdef PMT_NO_MID
     return false;
 #endif
     return cols > 16 * 128 && cols <= PMT_MID_BIGCOLS && rows >= 1 && rows * cols < PMT_MID_BIGEL;
 }
-bool gram_mid_applies(int64_t rows, int64_t cols) {
+static bool gram_mid_applies(int64_t rows, int64_t cols) {
 #ifdef PMT_NO_MID
     return false;
 #endif
@@ -192,371 +156,56 @@ static int linear_splits(int64_t rows, int64_t cols) {
     return (int)std::max<int64_t>(1, std::min(cdiv(LIN_WAVES, cols), rows / LIN_CHUNK_MIN));
 }
 
-}  // namespace pmt
+// The form of the node, decided here and nowhere else (the measured thresholds are at the predicates):
+//   Tiny           a plain call (no CSC values, no delivery) of a tiny shape (gram_tiny): a node of the small-plan interpreter (small.hip)
+//   Mid            2049 .. 4096 columns unless delivered (gram_mid_big), the wide shapes of gram_mid_applies: one launch (gram_mid.hip)
+//   Fused          the rest of up to 2048 columns: gram_tall.hip's diagonal tiles, q and c'c in one pass, then the strict stream-K launch
+//   StreamKStaged  a delivered call of any other shape: the stream-K contraction in stages, its column bands shipped while it runs
+//   StreamK        everything else, cols == 0 included: the stream-K contraction (gram_sk.hip), q and c'c on a side stream
+enum class GramForm { Tiny, Fused, Mid, StreamK, StreamKStaged };
+static GramForm gram_form(int64_t rows, int64_t cols, bool csc, bool deliver) {
+    if (!deliver && !csc && gram_tiny(rows, cols)) return GramForm::Tiny;
+    const bool big = gram_mid_big(rows, cols);
+    if ((big && !deliver) || (!big && gram_mid_applies(rows, cols))) return GramForm::Mid;
+    if (gram_tall_applies(rows, cols) || gram_tall_diag_applies(rows, cols)) return GramForm::Fused;
+    return deliver && cols > 0 ? GramForm::StreamKStaged : GramForm::StreamK;         // (no predicate holds for cols <= 0)
+}
 
-namespace pmt {
-
-// One non-blocking side stream + fork/join events PER CALLING STREAM (= per plan: a plan is one stream), created on first use on the
-// calling stream's device.  Two plans driven from two host threads therefore never share an event (different plans are
-// independent); calls on ONE stream must be serialised by the caller, as for any HIP stream.
-// `counters` (library-owned device memory, zeroed once here, re-armed by the courier kernel): the courier's per-group flags of a host
-// delivery (MAXGROUPS x i64) and its own completion count / error flag — calls on one stream are serialised, so one set per
-// calling stream is enough.
-// `fetch` is the calling stream's DEVICE-TO-HOST stream (created on first use, highest priority so that it has a hardware queue of its
-// own class): recorded fetches (pmt_plan_record_fetch) and the band-wise delivery of pmt_quad_gram_csc_deliver_f64 travel on it while
-// the kernels go on; `fetch_done` is recorded behind the last copy enqueued so far.
-struct SideStream {
-    hipStream_t stream = nullptr; hipEvent_t fork = nullptr, join = nullptr, join2 = nullptr; int device = -1;
-    void *counters = nullptr;
-    // error word of the kernels that wait on other workgroups with a bound (the courier, the pair fold of gram_sk.hip): page-locked host
-    // memory the kernels store to (system scope) and the host reads without a copy in fetch_synchronize.  0 = fine, ERR_* otherwise
-    int *err_host = nullptr, *err_dev = nullptr;
-    hipStream_t fetch = nullptr; hipEvent_t fetch_done = nullptr; bool fetch_pending = false;
-    std::vector<std::pair<dma::Engine *, dma::Signal>> dma_pending;     // completion signals of copy-engine transfers in flight
-    std::vector<std::shared_ptr<void>> keepalive;                        // ... and the owners of their signals (an immediate call's go with the call)
-    bool in_replay = false;                                              // a plan's tape is being replayed: P's transfers are submitted at its end
-    std::vector<std::function<int()>> deferred;
-};
-constexpr int ERR_COURIER = 1, ERR_PAIR_FOLD = 2;
-// layout of `counters`: [MAXGROUPS x u64 unused][MAXGROUPS x i64 courier flags (armed = 1)][u32 courier done][u32 unused]
-constexpr size_t PROGRESS_OFFSET = 0;
-constexpr size_t FLAGS_OFFSET = PROGRESS_OFFSET + MAXGROUPS * sizeof(unsigned long long);
-constexpr size_t DONE_OFFSET = FLAGS_OFFSET + MAXGROUPS * sizeof(long long);
-constexpr size_t MID_OFFSET = DONE_OFFSET + 2 * sizeof(unsigned);                  // per-tile arrival counts of the one-launch mid-size node (gram_mid.hip)
-constexpr size_t MID_COUNTER_BYTES = 135168;         // 16 words per tile, 2080 tiles at 4096 columns
-constexpr size_t COUNTER_BYTES = MID_OFFSET + MID_COUNTER_BYTES;
-static std::mutex g_side_mu;
-static std::unordered_map<hipStream_t, SideStream> g_side;
-static int wait_dma_pending(SideStream *ss);
-static SideStream *side_stream(hipStream_t s) {
-#ifdef PMT_TUNING
-    static const bool enabled = [] { const char *e = getenv("PMT_GRAM_SIDE_STREAM"); return !(e && e[0] == '0'); }();
-    if (!enabled) return nullptr;
-#endif
-    int dev = 0;
-    if (hipStreamGetDevice(s, &dev) != hipSuccess) {
-        (void)hipGetLastError();
-        if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+// the summation order of c'c a form gives (include/parametron_hip.h: pmt_quad_gram_constant_order; a tiny node's is row order, order 0)
+struct ConstantOrder { int order, groups, stage_rows; };
+static ConstantOrder constant_order(GramForm form, int64_t rows, int64_t cols) {
+    if (form == GramForm::Fused) {
+        const int lanes = gram_tall_run_lanes(rows, cols);
+        return {lanes == 4 ? 4 : lanes == 16 ? 3 : 2, gram_tall_groups(rows, cols), gram_tall_stage_rows(rows, cols)};
     }
-    std::lock_guard<std::mutex> lock(g_side_mu);
-    SideStream &ss = g_side[s];
-    if (ss.stream && ss.device == dev) return &ss;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    if (prev != dev && hipSetDevice(dev) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    // LOWEST priority: (1) HIP multiplexes streams onto a few hardware queues per priority class, so a side stream of its own class
-    // never shares a queue with the (normal-priority) stream it serves — sharing one makes the contraction queue up behind its own side
-    // kernels (config 2 under torch.distributed, whose RCCL streams take queues too: 1.35 instead of 1.24 ms per step); (2) when both
-    // have packets ready, the contraction's workgroups are placed first.
-    int prio_least = 0, prio_greatest = 0;
-    (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-    bool ok = hipStreamCreateWithPriority(&ss.stream, hipStreamNonBlocking, prio_least) == hipSuccess &&
-              hipEventCreateWithFlags(&ss.fork, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&ss.join, hipEventDisableTiming) == hipSuccess &&
-              hipEventCreateWithFlags(&ss.join2, hipEventDisableTiming) == hipSuccess &&
-              hipMalloc(&ss.counters, COUNTER_BYTES) == hipSuccess &&
-              hipHostMalloc(reinterpret_cast<void **>(&ss.err_host), 64, hipHostMallocDefault) == hipSuccess &&
-              hipMemsetAsync(ss.counters, 0, COUNTER_BYTES, s) == hipSuccess;      // on the calling stream: ordered before its first kernel
-    if (ok) {
-        memset(ss.err_host, 0, 64);
-        ss.err_dev = static_cast<int *>(host_device_pointer(ss.err_host));
-        ok = ss.err_dev != nullptr;
-    }
-    if (ok) {
-        static const long long armed[MAXGROUPS] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
-        ok = hipMemcpyAsync(static_cast<char *>(ss.counters) + FLAGS_OFFSET, armed, sizeof armed, hipMemcpyHostToDevice, s) == hipSuccess;
-    }
-    if (prev != dev) (void)hipSetDevice(prev);
-    if (!ok) {
-        (void)hipGetLastError();
-        if (ss.err_host) (void)hipHostFree(ss.err_host);
-        if (ss.counters) (void)hipFree(ss.counters);
-        g_side.erase(s);
-        return nullptr;
-    }
-    ss.device = dev;
-    return &ss;
-}
-
-// the side stream of calling stream `s` for other users (the plan's side lane, plan.hip): work queued here lines up BEHIND the Gram
-// node's two small reductions, i.e. it is dispatched once the contraction's workgroups are placed and runs as they drain
-// a plan that goes away takes the side stream of its stream with it (pmt_plan_destroy): HIP multiplexes streams onto a handful of hardware
-// queues, and a leaked side stream can end up sharing the queue of a later plan's stream — its contraction then queues BEHIND its own side
-// kernels instead of running beside them (measured: config 3 1.27 -> 1.45 ms when run after another plan in the same process)
-// Plans that share one external stream share its side stream: it is reference-counted by plan (pmt_plan_create retains, pmt_plan_destroy
-// releases) and goes away with the LAST of them, not with the first.
-static std::unordered_map<hipStream_t, int> g_side_refs;
-void retain_side_stream(hipStream_t s) {
-    std::lock_guard<std::mutex> lock(g_side_mu);
-    ++g_side_refs[s];
-}
-void release_side_stream(hipStream_t s) {
-    std::lock_guard<std::mutex> lock(g_side_mu);
-    auto rc = g_side_refs.find(s);
-    if (rc != g_side_refs.end()) {
-        if (--rc->second > 0) return;
-        g_side_refs.erase(rc);
-    }
-    auto it = g_side.find(s);
-    if (it == g_side.end()) return;
-    if (it->second.stream) {
-        (void)hipStreamSynchronize(it->second.stream);
-        (void)hipStreamDestroy(it->second.stream);
-    }
-    if (it->second.fork) (void)hipEventDestroy(it->second.fork);
-    if (it->second.join) (void)hipEventDestroy(it->second.join);
-    if (it->second.join2) (void)hipEventDestroy(it->second.join2);
-    if (it->second.fetch) {
-        (void)hipStreamSynchronize(it->second.fetch);
-        (void)hipStreamDestroy(it->second.fetch);
-    }
-    if (it->second.fetch_done) (void)hipEventDestroy(it->second.fetch_done);
-    (void)wait_dma_pending(&it->second);
-    if (it->second.counters) (void)hipFree(it->second.counters);
-    if (it->second.err_host) (void)hipHostFree(it->second.err_host);
-    g_side.erase(it);
-}
-
-// ---- the calling stream's device-to-host stream -----------------------------------------------------------------------------------
-static int ensure_fetch_stream(SideStream *ss) {
-    if (ss->fetch) return PMT_OK;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    if (prev != ss->device) PMT_HIP_CHECK(hipSetDevice(ss->device));
-    int prio_least = 0, prio_greatest = 0;
-    (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-    hipError_t e = hipStreamCreateWithPriority(&ss->fetch, hipStreamNonBlocking, prio_greatest);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&ss->fetch_done, hipEventDisableTiming);
-    if (prev != ss->device) (void)hipSetDevice(prev);
-    if (e != hipSuccess) { (void)hipGetLastError(); return fail(PMT_HIP_ERROR, std::string("fetch stream: ") + hipGetErrorString(e)); }
-    return PMT_OK;
-}
-
-FetchState::~FetchState() {
-    if (eng && created) { dma::signal_destroy(eng, dep); dma::signal_destroy(eng, done); }
-}
-
-// D2H copy ordered behind everything enqueued on `after` (the plan's stream or its side stream) so far.  Preferred: the copy engine, started
-// by a signal that a one-thread kernel on `after` sets (hsadma.hip) — nothing of it runs on a CU.  Otherwise a kernel copy / the runtime's
-// copy on the fetch stream of `s`.  r.height > 0: a PITCHED copy of r.height rows of `bytes` bytes each (a matrix block whose device copy
-// is padded, or that lands in a column range of a wider host matrix); the engine does those natively (hsa_amd_memory_async_copy_rect).
-int fetch_async(hipStream_t s, hipStream_t after, hipEvent_t order_event, void *host_dst, const void *device_src, size_t bytes, FetchState *st, FetchRect r) {
-    SideStream *ss = side_stream(s);
-    if (!ss) return fail(PMT_STATE_ERROR, "fetch_async: no auxiliary streams for this stream");
-    // A fetch behind the plan's OWN stream inside a replay (its producer finishes with the objective's kernels, e.g. the constant, whose
-    // serial chain is itself queued at the end of the replay) is issued at the end of the replay, behind that chain's join and behind the
-    // band groups of a delivery (the copy engine's queue is first in, first out).
-    if (ss->in_replay && after == s) {
-        ss->deferred.push_back([=]() -> int { return fetch_async(s, after, order_event, host_dst, device_src, bytes, st, r); });
-        return PMT_OK;
-    }
-    const int mode = dma::delivery_mode();
-    // whichever way this entry's previous copy went, it has read the device buffer (and left the host one) before the next one is queued
-    if (st && st->pending) { if (int rc = dma::wait(st->eng, st->done, 10.0)) return rc; st->pending = false; }
-    // the engine is handed physical pages: only page-locked, device-mapped destinations qualify (a pageable numpy / Julia array takes the
-    // runtime's copy below, which stages it)
-    if (st && st->pinned < 0) st->pinned = host_device_pointer(host_dst) ? 1 : 0;
-    if (mode != 2 && st && st->pinned == 1 && !st->created && !st->tried) {
-        st->tried = true;
-        st->eng = dma::get(ss->device);
-        if (st->eng) {
-            if (dma::signal_create(st->eng, 1, &st->dep) == PMT_OK && dma::signal_create(st->eng, 0, &st->done) == PMT_OK) st->created = true;
-            else st->eng = nullptr;
-        }
-    }
-    const bool engine = mode != 2 && st && st->created;
-    if (mode == 1 && !engine)
-        return fail(PMT_STATE_ERROR, "host delivery: the copy engine was demanded (pmt_set_host_delivery(1)) but is not available for this transfer "
-                                     "(no HSA agent match, or a pageable destination)");
-    if (engine) {
-        dma::signal_set(st->eng, st->dep, 1);
-        dma::signal_set(st->eng, st->done, 1);
-        if (int rc = dma::launch_signal_store(st->dep, after)) return rc;
-        st->pending = true;
-        ss->dma_pending.emplace_back(st->eng, st->done);
-        if (r.height) return dma::copy_rect_to_host(st->eng, host_dst, r.dst_pitch, device_src, r.src_pitch, bytes, r.height, &st->dep, st->done);
-        return dma::copy_to_host(st->eng, host_dst, device_src, bytes, &st->dep, st->done);
-    }
-    if (int rc = ensure_fetch_stream(ss)) return rc;
-    PMT_HIP_CHECK(hipEventRecord(order_event, after));
-    PMT_HIP_CHECK(hipStreamWaitEvent(ss->fetch, order_event, 0));
-    // a <= 16-VGPR copy kernel that is co-resident with the contraction (deliver.hip) when the destination is page-locked, 8-byte words
-    // and below 16 GiB; the runtime's copy otherwise
-    const size_t total = r.height ? r.height * r.dst_pitch : bytes;
-    const bool words = bytes % 8 == 0 && (!r.height || (r.dst_pitch % 8 == 0 && r.src_pitch % 8 == 0));
-    void *dst_dev = (words && total / 8 < (size_t)1 << 31) ? host_device_pointer(host_dst) : nullptr;
-    if (dst_dev && r.height) { if (int rc = launch_to_host_2d(device_src, r.src_pitch, dst_dev, r.dst_pitch, bytes, r.height, ss->fetch)) return rc; }
-    else if (dst_dev) { if (int rc = launch_to_host(device_src, dst_dev, bytes, ss->fetch)) return rc; }
-    else if (r.height) PMT_HIP_CHECK(hipMemcpy2DAsync(host_dst, r.dst_pitch, device_src, r.src_pitch, bytes, r.height, hipMemcpyDeviceToHost, ss->fetch));
-    else PMT_HIP_CHECK(hipMemcpyAsync(host_dst, device_src, bytes, hipMemcpyDeviceToHost, ss->fetch));
-    PMT_HIP_CHECK(hipEventRecord(ss->fetch_done, ss->fetch));
-    ss->fetch_pending = true;
-    return PMT_OK;
-}
-
-#ifdef PMT_TUNING
-static double g_replay_t0 = 0;
-static double host_us() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3; }
-// debugging aid (PMT_DMA_DEBUG=2): poll every pending completion signal and the calling stream, print when each changes
-static void trace_dma_pending(SideStream *ss, hipStream_t s) {
-    std::vector<long> last(ss->dma_pending.size(), -100);
-    bool stream_done = false;
-    const double t0 = host_us();
-    for (;;) {
-        bool all = true;
-        for (size_t i = 0; i < ss->dma_pending.size(); ++i) {
-            const long v = (long)*ss->dma_pending[i].second.value;
-            if (v != last[i]) { fprintf(stderr, "[trace +%.0f us] transfer set %zu: %ld left\n", host_us() - g_replay_t0, i, v); last[i] = v; }
-            if (v > 0) all = false;
-        }
-        if (!stream_done && hipStreamQuery(s) == hipSuccess) { stream_done = true; fprintf(stderr, "[trace +%.0f us] the plan's stream is idle\n", host_us() - g_replay_t0); }
-        if ((all && stream_done) || host_us() - t0 > 1e6) break;
-    }
-}
-#endif
-
-static int wait_dma_pending(SideStream *ss) {
-    int rc = PMT_OK;
-    for (auto &p : ss->dma_pending) { const int r = dma::wait(p.first, p.second, 10.0); if (r && !rc) rc = r; }
-    ss->dma_pending.clear();
-    ss->keepalive.clear();
-    return rc;
-}
-
-// `s` waits until the copies enqueued on its fetch stream so far have read their device buffers (start of the next re-evaluation)
-int fetch_fence(hipStream_t s) {
-    std::unique_lock<std::mutex> lock(g_side_mu);
-    auto it = g_side.find(s);
-    if (it == g_side.end()) return PMT_OK;
-    SideStream *ss = &it->second;
-    lock.unlock();
-    // copy-engine transfers are not stream work: the HOST waits for them (a no-op when the caller has synchronised, as solve! does)
-    if (int rc = wait_dma_pending(ss)) return rc;
-    if (!ss->fetch_pending) return PMT_OK;
-    PMT_HIP_CHECK(hipStreamWaitEvent(s, ss->fetch_done, 0));
-    ss->fetch_pending = false;
-    return PMT_OK;
-}
-
-// a plan's replay brackets its tape with these: transfers that should queue up behind the tape's own are submitted by replay_end
-void replay_begin(hipStream_t s) {
-#ifdef PMT_TUNING
-    g_replay_t0 = host_us();
-#endif
-    std::lock_guard<std::mutex> lock(g_side_mu);
-    auto it = g_side.find(s);
-    if (it != g_side.end()) it->second.in_replay = true;
-}
-int replay_end(hipStream_t s) {
-    std::unique_lock<std::mutex> lock(g_side_mu);
-    auto it = g_side.find(s);
-    if (it == g_side.end()) return PMT_OK;
-    SideStream *ss = &it->second;
-    lock.unlock();
-    ss->in_replay = false;
-    int rc = PMT_OK;
-    for (auto &f : ss->deferred) { const int r = f(); if (r && !rc) rc = r; }
-    ss->deferred.clear();
-    return rc;
-}
-
-// `f` (launches on `s`) behind what a plan's replay has queued at its end for `s` so far — the stream-K node's c'c (const_part above):
-// appended to that queue inside a replay that has one, run now otherwise.  A consumer of a Gram node's constant (gram_sum.hip) goes
-// through this, so that it reads the constant after it has been written.
-int gram_after_deferred(hipStream_t s, std::function<int()> f) {
-    std::unique_lock<std::mutex> lock(g_side_mu);
-    auto it = g_side.find(s);
-    if (it != g_side.end() && it->second.in_replay && !it->second.deferred.empty()) {
-        it->second.deferred.push_back(std::move(f));
-        return PMT_OK;
-    }
-    lock.unlock();
-    return f();
-}
-
-// host: block until every copy enqueued on the fetch stream of `s` has landed
-int fetch_synchronize(hipStream_t s) {
-    std::unique_lock<std::mutex> lock(g_side_mu);
-    auto it = g_side.find(s);
-    if (it == g_side.end()) return PMT_OK;
-    SideStream *ss = &it->second;
-    hipStream_t f = ss->fetch;
-    void *counters = ss->counters;
-    lock.unlock();
-#ifdef PMT_TUNING
-    { const char *e = getenv("PMT_DMA_DEBUG"); if (e && e[0] == '2') trace_dma_pending(ss, s); }
-#endif
-    int rc = wait_dma_pending(ss);
-    if (!rc && f) PMT_HIP_CHECK(hipStreamSynchronize(f));
-    // the kernels' error word (page-locked, written with system-scope stores before the data the transfers above carried)
-    const int err = ss->err_host ? __atomic_exchange_n(ss->err_host, 0, __ATOMIC_ACQ_REL) : 0;
-    if (err == ERR_COURIER) {
-        // the courier left without re-arming: flags back to "in the making", completion count to zero
-        static const long long armed[MAXGROUPS] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
-        PMT_HIP_CHECK(hipMemset(counters, 0, COUNTER_BYTES));
-        PMT_HIP_CHECK(hipMemcpy(static_cast<char *>(counters) + FLAGS_OFFSET, armed, sizeof armed, hipMemcpyHostToDevice));
-        return fail(PMT_HIP_ERROR, "host delivery: the courier saw no progress of the contraction for 2 s and gave up; the host arrays are incomplete");
-    }
-    if (err == ERR_PAIR_FOLD)
-        return fail(PMT_HIP_ERROR, "host delivery: a split tile of the contraction never received its first half (pair fold); the tile was "
-                                   "written as NaN and the delivered quadratic coefficients are invalid");
-    if (err) return fail(PMT_HIP_ERROR, "host delivery: unknown device error " + std::to_string(err));
-    return rc;
-}
-
-hipStream_t side_stream_of(hipStream_t s) {
-    SideStream *ss = side_stream(s);
-    return ss ? ss->stream : nullptr;
-}
-
-}  // namespace pmt
-
-using namespace pmt;
-
-extern "C" int pmt_quad_gram_constant_order(int64_t rows, int64_t cols, int *order, int *groups, int *stage_rows) {
-    PMT_REQUIRE(rows >= 0 && cols >= 0 && order, PMT_INVALID_ARGUMENT, "quad_gram_constant_order: bad argument");
-    if (cols > 0 && gram_mid_applies(rows, cols)) {          // the fix-up launch's last workgroup: 512 strided chains, wave trees, waves in order
-        *order = 5;
-        if (groups) *groups = 1;
-        if (stage_rows) *stage_rows = 512;
-        return PMT_OK;
-    }
-    const bool tall = cols > 0 && (gram_tall_applies(rows, cols) || gram_tall_diag_applies(rows, cols));
-    *order = tall ? (gram_tall_run_lanes(rows, cols) == 4 ? 4 : gram_tall_run_lanes(rows, cols) == 16 ? 3 : 2) : (constant_chained(rows, cols) ? 1 : 0);
-    if (groups) *groups = tall ? gram_tall_groups(rows, cols) : (*order == 1 ? 2048 : 1);
-    if (stage_rows) *stage_rows = tall ? gram_tall_stage_rows(rows, cols) : 0;
-    return PMT_OK;
-}
-
-extern "C" size_t pmt_quad_gram_workspace_bytes(int64_t rows, int64_t cols) {
-    // behind the contraction's partial tiles: chunk sums of q (tall matrices) and the chains of the constant (long vectors); the fused
-    // tall form (gram_tall.hip) keeps its per-chunk partials in the same buffer
-    return std::max(std::max(gram_tall_workspace_bytes(rows, cols), gram_mid_applies(rows, cols) ? gram_mid_workspace_bytes(rows, cols) : (size_t)0),
-                    gram_sk_workspace_bytes(rows, cols) + sizeof(double) * ((size_t)linear_splits(rows, cols) * (size_t)std::max<int64_t>(cols, 0) +
-                                                                            blocked_dot_scratch_doubles()));
+    // the one-launch form's 512 strided chains — also in the staged delivery of a shape that form takes otherwise: every call form agrees
+    if (form == GramForm::Mid || (form == GramForm::StreamKStaged && gram_form(rows, cols, true, false) == GramForm::Mid)) return {5, 1, 512};
+    return constant_chained(rows, cols) ? ConstantOrder{1, 2048, 0} : ConstantOrder{0, 1, 0};
 }
 
 // the signals of one recorded delivery: a dependency signal per band group (a one-thread kernel behind the stage that completes the group
-// stores 0 into its value when the group is in memory) and one completion signal that counts the groups' transfers down
+// stores 0 into its value when the group is in memory) and one completion signal that counts the groups' transfers down; `engine`: this
+// launch's transfers go through the copy engine (else through the courier kernel on the fetch stream)
 struct DeliverSignals {
     dma::Engine *eng = nullptr;
     dma::Signal dep[MAXGROUPS], done;
     int n = 0;
-    bool tried = false, pending = false;
+    bool tried = false, pending = false, engine = false;
     ~DeliverSignals() {
-        if (!eng) return;
-        for (int i = 0; i < n; ++i) dma::signal_destroy(eng, dep[i]);
-        dma::signal_destroy(eng, done);
+        for (int i = 0; eng && i < n; ++i) dma::signal_destroy(eng, dep[i]);
+        if (eng) dma::signal_destroy(eng, done);
     }
 };
 
-// Host delivery of the CSC values (pmt_quad_gram_csc_deliver_f64): the contraction runs as a sequence of STAGES, each a launch over a range
-// of the tile sequence (column-band-major, sk_colseq_unrank) followed by its fix-up; a stage that completes column bands ends with a one-thread
-// kernel that releases the copy engine's transfer of those bands.
+// Host delivery of the CSC values or the terms.  StreamKStaged: the contraction runs in STAGES, each a launch over a range of the tile sequence
+// and its fix-up; a stage that completes bands ends with a one-thread kernel that releases their transfer.  Fused and Mid: ONE transfer of
+// the whole array behind the node's last kernel — staging pays for hundreds of megabytes (config 2), not for the <= 50 MB of these shapes.
 struct DeliverPlan {
-    double *host = nullptr;                 // page-locked destination, same layout as out_csc
+    double *host = nullptr;                 // page-locked destination, same layout as the delivered array
     double *host_dev = nullptr;             // ... and its device-visible address
-    int nstages = 0;
+    const double *src = nullptr;            // the delivered array, as doubles: out_csc, or out_quad (three doubles per term)
+    std::shared_ptr<DeliverSignals> sig;    // lives as long as the recorded call
+    int order_w = 0, nstages = 0;           // the stages' tile order (launch_gram_sk) and count
     int64_t seq_begin[MAXGROUPS], seq_count[MAXGROUPS];
     int group_of[MAXGROUPS];                // index of the band group the stage completes, or -1
     int ngroups = 0;
@@ -571,17 +220,23 @@ struct DeliverPlan {
 // the summation order of a split tile (two half sums added) — within the stated tolerance, deterministic, and the delivered host array is
 // the device array of the same run bit for bit.  `nstages_hint` (the entry point's ngroups) > 0 overrides the number of stages.
 // quad: the delivered array is out_quad (24-byte terms, ROW-major upper triangle): tile order 0 (super-rows of four tile rows, sk_seq_unrank), the
-// groups are row bands and the offsets count doubles (three per term); else out_csc (column bands, super-columns of `order_w`).
-static DeliverPlan deliver_plan(int64_t rows, int64_t cols, int nstages_hint, int order_w, double *host, bool quad) {
+// groups are row bands and the offsets count doubles (three per term); else out_csc (column bands, super-columns of DELIVER_ORDER_W).
+static DeliverPlan deliver_plan(int64_t rows, int64_t cols, bool staged, int nstages_hint, bool quad) {
     DeliverPlan d;
-    d.host = host;
-    const int nt = (int)cdiv(cols, GT);
+#ifdef PMT_TUNING
+    static const int order_w = [] { const char *e = getenv("PMT_DELIVER_ORDER_W"); return e ? atoi(e) : DELIVER_ORDER_W; }();
+#else
+    constexpr int order_w = DELIVER_ORDER_W;
+#endif
+    d.order_w = quad ? 0 : -order_w;
+    const int nt = (int)cdiv(cols, ST);
     const int64_t T = (int64_t)nt * (nt + 1) / 2;
     const int64_t nchunk = std::max<int64_t>(1, cdiv(rows, 256));
     const int64_t G = std::min<int64_t>(T * nchunk, 256);                  // as launch_gram_sk (gram_sk.hip)
     int64_t per = nchunk >= 2 ? std::max<int64_t>(1, G / 2) : G;           // tiles per stage: half a grid's worth (whole tiles if there is nothing to split)
     if (nstages_hint > 0) per = std::max<int64_t>(1, cdiv(T, std::min(nstages_hint, MAXGROUPS)));
     if (cdiv(T, per) > MAXGROUPS) per = cdiv(T, MAXGROUPS);
+    if (!staged) per = T;               // (one stage that completes every band: one group, the whole array)
     // position in the walk after which each band is complete, and the band's range of the delivered array
     std::vector<int64_t> seq_end_of_band((size_t)nt), bandbeg((size_t)nt), bandend((size_t)nt);
     int64_t seq_end = 0;
@@ -593,7 +248,7 @@ static DeliverPlan deliver_plan(int64_t rows, int64_t cols, int nstages_hint, in
             for (int jb = j0; jb < j0 + h; ++jb) seq_end_of_band[(size_t)jb] = seq_end;
         }
         for (int jb = 0; jb < nt; ++jb) {
-            const int64_t J0 = (int64_t)jb * GT, J = std::min<int64_t>(cols, (int64_t)(jb + 1) * GT);
+            const int64_t J0 = (int64_t)jb * ST, J = std::min<int64_t>(cols, (int64_t)(jb + 1) * ST);
             bandbeg[(size_t)jb] = 3 * (J0 * cols - J0 * (J0 - 1) / 2);      // rows 0 .. J-1 of the row-major upper triangle, 3 doubles per term
             bandend[(size_t)jb] = 3 * (J * cols - J * (J - 1) / 2);
         }
@@ -608,7 +263,7 @@ static DeliverPlan deliver_plan(int64_t rows, int64_t cols, int nstages_hint, in
         }
         for (int kb = 0; kb < nt; ++kb) {
             seq_end_of_band[(size_t)kb] = T - start_of_super[(size_t)kb];     // the walk has passed the band's whole super-column
-            const int64_t c0 = (int64_t)kb * GT, cend = std::min<int64_t>(cols, (int64_t)(kb + 1) * GT);
+            const int64_t c0 = (int64_t)kb * ST, cend = std::min<int64_t>(cols, (int64_t)(kb + 1) * ST);
             bandbeg[(size_t)kb] = c0 * (c0 + 1) / 2;
             bandend[(size_t)kb] = cend * (cend + 1) / 2;
         }
@@ -635,235 +290,242 @@ static DeliverPlan deliver_plan(int64_t rows, int64_t cols, int nstages_hint, in
     return d;
 }
 
-// the whole node: contraction on the main stream, q = 2A'c and c'c on a side stream.  out_quad (term structs) and out_csc (solver
-// values, alpha-scaled) are independent optional outputs of the same contraction.  host_csc != null: out_csc is also DELIVERED to that
-// page-locked host buffer, band group by band group, on the stream's fetch stream while the contraction is still running.
-static int gram_node(const double *A, int64_t lda, int64_t rows, int64_t cols, const int64_t *xvar, const double *b, int sign,
-                     int moi, const int64_t *varmap, pmt_quadratic_term *out_quad, double *out_csc, double alpha, pmt_linear_term *out_lin,
-                     double *out_const, void *workspace, double *host_csc, int ngroups, void *stream, pmt_quadratic_term *host_quad = nullptr) {
-    PMT_REQUIRE(rows >= 0 && cols >= 0, PMT_DIMENSION_MISMATCH, "quad_gram: negative dimension");
-    PMT_REQUIRE(lda >= rows, PMT_DIMENSION_MISMATCH, "quad_gram: lda < rows");
-    PMT_REQUIRE(sign >= -1 && sign <= 1, PMT_INVALID_ARGUMENT, "quad_gram: sign must be -1, 0 or +1");
-    PMT_REQUIRE(out_const, PMT_INVALID_ARGUMENT, "quad_gram: null out_const");
-    PMT_REQUIRE(sign == 0 || b || rows == 0, PMT_INVALID_ARGUMENT, "quad_gram: sign != 0 needs b");
-    if (cols > 0) PMT_REQUIRE(xvar && (out_quad || out_csc) && out_lin && (A || rows == 0), PMT_INVALID_ARGUMENT, "quad_gram: null pointer");
-    PMT_REQUIRE(cols < (int64_t)GT * 32000, PMT_DIMENSION_MISMATCH, "quad_gram: too many columns");
-    if (int rc = check_strictly_increasing(xvar, cols, stream)) return rc;
-    DeliverPlan dplan;
-    std::shared_ptr<DeliverSignals> sig = std::make_shared<DeliverSignals>();      // lives as long as the recorded call
-    PMT_REQUIRE(!(host_csc && host_quad), PMT_INVALID_ARGUMENT, "quad_gram: one delivered array per call");
-    // the array a delivery ships, as doubles: out_csc, or out_quad (three doubles per term)
-    double *deliver_host = host_quad ? reinterpret_cast<double *>(host_quad) : host_csc;
-    const double *deliver_src = host_quad ? reinterpret_cast<const double *>(out_quad) : out_csc;
-#ifdef PMT_TUNING
-    static const int deliver_w = [] { const char *e = getenv("PMT_DELIVER_ORDER_W"); return e ? atoi(e) : DELIVER_ORDER_W; }();
-#else
-    constexpr int deliver_w = DELIVER_ORDER_W;
-#endif
-    const int deliver_order = host_quad ? 0 : -deliver_w;
-    // shapes of up to 2048 columns take the fused tall forms (gram_tall.hip) whatever the outputs: one 128-column tile — triangle, q and c'c in
-    // ONE pass over A, no side stream, no separate reductions —, or several — the diagonal tiles, q and c'c in one fused pass, then the strictly
-    // upper tiles in ONE ranged launch of the stream-K kernel (SKArgs::strict: its tile sequence leaves the diagonal out; the partials of both
-    // forms share the workspace in stream order).  A host delivery of such a node is ONE transfer of the whole array behind it: the staged
-    // contraction pays for hundreds of megabytes (config 2), not for the <= 50 MB of these shapes.
-    // (2049 .. 4096 columns: the one-launch form unless a staged delivery is asked for — gram_mid_big)
-    const bool mid_big = cols > 0 && workspace && !deliver_host && gram_mid_big(rows, cols);
-    const bool tall_form = cols > 0 && workspace && (gram_tall_applies(rows, cols) || gram_tall_diag_applies(rows, cols) || mid_big);
-    if (deliver_host && cols > 0) {
-        if (tall_form) {
-            dplan.host = deliver_host;
-            dplan.nstages = 0; dplan.ngroups = 1; dplan.gbeg[0] = 0;
-            dplan.gend[0] = (host_quad ? 3 : 1) * (cols * (cols + 1) / 2);
-        } else dplan = deliver_plan(rows, cols, ngroups, deliver_w, deliver_host, host_quad != nullptr);
-        dplan.host_dev = static_cast<double *>(host_device_pointer(deliver_host));
-        PMT_REQUIRE(dplan.host_dev, PMT_INVALID_ARGUMENT, "quad_gram_csc_deliver: host_P_values must be page-locked host memory (pmt_host_alloc)");
-        mark_no_graph(stream);
+struct GramArgs {          // the operands of one node
+    const double *A; int64_t lda, rows, cols; const int64_t *xvar; const double *b; int sign, moi; const int64_t *varmap;
+    pmt_quadratic_term *out_quad; double *out_csc; double alpha; pmt_linear_term *out_lin; double *out_const; void *workspace;
+};
+
+// before the node's kernels: the previous delivery of this call has read its array, and this launch's transfers are armed
+static int deliver_arm(const DeliverPlan &d, SideStream *side, hipStream_t s) {
+    PMT_REQUIRE(side && side->counters, PMT_STATE_ERROR, "quad_gram_csc_deliver: no auxiliary streams for this stream");
+    DeliverSignals *sig = d.sig.get();
+    // Preferred: one copy-engine transfer per band group, each started by the signal set behind the group's stage (hsadma.hip)
+    const int mode = dma::delivery_mode();
+    // the previous delivery of this entry must have read its array before this contraction overwrites it (whichever way it went)
+    if (sig->pending) { if (int rc = dma::wait(sig->eng, sig->done, 10.0)) return rc; sig->pending = false; }
+    // an immediate (unrecorded) call owns fresh signals: what earlier calls on this stream handed to the engine is awaited here
+    if (!side->in_replay) { if (int rc = wait_dma_pending(side)) return rc; }
+    if (mode != 2 && !sig->tried) {
+        sig->tried = true;
+        dma::Engine *eng = dma::get(side->device);
+        bool ok = eng && dma::signal_create(eng, 0, &sig->done) == PMT_OK;
+        for (int i = 0; ok && i < d.ngroups; ++i) { ok = dma::signal_create(eng, 1, &sig->dep[i]) == PMT_OK; if (ok) sig->n = i + 1; }
+        if (ok) sig->eng = eng;
     }
-    Launch node = [=](hipStream_t s) {
-        // fork: the two small reductions of this node (q = 2 A'c, HBM-bound; c'c, a serial chain) run on a side stream while
-        // the MFMA-bound contraction owns the main stream; join before returning control of `s`.  Legal under stream capture.
-        SideStream *side = side_stream(s);
-        const bool deliver = dplan.host != nullptr;
-        bool use_engine = false;
-        if (deliver) {
-            PMT_REQUIRE(side && side->counters, PMT_STATE_ERROR, "quad_gram_csc_deliver: no auxiliary streams for this stream");
-            // Preferred: one copy-engine transfer per band group, each started by the signal set behind the group's stage (hsadma.hip)
-            const int mode = dma::delivery_mode();
-            // the previous delivery of this entry must have read its array before this contraction overwrites it (whichever way it went)
-            if (sig->pending) { if (int rc = dma::wait(sig->eng, sig->done, 10.0)) return rc; sig->pending = false; }
-            // an immediate (unrecorded) call owns fresh signals: what earlier calls on this stream handed to the engine is awaited here
-            if (!side->in_replay) { if (int rc = wait_dma_pending(side)) return rc; }
-            if (mode != 2 && !sig->tried) {
-                sig->tried = true;
-                dma::Engine *eng = dma::get(side->device);
-                if (eng) {
-                    bool ok = dma::signal_create(eng, 0, &sig->done) == PMT_OK;
-                    for (int i = 0; ok && i < dplan.ngroups; ++i) { ok = dma::signal_create(eng, 1, &sig->dep[i]) == PMT_OK; if (ok) sig->n = i + 1; }
-                    if (ok) sig->eng = eng;
-                }
-            }
-            use_engine = mode != 2 && sig->eng != nullptr;
-            PMT_REQUIRE(mode != 1 || use_engine, PMT_STATE_ERROR, "host delivery: the copy engine was demanded (pmt_set_host_delivery(1)) but is not available");
-            if (use_engine) {
-                // (a previous delivery that went through the courier — the mode was switched in between — is ordered by its event)
-                if (side->fetch_pending) { PMT_HIP_CHECK(hipStreamWaitEvent(s, side->fetch_done, 0)); side->fetch_pending = false; }
-                for (int i = 0; i < dplan.ngroups; ++i) dma::signal_set(sig->eng, sig->dep[i], 1);
-                dma::signal_set(sig->eng, sig->done, dplan.ngroups);
-            } else {
-                if (int rc = ensure_fetch_stream(side)) return rc;
-                if (side->fetch_pending) { PMT_HIP_CHECK(hipStreamWaitEvent(s, side->fetch_done, 0)); side->fetch_pending = false; }
-            }
-        }
-        hipStream_t s2 = s;
-        if (side && !tall_form) {
-            PMT_HIP_CHECK(hipEventRecord(side->fork, s));
-            PMT_HIP_CHECK(hipStreamWaitEvent(side->stream, side->fork, 0));
-            s2 = side->stream;
-        }
-        int rc = PMT_OK;
-        double *scratch = workspace ? reinterpret_cast<double *>(static_cast<char *>(workspace) + gram_sk_workspace_bytes(rows, cols)) : nullptr;
-        const int nsplit = (scratch && b && sign) ? linear_splits(rows, cols) : 1;
-        if (tall_form || PMT_GRAM_ABL_NO_LINEAR) {
-        } else if (cols > 0 && nsplit > 1) {
-            const int64_t chunk = 64 * cdiv(cdiv(rows, nsplit), 64);
-            PMT_LAUNCH(gram_linear_split_kernel, dim3((unsigned)cdiv(cols, 4), (unsigned)nsplit), dim3(256), 0, s2, A, lda, rows, cols, b, sign, chunk, scratch);
-            PMT_LAUNCH(gram_linear_finish_kernel, dim3((unsigned)cdiv(cols, 256)), dim3(256), 0, s2, scratch, nsplit, cols, xvar, moi, varmap, out_lin);
-            rc = check_launch("gram_linear_split_kernel");
-        } else if (cols > 0) {
-            PMT_LAUNCH(gram_linear_kernel, dim3((unsigned)cdiv(cols, 4)), dim3(256), 0, s2, A, lda, rows, cols, xvar, b, sign, moi, varmap, out_lin);
-            rc = check_launch("gram_linear_kernel");
-        }
-        // c'c: a serial chain of `rows` additions on ONE wave (bit for bit the reference's left-to-right sum) — ~50 us alone, ~0.3 ms beside
-        // the contraction.  Inside a plan's replay it is queued at the END of the replay, i.e. behind the tape's side-lane entries on the
-        // side stream (the MOI copies of the constraints, the hand-off gathers and their fetches), which used to wait for it.
-        double *chains = scratch ? scratch + (size_t)linear_splits(rows, cols) * (size_t)cols : nullptr;
-        auto const_part = [=]() -> int {
-            int rc2 = PMT_OK;
-            if (gram_mid_big(rows, cols)) rc2 = launch_gram_mid_constant(b, sign, rows, out_const, s2);      // (a staged delivery: the one-launch form's order)
-            else if (b && sign && rows > 0) rc2 = launch_blocked_dot(b, sign, b, sign, rows, chains, out_const, s2, constant_chained(rows, cols) ? 1 : 0);
-            else if (hipMemsetAsync(out_const, 0, sizeof(double), s2) != hipSuccess) rc2 = fail(PMT_HIP_ERROR, "hipMemsetAsync(out_const)");
-            if (side) {
-                PMT_HIP_CHECK(hipEventRecord(side->join2, side->stream));
-                PMT_HIP_CHECK(hipStreamWaitEvent(s, side->join2, 0));
-            }
-            return rc2;
-        };
-        const bool defer_const = side && side->in_replay && !tall_form;
-        if (!rc && defer_const) side->deferred.push_back(const_part);
-        if (side && !tall_form) PMT_HIP_CHECK(hipEventRecord(side->join, side->stream));          // the affine part: `s` joins it behind the contraction's launch
-        if (!rc && cols > 0) {
-            if (tall_form && (mid_big || (gram_mid_applies(rows, cols) && !gram_mid_big(rows, cols)))) {
-                // WIDE shapes of up to 2048 columns (gram_mid_applies): the whole node — every tile, q and c'c — in ONE launch on 64 x 64 tiles
-                // (gram_mid.hip); the per-tile arrival counts are this calling stream's
-                PMT_REQUIRE(side && side->counters && (size_t)gram_mid_counters(cols) * sizeof(unsigned) <= MID_COUNTER_BYTES, PMT_STATE_ERROR,
-                            "quad_gram: no auxiliary state for this stream");
-                rc = launch_gram_mid(A, lda, rows, cols, xvar, b, sign, moi, varmap, out_quad, out_csc, alpha, out_lin, out_const, workspace,
-                                     reinterpret_cast<unsigned *>(static_cast<char *>(side->counters) + MID_OFFSET), s);
-                if (!rc && side && side->in_replay) {          // side-lane entries behind this node may read its affine part (see below)
-                    PMT_HIP_CHECK(hipEventRecord(side->fork, s));
-                    PMT_HIP_CHECK(hipStreamWaitEvent(side->stream, side->fork, 0));
-                }
-                if (!rc && deliver) {
-                    char *cb = static_cast<char *>(side->counters);
-                    dma::Signal word = use_engine ? sig->dep[0] : dma::Signal{0, reinterpret_cast<int64_t *>(cb + FLAGS_OFFSET)};
-                    rc = dma::launch_signal_store(word, s);
-                }
-            } else
-            if (tall_form) {
-                rc = launch_gram_tall(A, lda, rows, cols, xvar, b, sign, moi, varmap, out_quad, out_csc, alpha, out_lin, out_const, workspace, s);
-                // a plan's side-lane entries recorded behind this node may read its AFFINE part (the hand-off's q gather; plan.hip `replay`): with
-                // the stream-K form they queue behind gram_linear on the side stream — here the side stream is told to wait for the fix-up
-                // that has just written q and the constant (the strictly upper tiles below then run beside those entries)
-                if (!rc && side && side->in_replay) {
-                    PMT_HIP_CHECK(hipEventRecord(side->fork, s));
-                    PMT_HIP_CHECK(hipStreamWaitEvent(side->stream, side->fork, 0));
-                }
-                const int64_t nt = cdiv(cols, GT);
-                if (!rc && nt > 1)
-                    rc = launch_gram_sk(A, lda, rows, cols, xvar, varmap, moi, out_quad, out_csc, alpha, workspace, 0, 0, nt * (nt - 1) / 2, nullptr, 0, nullptr, s, 1);
-                if (!rc && deliver) {                 // the whole array is in memory behind the node's last kernel: release its one transfer
-                    char *cb = static_cast<char *>(side->counters);
-                    dma::Signal word = use_engine ? sig->dep[0] : dma::Signal{0, reinterpret_cast<int64_t *>(cb + FLAGS_OFFSET)};
-                    rc = dma::launch_signal_store(word, s);
-                }
-            } else if (!deliver) {
-                rc = launch_gram_sk(A, lda, rows, cols, xvar, varmap, moi, out_quad, out_csc, alpha, workspace, 0, 0, -1, nullptr, 0, nullptr, s);
-            } else {
-                // stage by stage; behind a stage that completes column bands, one thread stores 0 into the word the transfer of those bands waits
-                // for: the value of its dependency signal (copy engine, hsadma.hip) or the courier's flag (deliver.hip)
-                char *cb = static_cast<char *>(side->counters);
-                // flags of the pair fold (gram_sk.hip): the tail of the partial-tile workspace, beyond the slots a grid of 256 uses; cleared
-                // per delivery, stage st writes / waits for the value st + 1
-                unsigned *pair_flags = workspace ? reinterpret_cast<unsigned *>(static_cast<char *>(workspace) + gram_sk_workspace_bytes(rows, cols) - PAIR_FLAG_BYTES) : nullptr;
-                if (pair_flags) PMT_HIP_CHECK(hipMemsetAsync(pair_flags, 0, PAIR_FLAG_BYTES, s));
-                for (int st = 0; !rc && st < dplan.nstages; ++st) {
-                    rc = launch_gram_sk(A, lda, rows, cols, xvar, varmap, moi, out_quad, out_csc, alpha, workspace, deliver_order, dplan.seq_begin[st],
-                                        dplan.seq_count[st], pair_flags, (unsigned)(st + 1), side->err_dev, s);
-                    const int grp = dplan.group_of[st];
-                    if (!rc && grp >= 0) {
-                        dma::Signal word = use_engine ? sig->dep[grp] : dma::Signal{0, reinterpret_cast<int64_t *>(cb + FLAGS_OFFSET) + grp};
-                        rc = dma::launch_signal_store(word, s);
-                    }
-                }
-            }
-            if (!rc && deliver) {
-                if (use_engine) {
-                    // The engine works through its queue in submission order.  Inside a plan's replay the groups' transfers are therefore
-                    // submitted at the END of the replay, behind the recorded fetches of the tape (q, A's values, bounds: ready within the
-                    // first tenth of the contraction) — submitted here they would hold those back until the last band group has left.
-                    auto submit = [=]() -> int {
-                        for (int i = 0; i < dplan.ngroups; ++i)
-                            if (int rc2 = dma::copy_to_host(sig->eng, dplan.host + dplan.gbeg[i], deliver_src + dplan.gbeg[i],
-                                                            sizeof(double) * (size_t)(dplan.gend[i] - dplan.gbeg[i]), &sig->dep[i], sig->done, 1)) return rc2;
-                        return PMT_OK;
-                    };
-                    sig->pending = true;
-                    side->dma_pending.emplace_back(sig->eng, sig->done);
-                    side->keepalive.push_back(sig);
-                    if (side->in_replay) side->deferred.push_back(submit);
-                    else if (int rc2 = submit()) return rc2;
-                } else {
-                    // fallback, fetch stream: ONE courier launch, queued now that the contraction's workgroups are on their way; it polls the
-                    // band groups' flags and stores each finished group straight into the host array (deliver.hip)
-                    char *cb = static_cast<char *>(side->counters);
-                    rc = launch_courier(deliver_src, dplan.host_dev, reinterpret_cast<long long *>(cb + FLAGS_OFFSET), reinterpret_cast<unsigned *>(cb + DONE_OFFSET),
-                                        side->err_dev, dplan.ngroups, dplan.gbeg, dplan.gend, side->fetch);
-                    if (rc) return rc;
-                    PMT_HIP_CHECK(hipEventRecord(side->fetch_done, side->fetch));
-                    side->fetch_pending = true;
-                }
-            }
-        }
-        if (tall_form) return rc;
-        if (side) PMT_HIP_CHECK(hipStreamWaitEvent(s, side->join, 0));
-        if (!rc && !defer_const) rc = const_part();          // (behind the contraction's launch: its workgroups are placed first)
-        return rc;
+    sig->engine = mode != 2 && sig->eng != nullptr;
+    PMT_REQUIRE(mode != 1 || sig->engine, PMT_STATE_ERROR, "host delivery: the copy engine was demanded (pmt_set_host_delivery(1)) but is not available");
+    // (what went through the fetch stream before — a previous delivery by the courier, a recorded fetch — is ordered by its event)
+    if (side->fetch_pending) { PMT_HIP_CHECK(hipStreamWaitEvent(s, side->fetch_done, 0)); side->fetch_pending = false; }
+    if (!sig->engine) return ensure_fetch_stream(side);
+    for (int i = 0; i < d.ngroups; ++i) dma::signal_set(sig->eng, sig->dep[i], 1);
+    dma::signal_set(sig->eng, sig->done, d.ngroups);
+    return PMT_OK;
+}
+
+// behind the kernel that completes band group `grp`, one thread stores 0 into the word the group's transfer waits for: the value of its
+// dependency signal (copy engine, hsadma.hip) or the courier's flag (deliver.hip)
+static int release_group(const DeliverPlan &d, SideStream *side, int grp, hipStream_t s) {
+    const dma::Signal flag{0, reinterpret_cast<int64_t *>(static_cast<char *>(side->counters) + FLAGS_OFFSET) + grp};
+    return dma::launch_signal_store(d.sig->engine ? d.sig->dep[grp] : flag, s);
+}
+
+// behind the node's kernels: hand the groups' transfers over
+static int deliver_submit(const DeliverPlan &d, SideStream *side) {
+    if (!d.sig->engine) {
+        // fallback, fetch stream: ONE courier launch, queued now that the contraction's workgroups are on their way; it polls the
+        // band groups' flags and stores each finished group straight into the host array (deliver.hip)
+        char *cb = static_cast<char *>(side->counters);
+        if (int rc = launch_courier(d.src, d.host_dev, reinterpret_cast<long long *>(cb + FLAGS_OFFSET), reinterpret_cast<unsigned *>(cb + DONE_OFFSET),
+                                    side->err_dev, d.ngroups, d.gbeg, d.gend, side->fetch)) return rc;
+        PMT_HIP_CHECK(hipEventRecord(side->fetch_done, side->fetch));
+        side->fetch_pending = true;
+        return PMT_OK;
+    }
+    // The engine works through its queue in submission order.  Inside a plan's replay the groups' transfers are therefore submitted at
+    // the END of the replay, behind the recorded fetches of the tape (q, A's values, bounds: ready within the first tenth of the
+    // contraction) — submitted here they would hold those back until the last band group has left.
+    auto submit = [p = d]() -> int {
+        for (int i = 0; i < p.ngroups; ++i)
+            if (int rc = dma::copy_to_host(p.sig->eng, p.host + p.gbeg[i], p.src + p.gbeg[i], sizeof(double) * (size_t)(p.gend[i] - p.gbeg[i]),
+                                           &p.sig->dep[i], p.sig->done, 1)) return rc;
+        return PMT_OK;
     };
-    // tiny shapes (README Example 1 with the canonical objective: 8 x 8): also a small-plan node — row-order sums by the interpreter kernel
-    // instead of four launches and a side-stream fork
-    if (!deliver_host && !out_csc && gram_tiny(rows, cols)) {
+    d.sig->pending = true;
+    side->dma_pending.emplace_back(d.sig->eng, d.sig->done);
+    side->keepalive.push_back(d.sig);
+    if (!side->in_replay) return submit();
+    side->deferred.push_back(submit);
+    return PMT_OK;
+}
+
+// the side stream waits for what `s` has queued so far — also for a plan's side-lane entries behind a fused or one-launch node, which may
+// read its AFFINE part (the hand-off's q gather; plan.hip `replay`) as they would behind the stream-K form's gram_linear
+static int fork_side(SideStream *side, hipStream_t s) {
+    PMT_HIP_CHECK(hipEventRecord(side->fork, s));
+    PMT_HIP_CHECK(hipStreamWaitEvent(side->stream, side->fork, 0));
+    return PMT_OK;
+}
+
+// Fused: the diagonal tiles, q and c'c in ONE pass over A (gram_tall.hip), then the strictly upper tiles in ONE ranged launch of the stream-K
+// kernel (SKArgs::strict; the partials of both share the workspace in stream order) — no side stream, no separate reductions
+static int fused_node(const GramArgs &g, SideStream *side, hipStream_t s) {
+    int rc = launch_gram_tall(g.A, g.lda, g.rows, g.cols, g.xvar, g.b, g.sign, g.moi, g.varmap, g.out_quad, g.out_csc, g.alpha, g.out_lin,
+                              g.out_const, g.workspace, s);
+    if (!rc && side && side->in_replay) rc = fork_side(side, s);          // (the strictly upper tiles then run beside those entries)
+    const int64_t nt = cdiv(g.cols, ST);
+    if (!rc && nt > 1)
+        rc = launch_gram_sk(g.A, g.lda, g.rows, g.cols, g.xvar, g.varmap, g.moi, g.out_quad, g.out_csc, g.alpha, g.workspace, 0, 0, nt * (nt - 1) / 2,
+                            nullptr, 0, nullptr, s, 1);
+    return rc;
+}
+
+// Mid: every tile, q and c'c in ONE launch on 64 x 64 tiles (gram_mid.hip); the per-tile arrival counts are the calling stream's
+static int mid_node(const GramArgs &g, SideStream *side, hipStream_t s) {
+    PMT_REQUIRE(side && side->counters && (size_t)gram_mid_counters(g.cols) * sizeof(unsigned) <= MID_COUNTER_BYTES, PMT_STATE_ERROR,
+                "quad_gram: no auxiliary state for this stream");
+    int rc = launch_gram_mid(g.A, g.lda, g.rows, g.cols, g.xvar, g.b, g.sign, g.moi, g.varmap, g.out_quad, g.out_csc, g.alpha, g.out_lin,
+                             g.out_const, g.workspace, reinterpret_cast<unsigned *>(static_cast<char *>(side->counters) + MID_OFFSET), s);
+    return !rc && side->in_replay ? fork_side(side, s) : rc;
+}
+
+// StreamK: the contraction on `s`, q = 2 A'c and c'c on the side stream; staged: stage by stage (deliver_plan), releasing band groups
+static int stream_k_node(const GramArgs &g, bool staged, const DeliverPlan &d, SideStream *side, hipStream_t s) {
+    // fork: the two small reductions of this node (q = 2 A'c, HBM-bound; c'c, a serial chain) run on a side stream while
+    // the MFMA-bound contraction owns the main stream; join before returning control of `s`.  Legal under stream capture.
+    hipStream_t s2 = side ? side->stream : s;
+    if (side) { if (int rc = fork_side(side, s)) return rc; }
+    const int64_t rows = g.rows, cols = g.cols;
+    int rc = PMT_OK;
+    double *scratch = g.workspace ? reinterpret_cast<double *>(static_cast<char *>(g.workspace) + gram_sk_workspace_bytes(rows, cols)) : nullptr;
+    const int nsplit = (scratch && g.b && g.sign) ? linear_splits(rows, cols) : 1;
+    if (PMT_GRAM_ABL_NO_LINEAR) {
+    } else if (cols > 0 && nsplit > 1) {
+        const int64_t chunk = 64 * cdiv(cdiv(rows, nsplit), 64);
+        PMT_LAUNCH(gram_linear_split_kernel, dim3((unsigned)cdiv(cols, 4), (unsigned)nsplit), dim3(256), 0, s2, g.A, g.lda, rows, cols, g.b, g.sign, chunk, scratch);
+        PMT_LAUNCH(gram_linear_finish_kernel, dim3((unsigned)cdiv(cols, 256)), dim3(256), 0, s2, scratch, nsplit, cols, g.xvar, g.moi, g.varmap, g.out_lin);
+        rc = check_launch("gram_linear_split_kernel");
+    } else if (cols > 0) {
+        PMT_LAUNCH(gram_linear_kernel, dim3((unsigned)cdiv(cols, 4)), dim3(256), 0, s2, g.A, g.lda, rows, cols, g.xvar, g.b, g.sign, g.moi, g.varmap, g.out_lin);
+        rc = check_launch("gram_linear_kernel");
+    }
+    // c'c: a serial chain of `rows` additions on ONE wave (bit for bit the reference's left-to-right sum) — ~50 us alone, ~0.3 ms beside
+    // the contraction.  Inside a plan's replay it is queued at the END of the replay, i.e. behind the tape's side-lane entries on the
+    // side stream (the MOI copies of the constraints, the hand-off gathers and their fetches), which used to wait for it.
+    double *chains = scratch ? scratch + (size_t)linear_splits(rows, cols) * (size_t)cols : nullptr;
+    const int order = constant_order(staged ? GramForm::StreamKStaged : GramForm::StreamK, rows, cols).order;
+    auto const_part = [=]() -> int {
+        int rc2 = PMT_OK;
+        if (order == 5) rc2 = launch_gram_mid_constant(g.b, g.sign, rows, g.out_const, s2);      // (a staged delivery: the one-launch form's order)
+        else if (g.b && g.sign && rows > 0) rc2 = launch_blocked_dot(g.b, g.sign, g.b, g.sign, rows, chains, g.out_const, s2, order);
+        else if (hipMemsetAsync(g.out_const, 0, sizeof(double), s2) != hipSuccess) rc2 = fail(PMT_HIP_ERROR, "hipMemsetAsync(out_const)");
+        if (side) { PMT_HIP_CHECK(hipEventRecord(side->join2, side->stream)); PMT_HIP_CHECK(hipStreamWaitEvent(s, side->join2, 0)); }
+        return rc2;
+    };
+    const bool defer_const = side && side->in_replay;
+    if (!rc && defer_const) side->deferred.push_back(const_part);
+    if (side) PMT_HIP_CHECK(hipEventRecord(side->join, side->stream));          // the affine part: `s` joins it behind the contraction's launch
+    if (!rc && cols > 0 && !staged) rc = launch_gram_sk(g.A, g.lda, rows, cols, g.xvar, g.varmap, g.moi, g.out_quad, g.out_csc, g.alpha, g.workspace, 0, 0, -1,
+                                                        nullptr, 0, nullptr, s);
+    else if (!rc && cols > 0) {
+        // flags of the pair fold (gram_sk.hip): the tail of the partial-tile workspace, beyond the slots a grid of 256 uses; cleared
+        // per delivery, stage st writes / waits for the value st + 1
+        unsigned *pair_flags = g.workspace ? reinterpret_cast<unsigned *>(static_cast<char *>(g.workspace) + gram_sk_workspace_bytes(rows, cols) - PAIR_FLAG_BYTES) : nullptr;
+        if (pair_flags) PMT_HIP_CHECK(hipMemsetAsync(pair_flags, 0, PAIR_FLAG_BYTES, s));
+        for (int st = 0; !rc && st < d.nstages; ++st) {
+            rc = launch_gram_sk(g.A, g.lda, rows, cols, g.xvar, g.varmap, g.moi, g.out_quad, g.out_csc, g.alpha, g.workspace, d.order_w, d.seq_begin[st],
+                                d.seq_count[st], pair_flags, (unsigned)(st + 1), side->err_dev, s);
+            if (!rc && d.group_of[st] >= 0) rc = release_group(d, side, d.group_of[st], s);
+        }
+        if (!rc) rc = deliver_submit(d, side);
+    }
+    if (side) PMT_HIP_CHECK(hipStreamWaitEvent(s, side->join, 0));
+    if (!rc && !defer_const) rc = const_part();          // (behind the contraction's launch: its workgroups are placed first)
+    return rc;
+}
+
+// the whole node, in the form gram_form picks.  out_quad (term structs) and out_csc (solver values, alpha-scaled) are independent optional
+// outputs of the same contraction; host != null: out_csc, or out_quad where there is no out_csc, is also DELIVERED to this page-locked buffer.
+static int gram_node(const GramArgs &g, void *stream, double *host = nullptr, int ngroups = 0) {
+    const int64_t rows = g.rows, cols = g.cols;
+    PMT_REQUIRE(rows >= 0 && cols >= 0, PMT_DIMENSION_MISMATCH, "quad_gram: negative dimension");
+    PMT_REQUIRE(g.lda >= rows, PMT_DIMENSION_MISMATCH, "quad_gram: lda < rows");
+    PMT_REQUIRE(g.sign >= -1 && g.sign <= 1, PMT_INVALID_ARGUMENT, "quad_gram: sign must be -1, 0 or +1");
+    PMT_REQUIRE(g.out_const, PMT_INVALID_ARGUMENT, "quad_gram: null out_const");
+    PMT_REQUIRE(g.sign == 0 || g.b || rows == 0, PMT_INVALID_ARGUMENT, "quad_gram: sign != 0 needs b");
+    if (cols > 0) PMT_REQUIRE(g.xvar && (g.out_quad || g.out_csc) && g.out_lin && (g.A || rows == 0), PMT_INVALID_ARGUMENT, "quad_gram: null pointer");
+    PMT_REQUIRE(cols < (int64_t)ST * 32000, PMT_DIMENSION_MISMATCH, "quad_gram: too many columns");
+    const GramForm form = gram_form(rows, cols, g.out_csc != nullptr, host != nullptr);
+    PMT_REQUIRE(g.workspace || (form != GramForm::Fused && form != GramForm::Mid), PMT_INVALID_ARGUMENT, "quad_gram: workspace required");
+    if (int rc = check_strictly_increasing(g.xvar, cols, stream)) return rc;
+    if (form == GramForm::Tiny) {
+        // (README Example 1 with the canonical objective: 8 x 8) row-order sums by the interpreter kernel; by itself — an immediate call, or
+        // a run of one — the node is ONE launch of the interpreter's body: the same bits as inside a run
         SmallNode nd;
-        nd.op = SOP_GRAM; nd.sign = (b && sign) ? sign : 0; nd.moi = moi; nd.d[0] = lda; nd.d[1] = rows; nd.d[2] = cols;
-        nd.in[0] = A; nd.in[1] = xvar; nd.in[2] = b; nd.in[3] = varmap; nd.out[0] = out_quad; nd.out[1] = out_lin; nd.out[2] = out_const;
+        nd.op = SOP_GRAM; nd.sign = (g.b && g.sign) ? g.sign : 0; nd.moi = g.moi; nd.d[0] = g.lda; nd.d[1] = rows; nd.d[2] = cols;
+        nd.in[0] = g.A; nd.in[1] = g.xvar; nd.in[2] = g.b; nd.in[3] = g.varmap; nd.out[0] = g.out_quad; nd.out[1] = g.out_lin; nd.out[2] = g.out_const;
         nd.work = rows * cols * (cols + 1) / 2 + 64 * rows;
-        // (by itself — an immediate call, or a run of one — the node is ONE launch of the interpreter's body: the same bits as inside a run)
         return dispatch(stream, [=](hipStream_t s) { return launch_small_one(nd, s); }, nd);
     }
-    return dispatch(stream, node);
+    DeliverPlan dplan;
+    if (host && cols > 0) {
+        dplan = deliver_plan(rows, cols, form == GramForm::StreamKStaged, ngroups, !g.out_csc);
+        dplan.host = host;
+        dplan.src = g.out_csc ? g.out_csc : reinterpret_cast<const double *>(g.out_quad);
+        dplan.host_dev = static_cast<double *>(host_device_pointer(host));
+        PMT_REQUIRE(dplan.host_dev, PMT_INVALID_ARGUMENT, "quad_gram_csc_deliver: host_P_values must be page-locked host memory (pmt_host_alloc)");
+        dplan.sig = std::make_shared<DeliverSignals>();
+        mark_no_graph(stream);
+    }
+    return dispatch(stream, [=](hipStream_t s) -> int {
+        SideStream *side = side_stream(s);
+        const bool deliver = dplan.host != nullptr;
+        if (deliver) { if (int rc = deliver_arm(dplan, side, s)) return rc; }
+        if (form == GramForm::StreamK || form == GramForm::StreamKStaged) return stream_k_node(g, form == GramForm::StreamKStaged, dplan, side, s);
+        int rc = form == GramForm::Fused ? fused_node(g, side, s) : mid_node(g, side, s);
+        // the whole array is in memory behind the node's last kernel: release its one transfer
+        if (!rc && deliver) rc = release_group(dplan, side, 0, s);
+        if (!rc && deliver) rc = deliver_submit(dplan, side);
+        return rc;
+    });
+}
+
+}  // namespace pmt
+
+using namespace pmt;
+
+extern "C" int pmt_quad_gram_constant_order(int64_t rows, int64_t cols, int *order, int *groups, int *stage_rows) {
+    PMT_REQUIRE(rows >= 0 && cols >= 0 && order, PMT_INVALID_ARGUMENT, "quad_gram_constant_order: bad argument");
+    // the form of an undelivered CSC call, which is never a tiny node: a tiny node sums in row order, as the stream-K node does at its
+    // <= 64 rows — except for one row of 129 .. 180 columns, the one-launch form here, where every order adds the same single square
+    const ConstantOrder o = constant_order(gram_form(rows, cols, true, false), rows, cols);
+    *order = o.order; if (groups) *groups = o.groups; if (stage_rows) *stage_rows = o.stage_rows;
+    return PMT_OK;
+}
+
+extern "C" size_t pmt_quad_gram_workspace_bytes(int64_t rows, int64_t cols) {
+    // The most that a form the shape takes across call kinds (plain or CSC, delivered; a tiny node none) needs, and never less than the
+    // stream-K node's need — its partial tiles (which the fused form's strict launch shares), the chunk sums of q, the chains of c'c.
+    size_t bytes = gram_sk_workspace_bytes(rows, cols) +
+                   sizeof(double) * ((size_t)linear_splits(rows, cols) * (size_t)std::max<int64_t>(cols, 0) + blocked_dot_scratch_doubles());
+    for (const bool deliver : {false, true}) {
+        const GramForm form = gram_form(rows, cols, true, deliver);
+        bytes = std::max(bytes, form == GramForm::Fused ? gram_tall_workspace_bytes(rows, cols) : form == GramForm::Mid ? gram_mid_workspace_bytes(rows, cols) : 0);
+    }
+    return bytes;
 }
 
 extern "C" int pmt_quad_gram_f64(const double *A, int64_t lda, int64_t rows, int64_t cols, const int64_t *xvar, const double *b, int sign,
                                  int moi, const int64_t *varmap, pmt_quadratic_term *out_quad, pmt_linear_term *out_lin, double *out_const,
                                  void *workspace, void *stream) {
     if (cols > 0) PMT_REQUIRE(out_quad, PMT_INVALID_ARGUMENT, "quad_gram: null out_quad");
-    return gram_node(A, lda, rows, cols, xvar, b, sign, moi, varmap, out_quad, nullptr, 1.0, out_lin, out_const, workspace, nullptr, 0, stream);
+    return gram_node({A, lda, rows, cols, xvar, b, sign, moi, varmap, out_quad, nullptr, 1.0, out_lin, out_const, workspace}, stream);
 }
 
 extern "C" int pmt_quad_gram_csc_f64(const double *A, int64_t lda, int64_t rows, int64_t cols, const int64_t *xvar, const double *b, int sign,
                                      const int64_t *varmap, double alpha, double *out_P_values, pmt_quadratic_term *out_quad,
                                      pmt_linear_term *out_lin, double *out_const, void *workspace, void *stream) {
     if (cols > 0) PMT_REQUIRE(out_P_values, PMT_INVALID_ARGUMENT, "quad_gram_csc: null out_P_values");
-    return gram_node(A, lda, rows, cols, xvar, b, sign, 1, varmap, out_quad, out_P_values, alpha, out_lin, out_const, workspace, nullptr, 0, stream);
+    return gram_node({A, lda, rows, cols, xvar, b, sign, 1, varmap, out_quad, out_P_values, alpha, out_lin, out_const, workspace}, stream);
 }
 
 extern "C" int pmt_quad_gram_deliver_f64(const double *A, int64_t lda, int64_t rows, int64_t cols, const int64_t *xvar, const double *b, int sign,
@@ -871,7 +533,7 @@ extern "C" int pmt_quad_gram_deliver_f64(const double *A, int64_t lda, int64_t r
                                          pmt_linear_term *out_lin, double *out_const, void *workspace, void *stream) {
     if (cols > 0) PMT_REQUIRE(out_quad && host_quad, PMT_INVALID_ARGUMENT, "quad_gram_deliver: null out_quad / host_quad");
     PMT_REQUIRE(nstages >= 0 && nstages <= MAXGROUPS, PMT_INVALID_ARGUMENT, "quad_gram_deliver: nstages must be 0 (default) .. 16");
-    return gram_node(A, lda, rows, cols, xvar, b, sign, moi, varmap, out_quad, nullptr, 1.0, out_lin, out_const, workspace, nullptr, nstages, stream, host_quad);
+    return gram_node({A, lda, rows, cols, xvar, b, sign, moi, varmap, out_quad, nullptr, 1.0, out_lin, out_const, workspace}, stream, reinterpret_cast<double *>(host_quad), nstages);
 }
 
 extern "C" int pmt_quad_gram_csc_deliver_f64(const double *A, int64_t lda, int64_t rows, int64_t cols, const int64_t *xvar, const double *b, int sign,
@@ -879,11 +541,5 @@ extern "C" int pmt_quad_gram_csc_deliver_f64(const double *A, int64_t lda, int64
                                              pmt_linear_term *out_lin, double *out_const, void *workspace, void *stream) {
     if (cols > 0) PMT_REQUIRE(out_P_values && host_P_values, PMT_INVALID_ARGUMENT, "quad_gram_csc_deliver: null P values pointer");
     PMT_REQUIRE(ngroups >= 0 && ngroups <= MAXGROUPS, PMT_INVALID_ARGUMENT, "quad_gram_csc_deliver: ngroups must be 0 (default) .. 16");
-    return gram_node(A, lda, rows, cols, xvar, b, sign, 1, varmap, nullptr, out_P_values, alpha, out_lin, out_const, workspace, host_P_values, ngroups,
-                     stream);
-}
-
-extern "C" int pmt_fetch_synchronize(void *stream) {
-    PMT_REQUIRE(!is_recording_handle(stream), PMT_INVALID_ARGUMENT, "fetch_synchronize: `stream` is a plan's recording handle; use pmt_plan_fetch_synchronize");
-    return fetch_synchronize(reinterpret_cast<hipStream_t>(stream));
+    return gram_node({A, lda, rows, cols, xvar, b, sign, 1, varmap, nullptr, out_P_values, alpha, out_lin, out_const, workspace}, stream, host_P_values, ngroups);
 }

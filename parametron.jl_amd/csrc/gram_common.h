@@ -1,5 +1,5 @@
 // Geometry of the canonical least-squares contraction (gram_sk.hip), kept apart from the kernel bodies: argument block, tile geometry,
-// work-unit numbering, the XCD-aware tile order, the accumulator lane map, the term store.
+// work-unit numbering, the XCD-aware tile order, the accumulator lane map, the term store; and the host side of the node's forms.
 #pragma once
 #include "common.h"
 
@@ -163,5 +163,33 @@ __device__ __forceinline__ void sk_store_term(const SKArgs &g, int jb, int kb, i
     p[1] = (u64)(g.moi ? map_var(g.varmap, jv) : jv);
     p[2] = (u64)(g.moi ? map_var(g.varmap, kv) : kv);
 }
+
+
+// ---- host side: the launchers of the node's forms, their size helpers and the predicates gram.hip's gram_form decides by; what else it calls
+int launch_gram_sk(const double *A, int64_t lda, int64_t rows, int64_t cols, const int64_t *xvar, const int64_t *varmap, int moi,
+                   pmt_quadratic_term *out_quad, double *out_csc, double alpha, void *workspace, int order_w, int64_t seq_begin, int64_t seq_count,
+                   unsigned *pair_flags, unsigned epoch, int *error_word, hipStream_t s, int strict = 0);
+size_t gram_sk_workspace_bytes(int64_t rows, int64_t cols);
+bool gram_tiny(int64_t rows, int64_t cols);
+bool gram_tall_applies(int64_t rows, int64_t cols);
+bool gram_tall_diag_applies(int64_t rows, int64_t cols);
+int gram_tall_groups(int64_t rows, int64_t cols);
+int gram_tall_stage_rows(int64_t rows, int64_t cols);
+int gram_tall_run_lanes(int64_t rows, int64_t cols);
+size_t gram_tall_workspace_bytes(int64_t rows, int64_t cols);
+int launch_gram_tall(const double *A, int64_t lda, int64_t rows, int64_t cols, const int64_t *xvar, const double *b, int sign, int moi,
+                     const int64_t *varmap, pmt_quadratic_term *out_quad, double *out_csc, double alpha, pmt_linear_term *out_lin,
+                     double *out_const, void *workspace, hipStream_t s);
+size_t gram_mid_workspace_bytes(int64_t rows, int64_t cols);
+int gram_mid_counters(int64_t cols);
+int launch_gram_mid(const double *A, int64_t lda, int64_t rows, int64_t cols, const int64_t *xvar, const double *b, int sign, int moi,
+                    const int64_t *varmap, pmt_quadratic_term *out_quad, double *out_csc, double alpha, pmt_linear_term *out_lin,
+                    double *out_const, void *workspace, unsigned *counters, hipStream_t s);
+int launch_gram_mid_constant(const double *b, int sign, int64_t rows, double *out_const, hipStream_t s);
+int check_strictly_increasing(const int64_t *xvar_dev, int64_t n, void *stream);
+void mark_no_graph(void *stream);
+int launch_blocked_dot(const double *a, int sign_a, const double *b, int sign_b, int64_t n, double *scratch, double *out, hipStream_t s, int chained);
+size_t blocked_dot_scratch_doubles();
+int launch_small_one(const SmallNode &nd, hipStream_t s);
 
 }  // namespace pmt

@@ -1,5 +1,5 @@
-// Canonical least-squares objective for WIDE shapes of 129 .. 2048 columns (from the sizes the reference is used at with a few hundred
-// variables up to what the fast load path reaches: gram.hip, gram_mid_applies) in ONE launch: upper triangle of A'A, q = 2 A'c and c'c.
+// Canonical least-squares objective for WIDE shapes of 129 .. 4096 columns (from the sizes the reference is used at with a few hundred
+// variables up to config 2, within what the fast load path reaches: gram.hip, gram_form) in ONE launch: upper triangle of A'A, q = 2 A'c, c'c.
 //
 // Reference semantics replaced: _vecdot!/muladd! literal expansion (src/functions.jl:702-709,548-576) + canonicalize!
 // (src/functions.jl:381-386, src/util.jl:9-26) + update!(::MOI.ScalarQuadraticFunction) (src/moi_interop.jl:45-62): SURVEY Appendix A.3.
@@ -846,7 +846,7 @@ size_t gram_mid_workspace_bytes(int64_t rows, int64_t cols) {
 }
 int gram_mid_counters(int64_t cols) { const int nb = (int)cdiv(cols, MT); return MCNT * (nb * (nb + 1) / 2) + 16; }      // (+ the tickets)
 
-// the whole node in one launch; `counters`: gram_mid_counters(cols) zeroed words owned by the calling stream (gram.hip: SideStream)
+// the whole node in one launch; `counters`: gram_mid_counters(cols) zeroed words owned by the calling stream (streams.h: SideStream)
 int launch_gram_mid(const double *A, int64_t lda, int64_t rows, int64_t cols, const int64_t *xvar, const double *b, int sign, int moi,
                     const int64_t *varmap, pmt_quadratic_term *out_quad, double *out_csc, double alpha, pmt_linear_term *out_lin,
                     double *out_const, void *workspace, unsigned *counters, hipStream_t s) {

@@ -493,7 +493,7 @@ __global__ __launch_bounds__(Cfg<TN>::NT, WPS) __attribute__((amdgpu_num_vgpr(10
                 // adds) and writes its 64 rows through the coalescing epilogue.  No fix-up launch, and half the partial traffic and half the
                 // write-out on each workgroup's path (round 3's fold had the second workgroup read 128 KB and write the whole tile while the
                 // first sat idle: ~10 us per stage).  The wait is bounded; a half whose partner never showed up is written as NaN and the
-                // launch's error word is raised (pmt_plan_fetch_synchronize returns PMT_HIP_ERROR, gram.hip).
+                // launch's error word is raised (pmt_plan_fetch_synchronize returns PMT_HIP_ERROR, streams.hip).
                 const bool first = c0 == 0;
                 const int keep = first ? 0 : 1;
                 const int ftid = sk_fresh_tid();                                 // (fresh: nothing of this is live across the stage loop)

@@ -4,7 +4,7 @@
 // scales them) and canonicalize! (:381-386) merges the duplicates before the MOI copy (src/moi_interop.jl:45-62).  Here block 1 of the sum
 // is already the canonical MOI function (pmt_quad_gram_f64, moi = 1); blocks 2..K are the CSC values of pmt_quad_gram_csc_f64 (the same
 // coefficients bit for bit).  These kernels weight and add them in place, in the order the header fixes.
-#include "common.h"
+#include "streams.h"
 
 namespace pmt {
 

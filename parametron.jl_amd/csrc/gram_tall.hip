@@ -1084,7 +1084,7 @@ bool gram_tall_applies(int64_t rows, int64_t cols) { return cols >= 1 && cols <=
 // form alone computes every diagonal tile as a full square (17 % of the executed flops at 512 columns) and needs two more kernels and a
 // side-stream fork for q and c'c.  Measured (profiles/r05_gram_tall.txt) against the stream-K node: better at every row count from 100 to
 // 2^20 (300 x 300: 64 -> 37 us; 4096 x 512: 112 -> 69 us; 262144 x 512: 1.76 -> 1.44 ms; 65536 x 2048: 5.69 -> 5.37 ms), equal at
-// 8192 x 1024 and 4096 x 2048.  Config 2 (4096 columns) keeps the plain stream-K node.
+// 8192 x 1024 and 4096 x 2048.  Most of these shapes now take the one-launch form instead (gram.hip: gram_form).
 #ifndef PMT_WIDE_MAXCOLS
 #define PMT_WIDE_MAXCOLS (16 * TCOLS)
 #endif

@@ -17,8 +17,7 @@
 
 #include <memory>
 
-#include "common.h"
-#include "dma.h"
+#include "streams.h"
 
 namespace pmt {
 
@@ -310,17 +309,6 @@ extern "C" int pmt_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) { (void)hipGetLastError(); return 0; }
     return n;
-}
-
-namespace pmt {
-hipStream_t side_stream_of(hipStream_t s);
-void retain_side_stream(hipStream_t s);
-void release_side_stream(hipStream_t s);
-int fetch_async(hipStream_t s, hipStream_t after, hipEvent_t order_event, void *host_dst, const void *device_src, size_t bytes, FetchState *st, FetchRect r);
-int fetch_fence(hipStream_t s);
-void replay_begin(hipStream_t s);
-int replay_end(hipStream_t s);
-int fetch_synchronize(hipStream_t s);
 }
 
 extern "C" int pmt_plan_create(int device, void *stream, pmt_plan **out) {

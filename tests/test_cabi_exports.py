@@ -284,6 +284,16 @@ def test_constant_order_is_host_arithmetic(lib):
         lib.call("pmt_quad_gram_constant_order", -1, 4, None, None, None)
 
 
+def test_fused_and_one_launch_gram_forms_reject_a_null_workspace(lib):
+    """pmt_quad_gram_f64 without a workspace on a shape of the fused form (4096 x 128) or of the one-launch form (300 x 300, 4096 x 4096):
+    ArgumentError before any device call, not a silent fall-back to the stream-K node, whose constant is summed in another order than
+    pmt_quad_gram_constant_order reports; no GPU needed"""
+    dummy = C.c_void_p(64)              # never dereferenced: the call is rejected first
+    for rows, cols in ((4096, 128), (300, 300), (4096, 4096)):
+        with pytest.raises(lib.ArgumentError, match="workspace"):
+            lib.call("pmt_quad_gram_f64", dummy, rows, rows, cols, dummy, dummy, -1, 1, dummy, dummy, dummy, dummy, None, dummy)
+
+
 def test_batch_shard_is_host_arithmetic(lib):
     per, first = C.c_int64(), C.c_int64()
     lib.call("pmt_batch_shard", 8192, 8, 3, C.byref(per), C.byref(first))
