@@ -307,6 +307,25 @@ int pmt_quad_gram_sum_f64(int64_t cols, const pmt_lsq_term *terms, int nterms, p
 int pmt_quad_gram_sum_sub_f64(int64_t cols, const pmt_lsq_term *terms, int nterms, const int64_t *const *term_cols, const int64_t *term_ncols,
                               pmt_quadratic_term *out_quad, pmt_linear_term *out_lin, double *out_const, void *stream);
 
+/* transpose(x) * Q * x as its canonical function, for Q an n x n matrix (column-major, leading dimension ldq: the device layout of a
+ * matrix Parameter) that need not be symmetric and x = n DISTINCT variables in strictly increasing order: bilinearmul! (src/functions.jl:840-858:
+ * all n^2 terms (Q[j,k], x_j, x_k)), canonicalize! (:381-386: the two terms of every pair {j, k} added) and the MOI copy
+ * (src/moi_interop.jl:45-62) in one pass.  An off-diagonal coefficient is the sum of exactly two numbers and IEEE addition commutes, so
+ * the result is defined bit for bit, whatever order the reference's sort combines in (the builder's Q' pairing, :840-858, drops out
+ * because Q + Q' is its own transpose):
+ *   out_quad[tri(j,k)] = (Q[j,k] + Q[k,j], vm[xvar[j]], vm[xvar[k]]) for j < k, (2*Q[j,j], vm[xvar[j]], vm[xvar[j]]) on the diagonal, on the
+ *                        row-major upper triangle (tri(j,k) = j*n - j*(j-1)/2 + k - j, 0-based: the positions pmt_quad_gram_f64 uses).
+ *                        moi == 0: native indices (varmap not read) and Q[j,j] undoubled on the diagonal — what canonicalize! alone yields.
+ *   out_P_values[k(k+1)/2 + j] = alpha * c(j,k), c the moi = 1 coefficient: the CSC layout and meaning of pmt_quad_gram_csc_f64.
+ *                        With alpha == 1.0 the values equal the term coefficients bit for bit.
+ *   out_lin[j] = (0.0, vm[xvar[j]]) and *out_const = 0.0 when given: with them the node's outputs stand wherever a least-squares block's
+ *                        stand in pmt_quad_gram_sum_f64 / _sum_sub_f64 (first block: out_quad / out_lin / out_const; later: values / lin / constant).
+ * At least one of out_quad / out_P_values; out_lin and out_const are optional.  A null Q or xvar, n < 1 (or beyond 2^21), ldq < n, moi != 0
+ * without a varmap: PMT_INVALID_ARGUMENT before any device call.  No workspace.  Q is read as n columns of ldq doubles; padding rows are
+ * never used.  One 64 x 64 tile of the upper triangle per workgroup: 8 n^2 bytes read, 24 / 8 / 32 bytes per entry written (csrc/form.hip). */
+int pmt_quad_form_f64(const double *Q, int64_t ldq, int64_t n, const int64_t *xvar, int moi, const int64_t *varmap, double alpha,
+                      pmt_quadratic_term *out_quad, double *out_P_values, pmt_linear_term *out_lin, double *out_const, void *stream);
+
 /* host: block until every copy on the fetch stream of `stream` (a HIP stream, not a recording handle) has landed.  PMT_HIP_ERROR when a
  * delivery failed on the device: a transfer that never started, a courier without progress, or a split tile of a staged contraction whose
  * first half never arrived (the tile is then NaN in out_P_values / out_quad — never a plausible half sum — and this call says so). */

@@ -166,6 +166,14 @@ affine_stack_columns!(out, ldo, table, ncols, rows, stream) =
     check(ccall((:pmt_affine_stack_columns_f64, lib), Cint, (DevPtr, Int64, Int64, DevPtr, Int64, Ptr{Cvoid}),
                 table, ncols, rows, out, ldo, stream))
 
+"transpose(x) * Q * x as its canonical function (bilinearmul! src/functions.jl:840-858, canonicalize! :381-386, MOI copy src/moi_interop.jl:45-62):
+ Q[j,k] + Q[k,j] on the row-major upper triangle, 2 Q[j,j] on the diagonal; out_quad or out_P_values may be C_NULL (not both), out_lin
+ (zero coefficients) and out_const (0.0) are optional"
+quad_form!(out_quad, out_P_values, out_lin, out_const, Q, ldq, n, xvar, moi, varmap, alpha, stream) =
+    check(ccall((:pmt_quad_form_f64, lib), Cint,
+                (DevPtr, Int64, Int64, DevPtr, Cint, DevPtr, Cdouble, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
+                Q, ldq, n, xvar, moi, varmap, alpha, out_quad, out_P_values, out_lin, out_const, stream))
+
 "structure of a solver matrix from 1-based (row, col) indices (host, once): perm, seg_ptr, colptr, rowval (0-based), nnz"
 function csc_order(rows::Vector{Int64}, cols::Vector{Int64}, nrows, ncols; upper::Bool=false)
     n = length(rows)

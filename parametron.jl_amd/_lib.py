@@ -109,6 +109,7 @@ SIGNATURES = {
     "pmt_quad_gram_sum_f64": (_ci, [_i64, _vp, _ci, _vp, _vp, _vp, _vp]),
     "pmt_quad_gram_sum_sub_f64": (_ci, [_i64, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pmt_affine_stack_columns_f64": (_ci, [_vp, _i64, _i64, _vp, _i64, _vp]),
+    "pmt_quad_form_f64": (_ci, [_vp, _i64, _i64, _vp, _ci, _vp, _f64, _vp, _vp, _vp, _vp, _vp]),
     "pmt_fetch_synchronize": (_ci, [_vp]),
     "pmt_set_host_delivery": (_ci, [_ci]),
     "pmt_get_host_delivery": (_ci, [_ci, C.POINTER(_ci), C.POINTER(_ci)]),

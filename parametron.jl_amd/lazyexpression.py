@@ -316,6 +316,7 @@ class DeviceNode(LazyExpression):
         self.gram_candidate = gram_candidate
         self.lsq_sum = None               # the node as a weighted sum of least-squares terms (LsqTerm list), or None
         self.stacked_gram = None          # dot(r, r) of a stacked residual r (DStackedAff): its Gram candidate on demand
+        self.form_candidate = None        # transpose(x) * Q * x over one x (QuadForm): the canonical node reads Q itself
 
     def prepare(self):
         if self._prepare is not None:
@@ -693,23 +694,41 @@ class _LazyRowTimesMatrix:
     __matmul__ = __mul__
 
 
+class QuadForm:
+    """transpose(x) * Q * x with Q a dense square matrix Parameter on the device and x ONE Variable vector in strictly increasing order: what
+    the canonical node pmt_quad_form_f64 reads (DeviceNode.form_candidate; LsqTerm 'form')."""
+
+    def __init__(self, mat, xvars):
+        self.mat, self.xvars = mat, xvars
+
+
 def _rule_bilinear(model, ctx, x, Q, y):                                         # rule :219-226, builder :840-858
     dx, dQ, dy = _dv(ctx, x), _dv(ctx, Q), _dv(ctx, y)
     if not (isinstance(dx, DVars) and isinstance(dy, DVars) and isinstance(dQ, DMat)):
         raise ArgumentError("transpose(x) * Q * y needs Variable vectors and a matrix")
     if (dQ.rows, dQ.cols) != (dx.n, dy.n):
         raise DimensionMismatch("bilinearmul!: size(Q) != (length(x), length(y))")   # src/functions.jl:845
-    out = DQuad(ctx, dx.n * dy.n, 0)
+    # x' Q x over one strictly increasing x with Q a matrix Parameter: the canonical objective reads Q itself (moi.py, pmt_quad_form_f64);
+    # the n^2 literal terms exist only once a literal consumer asks for them
+    form = isinstance(Q, Parameter) and dx.n >= 1 and np.array_equal(dx.vars, dy.vars) and dx.strictly_increasing()
+    out = DQuad(ctx, dx.n * dy.n, 0, alloc=not form)
 
     def emit(c):
+        if out.quad is None:
+            return                                                               # consumed by the canonical objective instead
         c.call("pmt_bilinear_f64", P(dQ.buf), dQ.lda, dQ.rows, dQ.cols, P(dx.buf), P(dy.buf), 0, None, P(out.quad))
-    return DeviceNode(model, "bilinearmul!", _inputs(x, Q, y), out, emit)
+    node = DeviceNode(model, "bilinearmul!", _inputs(x, Q, y), out, emit)
+    if form:
+        node.form_candidate = QuadForm(dQ, dx)
+        return _with_lsq(node, [LsqTerm("form", r=node.form_candidate)])
+    return node
 
 
 # ---- weighted sums of least-squares terms -------------------------------------------------------------------------
 class LsqTerm:
     """One term of a scalar node read as a weighted sum (DeviceNode.lsq_sum; combined by the canonical-sum objective, moi.py):
       'block'     dot(r, r) / transpose(r)*r, r = A*x (+|-) b a Gram candidate (r: its DDenseAff)
+      'form'      transpose(x) * Q * x, Q a matrix Parameter (r: its QuadForm); stands where a block stands in the combine
       'diag'      dot(x, x), or dot(x (+|-) v, x (+|-) v) with v a vector Parameter (xvars, vec, sign)
       'linear'    dot(c, x) / dot(x, c) with c a vector Parameter (xvars, vec)
       'constant'  a number (folded into scale) or a scalar Parameter (value)

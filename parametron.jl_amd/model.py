@@ -356,9 +356,16 @@ class Model:
                         st = getattr(r.expr, "stacked_gram", None)
                         if r.kind == "quad" and st is not None and r.expr.gram_candidate is None:
                             r.expr.gram_candidate = st.require_stack()
+                # transpose(x) * Q * x alone (lazyexpression._rule_bilinear): the canonical node reads Q itself (moi.py, mode "canonical-form") —
+                # MOI terms, or P's CSC values for the device hand-off when x keeps its order under the optimizer's index map
+                if not self._small and self.objective in records and self.objective.kind == "quad":
+                    form = getattr(self.objective.expr, "form_candidate", None)
+                    if form is not None and (self.handoff == "moi" or (
+                            self.handoff == "device" and np.all(np.diff(self.model_var_to_optimizer[form.xvars.vars - 1]) > 0))):
+                        self.objective.form = form
                 # a weighted sum of least-squares blocks over one x (the objective's lsq_sum): combined from the blocks' Gram nodes
                 # (moi.py, mode "canonical-sum") — the MOI boundary of a model beyond the small plan only
-                if not self._small and self.handoff == "moi" and self.objective in records:
+                if not self._small and self.handoff == "moi" and self.objective in records and getattr(self.objective, "form", None) is None:
                     self.objective.lsq_terms = moi.lsq_sum_terms(self.objective.expr)
                     for t in self.objective.lsq_terms or ():
                         if t.kind == "block" and hasattr(t.r, "require_stack"):
@@ -366,7 +373,8 @@ class Model:
                 # any other quadratic objective: generic device canonicalize! (sorted, duplicates combined) before the MOI copy
                 for r in records:
                     gram = getattr(r.expr, "gram_candidate", None)
-                    if r.kind == "quad" and not (gram is not None and gram.xvars.strictly_increasing()) and getattr(r, "lsq_terms", None) is None:
+                    if r.kind == "quad" and not (gram is not None and gram.xvars.strictly_increasing()) and getattr(r, "lsq_terms", None) is None and \
+                            getattr(r, "form", None) is None:
                         r.expr = r.expr.canonicalize()
             emitters = [r.compile(ctx, self._varmap_buf, self.quadratic_mode, self.model_var_to_optimizer if early else None) for r in records]
             self._order = schedule([r.expr for r in records])

@@ -268,6 +268,9 @@ class _Record:
                         c.call("pmt_quad_gram_f64", P(gram.mat.buf), gram.mat.lda, _gram_rows(gram), n, P(gram.xvars.buf), P(vec), gram.sign if vec else 0,
                                1, P(varmap_buf), P(dq), P(dl), P(dc), P(ws))
                 return emit
+            form = getattr(self, "form", None)
+            if form is not None:
+                return self._compile_form(ctx, varmap_buf, form, handoff_varmap)
             terms = getattr(self, "lsq_terms", None)
             if terms is not None:
                 return self._compile_lsq_sum(ctx, varmap_buf, terms)
@@ -381,13 +384,38 @@ class _Record:
             c.call("pmt_pack_vector_affine_f64", P(m.terms), P(m.row_ptr_buf), m.rows, m.row_len, P(varmap_buf), 0, P(dt))
         return emit
 
+    def _compile_form(self, ctx, varmap_buf, form, handoff_varmap):
+        """transpose(x) * Q * x alone (Model.initialize set self.form): pmt_quad_form_f64 reads the Parameter matrix and writes the canonical
+        MOI function — n(n+1)/2 quadratic terms, no linear terms, constant 0.0 — or, for the device hand-off, the CSC values of P."""
+        n = form.mat.cols
+        nq = n * (n + 1) // 2
+        self.mode = "canonical-form"
+        self._quad_delivered = False
+        if handoff_varmap is not None:
+            self.f = ScalarQuadraticFunction(n, 0, alloc=ctx.pinned_array)
+            dp, dl, dc = ctx.alloc(8 * nq), ctx.alloc(16 * n), ctx.alloc(8)
+            self.dev = {"P_values": dp, "P_vars": handoff_varmap[form.xvars.vars - 1], "lin": dl, "const": dc}
+            alpha = -1.0 if self.model.sense == "Maximize" else 1.0
+
+            def emit(c):
+                c.call("pmt_quad_form_f64", P(form.mat.buf), form.mat.lda, n, P(form.xvars.buf), 1, P(varmap_buf), alpha, None, P(dp), P(dl), P(dc))
+            return emit
+        self.f = ScalarQuadraticFunction(0, nq, alloc=ctx.pinned_array)
+        dq, dc = ctx.alloc(24 * nq), ctx.alloc(8)
+        self.dev = {"quad": dq, "const": dc}
+
+        def emit(c):
+            c.call("pmt_quad_form_f64", P(form.mat.buf), form.mat.lda, n, P(form.xvars.buf), 1, P(varmap_buf), 1.0, P(dq), None, None, P(dc))
+        return emit
+
     def _compile_lsq_sum(self, ctx, varmap_buf, terms):
         """The objective as a weighted sum of least-squares blocks over one x (lsq_sum_terms): block 1 by pmt_quad_gram_f64 straight into the
         MOI buffers, blocks 2..K as CSC values (pmt_quad_gram_csc_f64, bit for bit the same coefficients), then pmt_quad_gram_sum_f64 weights
-        and adds everything in place.  The terms are final only after the combine: no overlapped delivery of the quadratic terms."""
+        and adds everything in place.  A form transpose(x) * Q * x stands where a block stands: pmt_quad_form_f64 writes the same outputs
+        (its linear terms and constant are zero).  The terms are final only after the combine: no overlapped delivery of the quadratic terms."""
         from . import _lib
-        blocks = [t.r for t in terms if t.kind == "block"]
-        g1 = blocks[0]
+        blocks = [t for t in terms if t.kind in ("block", "form")]
+        g1 = blocks[0].r
         n = g1.mat.cols
         nq = n * (n + 1) // 2
         self.f = ScalarQuadraticFunction(n, nq, alloc=ctx.pinned_array)
@@ -395,14 +423,15 @@ class _Record:
         self.dev = {"quad": dq, "lin": dl, "const": dc}
         self.mode = "canonical-sum"
         self._quad_delivered = False
-        ws = [ctx.alloc(max(16, int(ctx.lib.pmt_quad_gram_workspace_bytes(_gram_rows(g), n)))) for g in blocks]
+        ws = [ctx.alloc(max(16, int(ctx.lib.pmt_quad_gram_workspace_bytes(_gram_rows(t.r), n)))) if t.kind == "block" else None for t in blocks]
         # per block 2..K: its CSC values, linear terms and constant
         parts = [(ctx.alloc(8 * max(nq, 1)), ctx.alloc(16 * max(n, 1)), ctx.alloc(8)) for _ in blocks[1:]]
         desc, k = [], 0
         for t in terms:
-            d = {"kind": {"block": _lib.PMT_LSQ_BLOCK, "diag": _lib.PMT_LSQ_DIAG, "linear": _lib.PMT_LSQ_LINEAR, "constant": _lib.PMT_LSQ_CONSTANT}[t.kind],
+            d = {"kind": {"block": _lib.PMT_LSQ_BLOCK, "form": _lib.PMT_LSQ_BLOCK, "diag": _lib.PMT_LSQ_DIAG, "linear": _lib.PMT_LSQ_LINEAR,
+                          "constant": _lib.PMT_LSQ_CONSTANT}[t.kind],
                  "scale": t.scale, "weight": t.param.buf if t.param is not None else None}
-            if t.kind == "block":
+            if t.kind in ("block", "form"):
                 if k > 0:
                     d["values"], d["lin"], d["constant"] = parts[k - 1]
                 k += 1
@@ -430,10 +459,20 @@ class _Record:
             vec = g.vec.buf if g.vec is not None else None
             return (P(g.mat.buf), g.mat.lda, _gram_rows(g), n, P(g.xvars.buf), P(vec), g.sign if vec else 0)
 
+        def emit_block(c, t, w, first, part):
+            if t.kind == "form":
+                q = t.r
+                outs = (P(dq), None, P(dl), P(dc)) if first else (None, P(part[0]), P(part[1]), P(part[2]))
+                c.call("pmt_quad_form_f64", P(q.mat.buf), q.mat.lda, n, P(q.xvars.buf), 1, P(varmap_buf), 1.0, *outs)
+            elif first:
+                c.call("pmt_quad_gram_f64", *gram_args(t.r), 1, P(varmap_buf), P(dq), P(dl), P(dc), P(w))
+            else:
+                c.call("pmt_quad_gram_csc_f64", *gram_args(t.r), P(varmap_buf), 1.0, P(part[0]), None, P(part[1]), P(part[2]), P(w))
+
         def emit(c):
-            c.call("pmt_quad_gram_f64", *gram_args(g1), 1, P(varmap_buf), P(dq), P(dl), P(dc), P(ws[0]))
-            for g, w, (dv, dlk, dck) in zip(blocks[1:], ws[1:], parts):
-                c.call("pmt_quad_gram_csc_f64", *gram_args(g), P(varmap_buf), 1.0, P(dv), None, P(dlk), P(dck), P(w))
+            emit_block(c, blocks[0], ws[0], True, None)
+            for t, w, part in zip(blocks[1:], ws[1:], parts):
+                emit_block(c, t, w, False, part)
             if sub:
                 c.call("pmt_quad_gram_sum_sub_f64", n, C.addressof(arr), len(desc), C.cast(ptrs, C.c_void_p), counts.ctypes.data_as(C.c_void_p),
                        P(dq), P(dl), P(dc))
@@ -456,7 +495,8 @@ class _Record:
         elif self.kind == "quad":
             if "quad" in d and not getattr(self, "_quad_delivered", False):
                 ctx.record_fetch(f.quadratic_terms, d["quad"], f.quadratic_terms.nbytes)
-            ctx.record_fetch(f.affine_terms, d["lin"], f.affine_terms.nbytes)
+            if "lin" in d:                                                # (absent for a bare form: no linear terms)
+                ctx.record_fetch(f.affine_terms, d["lin"], f.affine_terms.nbytes)
             ctx.record_fetch(self._c, d["const"], 8)
         else:
             ctx.record_fetch(f.terms, d["terms"], f.terms.nbytes)
@@ -502,14 +542,14 @@ class _Record:
 
 def lsq_sum_terms(expr):
     """The LsqTerm list of an objective the canonical-sum path takes (Model.initialize checks the model-level conditions), or None:
-    1 .. 8 least-squares blocks, at most PMT_LSQ_MAX_TERMS terms, every block over the same strictly increasing x (a stacked block over its
-    sorted union z), every diagonal / linear term over x or a strictly increasing part of it (pmt_quad_gram_sum_sub_f64, whose launch holds
+    1 .. 8 least-squares blocks — forms transpose(x) * Q * x count among them —, at most PMT_LSQ_MAX_TERMS terms, every block over the same
+    strictly increasing x (a stacked block over its sorted union z), every diagonal / linear term over x or a strictly increasing part of it (pmt_quad_gram_sum_sub_f64, whose launch holds
     at most PMT_LSQ_MAX_RUNS runs of positions)."""
     from . import _lib
     terms = getattr(expr, "lsq_sum", None) if isinstance(expr, DeviceNode) else None
     if not terms or len(terms) > _lib.PMT_LSQ_MAX_TERMS or getattr(expr, "gram_candidate", None) is not None:
         return None
-    blocks = [t for t in terms if t.kind == "block"]
+    blocks = [t for t in terms if t.kind in ("block", "form")]
     if not 1 <= len(blocks) <= _lib.PMT_LSQ_MAX_BLOCKS:
         return None
     x = blocks[0].r.xvars
@@ -517,7 +557,7 @@ def lsq_sum_terms(expr):
         return None
     runs = 0
     for t in terms:
-        if t.kind == "block":
+        if t.kind in ("block", "form"):
             if not np.array_equal(t.r.xvars.vars, x.vars):
                 return None
         elif t.xvars is not None and not np.array_equal(t.xvars.vars, x.vars):
