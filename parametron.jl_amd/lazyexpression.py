@@ -306,17 +306,15 @@ def const_device_value(ctx, x):
 class DeviceNode(LazyExpression):
     """A rewritten (`optimize`d) and wrapped LazyExpression: in-place builder + pre-allocated dest, here in HBM."""
 
-    def __init__(self, model, builder, inputs, out, emit, gram_candidate=None, prepare=None):
+    def __init__(self, model, builder, inputs, out, emit, prepare=None):
         self.model = model
         self.builder = builder            # name of the reference builder this node replaces
         self.inputs = inputs              # Parameters / DeviceNodes in the reference's argument order
         self.out = out
         self._emit = emit
         self._prepare = prepare           # run for every scheduled node before any emit (materialisation requests)
-        self.gram_candidate = gram_candidate
         self.lsq_sum = None               # the node as a weighted sum of least-squares terms (LsqTerm list), or None
-        self.stacked_gram = None          # dot(r, r) of a stacked residual r (DStackedAff): its Gram candidate on demand
-        self.form_candidate = None        # transpose(x) * Q * x over one x (QuadForm): the canonical node reads Q itself
+        self.lsq_bare = False             # the node IS its one block / form (dot(r, r), transpose(x) * Q * x), not a sum or scaling over it
 
     def prepare(self):
         if self._prepare is not None:
@@ -667,14 +665,10 @@ def _rule_dot(model, ctx, x, y):                                                
                 return                                                           # consumed by the canonical objective instead
             c.call("pmt_quad_expand_f64", n, P(dx.terms), nx, P(dx.consts), P(dy.terms), ny, P(dy.consts), 0, None,
                    P(out.quad), P(out.lin), P(out.const))
-        gram = dx if (dx is dy and isinstance(dx, DDenseAff)) else None
-        node = DeviceNode(model, "vecdot!", ins, out, emit, gram_candidate=gram, prepare=prepare)
-        if gram is not None:
-            return _with_lsq(node, [LsqTerm("block", r=gram)])
-        if dx is dy and isinstance(dx, DStackedAff):
-            # a Gram candidate once the model asks for its stacked matrix (canonical mode beyond the small plan: Model.initialize)
-            node.stacked_gram = dx
-            return _with_lsq(node, [LsqTerm("block", r=dx)])
+        node = DeviceNode(model, "vecdot!", ins, out, emit, prepare=prepare)
+        if dx is dy and isinstance(dx, (DDenseAff, DStackedAff)):
+            # dot(r, r): a Gram operand — a stacked r once the model asks for its stacked matrix (moi.quad_plan, Model.initialize)
+            return _with_lsq(node, [LsqTerm("block", r=dx)], bare=True)
         if isinstance(dx, DVarsAff) and isinstance(dy, DVarsAff) and np.array_equal(dx.xvars.vars, dy.xvars.vars) and dx.sign == dy.sign and \
                 dx.vec is not None and dy.vec is not None and dx.vec.buf == dy.vec.buf:
             return _with_lsq(node, [LsqTerm("diag", xvars=dx.xvars, vec=dx.vec, sign=dx.sign)])          # dot(x (+|-) v, x (+|-) v)
@@ -696,7 +690,7 @@ class _LazyRowTimesMatrix:
 
 class QuadForm:
     """transpose(x) * Q * x with Q a dense square matrix Parameter on the device and x ONE Variable vector in strictly increasing order: what
-    the canonical node pmt_quad_form_f64 reads (DeviceNode.form_candidate; LsqTerm 'form')."""
+    the canonical node pmt_quad_form_f64 reads (the r of an LsqTerm 'form')."""
 
     def __init__(self, mat, xvars):
         self.mat, self.xvars = mat, xvars
@@ -719,15 +713,14 @@ def _rule_bilinear(model, ctx, x, Q, y):                                        
         c.call("pmt_bilinear_f64", P(dQ.buf), dQ.lda, dQ.rows, dQ.cols, P(dx.buf), P(dy.buf), 0, None, P(out.quad))
     node = DeviceNode(model, "bilinearmul!", _inputs(x, Q, y), out, emit)
     if form:
-        node.form_candidate = QuadForm(dQ, dx)
-        return _with_lsq(node, [LsqTerm("form", r=node.form_candidate)])
+        return _with_lsq(node, [LsqTerm("form", r=QuadForm(dQ, dx))], bare=True)
     return node
 
 
 # ---- weighted sums of least-squares terms -------------------------------------------------------------------------
 class LsqTerm:
-    """One term of a scalar node read as a weighted sum (DeviceNode.lsq_sum; combined by the canonical-sum objective, moi.py):
-      'block'     dot(r, r) / transpose(r)*r, r = A*x (+|-) b a Gram candidate (r: its DDenseAff)
+    """One term of a scalar node read as a weighted sum (DeviceNode.lsq_sum; moi.quad_plan chooses the record's canonical form from it):
+      'block'     dot(r, r) / transpose(r)*r, r = A*x (+|-) b a Gram operand (r: its DDenseAff, or the DStackedAff of a stacked residual)
       'form'      transpose(x) * Q * x, Q a matrix Parameter (r: its QuadForm); stands where a block stands in the combine
       'diag'      dot(x, x), or dot(x (+|-) v, x (+|-) v) with v a vector Parameter (xvars, vec, sign)
       'linear'    dot(c, x) / dot(x, c) with c a vector Parameter (xvars, vec)
@@ -754,15 +747,15 @@ class _IndexVars:
         self.vars = np.asarray(indices, dtype=np.int64)
 
 
-def _with_lsq(node, terms):
-    node.lsq_sum = terms
+def _with_lsq(node, terms, bare=False):
+    node.lsq_sum, node.lsq_bare = terms, bare
     return node
 
 
 def _lsq_of(arg, dv):
     """the weighted-sum description of a scalar operand, or None"""
     if isinstance(arg, DeviceNode):
-        return getattr(arg, "lsq_sum", None)
+        return arg.lsq_sum
     if isinstance(arg, QuadraticFunction):
         # dot(x, x) of plain Variables is evaluated on the host when the expression is built (no Parameter in it): sum_i 1.0 * x_i * x_i
         q = arg.quadratic

@@ -164,12 +164,6 @@ def _write_mailbox(x, val):
         mb[0] = float(val)
 
 
-def _is_gram_record(r):
-    """a record whose MOI copy is the canonical least-squares node (bare, or the weighted sum of such nodes)"""
-    return getattr(r, "mode", "").startswith("canonical") and r.kind == "quad" and \
-        (getattr(r.expr, "gram_candidate", None) is not None or r.mode == "canonical-sum")
-
-
 class _Backend:
     """What MOI.copy_to sees of the ParametronMOIModel backend (src/moi_interop.jl:2-11)."""
 
@@ -348,35 +342,16 @@ class Model:
             self._varmap_buf = ctx.alloc(8 * max(self.nvars, 1))
             ident = np.arange(1, self.nvars + 1, dtype=np.int64)     # IdentityVarMap until mapindices! (src/moi_interop.jl:32-33)
             ctx.upload(self._varmap_buf, self.model_var_to_optimizer if early else ident)
-            if self.quadratic_mode == "canonical":
-                # dot(r, r) of a residual over several Variable vectors (a stacked residual, lazyexpression._stacked_form): the Gram candidate
-                # of its stacked matrix over the union z — beyond the small plan only
-                if not self._small:
-                    for r in records:
-                        st = getattr(r.expr, "stacked_gram", None)
-                        if r.kind == "quad" and st is not None and r.expr.gram_candidate is None:
-                            r.expr.gram_candidate = st.require_stack()
-                # transpose(x) * Q * x alone (lazyexpression._rule_bilinear): the canonical node reads Q itself (moi.py, mode "canonical-form") —
-                # MOI terms, or P's CSC values for the device hand-off when x keeps its order under the optimizer's index map
-                if not self._small and self.objective in records and self.objective.kind == "quad":
-                    form = getattr(self.objective.expr, "form_candidate", None)
-                    if form is not None and (self.handoff == "moi" or (
-                            self.handoff == "device" and np.all(np.diff(self.model_var_to_optimizer[form.xvars.vars - 1]) > 0))):
-                        self.objective.form = form
-                # a weighted sum of least-squares blocks over one x (the objective's lsq_sum): combined from the blocks' Gram nodes
-                # (moi.py, mode "canonical-sum") — the MOI boundary of a model beyond the small plan only
-                if not self._small and self.handoff == "moi" and self.objective in records and getattr(self.objective, "form", None) is None:
-                    self.objective.lsq_terms = moi.lsq_sum_terms(self.objective.expr)
-                    for t in self.objective.lsq_terms or ():
-                        if t.kind == "block" and hasattr(t.r, "require_stack"):
-                            t.r.require_stack()
-                # any other quadratic objective: generic device canonicalize! (sorted, duplicates combined) before the MOI copy
-                for r in records:
-                    gram = getattr(r.expr, "gram_candidate", None)
-                    if r.kind == "quad" and not (gram is not None and gram.xvars.strictly_increasing()) and getattr(r, "lsq_terms", None) is None and \
-                            getattr(r, "form", None) is None:
-                        r.expr = r.expr.canonicalize()
-            emitters = [r.compile(ctx, self._varmap_buf, self.quadratic_mode, self.model_var_to_optimizer if early else None) for r in records]
+            varmap = self.model_var_to_optimizer if early else None
+            for r in (r for r in records if r.kind == "quad"):
+                # the one decision on a quadratic record's form (moi.quad_plan); here: the stacked matrices it reads, canonicalize!
+                r.plan = plan = moi.quad_plan(r.expr.lsq_sum, r.expr.lsq_bare, r.kind, r.expr.out.nq, r is self.objective, self.quadratic_mode,
+                                              self._small, self.handoff, varmap)
+                for g in (g for g in [plan.gram] + [t.r for t in plan.terms or ()] if hasattr(g, "require_stack")):
+                    g.require_stack()
+                if plan.canonicalize:
+                    r.expr = r.expr.canonicalize()
+            emitters = [r.compile(ctx, self._varmap_buf, varmap) for r in records]
             self._order = schedule([r.expr for r in records])
             for x in self._order:
                 if isinstance(x, DeviceNode):
@@ -391,7 +366,7 @@ class Model:
                 # Constraint, src/moi_interop.jl:168-175).  Beside a canonical least-squares objective they go to the plan's side lane:
                 # queued behind the contraction's small reductions, they run while its workgroups drain and its fix-up pass runs,
                 # instead of adding their kernels and in-stream gaps behind it.
-                gram = any(_is_gram_record(r) for r in records)
+                gram = any(r.plan.gram_record for r in records)
                 self._lane_records = []
                 # one small kernel on the lane does not pay (config 2: the co-resident pack slows the contraction by what it saves); several
                 # do (config 3: -0.15 ms), and so does the device hand-off, whose launches join them on the lane
@@ -406,7 +381,7 @@ class Model:
                     # a SMALL model: the records are independent of each other, so the one whose MOI copy is not an interpreter node — the
                     # canonical least-squares objective beyond tiny shapes (gram_tall.hip: two launches) — goes last; the constraints' packs
                     # then join the run of small entries at the front of the tape (callbacks, residual) in its ONE launch
-                    emit_order = [re for re in emit_order if not _is_gram_record(re[0])] + [re for re in emit_order if _is_gram_record(re[0])]
+                    emit_order = [re for re in emit_order if not re[0].plan.gram_record] + [re for re in emit_order if re[0].plan.gram_record]
                 elif use_lane:
                     # round 6c: the side lane's records go in FRONT of the objective — its one-launch node (gram_mid.hip) holds every CU
                     # with persistent workgroups and lane entries recorded behind it wait for it; recorded first they take CUs first and

@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import LT, QT, VAT, ArgumentError, DimensionMismatch, ErrorException
-from .device import DAff, DAffVec, DDenseAff, DQuad, DSparseAff, DVarsAff, P
+from .device import DAff, DAffVec, DDenseAff, DQuad, DSparseAff, DStackedAff, DVarsAff, P
 from .functions import AffineFunction, LinearTerm, QuadraticFunction, QuadraticTerm, Variable, _isnum
 from .lazyexpression import DeviceNode, kind_of
 
@@ -161,14 +161,32 @@ def _gram_rows(gram):
     return padded
 
 
+def _gram_args(g):
+    """the leading arguments of the Gram family: r = mat*x (+|-) vec"""
+    vec = g.vec.buf if g.vec is not None else None
+    return (P(g.mat.buf), g.mat.lda, _gram_rows(g), g.mat.cols, P(g.xvars.buf), P(vec), g.sign if vec else 0)
+
+
+def _gram_workspace(ctx, g):
+    return ctx.alloc(max(16, int(ctx.lib.pmt_quad_gram_workspace_bytes(_gram_rows(g), g.mat.cols))))
+
+
+def _form_args(q, varmap_buf, alpha):                                    # the leading arguments of pmt_quad_form_f64
+    return (P(q.mat.buf), q.mat.lda, q.mat.cols, P(q.xvars.buf), 1, P(varmap_buf), alpha)
+
+
 class _Record:
     """Common part of Objective and Constraint (src/moi_interop.jl:113-129, 141-166)."""
+    mode = property(lambda self: self.plan.mode)                          # "literal" / "canonical" / "canonical-csc" / "-form" / "-sum"
+    lsq_terms = property(lambda self: self.plan.terms)                    # the LsqTerm list a "canonical-sum" record combines, or None
 
     def _setup(self, model, expr):
         self.model = model
         self.expr = expr
         self.isconstant = not isinstance(expr, DeviceNode)                # "it's just a value; not a LazyExpression" (:123)
         self.dev = None                                                   # device twin of the MOI buffers (set by compile)
+        self.plan = QuadPlan(None)                                        # a quadratic record's is decided in Model.initialize (quad_plan)
+        self._quad_delivered = False                                      # the contraction itself delivers f.quadratic_terms
         if self.isconstant:
             self.kind = canonical_function_kind(kind_of(expr))
             native = _to_native(self.kind, expr)
@@ -185,7 +203,7 @@ class _Record:
             self.nrows = expr.out.rows if self.kind == "affvec" else 1
 
     # ---- device side of update!(moi_f, expr(), varmap)
-    def compile(self, ctx, varmap_buf, quadratic_mode, handoff_varmap=None):
+    def compile(self, ctx, varmap_buf, handoff_varmap=None):
         """Allocate the MOI buffers (host + device twin) and return the emitter of the MOI copy.  `handoff_varmap` (host array,
         device hand-off only): the final model_var_to_optimizer; a Gram objective whose variables stay in increasing order under it
         writes the solver's CSC values of P directly from the contraction's epilogue and no quadratic term structs at all."""
@@ -218,18 +236,13 @@ class _Record:
                     c.call("pmt_copy_bytes", P(dconst), P(out.const), 8)
             return emit
         if self.kind == "quad":
-            gram = getattr(self.expr, "gram_candidate", None)
-            literal_terms = out.nq
-            use_gram = gram is not None and gram.xvars.strictly_increasing() and (
-                quadratic_mode == "canonical" or (quadratic_mode == "auto" and literal_terms > (1 << 24)))
-            if use_gram and handoff_varmap is not None and np.all(np.diff(handoff_varmap[gram.xvars.vars - 1]) > 0):
+            plan, gram = self.plan, self.plan.gram
+            if plan.mode == "canonical-csc":
                 n = gram.mat.cols
                 self.f = ScalarQuadraticFunction(n, 0, alloc=ctx.pinned_array)
                 dp, dl, dc = ctx.alloc(8 * max(n * (n + 1) // 2, 1)), ctx.alloc(16 * max(n, 1)), ctx.alloc(8)
-                ws = ctx.alloc(max(16, int(ctx.lib.pmt_quad_gram_workspace_bytes(_gram_rows(gram), n))))
+                ws = _gram_workspace(ctx, gram)
                 self.dev = {"P_values": dp, "P_vars": handoff_varmap[gram.xvars.vars - 1], "lin": dl, "const": dc}
-                self.mode = "canonical-csc"
-                vec = gram.vec.buf if gram.vec is not None else None
                 alpha = -1.0 if self.model.sense == "Maximize" else 1.0
                 host_P = None
                 if getattr(self.model, "handoff", "") == "host_csc" and getattr(self.model, "_overlap_fetch", False):
@@ -240,41 +253,32 @@ class _Record:
 
                 def emit(c):
                     if host_P is not None:
-                        c.call("pmt_quad_gram_csc_deliver_f64", P(gram.mat.buf), gram.mat.lda, _gram_rows(gram), n, P(gram.xvars.buf), P(vec),
-                               gram.sign if vec else 0, P(varmap_buf), alpha, P(dp), host_P.ctypes.data_as(C.c_void_p), 0, P(dl), P(dc), P(ws))
+                        c.call("pmt_quad_gram_csc_deliver_f64", *_gram_args(gram), P(varmap_buf), alpha, P(dp), host_P.ctypes.data_as(C.c_void_p), 0,
+                               P(dl), P(dc), P(ws))
                     else:
-                        c.call("pmt_quad_gram_csc_f64", P(gram.mat.buf), gram.mat.lda, _gram_rows(gram), n, P(gram.xvars.buf), P(vec),
-                               gram.sign if vec else 0, P(varmap_buf), alpha, P(dp), None, P(dl), P(dc), P(ws))
+                        c.call("pmt_quad_gram_csc_f64", *_gram_args(gram), P(varmap_buf), alpha, P(dp), None, P(dl), P(dc), P(ws))
                 return emit
-            if use_gram:
+            if plan.mode == "canonical":
                 n = gram.mat.cols
                 nq = n * (n + 1) // 2
                 self.f = ScalarQuadraticFunction(n, nq, alloc=ctx.pinned_array)
                 dq, dl, dc = twin(self.f.quadratic_terms, 24 * nq), twin(self.f.affine_terms, 16 * n), twin(self._cbuf, 8)
-                ws = ctx.alloc(max(16, int(ctx.lib.pmt_quad_gram_workspace_bytes(_gram_rows(gram), n))))
+                ws = _gram_workspace(ctx, gram)
                 self.dev = {"quad": dq, "lin": dl, "const": dc}
-                self.mode = "canonical"
-                vec = gram.vec.buf if gram.vec is not None else None
-
-                deliver = bool(getattr(self.model, "_overlap_moi", False)) and nq > 0
-                self._quad_delivered = deliver
+                deliver = self._quad_delivered = bool(getattr(self.model, "_overlap_moi", False)) and nq > 0
 
                 def emit(c):
                     if deliver:
                         # the quadratic terms leave for f.quadratic_terms (page-locked) row band by row band while the contraction runs
-                        c.call("pmt_quad_gram_deliver_f64", P(gram.mat.buf), gram.mat.lda, _gram_rows(gram), n, P(gram.xvars.buf), P(vec),
-                               gram.sign if vec else 0, 1, P(varmap_buf), P(dq), self.f.quadratic_terms.ctypes.data_as(C.c_void_p), 0, P(dl), P(dc), P(ws))
+                        c.call("pmt_quad_gram_deliver_f64", *_gram_args(gram), 1, P(varmap_buf), P(dq), self.f.quadratic_terms.ctypes.data_as(C.c_void_p), 0,
+                               P(dl), P(dc), P(ws))
                     else:
-                        c.call("pmt_quad_gram_f64", P(gram.mat.buf), gram.mat.lda, _gram_rows(gram), n, P(gram.xvars.buf), P(vec), gram.sign if vec else 0,
-                               1, P(varmap_buf), P(dq), P(dl), P(dc), P(ws))
+                        c.call("pmt_quad_gram_f64", *_gram_args(gram), 1, P(varmap_buf), P(dq), P(dl), P(dc), P(ws))
                 return emit
-            form = getattr(self, "form", None)
-            if form is not None:
-                return self._compile_form(ctx, varmap_buf, form, handoff_varmap)
-            terms = getattr(self, "lsq_terms", None)
-            if terms is not None:
-                return self._compile_lsq_sum(ctx, varmap_buf, terms)
-            self.mode = "literal"
+            if plan.mode == "canonical-form":
+                return self._compile_form(ctx, varmap_buf, plan.form, handoff_varmap)
+            if plan.mode == "canonical-sum":
+                return self._compile_lsq_sum(ctx, varmap_buf, plan.terms)
             out.materialize()
             self.f = ScalarQuadraticFunction(out.nl, out.nq, alloc=ctx.pinned_array)
             dq, dl = twin(self.f.quadratic_terms, 24 * out.nq), twin(self.f.affine_terms, 16 * out.nl)
@@ -385,12 +389,10 @@ class _Record:
         return emit
 
     def _compile_form(self, ctx, varmap_buf, form, handoff_varmap):
-        """transpose(x) * Q * x alone (Model.initialize set self.form): pmt_quad_form_f64 reads the Parameter matrix and writes the canonical
+        """transpose(x) * Q * x alone (plan.form): pmt_quad_form_f64 reads the Parameter matrix and writes the canonical
         MOI function — n(n+1)/2 quadratic terms, no linear terms, constant 0.0 — or, for the device hand-off, the CSC values of P."""
         n = form.mat.cols
         nq = n * (n + 1) // 2
-        self.mode = "canonical-form"
-        self._quad_delivered = False
         if handoff_varmap is not None:
             self.f = ScalarQuadraticFunction(n, 0, alloc=ctx.pinned_array)
             dp, dl, dc = ctx.alloc(8 * nq), ctx.alloc(16 * n), ctx.alloc(8)
@@ -398,18 +400,18 @@ class _Record:
             alpha = -1.0 if self.model.sense == "Maximize" else 1.0
 
             def emit(c):
-                c.call("pmt_quad_form_f64", P(form.mat.buf), form.mat.lda, n, P(form.xvars.buf), 1, P(varmap_buf), alpha, None, P(dp), P(dl), P(dc))
+                c.call("pmt_quad_form_f64", *_form_args(form, varmap_buf, alpha), None, P(dp), P(dl), P(dc))
             return emit
         self.f = ScalarQuadraticFunction(0, nq, alloc=ctx.pinned_array)
         dq, dc = ctx.alloc(24 * nq), ctx.alloc(8)
         self.dev = {"quad": dq, "const": dc}
 
         def emit(c):
-            c.call("pmt_quad_form_f64", P(form.mat.buf), form.mat.lda, n, P(form.xvars.buf), 1, P(varmap_buf), 1.0, P(dq), None, None, P(dc))
+            c.call("pmt_quad_form_f64", *_form_args(form, varmap_buf, 1.0), P(dq), None, None, P(dc))
         return emit
 
     def _compile_lsq_sum(self, ctx, varmap_buf, terms):
-        """The objective as a weighted sum of least-squares blocks over one x (lsq_sum_terms): block 1 by pmt_quad_gram_f64 straight into the
+        """The objective as a weighted sum of least-squares blocks over one x (plan.terms): block 1 by pmt_quad_gram_f64 straight into the
         MOI buffers, blocks 2..K as CSC values (pmt_quad_gram_csc_f64, bit for bit the same coefficients), then pmt_quad_gram_sum_f64 weights
         and adds everything in place.  A form transpose(x) * Q * x stands where a block stands: pmt_quad_form_f64 writes the same outputs
         (its linear terms and constant are zero).  The terms are final only after the combine: no overlapped delivery of the quadratic terms."""
@@ -421,9 +423,7 @@ class _Record:
         self.f = ScalarQuadraticFunction(n, nq, alloc=ctx.pinned_array)
         dq, dl, dc = ctx.alloc(24 * max(nq, 1)), ctx.alloc(16 * max(n, 1)), ctx.alloc(8)
         self.dev = {"quad": dq, "lin": dl, "const": dc}
-        self.mode = "canonical-sum"
-        self._quad_delivered = False
-        ws = [ctx.alloc(max(16, int(ctx.lib.pmt_quad_gram_workspace_bytes(_gram_rows(t.r), n)))) if t.kind == "block" else None for t in blocks]
+        ws = [_gram_workspace(ctx, t.r) if t.kind == "block" else None for t in blocks]
         # per block 2..K: its CSC values, linear terms and constant
         parts = [(ctx.alloc(8 * max(nq, 1)), ctx.alloc(16 * max(n, 1)), ctx.alloc(8)) for _ in blocks[1:]]
         desc, k = [], 0
@@ -455,19 +455,14 @@ class _Record:
             counts = np.array([len(p) if p is not None else 0 for p in lists], dtype=np.int64)
             self._sub_args = (ptrs, counts)
 
-        def gram_args(g):
-            vec = g.vec.buf if g.vec is not None else None
-            return (P(g.mat.buf), g.mat.lda, _gram_rows(g), n, P(g.xvars.buf), P(vec), g.sign if vec else 0)
-
         def emit_block(c, t, w, first, part):
             if t.kind == "form":
-                q = t.r
                 outs = (P(dq), None, P(dl), P(dc)) if first else (None, P(part[0]), P(part[1]), P(part[2]))
-                c.call("pmt_quad_form_f64", P(q.mat.buf), q.mat.lda, n, P(q.xvars.buf), 1, P(varmap_buf), 1.0, *outs)
+                c.call("pmt_quad_form_f64", *_form_args(t.r, varmap_buf, 1.0), *outs)
             elif first:
-                c.call("pmt_quad_gram_f64", *gram_args(t.r), 1, P(varmap_buf), P(dq), P(dl), P(dc), P(w))
+                c.call("pmt_quad_gram_f64", *_gram_args(t.r), 1, P(varmap_buf), P(dq), P(dl), P(dc), P(w))
             else:
-                c.call("pmt_quad_gram_csc_f64", *gram_args(t.r), P(varmap_buf), 1.0, P(part[0]), None, P(part[1]), P(part[2]), P(w))
+                c.call("pmt_quad_gram_csc_f64", *_gram_args(t.r), P(varmap_buf), 1.0, P(part[0]), None, P(part[1]), P(part[2]), P(w))
 
         def emit(c):
             emit_block(c, blocks[0], ws[0], True, None)
@@ -493,7 +488,7 @@ class _Record:
             ctx.record_fetch(f.terms, d["terms"], f.terms.nbytes)
             ctx.record_fetch(self._c, d["const"], 8)
         elif self.kind == "quad":
-            if "quad" in d and not getattr(self, "_quad_delivered", False):
+            if "quad" in d and not self._quad_delivered:
                 ctx.record_fetch(f.quadratic_terms, d["quad"], f.quadratic_terms.nbytes)
             if "lin" in d:                                                # (absent for a bare form: no linear terms)
                 ctx.record_fetch(f.affine_terms, d["lin"], f.affine_terms.nbytes)
@@ -540,35 +535,70 @@ class _Record:
             self.f.constant = float(self._c[0])
 
 
-def lsq_sum_terms(expr):
-    """The LsqTerm list of an objective the canonical-sum path takes (Model.initialize checks the model-level conditions), or None:
-    1 .. 8 least-squares blocks — forms transpose(x) * Q * x count among them —, at most PMT_LSQ_MAX_TERMS terms, every block over the same
-    strictly increasing x (a stacked block over its sorted union z), every diagonal / linear term over x or a strictly increasing part of it (pmt_quad_gram_sum_sub_f64, whose launch holds
-    at most PMT_LSQ_MAX_RUNS runs of positions)."""
+def _lsq_sum_combines(terms):
+    """Whether pmt_quad_gram_sum_f64 / _sub_f64 can combine this LsqTerm list: 1 .. PMT_LSQ_MAX_BLOCKS least-squares blocks — forms
+    transpose(x) * Q * x count among them —, at most PMT_LSQ_MAX_TERMS terms, every block over the same strictly increasing x (a stacked block
+    over its sorted union z), every diagonal / linear term over x or a strictly increasing part of it (pmt_quad_gram_sum_sub_f64, whose launch
+    holds at most PMT_LSQ_MAX_RUNS runs of positions)."""
     from . import _lib
-    terms = getattr(expr, "lsq_sum", None) if isinstance(expr, DeviceNode) else None
-    if not terms or len(terms) > _lib.PMT_LSQ_MAX_TERMS or getattr(expr, "gram_candidate", None) is not None:
-        return None
-    blocks = [t for t in terms if t.kind in ("block", "form")]
-    if not 1 <= len(blocks) <= _lib.PMT_LSQ_MAX_BLOCKS:
-        return None
+    blocks = [t for t in terms or () if t.kind in ("block", "form")]
+    if len(terms or ()) > _lib.PMT_LSQ_MAX_TERMS or not 1 <= len(blocks) <= _lib.PMT_LSQ_MAX_BLOCKS or not blocks[0].r.xvars.strictly_increasing():
+        return False
     x = blocks[0].r.xvars
-    if not x.strictly_increasing():
-        return None
     runs = 0
     for t in terms:
         if t.kind in ("block", "form"):
             if not np.array_equal(t.r.xvars.vars, x.vars):
-                return None
+                return False
         elif t.xvars is not None and not np.array_equal(t.xvars.vars, x.vars):
             v = t.xvars.vars
             pos = np.searchsorted(x.vars, v)
             if not (len(v) and np.all(np.diff(v) > 0) and np.all(pos < len(x.vars)) and np.array_equal(x.vars[np.minimum(pos, len(x.vars) - 1)], v)):
-                return None
+                return False
             runs += _lib.column_runs(pos)
-    if runs > _lib.PMT_LSQ_MAX_RUNS:
-        return None
-    return terms
+    return runs <= _lib.PMT_LSQ_MAX_RUNS
+
+
+class QuadPlan:
+    """How a quadratic record reaches its MOI function (quad_plan decides; Model.initialize and _Record.compile execute): the mode and what it
+    reads — the operand r of dot(r, r) (`gram`), the QuadForm (`form`) or the LsqTerm list (`terms`); `canonicalize`: through canonicalize! first."""
+    def __init__(self, mode, gram=None, form=None, terms=None, canonicalize=False):
+        self.mode, self.gram, self.form, self.terms, self.canonicalize = mode, gram, form, terms, canonicalize
+        # the MOI copy is the canonical least-squares node, bare or the weighted sum of such nodes (Model.initialize: side lane, small-plan order)
+        self.gram_record = mode in ("canonical", "canonical-csc", "canonical-sum")
+
+
+def quad_plan(terms, bare, kind, nq, is_objective, quadratic_mode, small, handoff, varmap=None):
+    """The QuadPlan of a record over a node described by (terms, bare) = DeviceNode.(lsq_sum, lsq_bare); no mode unless kind == "quad".  `nq`:
+    the terms of its literal expansion; `small`: Model._small; `varmap`: the optimizer's index map when it is fixed before the plan is recorded
+    (handoff "device" / "host_csc").  Host data only: nothing is allocated, no stacked matrix is asked for.  First match wins."""
+    if kind != "quad" or quadratic_mode == "literal":
+        return QuadPlan("literal" if kind == "quad" else None)
+    one = terms[0] if bare else None
+    block = one.r if bare and one.kind == "block" else None
+
+    def ordered(x):                       # x keeps its order under the index map fixed early
+        return handoff in ("device", "host_csc") and bool(np.all(np.diff(varmap[x.vars - 1]) > 0))
+    def gram_plan(g):                     # (ordered: P's CSC values straight from the contraction's epilogue, no quadratic term structs)
+        return QuadPlan("canonical-csc" if ordered(g.xvars) else "canonical", gram=g)
+    # dot(r, r), r = A*x (+|-) b over a strictly increasing x: the Gram node, in any record and any model — asked for, or ("auto") above 2^24 terms
+    if isinstance(block, DDenseAff) and block.xvars.strictly_increasing() and (quadratic_mode == "canonical" or nq > (1 << 24)):
+        return gram_plan(block)
+    if quadratic_mode == "auto":
+        return QuadPlan("literal")
+    if not small:
+        # dot(r, r) of a stacked residual (lazyexpression._stacked_form): the Gram node of its stacked matrix over the union z — beyond the small plan only
+        if isinstance(block, DStackedAff) and block.xvars.strictly_increasing():
+            return gram_plan(block)
+        # transpose(x) * Q * x alone (lazyexpression._rule_bilinear): the canonical node reads Q itself — MOI terms, or P's CSC values for
+        # the device hand-off when x keeps its order under the optimizer's index map
+        if is_objective and bare and one.kind == "form" and (handoff == "moi" or (handoff == "device" and ordered(one.r.xvars))):
+            return QuadPlan("canonical-form", form=one.r)
+        # a weighted sum of least-squares blocks over one x: combined from the blocks' Gram nodes — the MOI boundary of a model beyond the small plan only
+        if is_objective and handoff == "moi" and not bare and _lsq_sum_combines(terms):
+            return QuadPlan("canonical-sum", terms=terms)
+    # anything else: the literal function through the generic device canonicalize! (sorted, duplicates combined) before the MOI copy
+    return QuadPlan("literal", canonicalize=True)
 
 
 class Objective(_Record):                                                 # src/moi_interop.jl:113-137

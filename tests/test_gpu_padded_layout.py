@@ -109,7 +109,7 @@ def test_row_counts_that_are_not_a_multiple_of_16_use_zero_padded_copies(r, n):
     P.objective(model, P.Minimize, P.dot(res, res))
     for _ in range(2):
         P.solve(model)
-        assert A._dev.lda >= row_padded(r) and _gram_rows(model.objective.expr.gram_candidate) == row_padded(r) != r
+        assert A._dev.lda >= row_padded(r) and _gram_rows(model.objective.plan.gram) == row_padded(r) != r
         f = model.objective.f
         iu = np.triu_indices(n)
         np.testing.assert_allclose(f.quadratic_terms["coeff"], (2 * Av.T @ Av)[iu], rtol=1e-12)

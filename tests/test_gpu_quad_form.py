@@ -601,7 +601,7 @@ def test_fallback_modes(case):
     try:
         P.solve(model)
         obj = model.objective
-        assert getattr(obj, "form", None) is None and obj.mode == "literal"
+        assert obj.plan.form is None and obj.mode == "literal"
         if case == "small":
             assert model._small
         if case in ("auto", "literal"):
