@@ -326,6 +326,38 @@ int pmt_quad_gram_sum_sub_f64(int64_t cols, const pmt_lsq_term *terms, int nterm
 int pmt_quad_form_f64(const double *Q, int64_t ldq, int64_t n, const int64_t *xvar, int moi, const int64_t *varmap, double alpha,
                       pmt_quadratic_term *out_quad, double *out_P_values, pmt_linear_term *out_lin, double *out_const, void *stream);
 
+/* A sum whose least-squares blocks and forms lie over 2 .. PMT_QUAD_MAX_GROUPS pairwise DISJOINT, strictly increasing Variable vectors
+ * (transpose(x)*Q*x + transpose(u)*R*u; dot(r1, r1) + w*dot(r2, r2) with r1 over x and r2 over u) as one canonical MOI function.  No pair
+ * (j, k) is shared between two groups, so canonicalize! (src/functions.jl:381-386) combines nothing across them.  With z the sorted union
+ * of the groups' variables and n_g the size of group g, the function has sum_g n_g(n_g+1)/2 quadratic terms, sum_g n_g linear terms and
+ * one constant:
+ *   quadratic terms  rows in increasing model-variable index over z; row j of group g holds g's columns k >= j in increasing order — the
+ *                    (row, col) order of canonicalize! on the literal function; indices through the varmap.  Every term equals, word for
+ *                    word, the term pmt_quad_gram_sum_f64 / _sum_sub_f64 leaves for that group's term list alone (block 1 of the group by
+ *                    pmt_quad_gram_f64 or pmt_quad_form_f64; a group of one block with weight 1: only its diagonal, linear terms and
+ *                    constant are touched).
+ *   linear terms     the groups' linear terms merged by increasing variable, word for word.
+ *   constant         ((c_1 + c_2) + ..) + c_G over the groups' constants, groups in the order of the first appearance of one of their
+ *                    blocks in the expression (scalar constants of the expression belong to group 1); no fma.
+ * A group whose variables are consecutive in z owns one slice of out_quad / out_lin, and the entry points above write straight into it
+ * (term offset: the terms of the rows before it; an odd offset is an address 8 mod 16, which every one of them takes).  Otherwise the
+ * groups write into an arena of their own and pmt_quad_groups_gather_f64 places the rows:
+ *   out_quad words row_dst[r] .. row_dst[r+1]-1 = src_quad words row_src[r] ..   for r = 0 .. nrows-1   (a term is three 8-byte words)
+ *   out_lin[j] = src_lin[lin_src[j]]                                              for j = 0 .. nlin-1
+ * row_src (nrows), row_dst (nrows + 1, increasing, row_dst[0] = 0, row_dst[nrows] = 3*nterms: every row holds at least one term) and
+ * lin_src (nlin) are DEVICE tables built once; the call does no host work beyond the launch.  Source and destination segments may differ
+ * in parity; out_quad needs 8-byte alignment only; nothing outside the nterms / nlin terms is written.  HBM-bound: 48 bytes per
+ * quadratic term.  A negative size or nterms < nrows: PMT_DIMENSION_MISMATCH; a null table or array that a non-zero size needs:
+ * PMT_INVALID_ARGUMENT — before any device call (csrc/groups.hip). */
+#define PMT_QUAD_MAX_GROUPS 8
+int pmt_quad_groups_gather_f64(const pmt_quadratic_term *src_quad, const int64_t *row_src, const int64_t *row_dst, int64_t nrows,
+                               int64_t nterms, const pmt_linear_term *src_lin, const int64_t *lin_src, int64_t nlin,
+                               pmt_quadratic_term *out_quad, pmt_linear_term *out_lin, void *stream);
+/* *out_const = ((group_consts[0] + group_consts[1]) + ..) + group_consts[ngroups-1] (device doubles; out_const may be group_consts[0]).
+ * Queued behind the groups' own constant steps; in a plan's replay behind deferred stream-K constants, exactly as the constant step of
+ * pmt_quad_gram_sum_f64.  ngroups outside 1 .. PMT_QUAD_MAX_GROUPS or a null pointer: PMT_INVALID_ARGUMENT before any device call. */
+int pmt_quad_groups_constant_f64(const double *group_consts, int ngroups, double *out_const, void *stream);
+
 /* host: block until every copy on the fetch stream of `stream` (a HIP stream, not a recording handle) has landed.  PMT_HIP_ERROR when a
  * delivery failed on the device: a transfer that never started, a courier without progress, or a split tile of a staged contraction whose
  * first half never arrived (the tile is then NaN in out_P_values / out_quad — never a plausible half sum — and this call says so). */

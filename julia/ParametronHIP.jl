@@ -174,6 +174,17 @@ quad_form!(out_quad, out_P_values, out_lin, out_const, Q, ldq, n, xvar, moi, var
                 (DevPtr, Int64, Int64, DevPtr, Cint, DevPtr, Cdouble, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
                 Q, ldq, n, xvar, moi, varmap, alpha, out_quad, out_P_values, out_lin, out_const, stream))
 
+"rows of the groups' canonical functions (an arena, src_quad / src_lin) placed in the function over the sorted union of their disjoint
+ variable sets: device tables row_src (nrows), row_dst (nrows + 1) in 8-byte words, lin_src (nlin) — include/parametron_hip.h"
+quad_groups_gather!(out_quad, out_lin, src_quad, row_src, row_dst, nrows, nterms, src_lin, lin_src, nlin, stream) =
+    check(ccall((:pmt_quad_groups_gather_f64, lib), Cint,
+                (DevPtr, DevPtr, DevPtr, Int64, Int64, DevPtr, DevPtr, Int64, DevPtr, DevPtr, Ptr{Cvoid}),
+                src_quad, row_src, row_dst, nrows, nterms, src_lin, lin_src, nlin, out_quad, out_lin, stream))
+
+"out_const = ((c_1 + c_2) + ..) + c_G over the groups' constants (device doubles), queued behind their own constant steps"
+quad_groups_constant!(out_const, group_consts, ngroups, stream) =
+    check(ccall((:pmt_quad_groups_constant_f64, lib), Cint, (DevPtr, Cint, DevPtr, Ptr{Cvoid}), group_consts, ngroups, out_const, stream))
+
 "structure of a solver matrix from 1-based (row, col) indices (host, once): perm, seg_ptr, colptr, rowval (0-based), nnz"
 function csc_order(rows::Vector{Int64}, cols::Vector{Int64}, nrows, ncols; upper::Bool=false)
     n = length(rows)

@@ -19,6 +19,7 @@ VAT = np.dtype([("out", "<i8"), ("coeff", "<f8"), ("var", "<i8")])
 PMT_OK, PMT_DIMENSION_MISMATCH, PMT_INVALID_ARGUMENT, PMT_HIP_ERROR, PMT_STATE_ERROR, PMT_OUT_OF_MEMORY = range(6)
 PMT_LSQ_BLOCK, PMT_LSQ_DIAG, PMT_LSQ_LINEAR, PMT_LSQ_CONSTANT = 1, 2, 3, 4
 PMT_LSQ_MAX_TERMS, PMT_LSQ_MAX_BLOCKS, PMT_LSQ_MAX_RUNS = 32, 8, 64
+PMT_QUAD_MAX_GROUPS = 8
 STACK_COLUMN = np.dtype([("src", "<u8"), ("sign", "<i8")])       # pmt_stack_column
 
 
@@ -59,6 +60,40 @@ def column_runs(positions):
     """the number of runs of consecutive positions in a strictly increasing list (pmt_quad_gram_sum_sub_f64 holds PMT_LSQ_MAX_RUNS)"""
     p = np.asarray(positions, dtype=np.int64)
     return int(len(p) and 1 + np.count_nonzero(np.diff(p) != 1))
+
+
+class GroupsLayout:
+    """Where the canonical functions of groups over pairwise disjoint, strictly increasing variable sets (`sets`, in group order) stand in
+    the function over their sorted union z (include/parametron_hip.h, pmt_quad_groups_gather_f64).  Offsets in terms; the arena holds the
+    groups' functions one behind the other in group order.
+      z, owner              the union and the group of each of its variables
+      ordered               every group's variables are consecutive in z: its function is one slice of the destination
+      dst_quad, dst_lin     per group, the slice's first term (meaningful when ordered)
+      src_quad, src_lin     per group, its first term in the arena
+      row_src, row_dst      the gather's tables in 8-byte words (row_dst: len(z) + 1 entries);  lin_src: per variable of z, its arena term"""
+
+    def __init__(self, sets):
+        sets = [np.asarray(s, dtype=np.int64).reshape(-1) for s in sets]
+        n = np.array([len(s) for s in sets], dtype=np.int64)
+        if len(sets) < 1 or np.any(n < 1) or any(np.any(np.diff(s) <= 0) for s in sets):
+            raise ArgumentError("groups_layout: every group needs a non-empty, strictly increasing variable set")
+        z = np.concatenate(sets)
+        order = np.argsort(z, kind="stable")
+        self.z = z[order]
+        if np.any(np.diff(self.z) == 0):
+            raise ArgumentError("groups_layout: the groups' variable sets overlap")
+        self.owner = owner = np.repeat(np.arange(len(sets), dtype=np.int64), n)[order]
+        local = np.concatenate([np.arange(k, dtype=np.int64) for k in n])[order]          # the variable's position in its group
+        self.src_quad = np.concatenate([[0], np.cumsum(n * (n + 1) // 2)[:-1]]).astype(np.int64)
+        self.src_lin = np.concatenate([[0], np.cumsum(n)[:-1]]).astype(np.int64)
+        ng = n[owner]
+        self.row_dst = 3 * np.concatenate([[0], np.cumsum(ng - local)]).astype(np.int64)
+        self.row_src = 3 * (self.src_quad[owner] + local * ng - local * (local - 1) // 2)
+        self.lin_src = self.src_lin[owner] + local
+        self.nterms, self.nlin = int(self.row_dst[-1]) // 3, len(self.z)
+        self.ordered = int(np.count_nonzero(np.diff(owner))) == len(sets) - 1
+        first = np.array([int(np.flatnonzero(owner == g)[0]) for g in range(len(sets))], dtype=np.int64)
+        self.dst_quad, self.dst_lin = self.row_dst[first] // 3, first
 
 
 class DimensionMismatch(Exception):
@@ -110,6 +145,8 @@ SIGNATURES = {
     "pmt_quad_gram_sum_sub_f64": (_ci, [_i64, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pmt_affine_stack_columns_f64": (_ci, [_vp, _i64, _i64, _vp, _i64, _vp]),
     "pmt_quad_form_f64": (_ci, [_vp, _i64, _i64, _vp, _ci, _vp, _f64, _vp, _vp, _vp, _vp, _vp]),
+    "pmt_quad_groups_gather_f64": (_ci, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "pmt_quad_groups_constant_f64": (_ci, [_vp, _ci, _vp, _vp]),
     "pmt_fetch_synchronize": (_ci, [_vp]),
     "pmt_set_host_delivery": (_ci, [_ci]),
     "pmt_get_host_delivery": (_ci, [_ci, C.POINTER(_ci), C.POINTER(_ci)]),

@@ -347,7 +347,7 @@ class Model:
                 # the one decision on a quadratic record's form (moi.quad_plan); here: the stacked matrices it reads, canonicalize!
                 r.plan = plan = moi.quad_plan(r.expr.lsq_sum, r.expr.lsq_bare, r.kind, r.expr.out.nq, r is self.objective, self.quadratic_mode,
                                               self._small, self.handoff, varmap)
-                for g in (g for g in [plan.gram] + [t.r for t in plan.terms or ()] if hasattr(g, "require_stack")):
+                for g in (g for g in plan.operands() if hasattr(g, "require_stack")):
                     g.require_stack()
                 if plan.canonicalize:
                     r.expr = r.expr.canonicalize()

@@ -177,7 +177,7 @@ def _form_args(q, varmap_buf, alpha):                                    # the l
 
 class _Record:
     """Common part of Objective and Constraint (src/moi_interop.jl:113-129, 141-166)."""
-    mode = property(lambda self: self.plan.mode)                          # "literal" / "canonical" / "canonical-csc" / "-form" / "-sum"
+    mode = property(lambda self: self.plan.mode)                          # "literal" / "canonical" / "canonical-csc" / "-form" / "-sum" / "-groups"
     lsq_terms = property(lambda self: self.plan.terms)                    # the LsqTerm list a "canonical-sum" record combines, or None
 
     def _setup(self, model, expr):
@@ -279,6 +279,8 @@ class _Record:
                 return self._compile_form(ctx, varmap_buf, plan.form, handoff_varmap)
             if plan.mode == "canonical-sum":
                 return self._compile_lsq_sum(ctx, varmap_buf, plan.terms)
+            if plan.mode == "canonical-groups":
+                return self._compile_groups(ctx, varmap_buf, plan.groups)
             out.materialize()
             self.f = ScalarQuadraticFunction(out.nl, out.nq, alloc=ctx.pinned_array)
             dq, dl = twin(self.f.quadratic_terms, 24 * out.nq), twin(self.f.affine_terms, 16 * out.nl)
@@ -415,14 +417,21 @@ class _Record:
         MOI buffers, blocks 2..K as CSC values (pmt_quad_gram_csc_f64, bit for bit the same coefficients), then pmt_quad_gram_sum_f64 weights
         and adds everything in place.  A form transpose(x) * Q * x stands where a block stands: pmt_quad_form_f64 writes the same outputs
         (its linear terms and constant are zero).  The terms are final only after the combine: no overlapped delivery of the quadratic terms."""
+        n = [t for t in terms if t.kind in ("block", "form")][0].r.mat.cols
+        nq = n * (n + 1) // 2
+        self.f = ScalarQuadraticFunction(n, nq, alloc=ctx.pinned_array)
+        dq, dl, dc = ctx.alloc(24 * max(nq, 1)), ctx.alloc(16 * max(n, 1)), ctx.alloc(8)
+        self.dev = {"quad": dq, "lin": dl, "const": dc}
+        return self._lsq_sum_emitter(ctx, varmap_buf, terms, dq, dl, dc)
+
+    def _lsq_sum_emitter(self, ctx, varmap_buf, terms, dq, dl, dc):
+        """The steps of _compile_lsq_sum for the term list `terms`, writing the function into the device buffers dq / dl / dc (addresses;
+        n(n+1)/2 quadratic terms, n linear terms, the constant) — the whole objective's, or one group's part of it (_compile_groups)."""
         from . import _lib
         blocks = [t for t in terms if t.kind in ("block", "form")]
         g1 = blocks[0].r
         n = g1.mat.cols
         nq = n * (n + 1) // 2
-        self.f = ScalarQuadraticFunction(n, nq, alloc=ctx.pinned_array)
-        dq, dl, dc = ctx.alloc(24 * max(nq, 1)), ctx.alloc(16 * max(n, 1)), ctx.alloc(8)
-        self.dev = {"quad": dq, "lin": dl, "const": dc}
         ws = [_gram_workspace(ctx, t.r) if t.kind == "block" else None for t in blocks]
         # per block 2..K: its CSC values, linear terms and constant
         parts = [(ctx.alloc(8 * max(nq, 1)), ctx.alloc(16 * max(n, 1)), ctx.alloc(8)) for _ in blocks[1:]]
@@ -450,10 +459,9 @@ class _Record:
                  for t in terms]
         sub = any(p is not None for p in lists)
         if sub:
-            self._sub_lists = lists                                      # (the entry reads them when the call is recorded)
             ptrs = (C.c_void_p * len(lists))(*[p.ctypes.data if p is not None else None for p in lists])
             counts = np.array([len(p) if p is not None else 0 for p in lists], dtype=np.int64)
-            self._sub_args = (ptrs, counts)
+            self._sub_args = getattr(self, "_sub_args", []) + [(lists, ptrs, counts)]     # (the entry reads them when the call is recorded)
 
         def emit_block(c, t, w, first, part):
             if t.kind == "form":
@@ -473,6 +481,37 @@ class _Record:
                        P(dq), P(dl), P(dc))
             else:
                 c.call("pmt_quad_gram_sum_f64", n, C.addressof(arr), len(desc), P(dq), P(dl), P(dc))
+        return emit
+
+    def _compile_groups(self, ctx, varmap_buf, groups):
+        """The objective as a sum over groups of blocks / forms with pairwise disjoint Variable vectors (plan.groups): every group is written
+        by the steps of its own canonical-sum list (_lsq_sum_emitter) — straight into its slice of the MOI buffers when the groups' variables
+        are consecutive in the sorted union z (pointer + offset: no copy, no extra pass), into an arena otherwise, from where
+        pmt_quad_groups_gather_f64 places the rows through tables built here.  pmt_quad_groups_constant_f64 adds the groups' constants.
+        As in canonical-sum the terms are final only after the last step: no overlapped delivery of the quadratic terms."""
+        from . import _lib
+        lay = _lib.GroupsLayout([g.vars for g in groups])
+        G, n, nq = len(groups), lay.nlin, lay.nterms
+        self.f = ScalarQuadraticFunction(n, nq, alloc=ctx.pinned_array)
+        dq, dl, dc, consts = ctx.alloc(24 * nq), ctx.alloc(16 * n), ctx.alloc(8), ctx.alloc(8 * G)
+        self.dev = {"quad": dq, "lin": dl, "const": dc}
+        self.groups_ordered = lay.ordered
+        if lay.ordered:
+            bq, bl, oq, ol = dq, dl, lay.dst_quad, lay.dst_lin
+        else:
+            bq, bl, oq, ol = ctx.alloc(24 * nq), ctx.alloc(16 * n), lay.src_quad, lay.src_lin
+            tables = [ctx.alloc(8 * len(t)) for t in (lay.row_src, lay.row_dst, lay.lin_src)]
+            for buf, t in zip(tables, (lay.row_src, lay.row_dst, lay.lin_src)):
+                ctx.upload(buf, t)
+        emits = [self._lsq_sum_emitter(ctx, varmap_buf, g.terms, bq + 24 * int(oq[k]), bl + 16 * int(ol[k]), consts + 8 * k)
+                 for k, g in enumerate(groups)]
+
+        def emit(c):
+            for e in emits:
+                e(c)
+            if not lay.ordered:
+                c.call("pmt_quad_groups_gather_f64", P(bq), P(tables[0]), P(tables[1]), n, nq, P(bl), P(tables[2]), n, P(dq), P(dl))
+            c.call("pmt_quad_groups_constant_f64", P(consts), G, P(dc))
         return emit
 
     def record_fetch(self, ctx):
@@ -559,13 +598,62 @@ def _lsq_sum_combines(terms):
     return runs <= _lib.PMT_LSQ_MAX_RUNS
 
 
+# A sum over disjoint Variable vectors whose literal function is smaller than this keeps the literal expansion + canonicalize: such models
+# (a dozen variables per vector, beyond the small plan only because they replay a graph) take that path today, the canonical nodes round
+# differently from it, and a function of a few hundred KB gains nothing from them.  The mode is for the sums the literal path is slow
+# on or cannot build.
+GROUPS_MIN_LITERAL_TERMS = 1 << 14
+
+
+class QuadGroup:
+    """One group of a "canonical-groups" plan: its LsqTerm list in expression order and its sorted variables"""
+    def __init__(self, terms, vars_):
+        self.terms, self.vars = terms, vars_
+
+
+def _lsq_groups(terms):
+    """The QuadGroups of an LsqTerm list whose blocks / forms lie over 2 .. PMT_QUAD_MAX_GROUPS pairwise disjoint, strictly increasing
+    Variable vectors, or None: groups in the order of the first appearance of one of their blocks; a diagonal / linear term joins the group
+    that holds its variables (a strictly increasing part of ONE group's set: _lsq_sum_combines' subset rule), constants join the first group;
+    every group's list, expression order kept, is one the combine takes on its own (_lsq_sum_combines).  A term over variables of no group,
+    or of two, leaves the whole sum to the literal path."""
+    from . import _lib
+    groups = []
+    for t in terms or ():
+        if t.kind in ("block", "form") and not any(np.array_equal(t.r.xvars.vars, g.vars) for g in groups):
+            groups.append(QuadGroup([], t.r.xvars.vars))
+    if not 2 <= len(groups) <= _lib.PMT_QUAD_MAX_GROUPS or any(len(g.vars) == 0 or np.any(np.diff(g.vars) <= 0) for g in groups):
+        return None
+    z = np.concatenate([g.vars for g in groups])
+    if len(np.unique(z)) != len(z):                                      # overlapping sets
+        return None
+    for t in terms:
+        if t.kind in ("block", "form"):
+            home = [g for g in groups if np.array_equal(t.r.xvars.vars, g.vars)]
+        elif t.xvars is not None:
+            home = [g for g in groups if len(t.xvars.vars) and t.xvars.vars[0] in g.vars]
+        else:
+            home = groups[:1]
+        if not home:
+            return None
+        home[0].terms.append(t)
+    return groups if all(_lsq_sum_combines(g.terms) for g in groups) else None
+
+
 class QuadPlan:
     """How a quadratic record reaches its MOI function (quad_plan decides; Model.initialize and _Record.compile execute): the mode and what it
-    reads — the operand r of dot(r, r) (`gram`), the QuadForm (`form`) or the LsqTerm list (`terms`); `canonicalize`: through canonicalize! first."""
-    def __init__(self, mode, gram=None, form=None, terms=None, canonicalize=False):
-        self.mode, self.gram, self.form, self.terms, self.canonicalize = mode, gram, form, terms, canonicalize
+    reads — the operand r of dot(r, r) (`gram`), the QuadForm (`form`), the LsqTerm list (`terms`) or the QuadGroups of a sum over disjoint
+    Variable vectors (`groups`); `canonicalize`: through canonicalize! first."""
+    def __init__(self, mode, gram=None, form=None, terms=None, canonicalize=False, groups=None):
+        self.mode, self.gram, self.form, self.terms, self.canonicalize, self.groups = mode, gram, form, terms, canonicalize, groups
         # the MOI copy is the canonical least-squares node, bare or the weighted sum of such nodes (Model.initialize: side lane, small-plan order)
-        self.gram_record = mode in ("canonical", "canonical-csc", "canonical-sum")
+        self.gram_record = mode in ("canonical", "canonical-csc", "canonical-sum") or \
+            (mode == "canonical-groups" and any(t.kind == "block" for g in groups for t in g.terms))
+
+    def operands(self):
+        """what the plan's kernels read: the Gram operand, the forms and blocks of its term lists (Model.initialize: their stacked matrices)"""
+        lists = [self.terms or ()] + [g.terms for g in self.groups or ()]
+        return [r for r in [self.gram] + [t.r for ts in lists for t in ts] if r is not None]
 
 
 def quad_plan(terms, bare, kind, nq, is_objective, quadratic_mode, small, handoff, varmap=None):
@@ -597,6 +685,12 @@ def quad_plan(terms, bare, kind, nq, is_objective, quadratic_mode, small, handof
         # a weighted sum of least-squares blocks over one x: combined from the blocks' Gram nodes — the MOI boundary of a model beyond the small plan only
         if is_objective and handoff == "moi" and not bare and _lsq_sum_combines(terms):
             return QuadPlan("canonical-sum", terms=terms)
+        # such sums over pairwise disjoint Variable vectors (transpose(x)*Q*x + transpose(u)*R*u): the groups' own canonical functions,
+        # interleaved in (row, column) order — under the same conditions, from GROUPS_MIN_LITERAL_TERMS literal terms on
+        if is_objective and handoff == "moi" and not bare and nq >= GROUPS_MIN_LITERAL_TERMS:
+            groups = _lsq_groups(terms)
+            if groups:
+                return QuadPlan("canonical-groups", groups=groups)
     # anything else: the literal function through the generic device canonicalize! (sorted, duplicates combined) before the MOI copy
     return QuadPlan("literal", canonicalize=True)
 
