@@ -14,9 +14,14 @@ from ._lib import LT, QT, VAT, ArgumentError, DimensionMismatch
 
 class DeviceContext:
     def __init__(self, device=0):
+        # (declared before the first call that can raise: close() / __del__ run on a half-constructed context too)
+        self.plan = C.c_void_p()
+        self._pinned = []               # pinned_array: page-locked allocations, freed by close()
+        self._lane_streams = {}         # call_on_lane: lane -> the stream its entries are replayed on
+        self._replay_pending = False    # replay: a replay may still be reading host mailboxes (cleared by synchronize / Model._fast_update)
+        self._refreshing = False        # Model._refresh_parameters: inside update!'s walk over the Parameters
         _lib.require_gpu()
         self.lib = _lib.load()
-        self.plan = C.c_void_p()
         _lib.call("pmt_plan_create", int(device), None, C.byref(self.plan))
         self.stream = C.c_void_p(self.lib.pmt_plan_stream(self.plan))
         self.rec = C.c_void_p(self.lib.pmt_plan_recording_stream(self.plan))
@@ -32,7 +37,7 @@ class DeviceContext:
         if self.plan:
             self.lib.pmt_plan_destroy(self.plan)
             self.plan = C.c_void_p()
-            for p in getattr(self, "_pinned", []):
+            for p in self._pinned:
                 self.lib.pmt_host_free(C.c_void_p(p))
             self._pinned = []
 
@@ -43,8 +48,6 @@ class DeviceContext:
         nbytes = max(int(n) * dtype.itemsize, 16)
         p = C.c_void_p()
         _lib.call("pmt_host_alloc", nbytes, C.byref(p))
-        if not hasattr(self, "_pinned"):
-            self._pinned = []
         self._pinned.append(p.value)
         buf = (C.c_char * nbytes).from_address(p.value)
         return np.frombuffer(buf, dtype=dtype, count=int(n))
@@ -161,8 +164,6 @@ class DeviceContext:
     def call_on_lane(self, lane, name, *args):
         """an immediate call on the stream a lane's entries are replayed on (pmt_plan_lane_stream): device-side Parameter callbacks of values
         only side-lane entries read"""
-        if not hasattr(self, "_lane_streams"):
-            self._lane_streams = {}
         if lane not in self._lane_streams:
             st = C.c_void_p()
             _lib.call("pmt_plan_lane_stream", self.plan, int(lane), C.byref(st))
@@ -223,6 +224,7 @@ class DNum(DV):
     kind = "num"
 
     def __init__(self, ctx, value=None):
+        self._staging_slots, self._staged_bytes, self._staged_slot = {}, 0, 0     # lazyexpression._stage_value
         self.buf = ctx.alloc(8)
         if value is not None:
             ctx.upload(self.buf, np.array([value], dtype=np.float64))
@@ -234,6 +236,7 @@ class DVec(DV):
 
     def __init__(self, ctx, n):
         self.n = int(n)
+        self._staging_slots, self._staged_bytes, self._staged_slot = {}, 0, 0     # lazyexpression._stage_value: per slot, the staging buffer
         self.padded = row_padded(self.n)                 # allocated length; entries [n, padded) stay zero
         self.buf = ctx.alloc(8 * max(self.padded, 1))
         ctx.zero(self.buf, 8 * max(self.padded, 1))
@@ -263,6 +266,9 @@ class DMat(DV):
 
     def __init__(self, ctx, rows, cols):
         self.rows, self.cols = int(rows), int(cols)
+        self._stage = None                                # upload: the row-major bytes before the device transpose
+        self._stage_rm, self._staging_cm = {}, {}         # stage: per staging slot, the row-major / padded column-major second buffer
+        self._staged_kind, self._staged_slot = None, 0    # stage: "rowmajor" / "colmajor" until commit
         self.lda = padded_lda(self.rows)
         self.buf = ctx.alloc(8 * max(self.lda * self.cols, 1))
         if self.lda != self.rows:
@@ -276,7 +282,7 @@ class DMat(DV):
         if not (self.rows and self.cols):
             return
         if m.flags.c_contiguous and not m.flags.f_contiguous:
-            if getattr(self, "_stage", None) is None:
+            if self._stage is None:
                 self._stage = ctx.alloc(8 * self.rows * self.cols)
             ctx.upload(self._stage, m)
             # the row-major bytes are a column-major (cols x rows) matrix with leading dimension cols
@@ -295,8 +301,6 @@ class DMat(DV):
             self._staged_kind = None
             return
         slot = ctx._stage_slot                                     # one pair of staging buffers per slot (pmt_plan_stage_slot)
-        if not hasattr(self, "_stage_rm"):
-            self._stage_rm, self._staging_cm = {}, {}
         self._staged_slot = slot
         if m.flags.c_contiguous and not m.flags.f_contiguous:
             if slot not in self._stage_rm:
@@ -317,8 +321,7 @@ class DMat(DV):
 
     def commit(self, ctx):
         """plan stream: the staged value becomes the Parameter's value"""
-        kind = getattr(self, "_staged_kind", None)
-        slot = getattr(self, "_staged_slot", 0)
+        kind, slot = self._staged_kind, self._staged_slot
         if kind == "rowmajor":
             ctx.wait_staged()
             _lib.call("pmt_transpose_f64", C.c_void_p(self._stage_rm[slot]), self.cols, self.cols, self.rows, C.c_void_p(self.buf), self.lda, ctx.stream)
@@ -504,6 +507,7 @@ class DSpMat(DV):
         import ctypes as C
         self.rows, self.cols = csc.shape
         self.nnz = int(csc.nnz)
+        self._staging_slots, self._staged_bytes, self._staged_slot = {}, 0, 0     # lazyexpression._stage_value
         colptr = np.ascontiguousarray(csc.indptr, dtype=np.int64) + 1            # Julia 1-based
         rowval = np.ascontiguousarray(csc.indices, dtype=np.int64) + 1
         self.indptr, self.indices = csc.indptr.copy(), csc.indices.copy()

@@ -60,7 +60,7 @@ class _Rect:
     def host_resident(self):
         """the block's Parameter is updated by the HOST (val= buffer or callback, src/parameter.jl:88,101-102): its values are already
         there and need not come back from the device"""
-        return self.param is not None and not getattr(self.param, "device_resident", False) and self.offsets is None
+        return self.param is not None and not self.param.device_resident and self.offsets is None
 
 
 class CSC:
@@ -77,7 +77,7 @@ def _parameter_of(expr, dmat):
     from .lazyexpression import schedule
     from .parameter import Parameter
     for x in schedule([expr]):
-        if isinstance(x, Parameter) and getattr(x, "_dev", None) is dmat:
+        if isinstance(x, Parameter) and x._dev is dmat:
             return x
     return None
 
@@ -311,6 +311,7 @@ class DeviceQP:
                 ctx.upload(self.l_ptr + 8 * r0, lo); ctx.upload(self.u_ptr + 8 * r0, hi)
         ctx.synchronize()
         self._in_tape = False
+        self._in_tape_lane = None                   # "side" / "main" once the hand-off's launches are entries of the tape (below)
         self.host = HostQP(self) if host else None
         model._fetches_read_parameters = self.host is not None and self.A.only_rects
         if self.host is not None and self.A.only_rects and self.A.nnz:

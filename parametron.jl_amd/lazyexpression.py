@@ -122,10 +122,10 @@ def device_value_of(x, ctx=None):
         return x.out
     if isinstance(x, Parameter):
         ctx = ctx or x.model.device()
-        if getattr(x, "_staged_pending", False) and x._dev is not None:
+        if x._staged_pending and x._dev is not None:
             # the value of this solve was evaluated and put on the copy stream by Model.stage_parameters(): consume it on the plan's stream
             # (a Parameter only side-lane records read is committed on the side stream: the plan's stream does not wait for its upload)
-            side = getattr(x, "_commit_on_side_lane", False) and not (isinstance(x._dev, DMat) and getattr(x._dev, "_staged_kind", None) == "rowmajor")
+            side = x._commit_on_side_lane and not (isinstance(x._dev, DMat) and x._dev._staged_kind == "rowmajor")
             if side:
                 ctx.commit_lane(1)
             try:
@@ -136,29 +136,29 @@ def device_value_of(x, ctx=None):
             x._staged_pending = False
             x._dev_version = x.version
             ctx._staging_dirty = True
-            _sync_mailbox(ctx, x, getattr(x, "val", None))
+            _sync_mailbox(ctx, x, x.val)
             return x._dev
         val = Parameter.__call__(x)                 # evalarg(::Parameter) (src/lazyexpression.jl:51)
         if x._dev is None:
-            if getattr(x, "pattern", None) is not None:                   # DeviceUniformSparseParameter: fixed pattern, values made on the device
+            if x.pattern is not None:                                     # DeviceUniformSparseParameter: fixed pattern, values made on the device
                 x._dev = DSpMat(ctx, x.pattern)
-            elif getattr(x, "device_resident", False):
+            elif x.device_resident:
                 x._dev = DVec(ctx, x.shape[0]) if len(x.shape) == 1 else DMat(ctx, *x.shape)
             else:
                 x._dev = _alloc_like(ctx, val)
-        if x._dev_version != x.version and getattr(x, "_in_tape", False) and getattr(ctx, "_refreshing", False) and not ctx.recording:
+        if x._dev_version != x.version and x._in_tape and ctx._refreshing and not ctx.recording:
             # the callback is an entry of the tape (a small model, Model._record_parameter_callbacks): the replay that follows draws the values
-            if getattr(x, "_mailbox", None) is not None:
+            if x._mailbox is not None:
                 _sync_mailbox(ctx, x, val)
             else:
                 x._seed_word.value = x.current_seed() % (1 << 64)
             x._dev_version = x.version
             return x._dev
         if x._dev_version != x.version:
-            if getattr(x, "device_resident", False):
+            if x.device_resident:
                 # a value only side-lane records read is regenerated on the side stream (inside update! only: there the replay joins the
                 # side stream back): a transfer at the front of the side lane does not wait for the objective's callbacks on the plan's stream
-                side = getattr(x, "_commit_on_side_lane", False) and getattr(ctx, "_refreshing", False) and not ctx.recording
+                side = x._commit_on_side_lane and ctx._refreshing and not ctx.recording
                 call = (lambda *a: ctx.call_on_lane(1, *a)) if side else ctx.call
                 if isinstance(x._dev, DSpMat):
                     call("pmt_fill_uniform_f64", P(x._dev.buf), int(x._dev.nnz), C.c_uint64(x.current_seed()), x.scale)
@@ -167,14 +167,14 @@ def device_value_of(x, ctx=None):
                          C.c_uint64(x.current_seed()), x.scale)
                 else:
                     call("pmt_fill_uniform_f64", P(x._dev.buf), int(x.shape[0]), C.c_uint64(x.current_seed()), x.scale)
-                if not side and getattr(x, "_read_unordered_by_lane3", False) and not ctx.recording:
+                if not side and x._read_unordered_by_lane3 and not ctx.recording:
                     # a recorded transfer at the very front of the side lane (lane 3) reads this buffer WITHOUT waiting for the plan's
                     # stream: a value written on the plan's stream must be complete before the next replay can start it
                     ctx.synchronize()
             else:
                 _upload_value(ctx, x._dev, val)
                 _sync_mailbox(ctx, x, val)
-                if getattr(x, "_read_unordered_by_lane3", False) and not ctx.recording:
+                if x._read_unordered_by_lane3 and not ctx.recording:
                     ctx.synchronize()                   # (a serial upload travels on the plan's stream as well)
             x._dev_version = x.version
         return x._dev
@@ -184,12 +184,11 @@ def device_value_of(x, ctx=None):
 def _sync_mailbox(ctx, x, val):
     """A host-updated Parameter of a small model has a page-locked MAILBOX the tape copies into its device buffer at every replay
     (Model._record_parameter_callbacks): whatever path gives the Parameter a new value keeps the mailbox equal to it."""
-    if getattr(x, "_mailbox", None) is None or val is None:
+    if x._mailbox is None or val is None:
         return
-    if getattr(ctx, "_replay_pending", False):
+    if ctx._replay_pending:
         ctx.synchronize()                                 # the previous replay may still be reading the mailbox
-    from .model import _write_mailbox
-    _write_mailbox(x, val)
+    x._mailbox_write(val)
 
 
 def _alloc_like(ctx, val):
@@ -248,8 +247,6 @@ def _stage_value(ctx, dv, val):
     else:
         raise ArgumentError("cannot stage an upload into %s" % type(dv).__name__)
     slot = ctx._stage_slot                              # one staging buffer per slot (pmt_plan_stage_slot)
-    if not hasattr(dv, "_staging_slots"):
-        dv._staging_slots = {}
     if slot not in dv._staging_slots:
         dv._staging_slots[slot] = ctx.alloc(max(nbytes, 8))
     dv._staged_bytes, dv._staged_slot = nbytes, slot
@@ -259,7 +256,7 @@ def _stage_value(ctx, dv, val):
 def _commit_staged_value(ctx, dv):
     if isinstance(dv, DMat):
         dv.commit(ctx)
-    elif getattr(dv, "_staged_bytes", 0):
+    elif dv._staged_bytes:
         ctx.commit_staged(dv.buf, dv._staging_slots[dv._staged_slot], dv._staged_bytes)
 
 
@@ -1027,9 +1024,9 @@ SCALAR_FUNC_KINDS = {"aff", "quad", "var", "lt", "qt"}
 
 def _arg_kind(a):
     if isinstance(a, Parameter):
-        if getattr(a, "pattern", None) is not None:
+        if a.pattern is not None:
             return "spmat"
-        if getattr(a, "device_resident", False):
+        if a.device_resident:
             return "vec" if len(a.shape) == 1 else "mat"
         return kind_of(a())                           # evaluates the Parameter once, like evalarg at :187
     if isinstance(a, Transpose):

@@ -14,6 +14,7 @@ device fill); replay the recorded tape of node kernels and MOI-pack kernels on t
 them to the optimizer with MOI.set (third party from there on).
 """
 import ctypes as C
+import itertools
 
 import numpy as np
 
@@ -25,6 +26,7 @@ from .lazyexpression import DeviceNode, Relation, evaluate, lazy, schedule
 from .parameter import Parameter
 
 Minimize, Maximize = "Minimize", "Maximize"
+_NO_SLOT = itertools.repeat(-1)          # _walk_tape_parameters without a mask: no Parameter is registered with the library
 
 
 class AbstractOptimizer:
@@ -119,7 +121,8 @@ class MockOptimizer(AbstractOptimizer):
 
 
 def _mailbox_writer(x):
-    """_write_mailbox with the layout resolved once: val -> the mailbox, in the device layout"""
+    """val -> the page-locked mailbox of a host-updated Parameter, in the layout of its device buffer (padded leading dimension), resolved
+    once when the mailbox is created: every path that gives the Parameter a new value writes through it (Parameter._mailbox_write)"""
     from .device import DMat, DVec
     dv, mb = x._dev, x._mailbox
     if isinstance(dv, DMat):
@@ -144,24 +147,35 @@ def _mailbox_writer(x):
     return write
 
 
-def _write_mailbox(x, val):
-    """the value of a host-updated Parameter into its page-locked mailbox, in the layout of the device buffer (padded leading dimension)"""
-    from .device import DMat, DVec
-    if val is None:
-        return
-    dv, mb = x._dev, x._mailbox
-    if isinstance(dv, DMat):
-        m = np.asarray(val, dtype=np.float64)
-        if m.shape != (dv.rows, dv.cols):
-            raise DimensionMismatch("Parameter changed shape: %r -> %r" % ((dv.rows, dv.cols), m.shape))
-        mb.reshape(dv.cols, dv.lda)[:, :dv.rows] = m.T
-    elif isinstance(dv, DVec):
-        v = np.asarray(val, dtype=np.float64)
-        if v.shape != (dv.n,):
-            raise DimensionMismatch("Parameter changed shape: %r -> %r" % ((dv.n,), v.shape))
-        mb[:dv.n] = v
-    else:
-        mb[0] = float(val)
+def lane_order(records, small, side_lane, handoff, overlap_moi):
+    """Where the records' MOI copies go in the tape.  `records`: per record (plan.gram_record, side-lane eligible: Model._side_lane_ok).
+    Returns (the emit order as indices into `records`, the set of indices recorded on the side lane).
+
+    MOI copies of constraints built straight from their Parameters are independent of every other record (update! of one Constraint,
+    src/moi_interop.jl:168-175).  Beside a canonical least-squares objective they go to the plan's side lane: queued behind the
+    contraction's small reductions, they run while its workgroups drain and its fix-up pass runs, instead of adding their kernels and
+    in-stream gaps behind it."""
+    gram = [i for i, (g, _) in enumerate(records) if g]
+    # never in a SMALL model: its Parameter values arrive through entries at the FRONT of the tape — mailbox copies, seeded fills — while
+    # side-lane entries fork at the top of the replay and would read the buffers before those entries have run; and a lane would only cut
+    # the one-launch plan in pieces
+    eligible = [i for i, (_, ok) in enumerate(records) if ok] if (gram and side_lane and not small) else []
+    # one small kernel on the lane does not pay (config 2: the co-resident pack slows the contraction by what it saves); several do
+    # (config 3: -0.15 ms), and so does the device hand-off, whose launches join them on the lane (and with the overlapped MOI boundary
+    # a constraint on the lane is packed early: its terms cross PCIe during the contraction)
+    use_lane = len(eligible) >= 2 or (len(eligible) >= 1 and (handoff != "moi" or overlap_moi))
+    order = list(range(len(records)))
+    if small and gram:
+        # a SMALL model: the records are independent of each other, so the one whose MOI copy is not an interpreter node — the
+        # canonical least-squares objective beyond tiny shapes (gram_tall.hip: two launches) — goes last; the constraints' packs
+        # then join the run of small entries at the front of the tape (callbacks, residual) in its ONE launch
+        order = [i for i in order if i not in gram] + gram
+    elif use_lane:
+        # round 6c: the side lane's records go in FRONT of the objective — its one-launch node (gram_mid.hip) holds every CU
+        # with persistent workgroups and lane entries recorded behind it wait for it; recorded first they take CUs first and
+        # the node's workgroups start as CUs come free (config 3, staged uploads: 1.244 -> 1.222 ms per step)
+        order = eligible + [i for i in order if i not in eligible]
+    return order, set(eligible) if use_lane else set()
 
 
 class _Backend:
@@ -173,6 +187,17 @@ class _Backend:
 
 class Model:
     def __init__(self, optimizer, quadratic_mode="auto", device=0, use_graph=False, handoff="moi", side_lane=True, overlap_fetch=True):       # src/model.jl:10-22
+        self._ctx = None                        # device(): the DeviceContext (declared, with the state below, before the first raise: close())
+        # ---- the plan's state, set by initialize() and its steps
+        self._records = []                      # initialize: the non-constant records (objective, constraints)
+        self._order = []                        # initialize: Parameters and nodes in the reference's evaluation order (schedule)
+        self._varmap_buf = None                 # initialize: the device copy of model_var_to_optimizer
+        self._small = False                     # _decide_small: the whole update! replays as one small plan
+        self._lane_records = []                 # _record_tape: the records whose MOI copies are side-lane entries
+        self._tape_parameters = None            # _record_parameter_callbacks: the Parameters, when EVERY value enters through the tape
+        self._run_slot = []                     # ... and per Parameter its slot in the C model (_create_model_run), or -1: written here
+        self._model_run = None                  # _create_model_run: the pmt_model behind _fast_update
+        self._fetches_read_parameters = False   # handoff.DeviceQP: host_csc transfers leave straight out of Parameter buffers
         if quadratic_mode not in ("auto", "literal", "canonical"):
             raise ArgumentError("quadratic_mode must be 'auto', 'literal' or 'canonical'")
         if handoff not in ("moi", "device", "host_csc"):
@@ -199,10 +224,8 @@ class Model:
         self.model_var_to_optimizer = np.zeros(0, dtype=np.int64)
         self.quadratic_mode = quadratic_mode
         self._device_index = device
-        self._ctx = None
         self._use_graph = use_graph
         self._side_lane = side_lane
-        self._records = []
 
     def __repr__(self):
         return "Model{Float64, %s}(…)" % type(self.optimizer).__name__
@@ -226,7 +249,7 @@ class Model:
 
     def close(self):
         if self._ctx is not None:
-            if getattr(self, "_model_run", None) is not None:
+            if self._model_run is not None:
                 self._ctx.lib.pmt_model_destroy(self._model_run)
                 self._model_run = None
             self._ctx.close()
@@ -260,7 +283,7 @@ class Model:
         ctx._next_stage_slot ^= 1
         ctx.set_stage_slot(ctx._pending_slot)
         for x in self._order:
-            if not isinstance(x, Parameter) or getattr(x, "device_resident", False) or isinstance(x, DerivedParameter) or x._dev is None:
+            if not isinstance(x, Parameter) or x.device_resident or isinstance(x, DerivedParameter) or x._dev is None:
                 continue
             x.setdirty()
             val = Parameter.__call__(x)
@@ -329,99 +352,90 @@ class Model:
             self.model_var_to_optimizer = np.asarray(indexmap["variables"], dtype=np.int64).copy()
         if records:
             ctx = self.device()
-            # SMALL models (README Example 1): launch-bound on the device.  Their Parameter callbacks are recorded into the tape and the whole
-            # update! replays as one small plan (csrc/small.hip); overlapped recorded fetches — a signal kernel and a copy-engine transfer per
-            # MOI buffer, worth it for megabytes — would cut the run of small entries and cost more launches than the copies they hide
-            def _elements(ps):
-                return sum(int(getattr(getattr(p_, "val", None), "nnz", np.size(getattr(p_, "val", 0)))) for p_ in ps)
-            self._small = (not self._use_graph and self.handoff == "moi" and
-                           _elements(p_ for p_ in self.params if not getattr(p_, "device_resident", False)) <= self.SMALL_MODEL_ELEMENTS and
-                           _elements(p_ for p_ in self.params if getattr(p_, "device_resident", False)) <= self.SMALL_MODEL_DEVICE_ELEMENTS)
-            if self._small:
-                self._overlap_moi = False
+            self._decide_small()
             self._varmap_buf = ctx.alloc(8 * max(self.nvars, 1))
             ident = np.arange(1, self.nvars + 1, dtype=np.int64)     # IdentityVarMap until mapindices! (src/moi_interop.jl:32-33)
             ctx.upload(self._varmap_buf, self.model_var_to_optimizer if early else ident)
             varmap = self.model_var_to_optimizer if early else None
-            for r in (r for r in records if r.kind == "quad"):
-                # the one decision on a quadratic record's form (moi.quad_plan); here: the stacked matrices it reads, canonicalize!
-                r.plan = plan = moi.quad_plan(r.expr.lsq_sum, r.expr.lsq_bare, r.kind, r.expr.out.nq, r is self.objective, self.quadratic_mode,
-                                              self._small, self.handoff, varmap)
-                for g in (g for g in plan.operands() if hasattr(g, "require_stack")):
-                    g.require_stack()
-                if plan.canonicalize:
-                    r.expr = r.expr.canonicalize()
+            self._plan_quadratic_records(varmap)
             emitters = [r.compile(ctx, self._varmap_buf, varmap) for r in records]
             self._order = schedule([r.expr for r in records])
             for x in self._order:
                 if isinstance(x, DeviceNode):
                     x.prepare()
-            ctx.begin_record()
-            try:
-                self._record_parameter_callbacks(ctx)
-                for x in self._order:
-                    if isinstance(x, DeviceNode):
-                        x.emit(ctx)
-                # MOI copies of constraints built straight from their Parameters are independent of every other record (update! of one
-                # Constraint, src/moi_interop.jl:168-175).  Beside a canonical least-squares objective they go to the plan's side lane:
-                # queued behind the contraction's small reductions, they run while its workgroups drain and its fix-up pass runs,
-                # instead of adding their kernels and in-stream gaps behind it.
-                gram = any(r.plan.gram_record for r in records)
-                self._lane_records = []
-                # one small kernel on the lane does not pay (config 2: the co-resident pack slows the contraction by what it saves); several
-                # do (config 3: -0.15 ms), and so does the device hand-off, whose launches join them on the lane
-                # (never in a SMALL model: its Parameter values arrive through entries at the FRONT of the tape — mailbox copies, seeded fills
-                # — while side-lane entries fork at the top of the replay and would read the buffers before those entries have run; and a
-                # lane would only cut the one-launch plan in pieces)
-                eligible = [r for r in records if self._side_lane_ok(r)] if (gram and self._side_lane and not self._small) else []
-                # (and with the overlapped MOI boundary a constraint on the lane is packed early: its terms cross PCIe during the contraction)
-                use_lane = len(eligible) >= 2 or (len(eligible) >= 1 and (self.handoff != "moi" or self._overlap_moi))
-                emit_order = list(zip(records, emitters))
-                if self._small and gram:
-                    # a SMALL model: the records are independent of each other, so the one whose MOI copy is not an interpreter node — the
-                    # canonical least-squares objective beyond tiny shapes (gram_tall.hip: two launches) — goes last; the constraints' packs
-                    # then join the run of small entries at the front of the tape (callbacks, residual) in its ONE launch
-                    emit_order = [re for re in emit_order if not re[0].plan.gram_record] + [re for re in emit_order if re[0].plan.gram_record]
-                elif use_lane:
-                    # round 6c: the side lane's records go in FRONT of the objective — its one-launch node (gram_mid.hip) holds every CU
-                    # with persistent workgroups and lane entries recorded behind it wait for it; recorded first they take CUs first and
-                    # the node's workgroups start as CUs come free (config 3, staged uploads: 1.244 -> 1.222 ms per step)
-                    emit_order = [re for re in emit_order if any(re[0] is x for x in eligible)] + [re for re in emit_order if not any(re[0] is x for x in eligible)]
-                for r, e in emit_order:
-                    side = use_lane and any(r is x for x in eligible)
-                    if side:
-                        ctx.set_lane(1)
-                        self._lane_records.append(r)
-                        r.on_side_lane = True
-                    e(ctx)
-                    if self._overlap_moi:
-                        r.record_fetch(ctx)                    # behind its producers, on their lane
-                    if side:
-                        ctx.set_lane(0)
-            finally:
-                ctx.end_record()
-            self._model_run = None
+            self._record_tape(ctx, emitters)
             self._create_model_run(ctx)
             # first evaluation with the identity map so that copy_to sees sized, filled functions (src/moi_interop.jl:127,157)
             self._run_tape()
         if not early:
-            indexmap = self.optimizer.copy_to(backend)
-            self._mapindices(indexmap)
+            self._mapindices(self.optimizer.copy_to(backend))
         self.initialized = True
         if self.handoff != "moi":
-            from .handoff import DeviceQP
-            # When every constraint's MOI copy sits on the side lane and the objective is the Gram node (whose affine part is written on
-            # the same side stream), the hand-off launches read side-stream outputs only: they are appended to the tape as side-lane
-            # entries too and leave the plan's stream to the contraction.  Otherwise they are launched behind the tape on every update.
-            obj = self.objective
-            in_tape = bool(records) and (obj.isconstant or "P_values" in (obj.dev or {})) and \
-                all(c.isconstant or any(c is r for r in getattr(self, "_lane_records", [])) for c in self.constraints) and \
-                any(not c.isconstant for c in self.constraints)
-            host = None if self.handoff == "device" else ("overlap" if self._overlap_fetch else "serial")
-            self.device_qp = DeviceQP(self, in_tape="side" if in_tape else False, host=host)
+            self._create_handoff()
         self._mark_side_lane_parameters()
         if records and self._use_graph:
             self.device().instantiate_graph()
+
+    def _decide_small(self):
+        """SMALL models (README Example 1): launch-bound on the device.  Their Parameter callbacks are recorded into the tape and the whole
+        update! replays as one small plan (csrc/small.hip); overlapped recorded fetches — a signal kernel and a copy-engine transfer per
+        MOI buffer, worth it for megabytes — would cut the run of small entries and cost more launches than the copies they hide"""
+        def elements(ps):                                              # (a user's val: any number, array or scipy matrix)
+            return sum(int(getattr(p.val, "nnz", np.size(p.val))) for p in ps)
+        self._small = (not self._use_graph and self.handoff == "moi" and
+                       elements(p for p in self.params if not p.device_resident) <= self.SMALL_MODEL_ELEMENTS and
+                       elements(p for p in self.params if p.device_resident) <= self.SMALL_MODEL_DEVICE_ELEMENTS)
+        self._overlap_moi = self._overlap_moi and not self._small
+
+    def _plan_quadratic_records(self, varmap):
+        """the one decision on a quadratic record's form (moi.quad_plan); here: the stacked matrices it reads, canonicalize!"""
+        for r in (r for r in self._records if r.kind == "quad"):
+            r.plan = plan = moi.quad_plan(r.expr.lsq_sum, r.expr.lsq_bare, r.kind, r.expr.out.nq, r is self.objective, self.quadratic_mode,
+                                          self._small, self.handoff, varmap)
+            for g in (g for g in plan.operands() if hasattr(g, "require_stack")):
+                g.require_stack()
+            if plan.canonicalize:
+                r.expr = r.expr.canonicalize()
+
+    def _record_tape(self, ctx, emitters):
+        """the tape: Parameter callbacks of a small model, the nodes in the reference's order, the records' MOI copies as lane_order places them"""
+        records = self._records
+        # (eligibility is read before the nodes are emitted: no emit changes a node's need_terms — require_terms() / materialized() are called
+        # by the builders, by compile and by DeviceNode.__call__ only)
+        order, lane = lane_order([(r.plan.gram_record, self._side_lane_ok(r)) for r in records], self._small, self._side_lane, self.handoff,
+                                 self._overlap_moi)
+        self._lane_records = [records[i] for i in order if i in lane]
+        ctx.begin_record()
+        try:
+            self._record_parameter_callbacks(ctx)
+            for x in self._order:
+                if isinstance(x, DeviceNode):
+                    x.emit(ctx)
+            for i in order:
+                r, side = records[i], i in lane
+                if side:
+                    ctx.set_lane(1)
+                    r.on_side_lane = True
+                emitters[i](ctx)
+                if self._overlap_moi:
+                    r.record_fetch(ctx)                    # behind its producers, on their lane
+                if side:
+                    ctx.set_lane(0)
+        finally:
+            ctx.end_record()
+
+    def _create_handoff(self):
+        """handoff "device" / "host_csc": the solver's CSC data behind the tape (handoff.DeviceQP).  When every constraint's MOI copy sits on
+        the side lane and the objective is the Gram node (whose affine part is written on the same side stream), the hand-off launches read
+        side-stream outputs only: they are appended to the tape as side-lane entries too and leave the plan's stream to the contraction.
+        Otherwise they are launched behind the tape on every update."""
+        from .handoff import DeviceQP
+        obj = self.objective
+        in_tape = bool(self._records) and (obj.isconstant or "P_values" in (obj.dev or {})) and \
+            all(c.isconstant or any(c is r for r in self._lane_records) for c in self.constraints) and \
+            any(not c.isconstant for c in self.constraints)
+        host = None if self.handoff == "device" else ("overlap" if self._overlap_fetch else "serial")
+        self.device_qp = DeviceQP(self, in_tape="side" if in_tape else False, host=host)
 
     # measured crossover (tools/mid_table.py, solve! with host Parameters and a do-nothing optimizer): the small-model path (mailboxes, one or two
     # launches, MOI buffers stored straight into the function objects) beats uploads + separate kernels + overlapped fetches up to ~300 000
@@ -437,14 +451,13 @@ class Model:
         small plan: one launch (csrc/small.hip).  README Example 1's update! is launch-bound on the device: four callbacks + five kernels
         took ~48 us where the reference's CPU walk of the same DAG takes ~15 (README.md:132-136)."""
         from .parameter import DeviceUniformParameter
-        from .device import DMat, DVec
-        if not getattr(self, "_small", False):
+        from .device import DMat, DNum, DVec
+        if not self._small:
             return
         ps = [x for x in self._order if isinstance(x, Parameter)]
-        from .device import DNum
         for x in ps:
-            dv = getattr(x, "_dev", None)
-            if not isinstance(x, DeviceUniformParameter) and isinstance(dv, (DMat, DVec, DNum)) and not getattr(x, "device_resident", False):
+            dv = x._dev
+            if not isinstance(x, DeviceUniformParameter) and isinstance(dv, (DMat, DVec, DNum)) and not x.device_resident:
                 # a HOST-updated Parameter (callback f(val) or Parameter(model, val=buf), src/parameter.jl:57,88) of a small model: its value
                 # travels through a page-locked MAILBOX in the device layout, which the first entries of the tape copy into the Parameter's
                 # buffer — inside the one small-plan launch, read straight from host memory.  update! writes the mailbox (a numpy copy of a
@@ -455,36 +468,35 @@ class Model:
                 x._mailbox = ctx.pinned_array(n_doubles, np.float64)
                 x._mailbox[:] = 0.0
                 x._mailbox_write = _mailbox_writer(x)
-                _write_mailbox(x, x.val if getattr(x, "val", None) is not None else None)
+                if x.val is not None:
+                    x._mailbox_write(x.val)
                 ctx.call("pmt_copy_bytes", C.c_void_p(dv.buf), C.c_void_p(x._mailbox.ctypes.data), 8 * n_doubles)
                 x._in_tape = True
                 continue
-            if not isinstance(x, DeviceUniformParameter) or getattr(x, "pattern", None) is not None or not isinstance(dv, (DMat, DVec)):
+            if not isinstance(x, DeviceUniformParameter) or x.pattern is not None or not isinstance(dv, (DMat, DVec)):
                 continue
             x._seed_word = C.c_uint64(x.current_seed() % (1 << 64))
             rows, cols, lda = (dv.rows, dv.cols, dv.lda) if isinstance(dv, DMat) else (int(x.shape[0]), 1, int(x.shape[0]))
             ctx.call("pmt_fill_uniform_dyn_f64", C.c_void_p(dv.buf), rows, cols, lda, C.byref(x._seed_word), x.scale)
-            x._mailbox_write = None
             x._in_tape = True
-        if ps and all(getattr(x, "_in_tape", False) for x in ps):
-            self._tape_parameters = ps             # every value enters through the tape: _refresh_parameters' short walk
+        if ps and all(x._in_tape for x in ps):
+            self._tape_parameters = ps             # every value enters through the tape: _walk_tape_parameters
 
     def _create_model_run(self, ctx):
         """SMALL models: the per-solve walk behind ONE C call (pmt_model_update, csrc/modelrun.hip — the entry point a Julia / C host uses
         for the same walk): mailboxes of the host-updated Parameters whose value array is a float64 array that stays put (`val=` buffers,
         in-place callbacks) are registered with their strides — the library copies value -> mailbox itself —, the records' constants with
         the function objects' fields are finished there too.  Everything else keeps this host's own writers (dirty byte 0)."""
-        fast = getattr(self, "_tape_parameters", None)
-        if not getattr(self, "_small", False) or fast is None:
+        fast = self._tape_parameters
+        if not self._small or fast is None:
             return
         run = C.c_void_p()
         ctx.call("pmt_model_create", ctx.plan, C.byref(run))
-        self._run_slot = []                                   # per Parameter of `fast`: slot in the C model, or -1 (written here)
+        self._run_slot = []
         for x in fast:
             slot = -1
-            mb, dv = getattr(x, "_mailbox", None), x._dev
-            val = getattr(x, "val", None)
-            if getattr(x, "_mailbox_write", None) is not None and isinstance(val, np.ndarray) and val.dtype == np.float64 and \
+            mb, dv, val = x._mailbox, x._dev, x.val
+            if x._mailbox_write is not None and isinstance(val, np.ndarray) and val.dtype == np.float64 and \
                     val.ndim in (1, 2) and all(st % 8 == 0 and st >= 0 for st in val.strides):
                 from .device import DMat
                 rows, cols = (dv.rows, dv.cols) if isinstance(dv, DMat) else (val.shape[0], 0)
@@ -499,25 +511,23 @@ class Model:
             self._run_slot.append(slot)
         # what a record's fetch() would copy out of HBM (a buffer whose device twin IS the host array needs nothing): behind the replay, in C
         for r in self._records:
-            for host, key in r.fetch_list():
-                if key in r.dev and r.dev[key] != host.ctypes.data:
-                    ctx.call("pmt_model_add_fetch", run, C.c_void_p(host.ctypes.data), C.c_void_p(r.dev[key]), host.nbytes)
+            for host, dptr in r.copies():
+                ctx.call("pmt_model_add_fetch", run, C.c_void_p(host.ctypes.data), C.c_void_p(dptr), host.nbytes)
         self._run_nslots = int(ctx.lib.pmt_model_num_slots(run))
         self._run_mask = (C.c_ubyte * max(self._run_nslots, 1))()
         self._model_run = run
 
-    def _fast_update(self, ctx):
-        """update!(model) of a small model, synchronous: callbacks here (they are host functions), everything else in pmt_model_update"""
-        mask, slots = self._run_mask, self._run_slot
+    def _walk_tape_parameters(self, ctx, mask=None):
+        """A SMALL model whose every Parameter value enters through an entry of the tape (mailbox copy or seeded fill): evaluate, and write
+        the mailbox / the seed word of what changed.  With `mask` (the dirty bytes of pmt_model_update, per slot of _run_slot): a value that
+        still lives in the array registered with the library is only marked; without it every changed value is written here."""
         synced = False
-        for i, x in enumerate(self._tape_parameters):
+        for x, slot in zip(self._tape_parameters, self._run_slot if mask is not None else _NO_SLOT):
             val = Parameter.__call__(x)                                  # evalarg(::Parameter) (src/lazyexpression.jl:51)
-            slot = slots[i]
             if x._dev_version == x.version:
                 if slot >= 0:
                     mask[slot] = 0
                 continue
-            x._dev_version = x.version
             write = x._mailbox_write
             if write is None:
                 x._seed_word.value = x.current_seed() % (1 << 64)
@@ -526,12 +536,17 @@ class Model:
             else:
                 if slot >= 0:
                     mask[slot] = 0
-                if not synced and getattr(ctx, "_replay_pending", False):
+                if not synced and ctx._replay_pending:
                     ctx.synchronize()                                   # the previous replay may still be reading the mailboxes
                 synced = True
                 if val is not None:
                     write(val)
-        ctx.call("pmt_model_update", self._model_run, mask, self._run_nslots, 1)
+            x._dev_version = x.version                                   # (behind the write: a value that could not be written stays stale)
+
+    def _fast_update(self, ctx):
+        """update!(model) of a small model, synchronous: callbacks here (they are host functions), everything else in pmt_model_update"""
+        self._walk_tape_parameters(ctx, self._run_mask)
+        ctx.call("pmt_model_update", self._model_run, self._run_mask, self._run_nslots, 1)
         ctx._replay_pending = False
         for r in self._records:
             r.finish_fetch()
@@ -540,15 +555,14 @@ class Model:
         """Host-updated Parameters that ONLY side-lane records read (and, with a hand-off, only when its launches are side-lane entries too)
         are committed on the side stream (pmt_plan_commit_lane): the upload of a constraint's data then overlaps the contraction of the
         objective instead of standing in front of it.  Every other Parameter keeps the plan's stream."""
-        lane_records = getattr(self, "_lane_records", [])
-        handoff_ok = self.device_qp is None or getattr(self.device_qp, "_in_tape_lane", None) == "side"
+        handoff_ok = self.device_qp is None or self.device_qp._in_tape_lane == "side"
         for x, side_only in self._parameter_readers().values():
             # (a graph replay launches the side-lane entries as nodes of ONE graph on the plan's stream: no side stream to order against)
-            x._commit_on_side_lane = bool(side_only and handoff_ok and lane_records and not self._use_graph)
+            x._commit_on_side_lane = bool(side_only and handoff_ok and self._lane_records and not self._use_graph)
 
     def _parameter_readers(self):
         """{id(Parameter): [Parameter, read by side-lane records only]}"""
-        lane_records = getattr(self, "_lane_records", [])
+        lane_records = self._lane_records
         readers = {}
         for r in self._records:
             if not isinstance(r.expr, DeviceNode):
@@ -562,14 +576,14 @@ class Model:
     def _side_refreshed_parameter_ids(self):
         """Parameters whose values will be produced ON the side stream (committed / regenerated there) once a hand-off recorded on the side
         lane exists: what a front-of-lane transfer may read without waiting for the plan's stream (lane 3)"""
-        if self._use_graph or not getattr(self, "_lane_records", []):
+        if self._use_graph or not self._lane_records:
             return set()
         return {k for k, (x, side_only) in self._parameter_readers().items() if side_only}
 
     @staticmethod
     def _side_lane_ok(r):
         from .device import DDenseAff, DSparseAff, DVarsAff
-        if not getattr(r, "side_lane_ok", False) or not isinstance(r.expr, DeviceNode):
+        if not r.side_lane_ok or not isinstance(r.expr, DeviceNode):
             return False
         for x in schedule([r.expr]):                # every node below the record is an implicit block: nothing of it is in the tape
             if isinstance(x, DeviceNode) and not (isinstance(x.out, (DDenseAff, DVarsAff, DSparseAff)) and not x.out.need_terms):
@@ -583,29 +597,15 @@ class Model:
         if self._records:
             self.device().upload(self._varmap_buf, self.model_var_to_optimizer)
             for r in self._records:
-                for hook in getattr(r, "varmap_hooks", ()):
+                for hook in r.varmap_hooks:
                     hook(self.model_var_to_optimizer)
 
     def _refresh_parameters(self):
         ctx = self.device()
-        fast = getattr(self, "_tape_parameters", None)
-        if fast is not None and not ctx.recording and not any(getattr(x, "_staged_pending", False) for x in fast):
-            # a SMALL model: every Parameter's value enters through an entry of the tape (mailbox copy or seeded fill) — the general walk
-            # below (device_value_of: staging slots, lanes, uploads) reduces to "evaluate, write the mailbox / the seed word when it changed"
-            synced = False
-            for x in fast:
-                val = Parameter.__call__(x)                              # evalarg(::Parameter) (src/lazyexpression.jl:51)
-                if x._dev_version != x.version:
-                    write = x._mailbox_write
-                    if write is not None:
-                        if not synced and getattr(ctx, "_replay_pending", False):
-                            ctx.synchronize()                           # the previous replay may still be reading the mailboxes
-                        synced = True
-                        if val is not None:
-                            write(val)
-                    else:
-                        x._seed_word.value = x.current_seed() % (1 << 64)
-                    x._dev_version = x.version
+        fast = self._tape_parameters
+        if fast is not None and not ctx.recording and not any(x._staged_pending for x in fast):
+            # the general walk below (device_value_of: staging slots, lanes, uploads) reduces to the short one
+            self._walk_tape_parameters(ctx)
             return
         from .lazyexpression import device_value_of
         ctx._staging_dirty = False
@@ -624,12 +624,11 @@ class Model:
 
     def _run_tape(self, fetch=True):
         ctx = self.device()
-        if getattr(self, "_fetches_read_parameters", False):
+        if self._fetches_read_parameters:
             # host_csc: dense constraint blocks leave straight out of their Parameter buffers (handoff.py): the previous solve's transfers
             # have read them before this solve's callbacks / commits rewrite them (a no-op when the caller has synchronised, as solve! does)
             ctx.fetch_synchronize()
-        if fetch and getattr(self, "_model_run", None) is not None and not ctx.recording and \
-                not any(getattr(x, "_staged_pending", False) for x in self._tape_parameters):
+        if fetch and self._model_run is not None and not ctx.recording and not any(x._staged_pending for x in self._tape_parameters):
             self._fast_update(ctx)
             return
         self._refresh_parameters()
@@ -646,7 +645,7 @@ class Model:
 
     def update(self, synchronize=True):                                # src/model.jl:132-143
         for p in self.params:                                          # setdirty!(model) — except what stage_parameters() has already
-            if not getattr(p, "_staged_pending", False):               # evaluated for this solve
+            if not p._staged_pending:                                  # evaluated for this solve
                 p.setdirty()
         if self.device_qp is not None:
             # device hand-off: the MOI buffers never leave HBM; the solver's CSC data is rebuilt right behind the tape

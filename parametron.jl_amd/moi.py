@@ -184,9 +184,8 @@ class _Record:
         self.model = model
         self.expr = expr
         self.isconstant = not isinstance(expr, DeviceNode)                # "it's just a value; not a LazyExpression" (:123)
-        self.dev = None                                                   # device twin of the MOI buffers (set by compile)
-        self.plan = QuadPlan(None)                                        # a quadratic record's is decided in Model.initialize (quad_plan)
-        self._quad_delivered = False                                      # the contraction itself delivers f.quadratic_terms
+        self.plan = QuadPlan(None)                                        # a quadratic record's is decided in Model._plan_quadratic_records (quad_plan)
+        self._reset_compiled()
         if self.isconstant:
             self.kind = canonical_function_kind(kind_of(expr))
             native = _to_native(self.kind, expr)
@@ -202,197 +201,113 @@ class _Record:
             self.f = None                                                 # sized by compile()
             self.nrows = expr.out.rows if self.kind == "affvec" else 1
 
+    def _reset_compiled(self):
+        """what compile() leaves for the model that runs the record: declared here, and fresh at every compile"""
+        self.dev = None                                                   # compile: device twins of the MOI buffers, by key
+        self.buffers = []                                                 # compile: (host array, key of dev) in fetch order, the constant's word included
+        self.delivered = ()                                               # _compile_gram: keys of dev the producing kernel itself delivers to the host
+        self._cbuf = None                                                 # compile: the page-locked word the scalar functions' constant lands in
+        self.varmap_hooks = []                                            # _compile_sparse: called with the new host varmap whenever it changes
+        self.side_lane_ok = False                                         # _implicit_twins, _compile_static: reads Parameter values only, writes its own buffers
+        self.on_side_lane = False                                         # Model._record_tape, before the emitter runs
+        self.terms_static = False                                         # _compile_static: the terms are host data, only the constants are rebuilt
+        self.groups_ordered = None                                        # _compile_groups: every group is one slice of the destination
+        self._sub_args = []                                               # _lsq_sum_emitter: host arrays a recorded combine reads
+        self._fetch_recorded = False                                      # record_fetch: the copies are entries of the tape
+
     # ---- device side of update!(moi_f, expr(), varmap)
     def compile(self, ctx, varmap_buf, handoff_varmap=None):
-        """Allocate the MOI buffers (host + device twin) and return the emitter of the MOI copy.  `handoff_varmap` (host array,
-        device hand-off only): the final model_var_to_optimizer; a Gram objective whose variables stay in increasing order under it
-        writes the solver's CSC values of P directly from the contraction's epilogue and no quadratic term structs at all."""
-        out = self.expr.out
-        self.varmap_hooks = []                                            # called with the new host varmap whenever it changes
-        self.side_lane_ok = False
-        self.on_side_lane = False
-        # A SMALL model (Model.initialize: launch-bound on the device) has no device twin of its MOI buffers: the kernels store straight into
-        # the page-locked host arrays of the function object (a few KB over PCIe from inside the one launch), and update! ends with ONE stream
-        # synchronisation instead of a D2H copy per buffer (~10 us each: five of them were half of solve! at n = 100)
-        zero_copy = bool(getattr(self.model, "_small", False))
-
-        def twin(host, nbytes):
-            if zero_copy and nbytes > 0 and host.nbytes >= nbytes:
-                return host.ctypes.data
-            return ctx.alloc(max(nbytes, 16))
-        self._cbuf = ctx.pinned_array(1, np.float64)                      # the scalar functions' constant lands here
+        """Allocate the MOI buffers (host + device twin) and return the emitter of the MOI copy: one method per function form, each
+        sets self.f and self.dev.  `handoff_varmap` (host array, device hand-off only): the final model_var_to_optimizer; a Gram objective
+        whose variables stay in increasing order under it writes the solver's CSC values of P directly from the contraction's epilogue and
+        no quadratic term structs at all."""
+        self._reset_compiled()
+        self._cbuf = ctx.pinned_array(1, np.float64)
         if self.kind == "aff":
-            n = out.nterms
-            self.f = ScalarAffineFunction(n, alloc=ctx.pinned_array)
-            dev_terms = twin(self.f.terms, 16 * n)
-            # a small model: the constant (a word the expression's node left in HBM) is copied into its page-locked word by one more entry of
-            # the tape — a node of the one launch — instead of a D2H copy behind every replay (a hipMemcpyAsync of 8 bytes is ~5 us of host time)
-            dconst = self._cbuf.ctypes.data if zero_copy else out.const
-            self.dev = {"terms": dev_terms, "const": dconst}
-
-            def emit(c):
-                c.call("pmt_pack_scalar_affine_f64", P(out.terms), n, P(varmap_buf), P(dev_terms))
-                if zero_copy:
-                    c.call("pmt_copy_bytes", P(dconst), P(out.const), 8)
-            return emit
-        if self.kind == "quad":
-            plan, gram = self.plan, self.plan.gram
-            if plan.mode == "canonical-csc":
-                n = gram.mat.cols
-                self.f = ScalarQuadraticFunction(n, 0, alloc=ctx.pinned_array)
-                dp, dl, dc = ctx.alloc(8 * max(n * (n + 1) // 2, 1)), ctx.alloc(16 * max(n, 1)), ctx.alloc(8)
-                ws = _gram_workspace(ctx, gram)
-                self.dev = {"P_values": dp, "P_vars": handoff_varmap[gram.xvars.vars - 1], "lin": dl, "const": dc}
-                alpha = -1.0 if self.model.sense == "Maximize" else 1.0
-                host_P = None
-                if getattr(self.model, "handoff", "") == "host_csc" and getattr(self.model, "_overlap_fetch", False):
-                    # host solver hand-off: the contraction finishes P column band by column band and every finished group of bands leaves
-                    # for this page-locked array while the rest is still being computed (pmt_quad_gram_csc_deliver_f64)
-                    host_P = ctx.pinned_array(max(n * (n + 1) // 2, 1), np.float64)
-                    self.dev["P_host"] = host_P
-
-                def emit(c):
-                    if host_P is not None:
-                        c.call("pmt_quad_gram_csc_deliver_f64", *_gram_args(gram), P(varmap_buf), alpha, P(dp), host_P.ctypes.data_as(C.c_void_p), 0,
-                               P(dl), P(dc), P(ws))
-                    else:
-                        c.call("pmt_quad_gram_csc_f64", *_gram_args(gram), P(varmap_buf), alpha, P(dp), None, P(dl), P(dc), P(ws))
-                return emit
-            if plan.mode == "canonical":
-                n = gram.mat.cols
-                nq = n * (n + 1) // 2
-                self.f = ScalarQuadraticFunction(n, nq, alloc=ctx.pinned_array)
-                dq, dl, dc = twin(self.f.quadratic_terms, 24 * nq), twin(self.f.affine_terms, 16 * n), twin(self._cbuf, 8)
-                ws = _gram_workspace(ctx, gram)
-                self.dev = {"quad": dq, "lin": dl, "const": dc}
-                deliver = self._quad_delivered = bool(getattr(self.model, "_overlap_moi", False)) and nq > 0
-
-                def emit(c):
-                    if deliver:
-                        # the quadratic terms leave for f.quadratic_terms (page-locked) row band by row band while the contraction runs
-                        c.call("pmt_quad_gram_deliver_f64", *_gram_args(gram), 1, P(varmap_buf), P(dq), self.f.quadratic_terms.ctypes.data_as(C.c_void_p), 0,
-                               P(dl), P(dc), P(ws))
-                    else:
-                        c.call("pmt_quad_gram_f64", *_gram_args(gram), 1, P(varmap_buf), P(dq), P(dl), P(dc), P(ws))
-                return emit
-            if plan.mode == "canonical-form":
-                return self._compile_form(ctx, varmap_buf, plan.form, handoff_varmap)
-            if plan.mode == "canonical-sum":
-                return self._compile_lsq_sum(ctx, varmap_buf, plan.terms)
-            if plan.mode == "canonical-groups":
-                return self._compile_groups(ctx, varmap_buf, plan.groups)
-            out.materialize()
-            self.f = ScalarQuadraticFunction(out.nl, out.nq, alloc=ctx.pinned_array)
-            dq, dl = twin(self.f.quadratic_terms, 24 * out.nq), twin(self.f.affine_terms, 16 * out.nl)
-            dconst = self._cbuf.ctypes.data if zero_copy else out.const          # (as for the affine function above)
-            self.dev = {"quad": dq, "lin": dl, "const": dconst}
-
-            def emit(c):
-                c.call("pmt_pack_scalar_quadratic_f64", P(out.quad), out.nq, P(varmap_buf), P(dq))
-                c.call("pmt_pack_scalar_affine_f64", P(out.lin), out.nl, P(varmap_buf), P(dl))
-                if zero_copy:
-                    c.call("pmt_copy_bytes", P(dconst), P(out.const), 8)
-            return emit
-        # Vector{AffineFunction}
-        # handoff="host_csc": the deliverable is the solver's CSC arrays on the host and the index map is fixed (Model.initialize), so the MOI
-        # terms of a dense block A*x (+|-) b or of x (+|-) v would be an intermediate nobody reads: A's CSC values are the Parameter matrix
-        # column by column (they leave straight out of its buffer, handoff.py) and the coefficients of x (+|-) v are the constant 1.0.
-        # Only the constants 0 (+|-) b are rebuilt per re-evaluation; the term STRUCTURE (rows, optimizer variables) is static host data.
-        if handoff_varmap is not None and getattr(self.model, "handoff", None) == "host_csc" and isinstance(out, (DDenseAff, DVarsAff)) and not out.need_terms:
-            xv = np.asarray(handoff_varmap, dtype=np.int64)[out.xvars.vars - 1]
-            dense = isinstance(out, DDenseAff)
-            if not dense or (len(xv) and np.all(np.diff(xv) > 0)):            # (a dense block whose columns are permuted or repeated keeps its terms)
-                self.f = VectorAffineFunction(out.nterms, out.rows)
-                t = self.f._terms
-                if dense:
-                    t["out"], t["var"], t["coeff"] = np.repeat(np.arange(1, out.rows + 1), out.mat.cols), np.tile(xv, out.rows), np.nan
-                    self.f.coefficients_unavailable = ("handoff=\"host_csc\": the MOI terms of a dense constraint block are not packed (its coefficients "
-                                                       "are the Parameter matrix, delivered as the CSC values of model.device_qp.host); use .structure for "
-                                                       "rows / variables, or handoff=\"moi\" for the reference's MOI functions")
-                else:
-                    t["out"], t["var"], t["coeff"] = np.arange(1, out.rows + 1), xv, 1.0
-                dc = ctx.alloc(8 * max(out.rows, 1))
-                ctx.zero(dc, 8 * max(out.rows, 1))
-                self.dev = {"consts": dc}
-                self.side_lane_ok = True
-                self.terms_static = True
-
-                def emit(c):
-                    if out.vec is not None and out.rows:
-                        c.call("pmt_consts_f64", P(out.vec.buf), out.rows, out.sign, P(dc))
-                return emit
-        self.f = VectorAffineFunction(out.nterms, out.rows, alloc=ctx.pinned_array)
-        dt = twin(self.f._terms, 24 * out.nterms)
-        if isinstance(out, DDenseAff) and not out.need_terms:
-            dc = twin(self.f.constants, 8 * out.rows)
-            self.dev = {"terms": dt, "consts": dc}
-            self.side_lane_ok = True          # reads Parameter values only, writes its own MOI buffers (Model.initialize: side lane)
-            vec = out.vec.buf if out.vec is not None else None
-
-            def emit(c):
-                # on the side lane (Model.initialize sets on_side_lane before recording): the low-footprint kernel that is co-resident with
-                # the contraction it runs beside
-                c.call("pmt_affine_pack_vector_background_f64" if self.on_side_lane else "pmt_affine_pack_vector_f64", P(out.mat.buf), out.mat.lda,
-                       out.mat.rows, out.mat.cols, P(out.xvars.buf), P(vec), out.sign if vec else 0, P(varmap_buf), 0, P(dt), P(dc))
-            return emit
-        if isinstance(out, DVarsAff) and not out.need_terms:
-            dc = twin(self.f.constants, 8 * out.rows)
-            self.dev = {"terms": dt, "consts": dc}
-            self.side_lane_ok = True          # reads Parameter values only, writes its own MOI buffers (Model.initialize: side lane)
-
-            def emit(c):
-                c.call("pmt_vars_addsub_f64", P(out.xvars.buf), out.rows, P(out.vec.buf), out.sign, P(varmap_buf), 0, None, P(dt), P(dc))
-            return emit
-        if isinstance(out, DSparseAff) and not out.need_terms:
-            dc = twin(self.f.constants, 8 * out.rows)
-            self.dev = {"terms": dt, "consts": dc}
-            self.side_lane_ok = True          # reads Parameter values only, writes its own MOI buffers (Model.initialize: side lane)
-            sp = out.spmat
-            # varmap folded into the static variable words: it changes with the optimizer's index map (mapindices!, src/model.jl:100-107),
-            # not per re-evaluation, so the kernel reads varmap[x[col]] instead of gathering it for every term.  Block form: one word per
-            # COLUMN (staged in LDS per column band); slab form: one per term
-            if sp.block_cw:
-                colvar = ctx.alloc(8 * max(sp.cols, 1))
-
-                def refresh(varmap_host):
-                    v = out.xvars.vars if varmap_host is None else np.asarray(varmap_host, dtype=np.int64)[out.xvars.vars - 1]
-                    ctx.upload(colvar, np.ascontiguousarray(v, dtype=np.int64))
-                self.varmap_hooks.append(refresh)
-                refresh(handoff_varmap)
-
-                def emit(c):
-                    # terms and constants (0 (+|-) d) in one launch
-                    c.call("pmt_sparse_pack_vector_blocks_f64", P(sp.buf), P(sp.block_desc_buf), P(sp.block_idx_buf), P(sp.block_band_buf), P(colvar),
-                           sp.rows, sp.cols, sp.nnz, sp.block_cw, None, 0, P(out.vec.buf) if out.vec is not None else None,
-                           out.sign if out.vec is not None else 0, P(dt), P(dc))
-                return emit
-            mapped = ctx.alloc((4 if sp.narrow else 8) * max(sp.nnz, 1))
-
-            def refresh(varmap_host):
-                if sp.nnz:
-                    v = out.term_var if varmap_host is None else np.asarray(varmap_host, dtype=np.int64)[out.term_var - 1]
-                    if sp.narrow and (v.max() >= 2 ** 32 or v.min() < 0):
-                        raise DimensionMismatch("sparse constraint: optimizer variable indices of 2^32 or more with a 32-bit pattern")
-                    ctx.upload(mapped, v.astype(np.uint32) if sp.narrow else np.ascontiguousarray(v))
-            self.varmap_hooks.append(refresh)
-            refresh(handoff_varmap)
-
-            def emit(c):
-                c.call("pmt_sparse_pack_vector_slabs_u32_f64" if sp.narrow else "pmt_sparse_pack_vector_slabs_f64", P(sp.buf), P(sp.perm_buf), P(mapped),
-                       P(sp.slab_ptr_buf), sp.rows, sp.nslab, None, 0, P(dt))
-                if out.vec is not None:
-                    c.call("pmt_consts_f64", P(out.vec.buf), out.rows, out.sign, P(dc))
-            return emit
-        m = out.materialized()
-        self.dev = {"terms": dt, "consts": m.consts}
-
-        def emit(c):
-            c.call("pmt_pack_vector_affine_f64", P(m.terms), P(m.row_ptr_buf), m.rows, m.row_len, P(varmap_buf), 0, P(dt))
+            emit = self._compile_affine(ctx, varmap_buf, handoff_varmap)
+            self.buffers = [(self.f.terms, "terms"), (self._cbuf, "const")]
+        elif self.kind == "quad":
+            emit = self._QUAD_FORMS[self.plan.mode](self, ctx, varmap_buf, handoff_varmap)
+            self.buffers = [(self.f.quadratic_terms, "quad"), (self.f.affine_terms, "lin"), (self._cbuf, "const")]
+        else:
+            emit = self._compile_vector(ctx, varmap_buf, handoff_varmap)
+            self.buffers = [(self.f._terms, "terms"), (self.f.constants, "consts")]
         return emit
 
-    def _compile_form(self, ctx, varmap_buf, form, handoff_varmap):
+    def _twin(self, ctx, host, nbytes):
+        """The device twin of a host MOI buffer.  A SMALL model (Model._decide_small: launch-bound on the device) has none: the kernels store
+        straight into the page-locked host arrays of the function object (a few KB over PCIe from inside the one launch), and update! ends with
+        ONE stream synchronisation instead of a D2H copy per buffer (~10 us each: five of them were half of solve! at n = 100)"""
+        if self.model._small and nbytes > 0 and host.nbytes >= nbytes:
+            return host.ctypes.data
+        return ctx.alloc(max(nbytes, 16))
+
+    def _const_twin(self, out):
+        """a small model: the constant (a word the expression's node left in HBM) is copied into its page-locked word by one more entry of
+        the tape — a node of the one launch — instead of a D2H copy behind every replay (a hipMemcpyAsync of 8 bytes is ~5 us of host time)"""
+        return self._cbuf.ctypes.data if self.model._small else out.const
+
+    def _compile_affine(self, ctx, varmap_buf, handoff_varmap):
+        out, zero_copy = self.expr.out, self.model._small
+        n = out.nterms
+        self.f = ScalarAffineFunction(n, alloc=ctx.pinned_array)
+        dev_terms, dconst = self._twin(ctx, self.f.terms, 16 * n), self._const_twin(out)
+        self.dev = {"terms": dev_terms, "const": dconst}
+
+        def emit(c):
+            c.call("pmt_pack_scalar_affine_f64", P(out.terms), n, P(varmap_buf), P(dev_terms))
+            if zero_copy:
+                c.call("pmt_copy_bytes", P(dconst), P(out.const), 8)
+        return emit
+
+    def _compile_literal(self, ctx, varmap_buf, handoff_varmap):
+        out, zero_copy = self.expr.out, self.model._small
+        out.materialize()
+        self.f = ScalarQuadraticFunction(out.nl, out.nq, alloc=ctx.pinned_array)
+        dq, dl = self._twin(ctx, self.f.quadratic_terms, 24 * out.nq), self._twin(ctx, self.f.affine_terms, 16 * out.nl)
+        dconst = self._const_twin(out)
+        self.dev = {"quad": dq, "lin": dl, "const": dconst}
+
+        def emit(c):
+            c.call("pmt_pack_scalar_quadratic_f64", P(out.quad), out.nq, P(varmap_buf), P(dq))
+            c.call("pmt_pack_scalar_affine_f64", P(out.lin), out.nl, P(varmap_buf), P(dl))
+            if zero_copy:
+                c.call("pmt_copy_bytes", P(dconst), P(out.const), 8)
+        return emit
+
+    def _compile_gram(self, ctx, varmap_buf, handoff_varmap):
+        """dot(r, r), r = A*x (+|-) b (plan.gram): MOI terms ("canonical"), or the CSC values of P for a hand-off under whose index map x
+        keeps its order ("canonical-csc")"""
+        gram = self.plan.gram
+        n = gram.mat.cols
+        nq = n * (n + 1) // 2
+        csc = self.plan.mode == "canonical-csc"
+        self.f = f = ScalarQuadraticFunction(n, 0 if csc else nq, alloc=ctx.pinned_array)
+        ws = _gram_workspace(ctx, gram)
+        if csc:
+            dp, dl, dc = ctx.alloc(8 * max(nq, 1)), ctx.alloc(16 * max(n, 1)), ctx.alloc(8)
+            self.dev = {"P_values": dp, "P_vars": handoff_varmap[gram.xvars.vars - 1], "lin": dl, "const": dc}
+            alpha = -1.0 if self.model.sense == "Maximize" else 1.0
+            if not (self.model.handoff == "host_csc" and self.model._overlap_fetch):
+                return lambda c: c.call("pmt_quad_gram_csc_f64", *_gram_args(gram), P(varmap_buf), alpha, P(dp), None, P(dl), P(dc), P(ws))
+            # host solver hand-off: the contraction finishes P column band by column band and every finished group of bands leaves
+            # for this page-locked array while the rest is still being computed (pmt_quad_gram_csc_deliver_f64)
+            host_P = self.dev["P_host"] = ctx.pinned_array(max(nq, 1), np.float64)
+            return lambda c: c.call("pmt_quad_gram_csc_deliver_f64", *_gram_args(gram), P(varmap_buf), alpha, P(dp),
+                                    host_P.ctypes.data_as(C.c_void_p), 0, P(dl), P(dc), P(ws))
+        dq, dl, dc = self._twin(ctx, f.quadratic_terms, 24 * nq), self._twin(ctx, f.affine_terms, 16 * n), self._twin(ctx, self._cbuf, 8)
+        self.dev = {"quad": dq, "lin": dl, "const": dc}
+        if not (self.model._overlap_moi and nq > 0):
+            return lambda c: c.call("pmt_quad_gram_f64", *_gram_args(gram), 1, P(varmap_buf), P(dq), P(dl), P(dc), P(ws))
+        # the quadratic terms leave for f.quadratic_terms (page-locked) row band by row band while the contraction runs
+        self.delivered = ("quad",)
+        return lambda c: c.call("pmt_quad_gram_deliver_f64", *_gram_args(gram), 1, P(varmap_buf), P(dq),
+                                f.quadratic_terms.ctypes.data_as(C.c_void_p), 0, P(dl), P(dc), P(ws))
+
+    def _compile_form(self, ctx, varmap_buf, handoff_varmap):
         """transpose(x) * Q * x alone (plan.form): pmt_quad_form_f64 reads the Parameter matrix and writes the canonical
         MOI function — n(n+1)/2 quadratic terms, no linear terms, constant 0.0 — or, for the device hand-off, the CSC values of P."""
+        form = self.plan.form
         n = form.mat.cols
         nq = n * (n + 1) // 2
         if handoff_varmap is not None:
@@ -400,23 +315,18 @@ class _Record:
             dp, dl, dc = ctx.alloc(8 * nq), ctx.alloc(16 * n), ctx.alloc(8)
             self.dev = {"P_values": dp, "P_vars": handoff_varmap[form.xvars.vars - 1], "lin": dl, "const": dc}
             alpha = -1.0 if self.model.sense == "Maximize" else 1.0
-
-            def emit(c):
-                c.call("pmt_quad_form_f64", *_form_args(form, varmap_buf, alpha), None, P(dp), P(dl), P(dc))
-            return emit
+            return lambda c: c.call("pmt_quad_form_f64", *_form_args(form, varmap_buf, alpha), None, P(dp), P(dl), P(dc))
         self.f = ScalarQuadraticFunction(0, nq, alloc=ctx.pinned_array)
         dq, dc = ctx.alloc(24 * nq), ctx.alloc(8)
-        self.dev = {"quad": dq, "const": dc}
+        self.dev = {"quad": dq, "const": dc}                              # (no "lin": a bare form has no linear terms)
+        return lambda c: c.call("pmt_quad_form_f64", *_form_args(form, varmap_buf, 1.0), P(dq), None, None, P(dc))
 
-        def emit(c):
-            c.call("pmt_quad_form_f64", *_form_args(form, varmap_buf, 1.0), P(dq), None, None, P(dc))
-        return emit
-
-    def _compile_lsq_sum(self, ctx, varmap_buf, terms):
+    def _compile_lsq_sum(self, ctx, varmap_buf, handoff_varmap):
         """The objective as a weighted sum of least-squares blocks over one x (plan.terms): block 1 by pmt_quad_gram_f64 straight into the
         MOI buffers, blocks 2..K as CSC values (pmt_quad_gram_csc_f64, bit for bit the same coefficients), then pmt_quad_gram_sum_f64 weights
         and adds everything in place.  A form transpose(x) * Q * x stands where a block stands: pmt_quad_form_f64 writes the same outputs
         (its linear terms and constant are zero).  The terms are final only after the combine: no overlapped delivery of the quadratic terms."""
+        terms = self.plan.terms
         n = [t for t in terms if t.kind in ("block", "form")][0].r.mat.cols
         nq = n * (n + 1) // 2
         self.f = ScalarQuadraticFunction(n, nq, alloc=ctx.pinned_array)
@@ -461,7 +371,7 @@ class _Record:
         if sub:
             ptrs = (C.c_void_p * len(lists))(*[p.ctypes.data if p is not None else None for p in lists])
             counts = np.array([len(p) if p is not None else 0 for p in lists], dtype=np.int64)
-            self._sub_args = getattr(self, "_sub_args", []) + [(lists, ptrs, counts)]     # (the entry reads them when the call is recorded)
+            self._sub_args.append((lists, ptrs, counts))                    # (the entry reads them when the call is recorded)
 
         def emit_block(c, t, w, first, part):
             if t.kind == "form":
@@ -483,13 +393,14 @@ class _Record:
                 c.call("pmt_quad_gram_sum_f64", n, C.addressof(arr), len(desc), P(dq), P(dl), P(dc))
         return emit
 
-    def _compile_groups(self, ctx, varmap_buf, groups):
+    def _compile_groups(self, ctx, varmap_buf, handoff_varmap):
         """The objective as a sum over groups of blocks / forms with pairwise disjoint Variable vectors (plan.groups): every group is written
         by the steps of its own canonical-sum list (_lsq_sum_emitter) — straight into its slice of the MOI buffers when the groups' variables
         are consecutive in the sorted union z (pointer + offset: no copy, no extra pass), into an arena otherwise, from where
         pmt_quad_groups_gather_f64 places the rows through tables built here.  pmt_quad_groups_constant_f64 adds the groups' constants.
         As in canonical-sum the terms are final only after the last step: no overlapped delivery of the quadratic terms."""
         from . import _lib
+        groups = self.plan.groups
         lay = _lib.GroupsLayout([g.vars for g in groups])
         G, n, nq = len(groups), lay.nlin, lay.nterms
         self.f = ScalarQuadraticFunction(n, nq, alloc=ctx.pinned_array)
@@ -514,64 +425,154 @@ class _Record:
             c.call("pmt_quad_groups_constant_f64", P(consts), G, P(dc))
         return emit
 
+    # the quadratic forms by plan.mode (quad_plan)
+    _QUAD_FORMS = {"literal": _compile_literal, "canonical": _compile_gram, "canonical-csc": _compile_gram, "canonical-form": _compile_form,
+                   "canonical-sum": _compile_lsq_sum, "canonical-groups": _compile_groups}
+
+    # ---- Vector{AffineFunction}
+    def _compile_vector(self, ctx, varmap_buf, handoff_varmap):
+        out = self.expr.out
+        implicit = isinstance(out, (DDenseAff, DVarsAff, DSparseAff)) and not out.need_terms
+        if implicit and handoff_varmap is not None and self.model.handoff == "host_csc" and not isinstance(out, DSparseAff):
+            emit = self._compile_static(ctx, np.asarray(handoff_varmap, dtype=np.int64)[out.xvars.vars - 1])
+            if emit is not None:
+                return emit
+        self.f = VectorAffineFunction(out.nterms, out.rows, alloc=ctx.pinned_array)
+        if isinstance(out, DDenseAff) and implicit:
+            return self._compile_dense(ctx, varmap_buf)
+        if isinstance(out, DVarsAff) and implicit:
+            return self._compile_vars(ctx, varmap_buf)
+        if isinstance(out, DSparseAff) and implicit:
+            return (self._compile_sparse_blocks if out.spmat.block_cw else self._compile_sparse_slabs)(ctx, handoff_varmap)
+        dt = self._twin(ctx, self.f._terms, 24 * out.nterms)
+        m = out.materialized()
+        self.dev = {"terms": dt, "consts": m.consts}
+        return lambda c: c.call("pmt_pack_vector_affine_f64", P(m.terms), P(m.row_ptr_buf), m.rows, m.row_len, P(varmap_buf), 0, P(dt))
+
+    def _compile_static(self, ctx, xv):
+        """handoff="host_csc": the deliverable is the solver's CSC arrays on the host and the index map is fixed (Model.initialize), so the MOI
+        terms of a dense block A*x (+|-) b or of x (+|-) v would be an intermediate nobody reads: A's CSC values are the Parameter matrix
+        column by column (they leave straight out of its buffer, handoff.py) and the coefficients of x (+|-) v are the constant 1.0.
+        Only the constants 0 (+|-) b are rebuilt per re-evaluation; the term STRUCTURE (rows, optimizer variables `xv`) is static host data.
+        None: a dense block whose columns are permuted or repeated keeps its terms."""
+        out = self.expr.out
+        dense = isinstance(out, DDenseAff)
+        if dense and not (len(xv) and np.all(np.diff(xv) > 0)):
+            return None
+        self.f = VectorAffineFunction(out.nterms, out.rows)
+        t = self.f._terms
+        if dense:
+            t["out"], t["var"], t["coeff"] = np.repeat(np.arange(1, out.rows + 1), out.mat.cols), np.tile(xv, out.rows), np.nan
+            self.f.coefficients_unavailable = ("handoff=\"host_csc\": the MOI terms of a dense constraint block are not packed (its coefficients "
+                                               "are the Parameter matrix, delivered as the CSC values of model.device_qp.host); use .structure for "
+                                               "rows / variables, or handoff=\"moi\" for the reference's MOI functions")
+        else:
+            t["out"], t["var"], t["coeff"] = np.arange(1, out.rows + 1), xv, 1.0
+        dc = ctx.alloc(8 * max(out.rows, 1))
+        ctx.zero(dc, 8 * max(out.rows, 1))
+        self.dev = {"consts": dc}                                         # (no "terms": they never leave the host)
+        self.side_lane_ok = True
+        self.terms_static = True
+
+        def emit(c):
+            if out.vec is not None and out.rows:
+                c.call("pmt_consts_f64", P(out.vec.buf), out.rows, out.sign, P(dc))
+        return emit
+
+    def _implicit_twins(self, ctx):
+        """terms + constants twins of an implicit block (A*x (+|-) b, x (+|-) v, C*x (+|-) d): its pack reads Parameter values only and writes
+        its own MOI buffers, so it may go to the side lane (Model.lane_order)"""
+        out = self.expr.out
+        dt, dc = self._twin(ctx, self.f._terms, 24 * out.nterms), self._twin(ctx, self.f.constants, 8 * out.rows)
+        self.dev = {"terms": dt, "consts": dc}
+        self.side_lane_ok = True
+        return dt, dc
+
+    def _compile_dense(self, ctx, varmap_buf):
+        out = self.expr.out
+        dt, dc = self._implicit_twins(ctx)
+        vec = out.vec.buf if out.vec is not None else None
+
+        def emit(c):
+            # on the side lane (Model._record_tape sets on_side_lane before the emitter runs): the low-footprint kernel that is co-resident
+            # with the contraction it runs beside
+            c.call("pmt_affine_pack_vector_background_f64" if self.on_side_lane else "pmt_affine_pack_vector_f64", P(out.mat.buf), out.mat.lda,
+                   out.mat.rows, out.mat.cols, P(out.xvars.buf), P(vec), out.sign if vec else 0, P(varmap_buf), 0, P(dt), P(dc))
+        return emit
+
+    def _compile_vars(self, ctx, varmap_buf):
+        out = self.expr.out
+        dt, dc = self._implicit_twins(ctx)
+        return lambda c: c.call("pmt_vars_addsub_f64", P(out.xvars.buf), out.rows, P(out.vec.buf), out.sign, P(varmap_buf), 0, None, P(dt), P(dc))
+
+    # The sparse forms fold varmap into static variable words: it changes with the optimizer's index map (mapindices!, src/model.jl:100-107),
+    # not per re-evaluation, so the kernel reads varmap[x[col]] instead of gathering it for every term.  Block form: one word per COLUMN
+    # (staged in LDS per column band); slab form: one per term
+    def _compile_sparse_blocks(self, ctx, handoff_varmap):
+        out, sp = self.expr.out, self.expr.out.spmat
+        dt, dc = self._implicit_twins(ctx)
+        colvar = ctx.alloc(8 * max(sp.cols, 1))
+
+        def refresh(varmap_host):
+            v = out.xvars.vars if varmap_host is None else np.asarray(varmap_host, dtype=np.int64)[out.xvars.vars - 1]
+            ctx.upload(colvar, np.ascontiguousarray(v, dtype=np.int64))
+        self.varmap_hooks.append(refresh)
+        refresh(handoff_varmap)
+        # terms and constants (0 (+|-) d) in one launch
+        return lambda c: c.call("pmt_sparse_pack_vector_blocks_f64", P(sp.buf), P(sp.block_desc_buf), P(sp.block_idx_buf), P(sp.block_band_buf),
+                                P(colvar), sp.rows, sp.cols, sp.nnz, sp.block_cw, None, 0, P(out.vec.buf) if out.vec is not None else None,
+                                out.sign if out.vec is not None else 0, P(dt), P(dc))
+
+    def _compile_sparse_slabs(self, ctx, handoff_varmap):
+        out, sp = self.expr.out, self.expr.out.spmat
+        dt, dc = self._implicit_twins(ctx)
+        mapped = ctx.alloc((4 if sp.narrow else 8) * max(sp.nnz, 1))
+
+        def refresh(varmap_host):
+            if sp.nnz:
+                v = out.term_var if varmap_host is None else np.asarray(varmap_host, dtype=np.int64)[out.term_var - 1]
+                if sp.narrow and (v.max() >= 2 ** 32 or v.min() < 0):
+                    raise DimensionMismatch("sparse constraint: optimizer variable indices of 2^32 or more with a 32-bit pattern")
+                ctx.upload(mapped, v.astype(np.uint32) if sp.narrow else np.ascontiguousarray(v))
+        self.varmap_hooks.append(refresh)
+        refresh(handoff_varmap)
+
+        def emit(c):
+            c.call("pmt_sparse_pack_vector_slabs_u32_f64" if sp.narrow else "pmt_sparse_pack_vector_slabs_f64", P(sp.buf), P(sp.perm_buf), P(mapped),
+                   P(sp.slab_ptr_buf), sp.rows, sp.nslab, None, 0, P(dt))
+            if out.vec is not None:
+                c.call("pmt_consts_f64", P(out.vec.buf), out.rows, out.sign, P(dc))
+        return emit
+
+    # ---- the MOI buffers' way to the host: every user of `buffers` goes through copies()
+    def copies(self, skip=()):
+        """(host array, device address) of the entries of `buffers` that need a D2H copy: a key absent from dev has none (P's CSC values are
+        written instead of quadratic terms, a bare form has no linear terms, static terms never leave the host), and neither has a twin
+        that IS the host array (a small model, _twin)"""
+        d = self.dev or {}
+        return [(host, d[key]) for host, key in self.buffers if key in d and key not in skip and d[key] != host.ctypes.data]
+
     def record_fetch(self, ctx):
         """while recording (Model._overlap_moi): the same copies as fetch(), as tape entries behind this record's launches on their lane —
-        they leave while the rest of the tape is still running (pmt_plan_record_fetch); the objective's quadratic terms are delivered by
-        the contraction itself when it is the canonical node"""
-        f, d = self.f, self.dev
-        if self.isconstant or d is None:
-            return
-        if self.kind in ("aff", "quad"):
-            self._c = ctx.pinned_array(1, np.float64)
-        if self.kind == "aff":
-            ctx.record_fetch(f.terms, d["terms"], f.terms.nbytes)
-            ctx.record_fetch(self._c, d["const"], 8)
-        elif self.kind == "quad":
-            if "quad" in d and not self._quad_delivered:
-                ctx.record_fetch(f.quadratic_terms, d["quad"], f.quadratic_terms.nbytes)
-            if "lin" in d:                                                # (absent for a bare form: no linear terms)
-                ctx.record_fetch(f.affine_terms, d["lin"], f.affine_terms.nbytes)
-            ctx.record_fetch(self._c, d["const"], 8)
-        else:
-            ctx.record_fetch(f.terms, d["terms"], f.terms.nbytes)
-            ctx.record_fetch(f.constants, d["consts"], f.constants.nbytes)
+        they leave while the rest of the tape is still running (pmt_plan_record_fetch); what the contraction delivers itself (`delivered`:
+        the quadratic terms of the canonical node) is not fetched"""
+        for host, dptr in self.copies(skip=self.delivered):
+            ctx.record_fetch(host, dptr, host.nbytes)
         self._fetch_recorded = True
 
     def fetch(self, ctx):
-        """D2H of the MOI buffers into the host function object (asynchronous; caller synchronises).  A buffer whose device twin IS the
-        host array (a small model, compile) needs no copy."""
-        if getattr(self, "_fetch_recorded", False):
-            return
-        f, d = self.f, self.dev
-
-        def get(host, key):
-            if key in d and d[key] != host.ctypes.data:
-                ctx.fetch(host, d[key], host.nbytes)
-        if self.kind == "aff":
-            get(f.terms, "terms")
-            self._c = self._cbuf; get(self._c, "const")
-        elif self.kind == "quad":
-            get(f.quadratic_terms, "quad")                                # (absent when P's CSC values are written directly)
-            get(f.affine_terms, "lin")
-            self._c = self._cbuf; get(self._c, "const")
-        else:
-            get(f._terms, "terms")                                        # (absent for a host_csc record whose terms are static, compile)
-            get(f.constants, "consts")
+        """D2H of the MOI buffers into the host function object (asynchronous; caller synchronises)"""
+        if not self._fetch_recorded:
+            for host, dptr in self.copies():
+                ctx.fetch(host, dptr, host.nbytes)
 
     def fetch_list(self):
-        """(host array, key of self.dev) pairs fetch() copies — for a host that registers them once (Model._create_model_run)"""
-        f = self.f
-        if self.kind == "aff":
-            self._c = self._cbuf
-            return [(f.terms, "terms"), (self._c, "const")]
-        if self.kind == "quad":
-            self._c = self._cbuf
-            return [(f.quadratic_terms, "quad"), (f.affine_terms, "lin"), (self._c, "const")]
-        return [(f._terms, "terms"), (f.constants, "consts")]
+        """(host array, key of self.dev) pairs fetch() copies — for a host that registers them once"""
+        return list(self.buffers)
 
     def finish_fetch(self):
         if self.kind in ("aff", "quad"):
-            self.f.constant = float(self._c[0])
+            self.f.constant = float(self._cbuf[0])
 
 
 def _lsq_sum_combines(terms):
@@ -646,7 +647,7 @@ class QuadPlan:
     Variable vectors (`groups`); `canonicalize`: through canonicalize! first."""
     def __init__(self, mode, gram=None, form=None, terms=None, canonicalize=False, groups=None):
         self.mode, self.gram, self.form, self.terms, self.canonicalize, self.groups = mode, gram, form, terms, canonicalize, groups
-        # the MOI copy is the canonical least-squares node, bare or the weighted sum of such nodes (Model.initialize: side lane, small-plan order)
+        # the MOI copy is the canonical least-squares node, bare or the weighted sum of such nodes (model.lane_order: side lane, small-plan order)
         self.gram_record = mode in ("canonical", "canonical-csc", "canonical-sum") or \
             (mode == "canonical-groups" and any(t.kind == "block" for g in groups for t in g.terms))
 

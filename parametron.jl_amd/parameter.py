@@ -18,6 +18,8 @@ class Parameter:
     Parameter(f, val, model)        in-place: f(val) mutates val     (src/parameter.jl:57)
     Parameter(model, val=val)       identity in-place: a work buffer the user updates manually (src/parameter.jl:88)
     """
+    device_resident = False         # DeviceUniformParameter: the value is regenerated in HBM, never uploaded
+    pattern = None                  # DeviceUniformSparseParameter: the fixed sparsity pattern
 
     def __init__(self, *args, val=None):
         if len(args) == 1:
@@ -42,6 +44,15 @@ class Parameter:
         self.version = 0            # bumped every time the update function ran
         self._dev = None            # device mirror (lazyexpression.DeviceValue), created on first device use
         self._dev_version = -1
+        # ---- how the value reaches the device (set by the model that runs the plan)
+        self._staged_pending = False            # Model.stage_parameters: evaluated and on the copy stream; consumed by device_value_of
+        self._commit_on_side_lane = False       # Model._mark_side_lane_parameters: only side-lane records read it
+        self._read_unordered_by_lane3 = False   # handoff.DeviceQP: a front-of-lane transfer reads the buffer without waiting for the plan's stream
+        self._in_tape = False                   # Model._record_parameter_callbacks (small model): the value enters through an entry of the tape ...
+        self._mailbox = None                    # ... a copy out of this page-locked array in the device layout,
+        self._mailbox_write = None              # written by this function (model._mailbox_writer),
+        self._seed_word = None                  # ... or a fill seeded from this host word (DeviceUniformParameter)
+        self._run_val = None                    # Model._create_model_run: the value array registered with the library
         model.addparameter(self)
 
     def __repr__(self):
@@ -124,6 +135,7 @@ class DeviceUniformParameter(Parameter):
         self.shape = tuple(int(s) for s in (shape if isinstance(shape, (tuple, list)) else (shape,)))
         self.seed, self.scale, self.advance = int(seed), float(scale), advance
         self.epoch = -1
+        self._host_stale = True                 # the host copy is older than the device value
         proto = np.zeros(self.shape if len(self.shape) == 1 else self.shape, dtype=np.float64, order="F")
         super().__init__(lambda v: v, proto, model)
         self.device_resident = True
@@ -140,7 +152,7 @@ class DeviceUniformParameter(Parameter):
         super().__call__()
         from .lazyexpression import device_value_of
         dv = device_value_of(self)                       # uploads / regenerates if stale
-        if getattr(self, "_host_stale", True):
+        if self._host_stale:
             ctx = self.model.device()
             if len(self.shape) == 2:
                 self.val = dv.fetch(ctx)                              # pitched copy out of the padded device layout
@@ -166,6 +178,7 @@ class DeviceUniformSparseParameter(DeviceUniformParameter):
         self.shape = tuple(int(s) for s in pattern.shape)
         self.seed, self.scale, self.advance = int(seed), float(scale), advance
         self.epoch = -1
+        self._host_stale = True
         Parameter.__init__(self, lambda v: v, self.pattern, model)
         self.device_resident = True
 
@@ -173,7 +186,7 @@ class DeviceUniformSparseParameter(DeviceUniformParameter):
         Parameter.__call__(self)
         from .lazyexpression import device_value_of
         dv = device_value_of(self)
-        if getattr(self, "_host_stale", True):
+        if self._host_stale:
             ctx = self.model.device()
             host = np.empty(max(dv.nnz, 1), dtype=np.float64)
             ctx.fetch(host, dv.buf, 8 * dv.nnz)
