@@ -30,35 +30,6 @@
 
 #include "common.h"
 
-#ifndef PMT_BS_SKIP
-#define PMT_BS_SKIP 0      // profiling builds only: 1 = no contraction, 2 = no q, 8 = no chunk loads, 32 = no operand reads
-#endif
-#ifndef PMT_BS_PITCH
-#define PMT_BS_PITCH 34    // LDS pitch of a panel column in doubles: 2 (mod 32) is conflict-free for ds_read_b64 (an odd pitch for ds_read2_b64)
-#endif
-#ifndef PMT_BS_PRIO
-#define PMT_BS_PRIO 0      // s_setprio of the matrix waves (helpers stay at 0): 0, 2, 3 measured equal
-#endif
-#ifndef PMT_BS_FENCE
-#define PMT_BS_FENCE 1     // operand reads are hoisted at most one k-step ahead of their MFMAs (unfenced the scheduler hoists several k-steps and spills)
-#endif
-
-#ifndef PMT_BS_PIN
-#define PMT_BS_PIN 0       // (measured round 6c: 0.450 against 0.416 ms per step — SLOWER here, profiles/r06_batch_small_pin.txt; not shipped) 1: the matrix waves' k-step as one pinned instruction stream: one operand read behind every second MFMA (0: the reads of k-step ks + 1 in one run in front of the MFMAs of ks)
-#endif
-#ifndef PMT_BS_GLDS
-#define PMT_BS_GLDS 0      // 1: the FAST path's A chunks go global -> LDS directly (global_load_lds_dwordx4, no staging registers, no ds_write)
-#endif
-
-#ifndef PMT_BS_DIAG3
-#define PMT_BS_DIAG3 1    // the third rotation of diagonal sub-tiles is not computed (see matrix_wave)
-#endif
-#ifndef PMT_BS_NT
-#define PMT_BS_NT 3        // bit 0 = the A stream is loaded with the nt policy, bit 1 = the slab copy-out stores are nontemporal
-#endif
-// (measured, profiles/r04_batch_small.txt: A is read once and the slab written once — with both marked nontemporal the step takes 0.430 instead
-// of 0.443 ms; either alone is within noise)
-
 #ifndef PMT_BS_TRACE
 #define PMT_BS_TRACE 0     // tuning builds: s_memtime stamps of workgroup 0's matrix wave 0, read back with pmt_debug_bs_trace (the loader waves must not
                            // be instrumented: a stamp is a global store, and their hand-counted s_waitcnt assumes they issue loads only)
@@ -77,7 +48,12 @@ namespace {
 
 constexpr int SN = 128;                 // columns handled (smaller instances are zero padded)
 constexpr int CK = 32;                  // rows per chunk
-constexpr int SGP = PMT_BS_PITCH;
+constexpr int SGP = 34;                 // LDS pitch of a panel column in doubles: 2 (mod 32) is conflict-free for ds_read_b64 (an odd pitch for ds_read2_b64)
+constexpr bool BS_FENCE = true;         // operand reads are hoisted at most one k-step ahead of their MFMAs (unfenced the scheduler hoists several k-steps and spills)
+constexpr bool BS_DIAG3 = true;         // the third rotation of diagonal sub-tiles is not computed (see matrix_wave)
+// The A stream is loaded with the nt policy (bit 0) and the slab copy-out stores are nontemporal (bit 1): A is read once and the slab written
+// once — with both marked nontemporal the step takes 0.430 instead of 0.443 ms; either alone is within noise (profiles/r04_batch_small.txt)
+constexpr int BS_NT = 3;
 constexpr int NT = 512;                 // threads per workgroup: waves 0-3 matrix, waves 4-7 helpers
 constexpr int NH = 256;                 // first helper thread
 constexpr int NL = 128, NS = 128;       // loader / storer threads
@@ -87,16 +63,6 @@ constexpr int NPL = 16;                 // 16-byte pieces per loader thread per 
 constexpr int CREG = 16;                // constraint-block entries prefetched per storer thread (m*n <= 2048)
 
 typedef double f64x2 __attribute__((ext_vector_type(2)));
-
-// LDS-DMA panel layout (GL): a global_load_lds_dwordx4 writes 64 lanes x 16 bytes LINEARLY from a wave-uniform base, so the image cannot be
-// padded per column.  One instruction fills a GROUP of four columns (4 x 256 bytes; lane L = column L >> 4, 16-byte slot L & 15); groups
-// are 1088 bytes apart (64 bytes of padding: the panel is exactly as large as the padded one) and inside a group slot s of column cg holds
-// the row pair s ^ cg (the lane reads that pair from HBM: the swizzle is on the SOURCE address, a quarter wave still reads one whole 256-byte
-// column piece).  16 lanes reading the same row pair of 16 consecutive columns then touch 16 distinct 16-byte slots: (group & 3) * 64 +
-// ((pair ^ cg) & 3) * 16 + ... covers every bank once — conflict-free like the 34-double pitch, for 8- and 16-byte reads alike.
-constexpr int GLG = 136;                // doubles per column group (1088 bytes)
-// doubles offset of (column c, row r) in a GL panel
-__device__ __forceinline__ int gl_off(int c, int r) { return (c >> 2) * GLG + (c & 3) * 32 + ((((r >> 1) ^ (c & 3)) << 1) | (r & 1)); }
 
 struct SmallArgs {
     const double *A; int64_t lda, rows, cols, strideA;
@@ -115,7 +81,7 @@ __device__ __forceinline__ void phase_barrier() { __syncthreads(); }
 
 // ---- matrix wave W (0..3): column strips 7 - W (tm = 0 .. 7 - W) and W (tm = 0 .. W)
 // ALLCOLS: n == 128 (no column predicate on the staging stores)
-template <int W, bool ALLCOLS, bool GL>
+template <int W, bool ALLCOLS>
 __device__ __forceinline__ void matrix_wave(const SmallArgs &p, const Shared &sh, int lane, int n, int nchunk) {
     constexpr int KA = 8 - W, KB = W + 1, TNA = 7 - W, TNB = W;
     const int lm = lane & 15, lk = lane >> 4;
@@ -141,21 +107,9 @@ __device__ __forceinline__ void matrix_wave(const SmallArgs &p, const Shared &sh
 #pragma unroll
     for (int r = 0; r < 4; ++r) { cA[r] = TNA * 16 + 4 * ((bq + r) & 3) + j_; cB[r] = TNB * 16 + 4 * ((bq + r) & 3) + j_; }
     const int rowdA = (KA - 1) * 16 + 4 * bq + i_, rowdB = (KB - 1) * 16 + 4 * bq + i_;      // rows of the diagonal sub-tiles (tm == tn)
-    if (PMT_BS_PRIO) __builtin_amdgcn_s_setprio(PMT_BS_PRIO);                                                           // the matrix pipe's wave outranks the helper on its SIMD
+    // (s_setprio of the matrix waves above the helpers on their SIMDs: 0, 2, 3 measured equal)
     const int a0 = lm * SGP + lk;                                                            // sub-tile tm: + tm * 16 * SGP
     const int bA0 = (TNA * 16) * SGP + lk, bB0 = (TNB * 16) * SGP + lk;
-    // GL panels: (column 16 t + c', row 4 ks + lk) sits at gl_off; the row pair 2 ks + (lk >> 1) is XORed with the column's cg = c' & 3, whose
-    // bit 1 meets the parity of ks: one base for even and one for odd k-steps, everything else is an immediate (t * 544, (ks >> 1) * 8 doubles)
-    const int cgl = lm & 3;
-    const int glane = cgl * 32 + ((((lk >> 1) ^ (cgl & 1)) << 1) | (lk & 1));
-    const int gaE = (lm >> 2) * GLG + glane + (cgl >> 1) * 4, gaO = (lm >> 2) * GLG + glane + (1 - (cgl >> 1)) * 4;
-    int gbE[4], gbO[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int grp = ((lm >> 2) + r) & 3;
-        gbE[r] = grp * GLG + glane + (cgl >> 1) * 4;
-        gbO[r] = grp * GLG + glane + (1 - (cgl >> 1)) * 4;
-    }
     const int64_t G = gridDim.x;
     int cur = 0;
     int tphase = 0; (void)tphase;
@@ -164,106 +118,39 @@ __device__ __forceinline__ void matrix_wave(const SmallArgs &p, const Shared &sh
         for (int ch = 0; ch < nchunk; ++ch) {
             const double *pan = sh.panel + cur * PANEL;
             if (PMT_BS_TRACE && W == 0 && lane == 0) BS_STAMP(0, 4 * tphase + 0);
-            if (!(PMT_BS_SKIP & 1)) {
-                // explicit software pipeline: the operands of k-step ks + 1 are read (into the other register set) BEFORE the MFMAs of
-                // k-step ks are issued, so the LDS latency hides behind 36 MFMAs instead of idling this SIMD's matrix pipe (there is no second
-                // matrix wave on the SIMD to cover it).  The fences keep the reads from being hoisted further (register pressure).
-                double a[2][KA], bA[2][4], bB[2][4];
-                auto read_operands = [&](int s_, int ks) {
-                    if (PMT_BS_SKIP & 32) {
+            // explicit software pipeline: the operands of k-step ks + 1 are read (into the other register set) BEFORE the MFMAs of
+            // k-step ks are issued, so the LDS latency hides behind 36 MFMAs instead of idling this SIMD's matrix pipe (there is no second
+            // matrix wave on the SIMD to cover it).  The fences keep the reads from being hoisted further (register pressure).
+            double a[2][KA], bA[2][4], bB[2][4];
+            auto read_operands = [&](int s_, int ks) {
+                (void)lane;   // NOT dead code: `lane` is otherwise unused in this lambda, and this keeps it in the capture list.  The closure's layout decides
+                              // the kernel's schedule — without the capture both instantiations change (922 / 1585 lines of tools/isa_diff.py)
 #pragma unroll
-                        for (int i = 0; i < KA; ++i) a[s_][i] = (double)(lane + i + ks);
+                for (int i = 0; i < KA; ++i) a[s_][i] = pan[a0 + i * 16 * SGP + ks * 4];
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) { bA[s_][r] = (double)(lane + r); bB[s_][r] = (double)(lane - r); }
-                        return;
-                    }
-                    if (GL) {
-                        const int hi = (ks >> 1) * 8;
+                for (int r = 0; r < 4; ++r) { bA[s_][r] = pan[bA0 + rc[r] + ks * 4]; bB[s_][r] = pan[bB0 + rc[r] + ks * 4]; }
+            };
+            read_operands(0, 0);
+            // (The k-step as one pinned instruction stream, one operand read behind every second MFMA as in gram_mid.hip's mid_step, measured
+            // 0.450 against 0.416 ms per step: slower here — profiles/r06_batch_small_pin.txt.)
 #pragma unroll
-                        for (int i = 0; i < KA; ++i) a[s_][i] = pan[((ks & 1) ? gaO : gaE) + i * 4 * GLG + hi];
+            for (int ks = 0; ks < CK / 4; ++ks) {
+                const int s_ = ks & 1;
+                if (ks + 1 < CK / 4) read_operands(s_ ^ 1, ks + 1);
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const int b0 = (ks & 1) ? gbO[r] : gbE[r];
-                            bA[s_][r] = pan[b0 + TNA * 4 * GLG + hi];
-                            bB[s_][r] = pan[b0 + TNB * 4 * GLG + hi];
-                        }
-                        return;
-                    }
+                for (int r = 0; r < 4; ++r) {
+                    // (the third rotation of a DIAGONAL sub-tile — i = KA - 1 / KB - 1 — holds the transposes of the first one's 4 x 4 blocks:
+                    // not computed, the write-out below takes block (3, 0) of rotation 1 as (0, 3); gram_tall.hip tall_diag_rule)
 #pragma unroll
-                    for (int i = 0; i < KA; ++i) a[s_][i] = pan[a0 + i * 16 * SGP + ks * 4];
+                    for (int i = 0; i < KA; ++i)
+                        if (!(BS_DIAG3 && r == 3 && i == KA - 1))
+                            accA[i][r] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[s_][i], bA[s_][r], accA[i][r], 0, 0, 0);
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) { bA[s_][r] = pan[bA0 + rc[r] + ks * 4]; bB[s_][r] = pan[bB0 + rc[r] + ks * 4]; }
-                };
-                read_operands(0, 0);
-#if PMT_BS_PIN
-                // Round 6c: the k-step as ONE pinned instruction stream (gram_mid.hip: mid_step).  The matrix wave is alone with its SIMD's
-                // matrix pipe: the KA + 8 operand reads of k-step ks + 1 stood in one run in front of the 34-36 MFMAs of k-step ks, and a
-                // run of LDS instructions is issue time the pipe waits for.  Here ONE read stands behind every second MFMA, in the order
-                // the next k-step needs them (the A operands, then the B operands rotation by rotation); same MFMAs in the same order.
-                auto read_one = [&](int s_, int ks, int idx) {
-                    if (PMT_BS_SKIP & 32) { read_operands(s_, ks); return; }
-                    const int hi = (ks >> 1) * 8;
-                    if (idx < KA) {
-                        a[s_][idx] = GL ? pan[((ks & 1) ? gaO : gaE) + idx * 4 * GLG + hi] : pan[a0 + idx * 16 * SGP + ks * 4];
-                    } else {
-                        const int r = (idx - KA) >> 1;
-                        const bool isB = ((idx - KA) & 1) != 0;
-                        if (GL) {
-                            const int b0 = (ks & 1) ? gbO[r] : gbE[r];
-                            if (isB) bB[s_][r] = pan[b0 + TNB * 4 * GLG + hi]; else bA[s_][r] = pan[b0 + TNA * 4 * GLG + hi];
-                        } else {
-                            if (isB) bB[s_][r] = pan[bB0 + rc[r] + ks * 4]; else bA[s_][r] = pan[bA0 + rc[r] + ks * 4];
-                        }
-                    }
-                };
-#pragma unroll
-                for (int ks = 0; ks < CK / 4; ++ks) {
-                    const int s_ = ks & 1;
-                    const bool more = ks + 1 < CK / 4;
-                    int m = 0, nread = 0;
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-                        for (int i = 0; i < KA + KB; ++i) {
-                            const bool isA = i < KA;
-                            const int ii = isA ? i : i - KA;
-                            if (PMT_BS_DIAG3 && r == 3 && ii == (isA ? KA : KB) - 1) continue;
-                            if (isA) accA[ii][r] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[s_][ii], bA[s_][r], accA[ii][r], 0, 0, 0);
-                            else accB[ii][r] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[s_][ii], bB[s_][r], accB[ii][r], 0, 0, 0);
-                            if (more && (m & 1) == 0 && nread < KA + 8 && !(PMT_BS_SKIP & 32)) {
-                                __builtin_amdgcn_sched_barrier(0);
-                                read_one(s_ ^ 1, ks + 1, nread);
-                                __builtin_amdgcn_sched_barrier(0);
-                                ++nread;
-                            }
-                            ++m;
-                        }
-                    }
-                    if (more && (PMT_BS_SKIP & 32)) read_operands(s_ ^ 1, ks + 1);
-                    __builtin_amdgcn_sched_barrier(0);
+                    for (int i = 0; i < KB; ++i)
+                        if (!(BS_DIAG3 && r == 3 && i == KB - 1))
+                            accB[i][r] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[s_][i], bB[s_][r], accB[i][r], 0, 0, 0);
                 }
-#else
-#pragma unroll
-                for (int ks = 0; ks < CK / 4; ++ks) {
-                    const int s_ = ks & 1;
-                    if (ks + 1 < CK / 4) read_operands(s_ ^ 1, ks + 1);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        // (the third rotation of a DIAGONAL sub-tile — i = KA - 1 / KB - 1 — holds the transposes of the first one's 4 x 4 blocks:
-                        // not computed, the write-out below takes block (3, 0) of rotation 1 as (0, 3); gram_tall.hip tall_diag_rule)
-#pragma unroll
-                        for (int i = 0; i < KA; ++i)
-                            if (!(PMT_BS_DIAG3 && r == 3 && i == KA - 1))
-                                accA[i][r] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[s_][i], bA[s_][r], accA[i][r], 0, 0, 0);
-#pragma unroll
-                        for (int i = 0; i < KB; ++i)
-                            if (!(PMT_BS_DIAG3 && r == 3 && i == KB - 1))
-                                accB[i][r] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[s_][i], bB[s_][r], accB[i][r], 0, 0, 0);
-                    }
-                    if (PMT_BS_FENCE) asm volatile("" ::: "memory");
-                }
-#endif
+                if (BS_FENCE) asm volatile("" ::: "memory");
             }
             if (PMT_BS_TRACE && W == 0 && lane == 0) BS_STAMP(0, 4 * tphase + 1);
             if (ch == nchunk - 1) {
@@ -275,7 +162,7 @@ __device__ __forceinline__ void matrix_wave(const SmallArgs &p, const Shared &sh
                 for (int i = 0; i < KA; ++i) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        if (PMT_BS_DIAG3 && i == KA - 1) {
+                        if (BS_DIAG3 && i == KA - 1) {
                             // diagonal sub-tile: rotation 0 keeps row <= col, 2 keeps row < col, 1 keeps everything — its block (3, 0) at the
                             // transposed position —, 3 was not computed
                             const int row = rowdA, col = cA[r];
@@ -290,7 +177,7 @@ __device__ __forceinline__ void matrix_wave(const SmallArgs &p, const Shared &sh
                     if (i < KB) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
-                            if (PMT_BS_DIAG3 && i == KB - 1) {
+                            if (BS_DIAG3 && i == KB - 1) {
                                 const int row = rowdB, col = cB[r];
                                 if (r == 1 && row > col) { if (ALLCOLS || row < n) st[(col * n - (col * (col - 1)) / 2 - col) + row] = 2 * accB[i][r]; }
                                 else if (r != 3 && row <= col && (ALLCOLS || col < n)) st[rb[i] + col] = 2 * accB[i][r];
@@ -313,102 +200,8 @@ __device__ __forceinline__ void matrix_wave(const SmallArgs &p, const Shared &sh
 }
 
 // ---- loader waves 4, 5 (lt = 0..127): chunk loads -> LDS panels, and q from the LDS chunk
-// ---- loader waves 4, 5, LDS-DMA form (FAST shapes only): in phase g the 16 global_load_lds_dwordx4 of chunk g + 1 go straight into the panel
-// chunk g - 1 has just left (no staging registers, no ds_write pass), q is accumulated from panel g while they fly, and the wave waits for
-// them (vmcnt(0), by hand: the compiler does not count asm loads) just before the phase's barrier — the matrix waves read the panel one
-// phase after that wait.
-__device__ __forceinline__ void loader_waves_glds(const SmallArgs &p, const Shared &sh, int lt, int n, int nchunk) {
-    const int lane = lt & 63, lw = __builtin_amdgcn_readfirstlane(lt >> 6);
-    const int lm = lane & 15;
-    const int nq = n * (n + 1) / 2;
-    const int64_t G = gridDim.x;
-    const bool has_c = p.b && p.sign;
-    const double *csrc = has_c ? p.b : p.A;
-    const int64_t cstride = has_c ? p.strideb : p.strideA;
-    const int csign = has_c ? p.sign : 0;
-    // instruction q of this wave fills column group 16 lw + q; lane L of it: column 4 (16 lw + q) + (L >> 4), row pair (L & 15) ^ (L >> 4)
-    const int64_t lane_src = (int64_t)(lane >> 4) * p.lda + 2 * ((lane & 15) ^ (lane >> 4));
-    const unsigned pan_lds = (unsigned)reinterpret_cast<uintptr_t>(sh.panel) + (unsigned)(lw * 16 * GLG * 8);       // LDS byte address (low half of the generic one)
-    double cval = 0.0;
-    auto issue_chunk = [&](int64_t inst, int ch, int buf) {
-        const double *src0 = p.A + inst * p.strideA + (int64_t)(lw * 64) * p.lda + (int64_t)ch * CK + lane_src;
-        const unsigned dst0 = __builtin_amdgcn_readfirstlane(pan_lds + (unsigned)(buf * PANEL * 8));
-#pragma unroll
-        for (int q = 0; q < NPL; ++q) {
-            const double *src = src0 + (int64_t)(4 * q) * p.lda;
-            const unsigned dst = dst0 + (unsigned)(q * GLG * 8);
-            unsigned keep;
-            if (PMT_BS_NT & 1)
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
-                             : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-            else
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                             : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-        }
-        const double *cs = csrc + inst * cstride + (int64_t)ch * CK + (lt & (CK - 1));
-        asm volatile("global_load_dwordx2 %0, %1, off" : "=&v"(cval) : "v"(cs) : "memory");
-    };
-    auto land_chunk = [&](int buf) {
-        asm volatile("s_waitcnt vmcnt(0)" : "+v"(cval) : : "memory");
-        sh.cvec[buf * CK + (lt & (CK - 1))] = signed_const(cval, csign);                      // four threads write the same value: benign
-    };
-    // q as in the register form; (column c, rows 4 u + 2 lkp, + 1) is one aligned 16-byte read at gl_off(c, 4 u + 2 lkp): the pair index
-    // 2 u + lkp meets cg = c & 3, whose bit 1 meets the parity of u
-    double qpart[4] = {0.0, 0.0, 0.0, 0.0};
-    const int lkp = (lane >> 4) & 1, cg = lane >> 5;
-    const int c0 = 64 * lw + 16 * cg + lm, cgl = c0 & 3;
-    const int qbase = (c0 >> 2) * GLG + cgl * 32 + ((lkp ^ (cgl & 1)) << 1);
-    const int qE = qbase + (cgl >> 1) * 4, qO = qbase + (1 - (cgl >> 1)) * 4;
-    auto next_of = [&](int64_t i, int c, int64_t &ni, int &nc) { nc = c + 1; ni = i; if (nc == nchunk) { nc = 0; ni = i + G; } };
-
-    int64_t inst = blockIdx.x;
-    int ch = 0;
-    if (inst < p.B) {
-        issue_chunk(inst, 0, 0);
-        land_chunk(0);
-    }
-    phase_barrier();
-    int par = 0;
-    while (inst < p.B) {
-        const double *pan = sh.panel + par * PANEL;
-        int64_t n1i; int n1c;
-        next_of(inst, ch, n1i, n1c);
-        const bool more = n1i < p.B;
-        const bool last = (ch == nchunk - 1);
-        issue_chunk(more ? n1i : inst, more ? n1c : ch, par ^ 1);          // (past the end: a valid chunk again, never used)
-        if (!(PMT_BS_SKIP & 2)) {
-#pragma unroll
-            for (int u = 0; u < CK / 4; ++u) {
-                const f64x2 c2 = *reinterpret_cast<const f64x2 *>(sh.cvec + par * CK + 4 * u + 2 * lkp);
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const f64x2 a2 = *reinterpret_cast<const f64x2 *>(pan + ((u & 1) ? qO : qE) + j * 8 * GLG + (u >> 1) * 8);
-                    const double p0 = c2.x * a2.x, p1 = c2.y * a2.y;
-                    qpart[2 * j] = qpart[2 * j] + p0;
-                    qpart[2 * j + 1] = qpart[2 * j + 1] + p1;
-                }
-            }
-        }
-        if (last) {
-            phase_barrier();                                  // the previous slab has left the staging buffer
-            double *outp = p.out + inst * p.out_stride;
-            double *st = sh.stage + (int)((reinterpret_cast<uintptr_t>(outp) >> 3) & 1);
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const double p2 = __shfl(qpart[2 * j], lane + 16, 64), p3 = __shfl(qpart[2 * j + 1], lane + 16, 64);
-                const int col = 64 * lw + 32 * j + 16 * cg + lm;
-                if (lkp == 0 && col < n) st[nq + col] = 2 * (((qpart[2 * j] + qpart[2 * j + 1]) + p2) + p3);
-                qpart[2 * j] = 0.0;
-                qpart[2 * j + 1] = 0.0;
-            }
-        }
-        land_chunk(par ^ 1);
-        phase_barrier();
-        inst = n1i; ch = n1c;
-        par ^= 1;
-    }
-}
-
+// (An LDS-DMA form — global_load_lds_dwordx4 straight into a swizzled panel, no staging registers, no ds_write pass — was built, parity-green
+// and slower; it is gone.)
 template <bool FAST>
 __device__ __forceinline__ void loader_waves(const SmallArgs &p, const Shared &sh, int lt, int n, int nchunk) {
     const int lane = lt & 63, lw = lt >> 6;
@@ -435,16 +228,12 @@ __device__ __forceinline__ void loader_waves(const SmallArgs &p, const Shared &s
         constexpr int S = decltype(set_t)::value;
         const double *A = p.A + inst * p.strideA;
         const int64_t row = (int64_t)ch * CK + 2 * kp;
-        if (PMT_BS_SKIP & 8) {
-#pragma unroll
-            for (int q = 0; q < NPL; ++q) { R[S][q].x = 1.0; R[S][q].y = 2.0; }
-            cval[S] = 0.5;
-        } else if (FAST) {
+        if (FAST) {
 #pragma unroll
             for (int q = 0; q < NPL; ++q) {
                 const double *src = A + (int64_t)(cc0 + 8 * q) * p.lda + row;
                 f64x2 &dst = R[S][q];
-                if (PMT_BS_NT & 1) asm volatile("global_load_dwordx4 %0, %1, off nt" : "=&v"(dst) : "v"(src) : "memory");
+                if (BS_NT & 1) asm volatile("global_load_dwordx4 %0, %1, off nt" : "=&v"(dst) : "v"(src) : "memory");
                 else asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(dst) : "v"(src) : "memory");
             }
             // every thread reads c of row lt & 31 (no branch); without a b (sign 0) the read goes to A and signed_const(., 0) = 0
@@ -475,7 +264,7 @@ __device__ __forceinline__ void loader_waves(const SmallArgs &p, const Shared &s
     auto wait_chunk = [&](auto set_t, auto younger_t) {
         constexpr int S = decltype(set_t)::value;
         constexpr int YOUNGER = decltype(younger_t)::value;
-        if (FAST && !(PMT_BS_SKIP & 8)) {
+        if (FAST) {
             f64x2 (&r)[NPL] = R[S];                           // (asm operands inside a generic lambda must name locals)
             double &cv = cval[S];
             asm volatile("s_waitcnt vmcnt(%17)" : "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7]), "+v"(r[8]),
@@ -537,7 +326,7 @@ __device__ __forceinline__ void loader_waves(const SmallArgs &p, const Shared &s
         load_chunk(par_t, n2i, n2c);                          // chunk g + 2 -> set PAR (chunk g left it during phase g - 1)
         wait_chunk(Other{}, OneSet{});                        // chunk g + 1 (set PAR ^ 1, issued a phase ago) has landed ...
         store_chunk(Other{}, PAR ^ 1);                        // ... and goes into the other panel
-        if (!(PMT_BS_SKIP & 2)) {                             // q (vector ALU): two rows of two columns per 16-byte LDS read
+        {                                                     // q (vector ALU): two rows of two columns per 16-byte LDS read
 #pragma unroll
             for (int u = 0; u < CK / 4; ++u) {
                 const f64x2 c2 = *reinterpret_cast<const f64x2 *>(sh.cvec + PAR * CK + 4 * u + 2 * lkp);
@@ -603,7 +392,7 @@ __device__ __forceinline__ void storer_waves(const SmallArgs &p, const Shared &s
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            if (PMT_BS_NT & 2) __builtin_nontemporal_store(v[k], reinterpret_cast<f64x2 *>(cp_out + pos[k]));
+            if (BS_NT & 2) __builtin_nontemporal_store(v[k], reinterpret_cast<f64x2 *>(cp_out + pos[k]));
             else *reinterpret_cast<f64x2 *>(cp_out + pos[k]) = v[k];
         }
         cp_u += 4;
@@ -698,9 +487,8 @@ __device__ __forceinline__ void storer_waves(const SmallArgs &p, const Shared &s
 }  // namespace
 
 // FAST: cols == 128, rows a multiple of 32, 16-byte aligned columns — aligned 16-byte loads without bounds checks.
-template <bool FAST, bool GL = false>
+template <bool FAST>
 __global__ __launch_bounds__(NT, 2) void batch_small_kernel(SmallArgs p) {
-    static_assert(!GL || FAST, "the LDS-DMA panels serve the FAST shapes only");
     __shared__ __attribute__((aligned(16))) double panel[2 * PANEL];
     __shared__ __attribute__((aligned(16))) double stage[STAGE_CAP + 2];
     __shared__ __attribute__((aligned(16))) double cvec[2 * CK];
@@ -709,11 +497,11 @@ __global__ __launch_bounds__(NT, 2) void batch_small_kernel(SmallArgs p) {
     const int nchunk = (int)max((int64_t)1, (p.rows + CK - 1) / CK);
     Shared sh{panel, stage, cvec};
     // every wave executes the same number of barriers: one to start, one per phase, one more in the last phase of every instance
-    if (wave == 0) matrix_wave<0, FAST, GL>(p, sh, tid & 63, n, nchunk);
-    else if (wave == 1) matrix_wave<1, FAST, GL>(p, sh, tid & 63, n, nchunk);
-    else if (wave == 2) matrix_wave<2, FAST, GL>(p, sh, tid & 63, n, nchunk);
-    else if (wave == 3) matrix_wave<3, FAST, GL>(p, sh, tid & 63, n, nchunk);
-    else if (wave < 6) { if (GL) loader_waves_glds(p, sh, tid - NH, n, nchunk); else loader_waves<FAST>(p, sh, tid - NH, n, nchunk); }
+    if (wave == 0) matrix_wave<0, FAST>(p, sh, tid & 63, n, nchunk);
+    else if (wave == 1) matrix_wave<1, FAST>(p, sh, tid & 63, n, nchunk);
+    else if (wave == 2) matrix_wave<2, FAST>(p, sh, tid & 63, n, nchunk);
+    else if (wave == 3) matrix_wave<3, FAST>(p, sh, tid & 63, n, nchunk);
+    else if (wave < 6) loader_waves<FAST>(p, sh, tid - NH, n, nchunk);
     else storer_waves(p, sh, tid - NH - NL, n, nchunk);
 }
 
@@ -741,7 +529,7 @@ int launch_batch_small(const double *A, int64_t lda, int64_t rows, int64_t cols,
     const bool fast = (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (lda & 1) == 0 && (strideA & 1) == 0 && cols == SN && rows > 0 && (rows % CK) == 0;
     // one workgroup per CU (LDS-limited), each walks instances blockIdx.x, blockIdx.x + G, ...
     const dim3 grid((unsigned)std::min<int64_t>(B, cu_count()));
-    if (fast) PMT_LAUNCH_NAMED("batch_small_kernel", (batch_small_kernel<true, PMT_BS_GLDS != 0>), grid, dim3(NT), 0, s, p);
+    if (fast) PMT_LAUNCH_NAMED("batch_small_kernel", batch_small_kernel<true>, grid, dim3(NT), 0, s, p);
     else PMT_LAUNCH_NAMED("batch_small_kernel", batch_small_kernel<false>, grid, dim3(NT), 0, s, p);
     return check_launch("batch_small_kernel");
 }

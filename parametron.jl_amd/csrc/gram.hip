@@ -134,9 +134,6 @@ static bool gram_mid_applies(int64_t rows, int64_t cols) {
 #endif
     if (gram_mid_big(rows, cols)) return true;
     if (!gram_tall_diag_applies(rows, cols) || cols > PMT_MID_MAXCOLS) return false;
-#ifdef PMT_MID_ALWAYS
-    return true;                                                    // (A/B builds: every wide shape of up to PMT_MID_MAXCOLS columns)
-#endif
     // Measured with the pinned instruction stream of round 6c (gram_mid.hip: mid_step), one launch against four, us (profiles/r06_gram_mid.txt):
     //   wins   200000 x 224 287 (330), 230000 x 256 354 (381), 150000 x 288 304 (459), 160000 x 320 326 (498), 131072 x 384 358 (460),
     //          100000 x 448 375 (554), 262144 x 512 1282 (1387), 524288 x 512 2527 (2680), 2^20 x 384 2991 (3188), 4096 x 2048 359 (381),

@@ -40,10 +40,11 @@ struct SKArgs {
                                                // tiles of a wide tall matrix are computed by gram_tall.hip
 };
 
-// TN = 16-column MFMA tiles per wave along N (4: 64x64 wave tile, 4 waves; 2: 64x32 wave tile, 8 waves)
+// TN = 16-column MFMA tiles per wave along N.  One instance ships: TN = 2, 64x32 wave tiles, 8 waves.
 template <int TN>
 struct Cfg {
-    static constexpr int NW = (TN == 4) ? 4 : 8;
+    static_assert(TN == 2, "the geometry below is the shipped one only");
+    static constexpr int NW = 8;
     static constexpr int NT = NW * 64;
     static constexpr int WCOLS = 16 * TN;             // columns per wave
     static constexpr int NWC = ST / WCOLS;            // waves along N
@@ -135,6 +136,23 @@ __device__ __forceinline__ int sk_phase_a_index(const SKArgs &g, int bid, int t)
 }
 
 __device__ __forceinline__ int64_t sk_unit_begin(const SKArgs &g, int b) { return (int64_t)b * g.U / g.G; }
+
+// the workgroup whose range of phase-B units holds unit u
+__device__ __forceinline__ int sk_unit_owner(const SKArgs &g, int64_t u) {
+    int b = (int)((u * g.G) / g.U);
+    if (b >= g.G) b = g.G - 1;
+    while (b + 1 < g.G && sk_unit_begin(g, b + 1) <= u) ++b;
+    while (b > 0 && sk_unit_begin(g, b) > u) --b;
+    return b;
+}
+
+// the workspace slot in which workgroup b left its partial of remainder tile rtile: its first slot if its range begins in that tile
+__device__ __forceinline__ double *sk_partial_slot(const SKArgs &g, int b, int rtile) {
+    const int64_t bu0 = sk_unit_begin(g, b);
+    const int first_rtile = (int)(bu0 / g.nchunk);
+    const int slot = 2 * b + (first_rtile == rtile ? 0 : 1);
+    return g.ws + (int64_t)slot * SLOT;
+}
 
 // (row, col) inside the 128x128 tile of accumulator r = (tm*TN + tn)*4 + s of thread tid
 template <int TN>

@@ -33,7 +33,7 @@
 #define PMT_MID_MAXWG 2304         // workgroups at most (several rounds where the tiles alone are more than half of the CUs)
 #endif
 #ifndef PMT_MID_D
-#define PMT_MID_D 2                // iterations (8-row groups) in flight per wave (pinned stream, PMT_MID_SCHED 2: 2 33.6 us at 4096 x 512, 3 34.0, 4 35.4; 4096 x 1024 97.7 / 100.3 / 103.7 — with mid_compute + mid_load it was 3)
+#define PMT_MID_D 2                // iterations (8-row groups) in flight per wave (pinned stream, mid_step: 2 33.6 us at 4096 x 512, 3 34.0, 4 35.4; 4096 x 1024 97.7 / 100.3 / 103.7)
 #endif
 #ifndef PMT_MID_GROUP_US
 #define PMT_MID_GROUP_US 1.15      // the cost model's time of one 8-row group per wave (mid_plan)
@@ -41,26 +41,11 @@
 #ifndef PMT_MID_TAIL_US
 #define PMT_MID_TAIL_US 0.95       // the same in the plan of unsplit tiles with split tails (mid_plan)
 #endif
-#ifndef PMT_MID_XCD
-#define PMT_MID_XCD 1              // 0: workgroup ids tile-major (id = tile * S + chunk) whatever the size
-#endif
-#ifndef PMT_MID_SUPER
-#define PMT_MID_SUPER 1            // XCD-aware order: the tiles of a chunk in 8 x 8 super-tiles (mid_tile_of)
-#endif
-#ifndef PMT_MID_PERSIST
-#define PMT_MID_PERSIST 1          // launches of at least two rounds of work items run as PMT_MID_G persistent workgroups (gram_mid_kernel)
-#endif
 #ifndef PMT_MID_SB
 #define PMT_MID_SB 8               // edge of a super-tile in tiles
 #endif
 #ifndef PMT_MID_FB
 #define PMT_MID_FB 4               // chunks whose partials the last arriver loads together (64 loads per thread: a wave may have 63 outstanding; 8, or 16-byte loads: no faster)
-#endif
-#ifndef PMT_MID_SCHED
-#define PMT_MID_SCHED 2            // 2: an 8-row group and the loads of the group D further on as one pinned instruction stream (mid_step); 1: mid_compute + mid_load with scheduling barriers between the phases (37.3 -> 34.3 us at 4096 x 512, 1250 -> 1189 at 65536 x 1024)
-#endif
-#ifndef PMT_MID_ABL
-#define PMT_MID_ABL 0              // ablations (wrong results): 1 no MFMAs, 2 no loads after the first D groups, 3 no fold of the partials, 4 no epilogue
 #endif
 // The hand-over of a partial to the tile's last arriver.  0 (ships): the partial goes out as agent-scope write-through stores (sc1),
 // s_waitcnt vmcnt(0), then the relaxed agent-scope count; the last arriver reads the partials with agent-scope loads — per-access
@@ -245,7 +230,7 @@ __device__ __forceinline__ void mid_compute(double *__restrict__ rot, const f64x
     constexpr int BO = DIAG ? 0 : 4;
     const int lm = lane & 15, lrow = lane & 48;
 #pragma unroll
-    for (int t = 0; t < (PMT_MID_ABL == 5 || PMT_MID_ABL == 6 ? 0 : 4); ++t) *reinterpret_cast<f64x2 *>(rot + (t * 64 + lane) * 2) = buf[BO + t];
+    for (int t = 0; t < 4; ++t) *reinterpret_cast<f64x2 *>(rot + (t * 64 + lane) * 2) = buf[BO + t];
     // ALL rotated operands are asked for up front, and the MFMAs that need none of them (rotation 0: the loaded values themselves) go
     // first: the LDS round trip hides behind 32 MFMAs.  Read rotation by rotation in front of their first use, every wait for an LDS
     // read stood in the wave's one issue stream (one wave per SIMD): ~10 exposed waits per 8-row group, the loop at 0.55 of the pipe.
@@ -255,14 +240,11 @@ __device__ __forceinline__ void mid_compute(double *__restrict__ rot, const f64x
         bv[c][0] = buf[BO + c];
 #pragma unroll
         for (int r = 1; r < 4; ++r) {
-            if (PMT_MID_ABL == 5 || PMT_MID_ABL == 6) { bv[c][r] = buf[BO + (PMT_MID_ABL == 6 ? 0 : c)]; continue; }      // (ablation: no rotations)
             bv[c][r] = *reinterpret_cast<const f64x2 *>(rot + (c * 64 + lrow + ((lm + 4 * r) & 15)) * 2);
         }
     }
-#if PMT_MID_SCHED
     __builtin_amdgcn_sched_barrier(0);
-#endif
-    constexpr int NC = PMT_MID_ABL == 1 ? 0 : 4;
+    constexpr int NC = 4;
 #pragma unroll
     for (int c = 0; c < NC; ++c)
 #pragma unroll
@@ -277,9 +259,7 @@ __device__ __forceinline__ void mid_compute(double *__restrict__ rot, const f64x
             const int a = (tm * 4 + c) * 4;
             acc[a] = __builtin_amdgcn_mfma_f64_4x4x4f64(buf[tm].y, bv[c][0].y, acc[a], 0, 0, 0);
         }
-#if PMT_MID_SCHED
     __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
 #pragma unroll
@@ -308,7 +288,7 @@ __device__ __forceinline__ void mid_compute(double *__restrict__ rot, const f64x
     }
 }
 
-// One 8-row group AND the loads of the group D further on, as ONE pinned instruction stream (PMT_MID_SCHED 2, the FAST load path).  The
+// One 8-row group AND the loads of the group D further on, as ONE pinned instruction stream (the FAST load path).  The
 // workgroup has one wave per SIMD: whatever is not an MFMA stands in the wave's only issue stream.  mid_compute + mid_load put the 16 LDS
 // operations of a group in one run in front of the MFMAs and its 8 loads (with a 64-bit vector add each: the compiler hoists the zero
 // extension of the lane offsets out of the loop and loses the scalar-base form) in runs behind them: ~18.5 clocks per MFMA against 16.6 for
@@ -630,7 +610,9 @@ __device__ __forceinline__ void mid_body(const MidArgs &g, double *sh, int tid, 
     if (nfast > 0) {
 #pragma unroll
         for (int d = 0; d < D; ++d) mid_load<DIAG, FAST>(g, row_of(d), lane, cj0, ck0, voff, buf[d], cb[d]);
-        if (PMT_MID_SCHED == 2 && FAST && PMT_MID_ABL == 0) {
+        // FAST: the pinned stream; mid_compute + mid_load with scheduling barriers between the phases, which it replaced there (37.3 -> 34.3 us
+        // at 4096 x 512, 1250 -> 1189 at 65536 x 1024 — profiles/r06_gram_mid.txt), still serve the bounds-checked path and the leftovers
+        if (FAST) {
             // whole rounds of D groups as one branch-free block (a branch inside it and the compiler's vmcnt waits fall back to "all
             // loads": the number of loads in flight must not depend on the path); the loads beyond the last group repeat the last group
             int s0 = 0;
@@ -646,7 +628,7 @@ __device__ __forceinline__ void mid_body(const MidArgs &g, double *sh, int tid, 
 #pragma unroll
                 for (int d = 0; d < D; ++d) {
                     if (s0 + d < nfast) mid_compute<DIAG>(rot, buf[d], cb[d], g.sign, lane, acc, qacc);
-                    if (PMT_MID_ABL != 2) mid_load<DIAG, FAST>(g, row_of(s0 + d + D), lane, cj0, ck0, voff, buf[d], cb[d]);
+                    mid_load<DIAG, FAST>(g, row_of(s0 + d + D), lane, cj0, ck0, voff, buf[d], cb[d]);
                 }
             }
         }
@@ -678,7 +660,7 @@ __device__ __forceinline__ void mid_body(const MidArgs &g, double *sh, int tid, 
         if (tid == 0) *flag = __hip_atomic_fetch_add(c1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __syncthreads();
         MID_STAMP(3);
-        if (PMT_MID_ABL == 3 || *flag != (unsigned)(n1 - 1)) return;                   // (workgroup-uniform) not the last one of this tile / group
+        if (*flag != (unsigned)(n1 - 1)) return;                   // (workgroup-uniform) not the last one of this tile / group
 #if PMT_MID_FORMAL
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 #endif
@@ -720,7 +702,7 @@ __device__ __forceinline__ void mid_body(const MidArgs &g, double *sh, int tid, 
     }
     __syncthreads();
     MID_STAMP(5);
-    if (PMT_MID_ABL != 4) mid_epilogue(g, sh, tid, jb, kb);
+    mid_epilogue(g, sh, tid, jb, kb);
 #ifdef PMT_MID_TRACE
     __builtin_amdgcn_s_waitcnt(0);
     MID_STAMP(6);
@@ -777,7 +759,7 @@ __device__ __forceinline__ void mid_item(const MidArgs &g, double *sh, int tid, 
         const int chunk = k / ntile;
         const int rank = (tail ? nbody : 0) + (k - chunk * ntile);          // the tile's place in the walk: its workspace slots and its counters
         int t = rank, jb, kb;
-        if (PMT_MID_SUPER && g.xcd) mid_tile_of(t, g.nb, jb, kb);
+        if (g.xcd) mid_tile_of(t, g.nb, jb, kb);
         else {
             kb = 1;
             while (t >= kb) { t -= kb; ++kb; }                     // strictly upper tiles, column by column: (0,1), (0,2), (1,2), (0,3), ..
@@ -859,11 +841,11 @@ int launch_gram_mid(const double *A, int64_t lda, int64_t rows, int64_t cols, co
     g.nb = p.nb; g.n_off = p.n_off; g.s_off = p.s_off; g.s_diag = p.s_diag; g.gpc_off = p.gpc_off; g.gpc_diag = p.gpc_diag;
     g.n_tail = p.n_tail; g.s_tail = p.s_tail; g.gpc_tail = p.gpc_tail;
     g.ws = reinterpret_cast<double *>(workspace); g.counters = counters;
-    g.xcd = PMT_MID_XCD && rows * cols * 8 > ((int64_t)4 << 20);      // (a matrix that fits one L2 is all there on every XCD: 1024 x 512 23.0 against 25.6 us)
+    g.xcd = rows * cols * 8 > ((int64_t)4 << 20);      // (a matrix that fits one L2 is all there on every XCD: 1024 x 512 23.0 against 25.6 us)
     const bool fast = (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (lda & 1) == 0 && (reinterpret_cast<uintptr_t>(g.b) & 15) == 0 &&
                       (uint64_t)lda * (uint64_t)cols * 8 < (1ull << 32);
     g.total = p.wgs;
-    g.persist = PMT_MID_PERSIST && p.wgs >= 2 * PMT_MID_G;
+    g.persist = p.wgs >= 2 * PMT_MID_G;
     g.tickets = counters + gram_mid_counters(cols) - 16;
     const unsigned grid = g.persist ? (unsigned)PMT_MID_G : (unsigned)p.wgs;
     if (fast) PMT_LAUNCH_NAMED("gram_mid_kernel", (gram_mid_kernel<true>), dim3(grid), dim3(256), 0, s, g);

@@ -6,9 +6,9 @@
 //   * 528 tiles of 128x128 on 256 CUs quantise to 3 rounds of 2.06 needed; a persistent grid that splits the
 //     contraction (stream-K) gives every workgroup the same number of (tile, K-chunk) units.
 //   * PMC (SQ_VALU_MFMA_BUSY_CYCLES / GRBM_GUI_ACTIVE) showed the matrix pipe idle whenever the waves sharing a SIMD sit
-//     at the same barrier; variant "wg256" therefore runs TWO independent 4-wave workgroups per CU (one wave per SIMD
-//     each, 64x64 wave tiles) so that one workgroup's load/store/barrier phase overlaps the other's MFMA phase, while
-//     "wg512" runs one 8-wave workgroup (64x32 wave tiles).
+//     at the same barrier.  One 8-wave workgroup per CU (64x32 wave tiles, Cfg<2>) ships; two independent 4-wave workgroups per CU
+//     (64x64 wave tiles), meant to overlap one's load/store/barrier phase with the other's MFMA phase, measured equal within noise
+//     (profiles/r01b_gram_variants.txt) and are gone.
 // Work unit = (tile, K-chunk of KC rows).  Units are numbered tile-major and dealt out in contiguous, equal ranges to
 // G persistent workgroups.  A workgroup that covers all chunks of a tile writes the QuadraticTerms directly (fused
 // epilogue: x2, canonical upper-triangular position, varmap); otherwise it stores its partial accumulators in a
@@ -33,40 +33,26 @@
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__) && !defined(__gfx942__) && !defined(PMT_SK_PAIR_FORMAL)
 #define PMT_SK_PAIR_FORMAL 1
 #endif
+#ifndef PMT_SK_PAIR_FORMAL
+#define PMT_SK_PAIR_FORMAL 0
+#endif
 
-// Codegen knobs.  The compiler's schedule of the stage loop moves by +-10 % with source changes that do not touch the loop.  Rounds 1-2
+// Codegen.  This kernel is FROZEN: the compiler's schedule of the stage loop moves by +-10 % with source changes that do not touch the
+// loop, so a change here is judged by the instruction stream it produces (tools/isa_diff.py), not by a timing margin.  Rounds 1-2
 // shipped the luckiest draw of a sweep (246 VGPRs, 1.177 ms at n = r = 4096) — an allocation that only came out that way while a second,
-// unrelated instantiation shared the translation unit (alone: 256 + 7 spilled).  Round 3 takes the lottery out of it in two steps
+// unrelated instantiation shared the translation unit (alone: 256 + 7 spilled).  Round 3 took the lottery out of it in two steps
 // (profiles/r03_gram_codegen.txt): (1) the epilogue derives its lane-dependent offsets from a FRESH copy of threadIdx.x (sk_fresh_tid),
 // so nothing of it is live across the stage loop: the kernel's natural register need drops from ~263 to 183-231; (2) the register
-// budget is stated in the source (amdgpu_num_vgpr) and the scheduler works towards it.  Measured over budget x LOADKS x ORDER:
+// budget is stated in the source (amdgpu_num_vgpr) and the scheduler works towards it.  Measured over budget x load k-step x MFMA order:
 //   budget 248/232: 1.38 ms;  budget 216 and below (183-187 VGPRs allocated): 1.185-1.20 ms;  spills: none in any of them
-//   PMT_SK_ORDER 0   MFMA issue order (tn, tm, r)   (1: (tn, r, tm), consecutive MFMAs share the B operand: 1.198 ms)
-//   PMT_SK_LOADKS 1  the next stage's global loads are issued after the first k-step   (0: 1.26, 2: 1.23, 3: 1.26 ms)
 // gram_sk_kernel at n = r = 4096: 1.186 ms with 183 VGPRs — two waves per SIMD leave 146 of its 512 registers to co-resident kernels.
-#ifndef PMT_GRAM_SK_STAGGER
-#define PMT_GRAM_SK_STAGGER 0
-#endif
-#ifndef PMT_SK_LOADKS
-#define PMT_SK_LOADKS 1
-#endif
-#ifndef PMT_SK_ORDER
-#define PMT_SK_ORDER 0
-#endif
-#ifndef PMT_SK_STOREKS
-#define PMT_SK_STOREKS -1      // k-step in front of which the next stage's panels go from registers to LDS (-1: behind the last k-step)
-#endif
-#ifndef PMT_SK_STOREFENCE
-#define PMT_SK_STOREFENCE 0    // 1: a scheduling barrier behind those LDS stores (they may not sink to the end of the stage)
-#endif
-#ifndef PMT_SK_BK
-#define PMT_SK_BK 16          // rows per stage (one barrier per stage)
-#endif
-#ifndef PMT_SK_WPS
-#define PMT_SK_WPS 2          // __launch_bounds__ waves-per-SIMD hint of the shipped instantiation
-#endif
-
+// What the sweeps settled, by the switch names the profiles use, is tabulated in profiles/r12_settled_switches.txt.
 namespace pmt {
+
+constexpr int SK_LOADKS = 1;       // the next stage's global loads are issued after the first k-step   (0: 1.26, 2: 1.23, 3: 1.26 ms)
+constexpr int SK_BK = 16;          // rows per stage (one barrier per stage)
+constexpr int SK_WPS = 2;          // __launch_bounds__ waves-per-SIMD hint
+constexpr int SK_APB1_BELOW = 64;  // fix-up: one accumulator per workgroup (NACC workgroups per tile) while tiles x NACC / 4 stays below this
 
 // Tile epilogue through LDS: accumulators -> smem[64][129] (half a tile at a time) -> row-contiguous QuadraticTerm runs.
 // For output row j the tile's entries k = max(j, k0) .. k0+127 are consecutive terms of the canonical upper triangle, so
@@ -88,15 +74,6 @@ __device__ __forceinline__ int sk_fresh_tid() {
 template <int TN>
 __device__ __forceinline__ void sk_epilogue(const SKArgs &g, int jb, int kb, const double (&acc)[Cfg<TN>::NACC], double *smem, int, int hsel = -1) {
     using C = Cfg<TN>;
-#if defined(PMT_SK_EPI_ABL) && PMT_SK_EPI_ABL == 3
-    {   // ablation: no epilogue at all (the accumulators stay live through a store that never happens): what a FREE write-out would give
-        double sum = 0.0;
-#pragma unroll
-        for (int r = 0; r < C::NACC; ++r) sum += acc[r];
-        if (sum == 1.2345e300 && g.out_quad) reinterpret_cast<double *>(g.out_quad)[threadIdx.x] = sum;
-        return;
-    }
-#endif
     const int tid = sk_fresh_tid();
     typedef u64 u64x2 __attribute__((ext_vector_type(2)));
     const int64_t n = g.cols;
@@ -158,9 +135,6 @@ __device__ __forceinline__ void sk_epilogue(const SKArgs &g, int jb, int kb, con
             const double *trow = tile + row * EPITCH + coff;
             const u64 rv = rmap[row];
             auto word = [&](int q) -> u64 {
-#if defined(PMT_SK_EPI_ABL) && PMT_SK_EPI_ABL == 1
-                return (u64)q + rv;                          // ablation: no LDS reads, no selects
-#endif
                 const int t = q / 3, f = q - 3 * t;
                 return f == 0 ? (u64)__double_as_longlong(trow[t]) : (f == 1 ? rv : cmap[coff + t]);
             };
@@ -171,15 +145,7 @@ __device__ __forceinline__ void sk_epilogue(const SKArgs &g, int jb, int kb, con
                     u64x2 v;
                     v.x = word(q0);
                     v.y = word(q0 + 1);
-#if defined(PMT_SK_EPI_ABL) && PMT_SK_EPI_ABL == 2
-                    if (v.x == 0x7ff8dead7ff8deadull) seg[q0] = v.y;          // ablation: (practically) no global stores
-#else
-#if defined(PMT_SK_EPI_NT) && PMT_SK_EPI_NT
-                    __builtin_nontemporal_store(v, reinterpret_cast<u64x2 *>(seg + q0));      // tuning: the term array is written once and never re-read here
-#else
                     *reinterpret_cast<u64x2 *>(seg + q0) = v;
-#endif
-#endif
                 } else {
                     seg[q0] = word(q0);
                 }
@@ -230,23 +196,14 @@ __device__ __forceinline__ void sk_store_panel(double *panel, const f64x2 (&reg)
     }
 }
 
-// lane i of every 16-lane row receives the value of lane (i - N) mod 16 of the same row (DPP row_ror:N), both halves of the double
-template <int N>
-__device__ __forceinline__ double dpp_row_ror(double v) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, 0x120 + N, 0xf, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(0, hi, 0x120 + N, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-
 // acc = sum over rows [ibeg, iend) of A[i, j0 + .]' * A[i, k0 + .] for this thread's accumulators of the 128x128 tile.
 // K-contiguous column panels go global -> registers -> LDS (double buffered, one barrier per BK rows).
-// ABL: ablation switch for profiling only (0 = the kernel; 1 = no LDS operand reads; 2 = no global loads / LDS stores).
 // FAST: whole 128-column panels, aligned 16-byte loads, a multiple of BK rows — no bounds checks and no conditionals, so the stage
 // body is ONE basic block and the compiler interleaves the global loads and LDS traffic with the MFMA stream and sinks half of a
 // stage's MFMAs below the barrier (1.29 -> 1.20 ms at n = r = 4096; with the bounds-checked loads the body was ~40 blocks).
-template <int TN, int BK, int ABL, bool FAST>
-__device__ __forceinline__ void sk_accumulate_impl(const SKArgs &g, int64_t j0, int64_t k0, bool diag, int64_t ibeg, int64_t iend,
+// Diagonal tiles load their one panel twice (6 % of the tiles, L2 hits) rather than branch inside the stage loop.
+template <int TN, int BK, bool FAST>
+__device__ __forceinline__ void sk_accumulate_impl(const SKArgs &g, int64_t j0, int64_t k0, int64_t ibeg, int64_t iend,
                                                    double (&acc)[Cfg<TN>::NACC], double (&lds)[2][2][ST * (BK + 1)], int tid) {
     using C = Cfg<TN>;
     constexpr int GP = BK + 1;
@@ -254,7 +211,6 @@ __device__ __forceinline__ void sk_accumulate_impl(const SKArgs &g, int64_t j0, 
     const int lane = tid & 63, wave = tid >> 6;
     const int wr = wave / C::NWC, wc = wave % C::NWC;
     const int lm = lane & 15, lk = lane >> 4;
-    (void)diag;   // diagonal tiles load their one panel twice (6 % of the tiles, L2 hits) rather than branch inside the stage loop
 #pragma unroll
     for (int r = 0; r < C::NACC; ++r) acc[r] = 0.0;
 
@@ -275,61 +231,40 @@ __device__ __forceinline__ void sk_accumulate_impl(const SKArgs &g, int64_t j0, 
         const int cur = s & 1;
         const double *pj = lds[cur][0] + (wr * 64 + lm) * GP + lk;
         const double *pk = lds[cur][1] + (wc * C::WCOLS) * GP + lk;
-        // TN == 4 (128 accumulator VGPRs, 256-VGPR budget): keep the k-step loop rolled so operand reads are not hoisted
-        // a whole stage ahead (fully unrolled it spills ~100 VGPRs)
-#pragma unroll(TN == 4 ? 1 : BK / 4)
+#pragma unroll(BK / 4)
         for (int ks = 0; ks < BK / 4; ++ks) {
             // The global loads of the NEXT stage are issued after the first k-step's MFMAs are queued, not at the top of the
             // stage: right after the barrier both waves of a SIMD would otherwise spend ~450 cycles issuing loads with the
             // matrix pipe idle (in-kernel s_memtime stamps, profiles/r01c_gram_phases.txt).
             // (FAST: unconditional — the last stage re-loads itself — so the stage body stays one basic block)
-            if (ks == (BK / 4 > PMT_SK_LOADKS ? PMT_SK_LOADKS : 0) && ABL != 2 && (FAST || s + 1 < nstage)) {
+            if (ks == (BK / 4 > SK_LOADKS ? SK_LOADKS : 0) && (FAST || s + 1 < nstage)) {
                 const int64_t inext = stage_row(FAST ? min(s + 1, nstage - 1) : s + 1);
                 sk_load_panel<TN, BK, FAST>(g, j0, inext, iend, rj, tid);
                 sk_load_panel<TN, BK, FAST>(g, k0, inext, iend, rk, tid);
             }
-            if (PMT_SK_STOREKS >= 0 && ks == PMT_SK_STOREKS && ABL != 2 && (FAST || s + 1 < nstage)) {
-                // the next stage's panels go to LDS HERE, a k-step or two before the barrier: their write latency and the wait for the global
-                // loads are then covered by this stage's remaining MFMAs instead of sitting between the last MFMA and the barrier
-                sk_store_panel<TN, BK>(lds[cur ^ 1][0], rj, tid);
-                sk_store_panel<TN, BK>(lds[cur ^ 1][1], rk, tid);
-                if (PMT_SK_STOREFENCE) __builtin_amdgcn_sched_barrier(0);
-            }
             double a[4];
 #pragma unroll
-            for (int t = 0; t < 4; ++t) a[t] = (ABL == 1) ? (double)(tid + t) : pj[t * 16 * GP + ks * 4];
+            for (int t = 0; t < 4; ++t) a[t] = pj[t * 16 * GP + ks * 4];
 #pragma unroll
             for (int tn = 0; tn < TN; ++tn) {
                 double b[4];
-                if (ABL == 3) {
-                    // one LDS read + three in-register rotations of the 16-lane rows by 4/8/12 lanes (DPP row_ror) instead of four reads
-                    b[0] = pk[(tn * 16 + lm) * GP + ks * 4];
-                    b[1] = dpp_row_ror<12>(b[0]);
-                    b[2] = dpp_row_ror<8>(b[0]);
-                    b[3] = dpp_row_ror<4>(b[0]);
-                } else {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int rc = ((((lm >> 2) + r) & 3) << 2) | (lm & 3);      // column group rotated by r blocks
-                        b[r] = (ABL == 1) ? (double)(rc + r) : pk[(tn * 16 + rc) * GP + ks * 4];
-                    }
+                for (int r = 0; r < 4; ++r) {
+                    const int rc = ((((lm >> 2) + r) & 3) << 2) | (lm & 3);      // column group rotated by r blocks
+                    b[r] = pk[(tn * 16 + rc) * GP + ks * 4];
                 }
-#if PMT_SK_ORDER == 0
+                // MFMA issue order (tn, tm, r); (tn, r, tm), where consecutive MFMAs share the B operand, measured 1.198 against 1.186 ms
+                // (profiles/r03_gram_codegen.txt)
 #pragma unroll
                 for (int tm = 0; tm < 4; ++tm)
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
                         acc[(tm * TN + tn) * 4 + r] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[tm], b[r], acc[(tm * TN + tn) * 4 + r], 0, 0, 0);
-#else
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-#pragma unroll
-                    for (int tm = 0; tm < 4; ++tm)
-                        acc[(tm * TN + tn) * 4 + r] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[tm], b[r], acc[(tm * TN + tn) * 4 + r], 0, 0, 0);
-#endif
             }
         }
-        if (PMT_SK_STOREKS < 0 && ABL != 2 && (FAST || s + 1 < nstage)) {
+        // the next stage's panels go from registers to LDS behind the last k-step; a k-step or two earlier the wait for the global loads
+        // moves with them: 1.306-1.343 against 1.183 ms (profiles/r03_gram_codegen.txt, section 7)
+        if (FAST || s + 1 < nstage) {
             sk_store_panel<TN, BK>(lds[cur ^ 1][0], rj, tid);
             sk_store_panel<TN, BK>(lds[cur ^ 1][1], rk, tid);
         }
@@ -337,12 +272,12 @@ __device__ __forceinline__ void sk_accumulate_impl(const SKArgs &g, int64_t j0, 
     }
 }
 
-template <int TN, int BK, int ABL>
-__device__ __forceinline__ void sk_accumulate(const SKArgs &g, int64_t j0, int64_t k0, bool diag, int64_t ibeg, int64_t iend,
+template <int TN, int BK>
+__device__ __forceinline__ void sk_accumulate(const SKArgs &g, int64_t j0, int64_t k0, int64_t ibeg, int64_t iend,
                                               double (&acc)[Cfg<TN>::NACC], double (&lds)[2][2][ST * (BK + 1)], int tid) {
     const bool fast = g.vec_in && (k0 + ST <= g.cols) && ((iend - ibeg) % BK == 0);   // j0 <= k0: panel J is in range too
-    if (fast) sk_accumulate_impl<TN, BK, ABL, true>(g, j0, k0, diag, ibeg, iend, acc, lds, tid);
-    else sk_accumulate_impl<TN, BK, ABL, false>(g, j0, k0, diag, ibeg, iend, acc, lds, tid);
+    if (fast) sk_accumulate_impl<TN, BK, true>(g, j0, k0, ibeg, iend, acc, lds, tid);
+    else sk_accumulate_impl<TN, BK, false>(g, j0, k0, ibeg, iend, acc, lds, tid);
 }
 
 // ---- batched instances (BASELINE config 4): one workgroup per (instance, tile), coefficient-only output ----------------
@@ -365,7 +300,7 @@ __global__ __launch_bounds__(Cfg<2>::NT, 2) void batch_gram_kernel(BatchGramArgs
     int jb, kb;
     sk_tri_unrank((int)blockIdx.x, bg.ntiles, jb, kb);
     double acc[C::NACC];
-    sk_accumulate<TN, BK, 0>(g, (int64_t)jb * ST, (int64_t)kb * ST, jb == kb, 0, bg.rows, acc, lds, tid);
+    sk_accumulate<TN, BK>(g, (int64_t)jb * ST, (int64_t)kb * ST, 0, bg.rows, acc, lds, tid);
     // stage through LDS so that each output row segment is written contiguously (8 bytes per entry)
     double *tile = &lds[0][0][0];
     const int wave = tid >> 6, lane = tid & 63, wr = wave / C::NWC;
@@ -445,13 +380,35 @@ int launch_batch_gram(const double *A, int64_t lda, int64_t rows, int64_t cols, 
     return check_launch("batch_gram");
 }
 
-// ABL: ablation switch for profiling only; results are wrong for ABL != 0; selected with PMT_GRAM_SK_ABLATE.
+// Producer side of the balanced pair fold (gram_sk_kernel): a thread hands its accumulators to the partner workgroup.  gfx942 / gfx950: relaxed
+// agent-scope atomic (write-through, sc1) stores — the caller then waits for them (s_waitcnt) in front of the barrier; FORMAL: plain stores,
+// ordered by the flag's release.
+template <int NACC, int NT>
+__device__ __forceinline__ void sk_pair_store_partial(double *w, const double (&acc)[NACC]) {
+#pragma unroll
+    for (int r = 0; r < NACC; ++r) {
+#if !PMT_SK_PAIR_FORMAL
+        __hip_atomic_store(&w[r * NT], acc[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+        w[r * NT] = acc[r];
+#endif
+    }
+}
+// ... and announces them (one thread, behind the workgroup's barrier)
+__device__ __forceinline__ void sk_pair_publish(unsigned *flag, unsigned value) {
+#if !PMT_SK_PAIR_FORMAL
+    __hip_atomic_store(flag, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#else
+    __hip_atomic_store(flag, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+#endif
+}
+
 // amdgpu_num_vgpr(108): on gfx90a+ the attribute counts in pairs of the unified file, i.e. a budget of 216 registers.  The budget is part
 // of the source (and checked again by tools/kernel_resources.py at build time), not a by-product of which other instantiations share the
-// translation unit; the scheduler settles at 183-187 registers under it (see the knobs at the top of this file).
+// translation unit; the scheduler settles at 183-187 registers under it (see the top of this file).
 // RANGED: the launch covers the tiles from g.seq_begin on (a stage of a host delivery).  A separate instantiation: the one extra add in the
 // tile numbering of the plain kernel moved its schedule by 1 % (1.192 -> 1.204 ms at n = r = 4096).
-template <int TN, int BK, int WPS, int ABL, bool RANGED>
+template <int TN, int BK, int WPS, bool RANGED>
 __global__ __launch_bounds__(Cfg<TN>::NT, WPS) __attribute__((amdgpu_num_vgpr(108))) void gram_sk_kernel(SKArgs g) {
     using C = Cfg<TN>;
     constexpr int GP = BK + 1;
@@ -459,10 +416,8 @@ __global__ __launch_bounds__(Cfg<TN>::NT, WPS) __attribute__((amdgpu_num_vgpr(10
     const int tid = threadIdx.x;
     const int bid = blockIdx.x;
 
-    // Optional (PMT_GRAM_SK_STAGGER): half of the XCDs (workgroup b runs on XCD b % 8) do their stream-K share FIRST and their
-    // whole tiles afterwards, so the two halves of the chip reach their tile epilogues ~1/16 of a tile apart and the 200 MB of output
-    // are not written in two chip-wide bursts.  Measured: no gain (profiles/r01d_side_stream.txt); off.
-    const bool b_first = PMT_GRAM_SK_STAGGER && (bid & 4);
+    // (Phase B is written as a lambda in FRONT of phase A although it runs behind it: as straight-line code behind phase A the same
+    // statements compile to a different schedule of every kernel of this file that inlines sk_accumulate — tools/isa_diff.py.)
     auto phase_b = [&]() __attribute__((always_inline)) {
         // phase B: the remaining tiles (fewer than G) are split along the contraction: stream-K over their (tile, chunk) units
         const int64_t u0 = sk_unit_begin(g, bid), u1 = sk_unit_begin(g, bid + 1);
@@ -475,11 +430,10 @@ __global__ __launch_bounds__(Cfg<TN>::NT, WPS) __attribute__((amdgpu_num_vgpr(10
             if (RANGED && g.strict) sk_tile_unrank_strict(g, g.seq_begin + g.seq_step * tile, jb, kb);
             else sk_tile_unrank(g, RANGED ? g.seq_begin + g.seq_step * tile : tile, jb, kb);
             const int64_t j0 = (int64_t)jb * ST, k0 = (int64_t)kb * ST;
-            const bool diag = (jb == kb);
             const int64_t ibeg = (int64_t)c0 * g.skc, iend = min(g.rows, (int64_t)c1 * g.skc);
 
             double acc[C::NACC];
-            sk_accumulate<TN, BK, ABL>(g, j0, k0, diag, ibeg, iend, acc, lds, tid);
+            sk_accumulate<TN, BK>(g, j0, k0, ibeg, iend, acc, lds, tid);
 
             bool whole = c0 == 0 && c1 == g.nchunk;
             const bool pair = RANGED && g.pair_flags != nullptr && !whole;
@@ -498,41 +452,6 @@ __global__ __launch_bounds__(Cfg<TN>::NT, WPS) __attribute__((amdgpu_num_vgpr(10
                 const int keep = first ? 0 : 1;
                 const int ftid = sk_fresh_tid();                                 // (fresh: nothing of this is live across the stage loop)
                 const int mywr = __builtin_amdgcn_readfirstlane(ftid >> 6) / C::NWC;          // wave-uniform: the two roles are scalar branches
-#if defined(PMT_SK_PAIR_RELAXED) && PMT_SK_PAIR_RELAXED      // round 4's form, kept for the A/B (profiles/r05_pair_fold.txt)
-                if (mywr != keep) {
-                    double *w = g.ws + (int64_t)(2 * bid) * SLOT + ftid;
-    #pragma unroll
-                    for (int r = 0; r < C::NACC; ++r) __hip_atomic_store(&w[r * C::NT], acc[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                __builtin_amdgcn_s_waitcnt(0);
-                __syncthreads();
-                if (tid == 0) {
-                    __hip_atomic_store(&g.pair_flags[(first ? 0 : 512) + rtile], g.flag_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    const unsigned *other = &g.pair_flags[(first ? 512 : 0) + rtile];
-                    const long long t0 = (long long)__builtin_amdgcn_s_memrealtime();
-                    double late = 0.0;
-                    while (__hip_atomic_load(other, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != g.epoch) {
-                        __builtin_amdgcn_s_sleep(8);
-                        if ((long long)__builtin_amdgcn_s_memrealtime() - t0 > g.pair_timeout) { late = 1.0; break; }   // 2 s (100 MHz ticks)
-                    }
-                    if (late != 0.0 && g.error) __hip_atomic_store(g.error, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    lds[0][0][0] = late;                         // (the panels are idle between the stage loop and the epilogue)
-                }
-                __syncthreads();
-                const bool late = lds[0][0][0] != 0.0;
-                if (mywr == keep) {
-                    const double *w = g.ws + (int64_t)(2 * (bid ^ 1)) * SLOT + ftid;
-    #pragma unroll
-                    for (int r0 = 0; r0 < C::NACC; r0 += 4) {      // four loads in flight at a time (register budget)
-                        double other[4];
-    #pragma unroll
-                        for (int r = 0; r < 4; ++r) other[r] = __hip_atomic_load(&w[(r0 + r) * C::NT], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    #pragma unroll
-                        for (int r = 0; r < 4; ++r) acc[r0 + r] = late ? __builtin_nan("") : other[r] + acc[r0 + r];
-                        asm volatile("" ::: "memory");
-                    }
-                }
-#else
                 // The hand-off, measured in three forms (profiles/r05_pair_fold.txt; host_csc per solve, alternating runs on one box):
                 //   round 4   relaxed agent-scope atomic stores / loads of partial and flag + s_waitcnt               1.713-1.728 ms
                 //   FORMAL    plain stores, barrier, agent-scope RELEASE flag store; relaxed spin, agent-scope ACQUIRE fence, barrier, plain loads
@@ -546,25 +465,13 @@ __global__ __launch_bounds__(Cfg<TN>::NT, WPS) __attribute__((amdgpu_num_vgpr(10
                 // on the producer side, so there is no data race in the language model either; what the shipped form does not have is the
                 // model's release edge, and the soak (tools/soak_host_delivery.py, 6000 solves x 4 configurations) plus the fault-injection
                 // test cover what it rests on.
-                if (mywr != keep) {
-                    double *w = g.ws + (int64_t)(2 * bid) * SLOT + ftid;
-    #pragma unroll
-#if !(defined(PMT_SK_PAIR_FORMAL) && PMT_SK_PAIR_FORMAL)
-                    for (int r = 0; r < C::NACC; ++r) __hip_atomic_store(&w[r * C::NT], acc[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-                    for (int r = 0; r < C::NACC; ++r) w[r * C::NT] = acc[r];
-#endif
-                }
-#if !(defined(PMT_SK_PAIR_FORMAL) && PMT_SK_PAIR_FORMAL)
+                if (mywr != keep) sk_pair_store_partial<C::NACC, C::NT>(g.ws + (int64_t)(2 * bid) * SLOT + ftid, acc);
+#if !PMT_SK_PAIR_FORMAL
                 __builtin_amdgcn_s_waitcnt(0);
 #endif
                 __syncthreads();
                 if (tid == 0) {
-#if !(defined(PMT_SK_PAIR_FORMAL) && PMT_SK_PAIR_FORMAL)
-                    __hip_atomic_store(&g.pair_flags[(first ? 0 : 512) + rtile], g.flag_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-                    __hip_atomic_store(&g.pair_flags[(first ? 0 : 512) + rtile], g.flag_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-#endif
+                    sk_pair_publish(&g.pair_flags[(first ? 0 : 512) + rtile], g.flag_value);
                     const unsigned *other = &g.pair_flags[(first ? 512 : 0) + rtile];
                     const long long t0 = (long long)__builtin_amdgcn_s_memrealtime();
                     double late = 0.0;
@@ -572,9 +479,7 @@ __global__ __launch_bounds__(Cfg<TN>::NT, WPS) __attribute__((amdgpu_num_vgpr(10
                         __builtin_amdgcn_s_sleep(8);
                         if ((long long)__builtin_amdgcn_s_memrealtime() - t0 > g.pair_timeout) { late = 1.0; break; }   // 2 s (100 MHz ticks)
                     }
-#if !(defined(PMT_SK_PAIR_NOACQ) && PMT_SK_PAIR_NOACQ)
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
                     if (late != 0.0 && g.error) __hip_atomic_store(g.error, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                     lds[0][0][0] = late;                         // (the panels are idle between the stage loop and the epilogue)
                 }
@@ -582,21 +487,16 @@ __global__ __launch_bounds__(Cfg<TN>::NT, WPS) __attribute__((amdgpu_num_vgpr(10
                 const bool late = lds[0][0][0] != 0.0;
                 if (mywr == keep) {
                     const double *w = g.ws + (int64_t)(2 * (bid ^ 1)) * SLOT + ftid;
-    #pragma unroll
+#pragma unroll
                     for (int r0 = 0; r0 < C::NACC; r0 += 4) {      // four loads in flight at a time (register budget)
                         double other[4];
-    #pragma unroll
-#if defined(PMT_SK_PAIR_NOACQ) && PMT_SK_PAIR_NOACQ
-                        for (int r = 0; r < 4; ++r) other[r] = __hip_atomic_load(&w[(r0 + r) * C::NT], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
+#pragma unroll
                         for (int r = 0; r < 4; ++r) other[r] = w[(r0 + r) * C::NT];
-#endif
-    #pragma unroll
+#pragma unroll
                         for (int r = 0; r < 4; ++r) acc[r0 + r] = late ? __builtin_nan("") : other[r] + acc[r0 + r];
                         asm volatile("" ::: "memory");
                     }
                 }
-#endif
                 whole = true;
                 hsel = keep;
             }
@@ -607,30 +507,28 @@ __global__ __launch_bounds__(Cfg<TN>::NT, WPS) __attribute__((amdgpu_num_vgpr(10
                 // partial tile -> workspace slot, stored [accumulator index][thread] (coalesced); the fix-up kernel knows the map
                 const int slot = 2 * bid + (u == u0 ? 0 : 1);
                 double *w = g.ws + (int64_t)slot * SLOT + (RANGED ? sk_fresh_tid() : tid);
-    #pragma unroll
+#pragma unroll
                 for (int r = 0; r < C::NACC; ++r) w[r * C::NT] = acc[r];
             }
             u += (c1 - c0);
         }
     };
-    if (b_first) phase_b();
 
-    // phase A: tfull whole tiles per workgroup (contiguous, so consecutive tiles share their row panel in L2), written directly
+    // phase A: tfull whole tiles per workgroup (contiguous, so consecutive tiles share their row panel in L2), written directly.
+    // (Half of the XCDs doing phase B first, so that the chip's tile epilogues do not coincide: 1.196 against 1.183 ms, no gain —
+    // profiles/r01d_side_stream.txt, profiles/r03_gram_codegen.txt section 11.)
     for (int t = 0; t < g.tfull; ++t) {
         int jb, kb;
         if (RANGED && g.strict) sk_tile_unrank_strict(g, g.seq_begin + g.seq_step * sk_phase_a_index(g, bid, t), jb, kb);
         else sk_tile_unrank(g, RANGED ? g.seq_begin + g.seq_step * sk_phase_a_index(g, bid, t) : sk_phase_a_index(g, bid, t), jb, kb);
         double acc[C::NACC];
-        sk_accumulate<TN, BK, ABL>(g, (int64_t)jb * ST, (int64_t)kb * ST, jb == kb, 0, g.rows, acc, lds, tid);
+        sk_accumulate<TN, BK>(g, (int64_t)jb * ST, (int64_t)kb * ST, 0, g.rows, acc, lds, tid);
         sk_epilogue<TN>(g, jb, kb, acc, &lds[0][0][0], tid);
     }
 
-    if (!b_first) phase_b();
+    phase_b();
 }
 
-#ifndef PMT_SK_APB1_BELOW
-#define PMT_SK_APB1_BELOW 64       // fix-up: one accumulator per workgroup (NACC workgroups per tile) while tiles x NACC / 4 stays below this
-#endif
 // one workgroup per tile: if the tile was split, add its partials in ascending workgroup order and write the terms
 // APB = accumulators per thread handled by one workgroup: 4 normally; 1 when only a few tiles are split (tall matrices: one tile summed
 // over up to 256 partials) so that the sum is spread over NACC instead of NACC/4 workgroups per tile
@@ -641,26 +539,14 @@ __global__ __launch_bounds__(Cfg<TN>::NT) void gram_sk_fixup_kernel(SKArgs g) {
     const int tile = g.tfull * g.G + rtile;
     const int tid = threadIdx.x;
     const int64_t ub = (int64_t)rtile * g.nchunk, ue = ub + g.nchunk - 1;      // first / last remainder unit of this tile
-    auto owner = [&](int64_t u) {
-        int b = (int)((u * g.G) / g.U);
-        if (b >= g.G) b = g.G - 1;
-        while (b + 1 < g.G && sk_unit_begin(g, b + 1) <= u) ++b;
-        while (b > 0 && sk_unit_begin(g, b) > u) --b;
-        return b;
-    };
-    const int blo = owner(ub), bhi = owner(ue);
+    const int blo = sk_unit_owner(g, ub), bhi = sk_unit_owner(g, ue);
     if (blo == bhi) return;                                                   // one workgroup did the whole tile (and counted it)
     // blockIdx.y selects APB of the NACC accumulators of every thread, so a tile split many ways is summed by NACC/APB workgroups
     const int r0 = (int)blockIdx.y * APB;
     double acc[APB];
 #pragma unroll
     for (int r = 0; r < APB; ++r) acc[r] = 0.0;
-    auto slot_ptr = [&](int b) {
-        const int64_t bu0 = sk_unit_begin(g, b);
-        const int first_rtile = (int)(bu0 / g.nchunk);
-        const int slot = 2 * b + (first_rtile == rtile ? 0 : 1);
-        return g.ws + (int64_t)slot * SLOT + (int64_t)r0 * C::NT + tid;
-    };
+    auto slot_ptr = [&](int b) { return sk_partial_slot(g, b, rtile) + (int64_t)r0 * C::NT + tid; };
     // partials are ADDED in ascending workgroup order (deterministic) but LOADED LB workgroups at a time, so the kernel is not a
     // chain of dependent L2 round trips
     constexpr int LB = APB == 1 ? 16 : 4;
@@ -709,21 +595,9 @@ __global__ __launch_bounds__(512) void gram_sk_fixup_sliced_kernel(SKArgs g) {
     const int e = (int)blockIdx.z * 64 + el;                                  // the thread of the contraction whose accumulator this is
     const int r0 = (int)blockIdx.y;
     const int64_t ub = (int64_t)rtile * g.nchunk, ue = ub + g.nchunk - 1;
-    auto owner = [&](int64_t u) {
-        int b = (int)((u * g.G) / g.U);
-        if (b >= g.G) b = g.G - 1;
-        while (b + 1 < g.G && sk_unit_begin(g, b + 1) <= u) ++b;
-        while (b > 0 && sk_unit_begin(g, b) > u) --b;
-        return b;
-    };
-    const int blo = owner(ub), bhi = owner(ue);
+    const int blo = sk_unit_owner(g, ub), bhi = sk_unit_owner(g, ue);
     if (blo == bhi) return;
-    auto slot_ptr = [&](int b) {
-        const int64_t bu0 = sk_unit_begin(g, b);
-        const int first_rtile = (int)(bu0 / g.nchunk);
-        const int slot = 2 * b + (first_rtile == rtile ? 0 : 1);
-        return g.ws + (int64_t)slot * SLOT + (int64_t)r0 * C::NT + e;
-    };
+    auto slot_ptr = [&](int b) { return sk_partial_slot(g, b, rtile) + (int64_t)r0 * C::NT + e; };
     double acc = 0.0;
     int b = blo + sl;
     for (; b + 3 * NSL <= bhi; b += 4 * NSL) {
@@ -749,15 +623,6 @@ size_t gram_sk_workspace_bytes(int64_t rows, int64_t cols) {
     (void)rows; (void)cols;
     return (size_t)MAXG * 2 * SLOT * sizeof(double);
 }
-
-// Tuning builds only (-DPMT_TUNING, tools/): kernel variant / ablation / grid size from the environment.  The shipped library reads
-// no environment variable: its results cannot be changed from outside.
-#ifdef PMT_TUNING
-static int env_int(const char *name, int dflt) {
-    const char *e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-#endif
 
 // seq_count < 0: all tiles.  Otherwise the launch covers the tiles [seq_begin, seq_begin + seq_count) of the tile sequence (gram_common.h:
 // sk_tile_unrank) — a host delivery runs the contraction band range by band range (gram.hip), every range as its own stream-K launch over
@@ -785,26 +650,12 @@ int launch_gram_sk(const double *A, int64_t lda, int64_t rows, int64_t cols, con
         g.seq_begin = (int)((int64_t)g.ntiles * (g.ntiles + 1) / 2 - 1 - seq_begin);
         g.seq_step = -1;
     }
-    // variant: 0 = wg256 (two 4-wave workgroups per CU, 64x64 wave tiles), 1 = wg512 (one 8-wave workgroup per CU, 64x32), BK 16
-#ifdef PMT_TUNING
-#ifdef PMT_TUNING_ABLATE
-    static const int variant = env_int("PMT_GRAM_SK_VARIANT", 1);   // measured equal within noise (profiles/r01b_gram_variants.txt)
-    static const int abl = env_int("PMT_GRAM_SK_ABLATE", 0);
-#else
-    constexpr int variant = 1;
-#endif
-    static const int gdef = env_int("PMT_GRAM_SK_BLOCKS", 0);
-    static const int order_env = env_int("PMT_GRAM_SK_ORDER_W", -1);
-    if (order_env >= 0) order_w = order_env;
-#else
-    constexpr int variant = 1, gdef = 0;
-#endif
-    const int gwant = gdef > 0 ? gdef : (variant == 0 ? 512 : 256);
+    constexpr int gwant = 256;                        // one 8-wave workgroup per CU
     g.G = (int)std::min<int64_t>(T * g.nchunk, std::min(gwant, MAXG));
     // strict launches of tall matrices (few tiles, each split over many workgroups): a grid that is a MULTIPLE of the tile count gives every
     // tile the same row ranges, so that the workgroups of different tiles that share a column panel read the same rows of it at the same
     // time (Infinity Cache) — 65536 x 1024: 28 tiles on 252 instead of 256 workgroups, 1.178 -> 1.163 ms
-    if (g.strict && gdef == 0 && T >= 2 && T <= 32 && T * g.nchunk >= 4 * (int64_t)gwant) g.G = (int)(T * (gwant / T));
+    if (g.strict && T >= 2 && T <= 32 && T * g.nchunk >= 4 * (int64_t)gwant) g.G = (int)(T * (gwant / T));
     g.tfull = (int)(T / g.G);                         // at n = r = 4096: 528 tiles = 2 per workgroup + 16 split 16 ways
     const int64_t R = T - (int64_t)g.tfull * g.G;     // remainder tiles, < G
     g.U = R * g.nchunk;
@@ -824,40 +675,20 @@ int launch_gram_sk(const double *A, int64_t lda, int64_t rows, int64_t cols, con
     }
     if (g.nchunk > 1 && !workspace) return fail(PMT_INVALID_ARGUMENT, "quad_gram: workspace required");
     const dim3 grid((unsigned)g.G);
-#ifdef PMT_TUNING_ABLATE
-    // (ablation instantiations: profiling only, results are wrong for abl != 0; they are a separate switch because their mere presence in
-    // the translation unit moves the register allocation of the shipped kernel)
-#define SK_LAUNCH(TN, BK, WPS)                                                                                              \
-    do {                                                                                                                    \
-        if (abl == 1) PMT_LAUNCH_NAMED("gram_sk_kernel", (gram_sk_kernel<TN, BK, WPS, 1, false>), grid, dim3(Cfg<TN>::NT), 0, s, g);  \
-        else if (abl == 2) PMT_LAUNCH_NAMED("gram_sk_kernel", (gram_sk_kernel<TN, BK, WPS, 2, false>), grid, dim3(Cfg<TN>::NT), 0, s, g); \
-        else if (abl == 3) PMT_LAUNCH_NAMED("gram_sk_kernel", (gram_sk_kernel<TN, BK, WPS, 3, false>), grid, dim3(Cfg<TN>::NT), 0, s, g); \
-        else PMT_LAUNCH_NAMED("gram_sk_kernel", (gram_sk_kernel<TN, BK, WPS, 0, false>), grid, dim3(Cfg<TN>::NT), 0, s, g);       \
-    } while (0)
-    if (variant == 0) SK_LAUNCH(4, 16, 2);
-    else SK_LAUNCH(2, 16, PMT_SK_WPS);
-#undef SK_LAUNCH
-#else
     // Two instantiations, plain and ranged.  (The 32-row-stage instantiation used for tall matrices in rounds 1-2 spilled 49 VGPRs — +1 % at r = 16384 when it
     // was introduced — and is gone: all shapes take 16-row stages.  So is the delivery instantiation that counted finished tiles per band
     // group inside the kernel: a delivery is now a sequence of plain launches, gram.hip.)
-    if (seq_count >= 0) PMT_LAUNCH_NAMED("gram_sk_kernel", (gram_sk_kernel<2, PMT_SK_BK, PMT_SK_WPS, 0, true>), grid, dim3(Cfg<2>::NT), 0, s, g);
-    else PMT_LAUNCH_NAMED("gram_sk_kernel", (gram_sk_kernel<2, PMT_SK_BK, PMT_SK_WPS, 0, false>), grid, dim3(Cfg<2>::NT), 0, s, g);
-#endif
+    if (seq_count >= 0) PMT_LAUNCH_NAMED("gram_sk_kernel", (gram_sk_kernel<2, SK_BK, SK_WPS, true>), grid, dim3(Cfg<2>::NT), 0, s, g);
+    else PMT_LAUNCH_NAMED("gram_sk_kernel", (gram_sk_kernel<2, SK_BK, SK_WPS, false>), grid, dim3(Cfg<2>::NT), 0, s, g);
     int rc = check_launch("gram_sk_kernel");
     if (rc) return rc;
     if (g.nchunk > 1 && R > 0 && !fold) {
         // The split tiles are summed by a second launch.  (Round 3 measured the alternative — the workgroup that arrives last at a split tile
         // adds its partials inside the contraction: +55 us at n = r = 4096, one CU pulling 2 MB of partials, against 15 us of fix-up kernel
         // plus ~25 us of in-stream gaps; profiles/r03_gram_fold_experiment.txt.)
-#ifdef PMT_TUNING
-        static const int apb = env_int("PMT_GRAM_SK_FIXUP_APB", 0);
-#else
-        constexpr int apb = 0;
-#endif
         // (tiles split more than 32 ways each — few tiles, many rows: the sliced form)
-        if (apb == 0 && (int64_t)g.G >= 32 * R) PMT_LAUNCH_NAMED("gram_sk_fixup_sliced_kernel", (gram_sk_fixup_sliced_kernel<2>), dim3((unsigned)R, Cfg<2>::NACC, Cfg<2>::NT / 64), dim3(512), 0, s, g);
-        else if (apb == 1 || (apb == 0 && R * (Cfg<2>::NACC / 4) < PMT_SK_APB1_BELOW)) PMT_LAUNCH_NAMED("gram_sk_fixup_kernel", (gram_sk_fixup_kernel<2, 1>), dim3((unsigned)R, Cfg<2>::NACC), dim3(Cfg<2>::NT), 0, s, g);
+        if ((int64_t)g.G >= 32 * R) PMT_LAUNCH_NAMED("gram_sk_fixup_sliced_kernel", (gram_sk_fixup_sliced_kernel<2>), dim3((unsigned)R, Cfg<2>::NACC, Cfg<2>::NT / 64), dim3(512), 0, s, g);
+        else if (R * (Cfg<2>::NACC / 4) < SK_APB1_BELOW) PMT_LAUNCH_NAMED("gram_sk_fixup_kernel", (gram_sk_fixup_kernel<2, 1>), dim3((unsigned)R, Cfg<2>::NACC), dim3(Cfg<2>::NT), 0, s, g);
         else PMT_LAUNCH_NAMED("gram_sk_fixup_kernel", (gram_sk_fixup_kernel<2, 4>), dim3((unsigned)R, Cfg<2>::NACC / 4), dim3(Cfg<2>::NT), 0, s, g);
         rc = check_launch("gram_sk_fixup_kernel");
     }

@@ -35,17 +35,8 @@
 #ifndef PMT_TALL_MR
 #define PMT_TALL_MR 32
 #endif
-#ifndef PMT_TALL_ABL
-#define PMT_TALL_ABL 0
-#endif
 #ifndef PMT_TALL_MAXG
 #define PMT_TALL_MAXG 512
-#endif
-#ifndef PMT_TALL_K2
-#define PMT_TALL_K2 1
-#endif
-#ifndef PMT_TALL_DIAG3
-#define PMT_TALL_DIAG3 1         // a diagonal block's third rotation is not computed (tall_diag_rule)
 #endif
 
 namespace pmt {
@@ -54,7 +45,7 @@ constexpr int TBK = PMT_TALL_MR;            // rows per stage (one barrier per s
 constexpr int TGP = TBK + 2;                // LDS pitch of a column: 2 mod 32 — the 16 columns x 2 k of a half-wave operand read fall on 32 distinct
                                             // bank pairs, and even, so that the row pairs go to LDS as 16-byte stores
 constexpr int TSUB = TBK / 16;              // 16-row pieces of a column per stage
-constexpr int TLK = PMT_TALL_K2 ? 2 : 1;    // rows between the contraction slots of a k-step (see tall_stage)
+constexpr int TLK = 2;                      // rows between the contraction slots of a k-step (see tall_stage)
 constexpr int TCOLS = 128;                  // columns of the one tile
 constexpr int TBLK = 9;                     // 16 x 16 blocks per wave at most (NBC = 8)
 constexpr int TACC = TBLK * 4;              // accumulators per lane at most (4 rotations per block)
@@ -109,39 +100,18 @@ struct TallArgs {
     int vec_in;                           // A 16-byte aligned and lda even
 };
 
-// PMT_TALL_DPP (off; an experiment kept as a knob): the B operand of the r-th rotation of a 16 x 16 block is the value that the lane 4 r
-// further up its 16-lane row holds for r = 0 (column group (b + r) & 3 instead of b), and the r = 0 value of block column t IS the A
-// operand of block row t — so ONE LDS read per block column and k-step would do, the rotations being DPP row rotations (row_ror) of it:
-// NB reads instead of 5 NB.  Correct, and SLOWER (2^20 rows; 16 / 32 / 64 columns: 34 -> 36, 65 -> 74, 157 -> 171 us): two v_mov_dpp per
-// rotated double in the issue stream of the wave that also issues the MFMAs cost more than the LDS reads they replace, which the LDS
-// pipe serves beside the matrix pipe.  profiles/r05_gram_shapes.txt.
-#ifndef PMT_TALL_DPP
-#define PMT_TALL_DPP 0
-#endif
-template <int CTRL>
-__device__ __forceinline__ double dpp_row(double v) {
-    const long long bits = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_update_dpp(0, (int)(bits & 0xffffffffLL), CTRL, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, (int)(bits >> 32), CTRL, 0xf, 0xf, false);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-// value of the lane (lane + 4 r) mod 16 of the same row: row_ror by 16 - 4 r
-template <int R>
-__device__ __forceinline__ double rot_blocks(double v) {
-    if (R == 0) return v;
-    if (R == 1) return dpp_row<0x12C>(v);
-    if (R == 2) return dpp_row<0x128>(v);
-    return dpp_row<0x124>(v);
-}
+// (The B operands of the rotations as DPP row rotations of ONE LDS read per block column and k-step instead of 5: correct, and SLOWER —
+// 2^20 rows; 16 / 32 / 64 columns: 34 -> 36, 65 -> 74, 157 -> 171 us: two v_mov_dpp per rotated double in the issue stream of the wave that
+// also issues the MFMAs cost more than the LDS reads they replace, which the LDS pipe serves beside the matrix pipe.
+// profiles/r05_gram_shapes.txt.)
 
 // one stage of one wave from the panel in LDS (`panel` already points at this lane's k offset).
-// PMT_TALL_K2: the MFMA's contraction slot k = lane >> 4 of k-steps 2j and 2j + 1 is given the ADJACENT rows 8j + 2k and 8j + 2k + 1 (any
+// The MFMA's contraction slot k = lane >> 4 of k-steps 2j and 2j + 1 is given the ADJACENT rows 8j + 2k and 8j + 2k + 1 (any
 // assignment of rows to slots is a valid contraction as long as both operands use it), so ONE 16-byte LDS read per operand serves two
 // k-steps: half the LDS instructions and half the operand waits per MFMA.
 template <int NBC, int W>
 __device__ __forceinline__ void tall_stage(const double *__restrict__ panel, int lm, double (&acc)[tall_tacc(NBC)]) {
     constexpr int NR = tw_nr(NBC, W), NC = tw_nc(NBC, W), NBLK = tw_nblk(NBC, W);
-#if PMT_TALL_K2
 #pragma unroll PMT_TALL_UNROLL
     for (int kk = 0; kk < TBK / 8; ++kk) {
         f64x2 a[NR];
@@ -160,41 +130,15 @@ __device__ __forceinline__ void tall_stage(const double *__restrict__ panel, int
                 if (tw_blk(NBC, W, k, 1) != c) continue;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    if (PMT_TALL_DIAG3 && r == 3 && tw_row(NBC, W, tw_blk(NBC, W, k, 0)) == tw_col(NBC, W, c)) continue;      // (diagonal block: see below)
+                    // a DIAGONAL block's third rotation — 4 x 4 sub-blocks (b, b + 3) — holds the transposes of the first rotation's
+                    // (b + 1, b): never computed, the fix-up reads the (3, 0) sub-block of rotation 1 as (0, 3) (tall_diag_rule)
+                    if (r == 3 && tw_row(NBC, W, tw_blk(NBC, W, k, 0)) == tw_col(NBC, W, c)) continue;
                     acc[k * 4 + r] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[tw_blk(NBC, W, k, 0)].x, bv[r].x, acc[k * 4 + r], 0, 0, 0);
                     acc[k * 4 + r] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[tw_blk(NBC, W, k, 0)].y, bv[r].y, acc[k * 4 + r], 0, 0, 0);
                 }
             }
         }
     }
-#else
-#pragma unroll PMT_TALL_UNROLL
-    for (int ks = 0; ks < TBK / 4; ++ks) {
-        double a[NR];
-#pragma unroll
-        for (int t = 0; t < NR; ++t) a[t] = panel[(tw_row(NBC, W, t) * 16 + lm) * TGP + ks * 4];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            double bv[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int rc = ((((lm >> 2) + r) & 3) << 2) | (lm & 3);      // column group rotated by r blocks (gram_sk.hip, lane maps)
-                bv[r] = panel[(tw_col(NBC, W, c) * 16 + rc) * TGP + ks * 4];
-            }
-#pragma unroll
-            for (int k = 0; k < NBLK; ++k) {
-                if (tw_blk(NBC, W, k, 1) != c) continue;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    // a DIAGONAL block's third rotation — 4 x 4 sub-blocks (b, b + 3) — holds the transposes of the first rotation's
-                    // (b + 1, b): never computed, the fix-up reads the (3, 0) sub-block of rotation 1 as (0, 3) (tall_diag_rule)
-                    if (PMT_TALL_DIAG3 && r == 3 && tw_row(NBC, W, tw_blk(NBC, W, k, 0)) == tw_col(NBC, W, c)) continue;
-                    acc[k * 4 + r] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[tw_blk(NBC, W, k, 0)], bv[r], acc[k * 4 + r], 0, 0, 0);
-                }
-            }
-        }
-    }
-#endif
 }
 
 // thread (kp = tid & 7, cc = tid >> 3) owns the row pairs 16 j + 2 kp (j < TSUB) of the columns cc + 32 p (p < 4): the TSUB loads of a
@@ -301,33 +245,9 @@ __device__ __forceinline__ void tall_body(const TallArgs &g, double (&lds)[2][TC
     for (int s = 0; s < nstage; ++s) {
         const int cur = s & 1;
         const bool more = s + 1 < nstage;
-#if PMT_TALL_ABL == 1      // ablation (wrong results): no global loads / LDS stores after the first stage — the MFMA side alone
-        tall_stage<NBC, W>(lds[cur] + TLK * lk, lm, acc);
-#elif PMT_TALL_ABL == 2    // ablation (wrong results): no MFMAs — the memory side alone
-        if (more) tall_load<NBC, FAST>(g, stage_row(s + 1), rend, kp, cc, reg, cv);
-        if (more) tall_store(lds[cur ^ 1], reg, cv, g.sign, kp, cc, qacc, cacc);
-#elif PMT_TALL_ABL == 3    // ablation (wrong results): global loads + MFMAs, no register -> LDS phase (one add keeps the loads alive)
-        if (more) tall_load<NBC, FAST>(g, stage_row(s + 1), rend, kp, cc, reg, cv);
-        tall_stage<NBC, W>(lds[cur] + TLK * lk, lm, acc);
-        if (more) { cacc = cacc + reg[0][0].x; cacc = cacc + reg[3][TSUB - 1].y; cacc = cacc + cv[0].x; }
-#elif PMT_TALL_ABL == 4    // ablation (wrong results): MFMAs + the register -> LDS phase of stale registers, no global loads after the first stage
-        tall_stage<NBC, W>(lds[cur] + TLK * lk, lm, acc);
-        if (more) tall_store(lds[cur ^ 1], reg, cv, g.sign, kp, cc, qacc, cacc);
-#elif PMT_TALL_ABL == 5    // ablation (wrong results): everything but the q / c'c arithmetic (LDS stores only)
-        if (more) tall_load<NBC, FAST>(g, stage_row(s + 1), rend, kp, cc, reg, cv);
-        tall_stage<NBC, W>(lds[cur] + TLK * lk, lm, acc);
-        if (more) {
-#pragma unroll
-            for (int j = 0; j < TSUB; ++j)
-#pragma unroll
-                for (int p = 0; p < 4; ++p) *reinterpret_cast<f64x2 *>(lds[cur ^ 1] + (cc + 32 * p) * TGP + 16 * j + 2 * kp) = reg[p][j];
-            cacc = cacc + cv[0].x;
-        }
-#else
         if (more) tall_load<NBC, FAST>(g, stage_row(s + 1), rend, kp, cc, reg, cv);
         tall_stage<NBC, W>(lds[cur] + TLK * lk, lm, acc);
         if (more) tall_store(lds[cur ^ 1], reg, cv, g.sign, kp, cc, qacc, cacc);
-#endif
         __syncthreads();
     }
 
@@ -482,9 +402,6 @@ __global__ __launch_bounds__(1024) void gram_tall_fixup_kernel(TallFixArgs f) {
 #ifndef PMT_NARROW_MAXG
 #define PMT_NARROW_MAXG 512
 #endif
-#ifndef PMT_NARROW_ABL
-#define PMT_NARROW_ABL 0           // ablations (wrong results): 1 no loads after the first stage, 2 no MFMAs
-#endif
 template <int NB> struct Narrow {
     static constexpr int C = 16 * NB;                    // columns of the panel
     static constexpr int LPC = NB == 1 ? 16 : 8;         // lanes per column run (row pairs 2 kp of a piece)
@@ -572,15 +489,11 @@ __device__ __forceinline__ void narrow_store(double *__restrict__ panel, const f
 }
 
 // this wave's quarter of a stage: every block, KSTEPS k-steps (`panel` points at the wave's first row + this lane's k offset).
-// PMT_NARROW_K2 (as PMT_TALL_K2): the contraction slot k = lane >> 4 of k-steps 2j and 2j + 1 takes the ADJACENT rows 8j + 2k, 8j + 2k + 1, so
+// As in tall_stage, the contraction slot k = lane >> 4 of k-steps 2j and 2j + 1 takes the ADJACENT rows 8j + 2k, 8j + 2k + 1, so
 // ONE 16-byte LDS read per operand serves two k-steps.
-#ifndef PMT_NARROW_K2
-#define PMT_NARROW_K2 1
-#endif
 template <int NB>
 __device__ __forceinline__ void narrow_stage(const double *__restrict__ panel, int lm, double (&acc)[Narrow<NB>::NACC]) {
     using N = Narrow<NB>;
-#if PMT_NARROW_K2
     static_assert(N::KSTEPS % 2 == 0, "k-steps in pairs");
 #pragma unroll
     for (int kk = 0; kk < N::KSTEPS / 2; ++kk) {
@@ -592,7 +505,7 @@ __device__ __forceinline__ void narrow_stage(const double *__restrict__ panel, i
             f64x2 bv[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                if (PMT_TALL_DIAG3 && r == 3 && c == 0) { bv[r].x = 0.0; bv[r].y = 0.0; continue; }
+                if (r == 3 && c == 0) { bv[r].x = 0.0; bv[r].y = 0.0; continue; }         // (column 0 has the diagonal block only)
                 const int rc = ((((lm >> 2) + r) & 3) << 2) | (lm & 3);
                 bv[r] = *reinterpret_cast<const f64x2 *>(panel + (c * 16 + rc) * N::PITCH + kk * 8);
             }
@@ -600,43 +513,13 @@ __device__ __forceinline__ void narrow_stage(const double *__restrict__ panel, i
             for (int tm = 0; tm <= c; ++tm)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    if (PMT_TALL_DIAG3 && r == 3 && tm == c) continue;    // (diagonal block: tall_stage)
+                    if (r == 3 && tm == c) continue;    // (diagonal block: tall_stage)
                     const int k = c * (c + 1) / 2 + tm;
                     acc[k * 4 + r] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[tm].x, bv[r].x, acc[k * 4 + r], 0, 0, 0);
                     acc[k * 4 + r] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[tm].y, bv[r].y, acc[k * 4 + r], 0, 0, 0);
                 }
         }
     }
-#else
-#pragma unroll
-    for (int ks = 0; ks < N::KSTEPS; ++ks) {
-        double a[NB];
-#pragma unroll
-        for (int t = 0; t < NB; ++t) a[t] = panel[(t * 16 + lm) * N::PITCH + ks * 4];
-#pragma unroll
-        for (int c = 0; c < NB; ++c) {
-            double bv[4];
-#if PMT_TALL_DPP
-            bv[0] = a[c]; bv[1] = rot_blocks<1>(a[c]); bv[2] = rot_blocks<2>(a[c]); bv[3] = rot_blocks<3>(a[c]);
-#else
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (r == 3 && c == 0) { bv[r] = 0.0; continue; }         // (column 0 has the diagonal block only)
-                const int rc = ((((lm >> 2) + r) & 3) << 2) | (lm & 3);
-                bv[r] = panel[(c * 16 + rc) * N::PITCH + ks * 4];
-            }
-#endif
-#pragma unroll
-            for (int tm = 0; tm <= c; ++tm)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if (PMT_TALL_DIAG3 && r == 3 && tm == c) continue;    // (diagonal block: tall_stage)
-                    const int k = c * (c + 1) / 2 + tm;
-                    acc[k * 4 + r] = __builtin_amdgcn_mfma_f64_4x4x4f64(a[tm], bv[r], acc[k * 4 + r], 0, 0, 0);
-                }
-        }
-    }
-#endif
 }
 
 template <int NB, bool FAST>
@@ -670,17 +553,9 @@ __global__ __launch_bounds__(256, PMT_NARROW_WPS) void gram_narrow_kernel(TallAr
     for (int s = 0; s < nstage; ++s) {
         const int cur = s & 1;
         const bool more = s + 1 < nstage;
-#if PMT_NARROW_ABL == 1
-        narrow_stage<NB>(lds[cur] + wave * (N::R / 4) + (PMT_NARROW_K2 ? 2 : 1) * lk, lm, acc);
-        if (more) narrow_store<NB>(lds[cur ^ 1], reg, cv, g.sign, kp, cc, qacc, cacc);
-#elif PMT_NARROW_ABL == 2
         if (more) narrow_load<NB, FAST>(g, stage_row(s + 1), rend, kp, cc, reg, cv);
+        narrow_stage<NB>(lds[cur] + wave * (N::R / 4) + 2 * lk, lm, acc);
         if (more) narrow_store<NB>(lds[cur ^ 1], reg, cv, g.sign, kp, cc, qacc, cacc);
-#else
-        if (more) narrow_load<NB, FAST>(g, stage_row(s + 1), rend, kp, cc, reg, cv);
-        narrow_stage<NB>(lds[cur] + wave * (N::R / 4) + (PMT_NARROW_K2 ? 2 : 1) * lk, lm, acc);
-        if (more) narrow_store<NB>(lds[cur ^ 1], reg, cv, g.sign, kp, cc, qacc, cacc);
-#endif
         __syncthreads();
     }
 
@@ -725,8 +600,8 @@ __global__ __launch_bounds__(256, PMT_NARROW_WPS) void gram_narrow_kernel(TallAr
 // lk = lane >> 4) loads the 16 bytes of column 16 t + lm at rows 8 i + 2 lk, 8 i + 2 lk + 1 of its iteration: exactly the two values the
 // contraction slots k = lk of k-steps 2 i and 2 i + 1 take for BOTH operands (any assignment of rows to slots is a valid contraction as
 // long as both operands use it: narrow_stage) — D iterations in flight per wave in registers, and the rotated B operands of a block column
-// are DPP row rotations of the A operand (rot_blocks; in the panel kernel they cost more than the LDS reads they replaced, here there is
-// no LDS pipe to lean on and the VALU is idle).  A load instruction touches 64 contiguous bytes of each of 16 columns; the wave's IT
+// are the A operand read back rotated out of the wave's private piece of LDS (stream_compute; DPP row rotations of it doubled the matrix
+// phase, profiles/r06_gram_stream.txt).  A load instruction touches 64 contiguous bytes of each of 16 columns; the wave's IT
 // instructions of an iteration cover 64 IT contiguous bytes per column, neighbouring waves neighbouring pieces (iteration = global wave
 // index + k * waves: the chip reads one band of consecutive rows at a time, as the panel kernels do).  q = A'c and c'c ride on the VALU
 // with the loaded values.  The four waves of a workgroup add their sums in wave order through LDS once, at the end; the workgroups'
@@ -767,15 +642,6 @@ __global__ __launch_bounds__(256, PMT_NARROW_WPS) void gram_narrow_kernel(TallAr
 #ifndef PMT_STREAM_MAXG4
 #define PMT_STREAM_MAXG4 512       // 64 columns: the matrix pipe matters as much as the stream — two waves per SIMD (256 workgroups: 142 us against 118)
 #endif
-#ifndef PMT_STREAM_ABL
-#define PMT_STREAM_ABL 0           // ablations (wrong results): 1 no MFMAs / rotations, 2 no loads after the first D iterations
-#endif
-#ifndef PMT_STREAM_SADDR
-#define PMT_STREAM_SADDR 1         // scalar-base loads, no branch around b's load, whole rounds of D iterations as one branch-free block
-#endif
-#ifndef PMT_STREAM_DPP
-#define PMT_STREAM_DPP 1           // 0: the rotated operands are loaded again from global memory (L1 hits) instead of DPP rotations
-#endif
 template <int NB> struct Stream {
     static constexpr int IT = NB == 4 ? PMT_STREAM_IT4 : 4;           // 16-byte loads per column group, lane and iteration (= pairs of k-steps)
     static constexpr int RI = 8 * IT;                    // rows per iteration
@@ -800,23 +666,16 @@ __device__ __forceinline__ void stream_load(const TallArgs &g, int64_t row0, int
         const char *base = reinterpret_cast<const char *>(g.A + row0);
 #pragma unroll
         for (int t = 0; t < NB; ++t) {
-#if PMT_STREAM_SADDR
             // the lane offset passes through an empty asm: the compiler cannot hoist its zero extension out of the loop (it did, and
             // then paid a 64-bit vector add per load instead of the scalar-base form; gram_mid.hip: mid_step)
             asm volatile("" : "+v"(voff[t]));
-#endif
 #pragma unroll
             for (int i = 0; i < S::IT; ++i) buf[t][i] = *reinterpret_cast<const f64x2 *>(base + voff[t] + 64 * i);
         }
-#if PMT_STREAM_SADDR
         // no b: sign is 0 and signed_const ignores what is loaded — any valid address keeps the loop free of branches
         unsigned bo = 16u * (unsigned)bp;
         asm volatile("" : "+v"(bo));
         cb = *reinterpret_cast<const f64x2 *>(reinterpret_cast<const char *>((g.b ? g.b : g.A) + row0) + bo);
-#else
-        cb.x = 0.0; cb.y = 0.0;
-        if (g.b) cb = *reinterpret_cast<const f64x2 *>(reinterpret_cast<const char *>(g.b + row0) + 16u * (unsigned)bp);
-#endif
         return;
     }
 #pragma unroll
@@ -863,22 +722,19 @@ __device__ __forceinline__ void stream_compute(double *__restrict__ rot, const f
     f64x2 cs;
     cs.x = signed_const(cb.x, sign); cs.y = signed_const(cb.y, sign);
     *reinterpret_cast<f64x2 *>(rotb + lane * 2) = cs;
-#if PMT_STREAM_ABL != 4
 #pragma unroll
     for (int t = 0; t < NB; ++t)
 #pragma unroll
         for (int i = 0; i < S::IT; ++i) *reinterpret_cast<f64x2 *>(rot + ((t * S::IT + i) * 64 + lane) * 2) = buf[t][i];
-#endif
 #pragma unroll
     for (int i = 0; i < S::IT; ++i) {
 #pragma unroll
-        for (int c = 0; c < (PMT_STREAM_ABL == 1 ? 0 : NB); ++c) {
+        for (int c = 0; c < NB; ++c) {
             f64x2 bv[4];
             bv[0] = buf[c][i];
 #pragma unroll
             for (int r = 1; r < 4; ++r) {
                 if (r == 3 && c == 0) { bv[r].x = 0.0; bv[r].y = 0.0; continue; }      // (block column 0 holds the diagonal block only)
-                if (PMT_STREAM_ABL == 4) { bv[r] = buf[c][i]; continue; }                  // (ablation: no rotations)
                 bv[r] = *reinterpret_cast<const f64x2 *>(rot + ((c * S::IT + i) * 64 + lrow + ((lm + 4 * r) & 15)) * 2);
             }
 #pragma unroll
@@ -891,7 +747,6 @@ __device__ __forceinline__ void stream_compute(double *__restrict__ rot, const f
                     acc[k * 4 + r] = __builtin_amdgcn_mfma_f64_4x4x4f64(buf[tm][i].y, bv[r].y, acc[k * 4 + r], 0, 0, 0);
                 }
         }
-        if (PMT_STREAM_ABL == 5) continue;                                                // (ablation: no q / c'c)
         const f64x2 bi = *reinterpret_cast<const f64x2 *>(rotb + (4 * i + lk) * 2);        // rows 8 i + 2 lk, + 1 of c
         const double c0 = bi.x, c1 = bi.y;
 #pragma unroll
@@ -938,7 +793,7 @@ __global__ __launch_bounds__(256, NB == 4 ? PMT_STREAM_WPS4 : NB <= 2 ? PMT_STRE
     if (my > 0) {
 #pragma unroll
         for (int d = 0; d < S::D; ++d) stream_load<NB, FAST>(g, row_of(d), lane, voff, buf[d], cb[d]);
-        if (PMT_STREAM_SADDR && FAST && PMT_STREAM_ABL == 0) {
+        if (FAST) {
             // whole rounds of D iterations: one block without a branch (the number of loads in flight does not depend on the path, the
             // compiler's vmcnt waits stay counted ones); the loads beyond the wave's last iteration repeat the last one
             int s0 = 0;
@@ -957,7 +812,7 @@ __global__ __launch_bounds__(256, NB == 4 ? PMT_STREAM_WPS4 : NB <= 2 ? PMT_STRE
 #pragma unroll
                 for (int d = 0; d < S::D; ++d) {
                     if (s0 + d < my) stream_compute<NB>(rot, buf[d], cb[d], g.sign, lane, acc, qacc, cacc);
-                    if (PMT_STREAM_ABL != 2 && PMT_STREAM_ABL != 4 && PMT_STREAM_ABL != 5) stream_load<NB, FAST>(g, row_of(s0 + d + S::D), lane, voff, buf[d], cb[d]);
+                    stream_load<NB, FAST>(g, row_of(s0 + d + S::D), lane, voff, buf[d], cb[d]);
                 }
             }
         }
@@ -1155,11 +1010,7 @@ int launch_gram_tall(const double *A, int64_t lda, int64_t rows, int64_t cols, c
     const bool fast = g.vec_in && rows % TBK == 0 && (reinterpret_cast<uintptr_t>(g.b) & 15) == 0;
     // one tile of 65 .. 112 columns: the kernel built for 5 / 6 / 7 block columns (15 / 21 / 28 blocks instead of 36)
     const int nbc = nt == 1 ? (int)std::max<int64_t>(5, cdiv(cols, 16)) : 8;
-#ifdef PMT_TALL_NBC8
-    const int use = 8;
-#else
     const int use = nbc;
-#endif
 #define TALL_LAUNCH(N)                                                                                                          \
     do {                                                                                                                        \
         if (fast) PMT_LAUNCH_NAMED("gram_tall_kernel", (gram_tall_kernel<N, true>), dim3((unsigned)G, nt), dim3(256), 0, s, g);   \

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B over library builds of batch_small.hip (tools/build_variants_file.sh batch_small <name> "<flags>" ...):
-#   tools/bs_ab.sh base p34 ...   -> compute-only ms per 8192-instance step, order alternated over 3 repetitions
+#   tools/bs_ab.sh shipped <name> ...   -> compute-only ms per 8192-instance step, order alternated over 3 repetitions
 for rep in 1 2 3; do
   for v in "$@"; do
     if [ "$v" = "shipped" ]; then lib=$PWD/parametron.jl_amd/lib/libparametron_hip.so; else lib=$PWD/parametron.jl_amd/lib_variants/$v.so; fi
