@@ -171,3 +171,32 @@ def constant_in_the_library_order(r, n, b, sign=-1):
     for t in range(1, 16):
         total = total + slices[t]
     return order.value, float(total)
+
+
+def run_sum_sequential(values):
+    """A run's coefficients added left to right, starting from the first value — the order of csc_values_thread_kernel and
+    csc_values_gather_kernel (csrc/handoff.hip: acc = c[0]; acc += c[1]; ..)"""
+    acc = float(values[0])
+    for v in values[1:]:
+        acc = acc + float(v)
+    return acc
+
+
+def run_sum_wave(values, skip_empty):
+    """A run's coefficients added in the order of the one-wave-per-run kernels: lane l of 64 adds elements l, l + 64, .. in order, then the
+    __shfl_down tree over offsets 32, 16, .., 1 (lane i += lane i + off for i < off; the other lanes are not read again).
+    skip_empty=True is segment_sum_kernel (csrc/canon.hip): a lane without an element contributes nothing, not even +0.0, and the first
+    contribution is taken as it is.  skip_empty=False is csc_values_wave_kernel (csrc/handoff.hip): every lane starts at 0.0 and all 64
+    enter the tree."""
+    lanes = [None if skip_empty else 0.0] * 64
+    for k, v in enumerate(values):
+        l = k & 63
+        lanes[l] = float(v) if lanes[l] is None else lanes[l] + float(v)
+    off = 32
+    while off >= 1:
+        for i in range(off):
+            other = lanes[i + off]
+            if other is not None:
+                lanes[i] = other if lanes[i] is None else lanes[i] + other
+        off //= 2
+    return lanes[0]
