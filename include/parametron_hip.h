@@ -537,6 +537,50 @@ int pmt_sparse_assemble_blocks_f64(const double *nzval, const uint64_t *desc, co
 /* constants of the same node: out[i] = 0.0 (+|-) d[i]  (vecadd!/vecsubtract! on zero!'d functions, src/functions.jl:244,452,474) */
 int pmt_consts_f64(const double *d, int64_t n, int sign, double *out, void *stream);
 
+/* Sparse least-squares objective: dot(r, r), r = C*x (+|-) d with C the fixed-pattern CSC matrix above, as the canonical MOI function —
+ * vecdot! (src/functions.jl:702-709 over :548-576) of rows holding the STRUCTURAL terms only (the reference's output minus the structural
+ * zeros, as for the constraint node), canonicalize! (:381-386), the MOI copy (src/moi_interop.jl:45-62).  With c_i = 0.0 (+|-) d[i]:
+ *   out_quad[s] = (2 * sum_i C[i,j]*C[i,k], vm[xvar[j]], vm[xvar[k]])  one term per pair of columns j <= k that share at least one row,
+ *                 sorted by (j, k), the sum over the shared rows (diagonal included, as for pmt_quad_gram_f64); nq terms
+ *   out_lin[l]  = (2 * sum_i C[i,j]*c_i, vm[xvar[j]])                  one term per NON-EMPTY column j = lin_col[l]; without d the
+ *                 coefficients are sums of C[i,j]*0.0 — zeros — and the terms still exist
+ *   out_const   = sum_i c_i^2 over all `rows` rows (0.0 without d)
+ * moi == 0: native indices (no varmap) and the diagonal coefficients undoubled, as in pmt_quad_gram_f64.  The whole 24- and 16-byte structs
+ * are written at every call.  Requires a canonical pattern (rows strictly ascending within a column), xvar strictly increasing, fewer than
+ * 2^32 non-zeros and fewer than 2^31 products.
+ * Symbolic phase, host, once per pattern (colptr / rowval 1-based as above; linear in nprod + nnz + m + n, no comparison sort):
+ *   pmt_sparse_gram_count -> nq and nprod = sum over the rows of L(L+1)/2, L the row's length (nprod >= 2^31: nq = -1, not counted)
+ *   pmt_sparse_gram_order -> pair_j[nq], pair_k[nq] (0-based column positions, sorted by (j, k)); seg_ptr[nq+1]; prod[nprod] of
+ *                            { uint32 ta, uint32 tb }: positions in nzval, ta in column j, tb in column k, within a segment in ascending
+ *                            row order; lin_col[*nlin] (capacity n): the non-empty columns.  nq / nprod are those of _count.
+ *   pmt_sparse_gram_runs  -> how one launch is cut: runs[2r], runs[2r+1] = the first and one past the last segment of workgroup run r —
+ *                            whole segments of fewer than 64 products, at most `cap` (64 .. 2048) products together — and long_seg[]: the
+ *                            segments of 64 products or more.  runs / long_seg NULL: the counts only.
+ *   a 0-based colptr is PMT_INVALID_ARGUMENT, an out-of-range row PMT_DIMENSION_MISMATCH, rows that do not ascend PMT_INVALID_ARGUMENT.
+ * The arithmetic is part of this contract and does not depend on the runs (no fused multiply-add anywhere):
+ *   product        p = nzval[ta]*nzval[tb]                        (linear terms: nzval[t]*c_i over column j's entries in CSC order)
+ *   short segment  (fewer than 64 products)  acc = p_0; acc += p_1; ..  left to right; the coefficient is 2.0*acc
+ *   long segment   every lane of 64 starts at 0.0, lane l adds products l, l + 64, .. in order, then the __shfl_down tree over
+ *                  32, 16, .., 1 (the one-wave order of pmt_csc_values_f64's long runs); the coefficient is 2.0*total
+ *   constant       256 chains (chain t adds rows t, t + 256, .. in order), then the halving tree — S_d's order in pmt_quad_gram_sum_f64
+ * Per call: the kernels stream the product list (8 bytes per product), gather the two values from nzval and add every segment's products
+ * from LDS; no floating-point atomics.  The linear terms are cut the same way: lin_seg[l] (nlin + 1 entries, 0-based) is the position in nzval
+ * of the first entry of column lin_col[l] (the last entry: nnz) — the non-empty columns lie back to back in CSC storage —, rowidx0 (nnz,
+ * 0-based) the entries' rows, lin_runs / lin_long the runs and long segments pmt_sparse_gram_runs makes of lin_seg.  Null pointers,
+ * negative counts and moi without varmap are PMT_INVALID_ARGUMENT before any device call. */
+int pmt_sparse_gram_count(int64_t m, int64_t n, const int64_t *host_colptr, const int64_t *host_rowval, int64_t *nq, int64_t *nprod);
+int pmt_sparse_gram_order(int64_t m, int64_t n, const int64_t *host_colptr, const int64_t *host_rowval, int64_t nq, int64_t nprod,
+                          uint32_t *host_pair_j, uint32_t *host_pair_k, int64_t *host_seg_ptr, void *host_prod, uint32_t *host_lin_col,
+                          int64_t *nlin);
+int pmt_sparse_gram_runs(const int64_t *host_seg_ptr, int64_t nq, int64_t cap, int64_t *host_runs, int64_t *nruns, int64_t *host_long_seg,
+                         int64_t *nlong);
+int pmt_sparse_gram_f64(const double *nzval, const void *prod, const int64_t *seg_ptr, const uint32_t *pair_j, const uint32_t *pair_k,
+                        int64_t nq, const int64_t *runs, int64_t nruns, const int64_t *long_seg, int64_t nlong,
+                        const int64_t *lin_seg, const uint32_t *rowidx0, const uint32_t *lin_col, int64_t nlin, const int64_t *lin_runs,
+                        int64_t nlin_runs, const int64_t *lin_long, int64_t nlin_long, int64_t rows, const int64_t *xvar, const double *d,
+                        int sign, int moi, const int64_t *varmap, pmt_quadratic_term *out_quad, pmt_linear_term *out_lin, double *out_const,
+                        void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * Batched independent QPs (BASELINE config 4).  In the reference a batch is many independent Models (src/model.jl:1-22); all
  * instances share one structure, so per re-evaluation only coefficients are produced: one slab of

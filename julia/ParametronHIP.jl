@@ -271,6 +271,51 @@ sparse_assemble_blocks!(out_terms::DevPtr, out_consts::DevPtr, nzval::DevPtr, de
 consts!(out::DevPtr, d::DevPtr, n, sign, stream) =
     check(ccall((:pmt_consts_f64, lib), Cint, (DevPtr, Int64, Cint, DevPtr, Ptr{Cvoid}), d, n, sign, out, stream))
 
+"symbolic phase of the sparse least-squares objective dot(C*x (+|-) d, C*x (+|-) d) (host, once per pattern): the pairs of columns sharing a
+row sorted by (j, k), their product list (positions in nzval, rows ascending within a segment), the non-empty columns, and the cut of one
+launch into workgroup runs of at most `cap` products (segments of 64 products or more apart, one wave each)"
+function sparse_gram_plan(C::SparseMatrixCSC{Float64,Int64}; cap::Integer=2048)
+    m, n = size(C)
+    nq, nprod = Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:pmt_sparse_gram_count, lib), Cint, (Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ref{Int64}, Ref{Int64}), m, n, C.colptr, C.rowval, nq, nprod))
+    nprod[] < 2^31 || throw(ArgumentError("sparse dot(r, r): nprod = $(nprod[]) products, 2^31 or more: hold the matrix in a dense Parameter"))
+    pj, pk, seg = zeros(UInt32, max(nq[], 1)), zeros(UInt32, max(nq[], 1)), zeros(Int64, nq[] + 1)
+    prod, lin_col, nlin = zeros(UInt64, max(nprod[], 1)), zeros(UInt32, max(n, 1)), Ref{Int64}(0)
+    check(ccall((:pmt_sparse_gram_order, lib), Cint,
+                (Int64, Int64, Ptr{Int64}, Ptr{Int64}, Int64, Int64, Ptr{UInt32}, Ptr{UInt32}, Ptr{Int64}, Ptr{Cvoid}, Ptr{UInt32}, Ref{Int64}),
+                m, n, C.colptr, C.rowval, nq[], nprod[], pj, pk, seg, prod, lin_col, nlin))
+    runs, nruns, long_seg, nlong = sparse_gram_runs(seg, nq[], cap)
+    resize!(lin_col, nlin[])
+    lin_seg = Int64[C.colptr[j + 1] - 1 for j in lin_col]        # the first entry of every non-empty column, 0-based; then nnz
+    push!(lin_seg, length(C.nzval))
+    lin_runs, nlin_runs, lin_long, nlin_long = sparse_gram_runs(lin_seg, nlin[], cap)
+    (nq = nq[], nprod = nprod[], pair_j = pj, pair_k = pk, seg_ptr = seg, prod = prod, runs = runs, nruns = nruns, long_seg = long_seg,
+     nlong = nlong, lin_seg = lin_seg, rowidx0 = UInt32.(C.rowval .- 1), lin_col = lin_col, nlin = nlin[], lin_runs = lin_runs,
+     nlin_runs = nlin_runs, lin_long = lin_long, nlin_long = nlin_long)
+end
+
+"the cut of a segment table into workgroup runs of at most `cap` products and the long segments (64 products or more): count, then fill"
+function sparse_gram_runs(seg::Vector{Int64}, nseg, cap)
+    nruns, nlong = Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:pmt_sparse_gram_runs, lib), Cint, (Ptr{Int64}, Int64, Int64, Ptr{Int64}, Ref{Int64}, Ptr{Int64}, Ref{Int64}),
+                seg, nseg, cap, C_NULL, nruns, C_NULL, nlong))
+    runs, long_seg = zeros(Int64, 2 * max(nruns[], 1)), zeros(Int64, max(nlong[], 1))
+    check(ccall((:pmt_sparse_gram_runs, lib), Cint, (Ptr{Int64}, Int64, Int64, Ptr{Int64}, Ref{Int64}, Ptr{Int64}, Ref{Int64}),
+                seg, nseg, cap, runs, nruns, long_seg, nlong))
+    runs, nruns[], long_seg, nlong[]
+end
+
+"the canonical MOI function of dot(r, r), r = C*x (+|-) d with a sparse C (csrc/sparse_gram.hip): the tables of sparse_gram_plan as device
+copies; `d = C_NULL`, `sign = 0`: no d"
+sparse_gram!(out_quad::DevPtr, out_lin::DevPtr, out_const::DevPtr, nzval::DevPtr, prod::DevPtr, seg_ptr::DevPtr, pair_j::DevPtr, pair_k::DevPtr, nq,
+             runs::DevPtr, nruns, long_seg::DevPtr, nlong, lin_seg::DevPtr, rowidx0::DevPtr, lin_col::DevPtr, nlin, lin_runs::DevPtr, nlin_runs,
+             lin_long::DevPtr, nlin_long, rows, xvar::DevPtr, d::DevPtr, sign, moi, varmap::DevPtr, stream) =
+    check(ccall((:pmt_sparse_gram_f64, lib), Cint,
+                (DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, Int64, DevPtr, Int64, DevPtr, Int64, DevPtr, DevPtr, DevPtr, Int64, DevPtr, Int64, DevPtr, Int64,
+                 Int64, DevPtr, DevPtr, Cint, Cint, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
+                nzval, prod, seg_ptr, pair_j, pair_k, nq, runs, nruns, long_seg, nlong, lin_seg, rowidx0, lin_col, nlin, lin_runs, nlin_runs, lin_long,
+                nlin_long, rows, xvar, d, sign, moi, varmap, out_quad, out_lin, out_const, stream))
+
 "dst (cols x rows, leading dimension ldd) = transpose of src (rows x cols, leading dimension lds) — the adjoint rule, src/lazyexpression.jl:206-217"
 transpose!(dst::DevPtr, ldd, src::DevPtr, lds, rows, cols, stream) =
     check(ccall((:pmt_transpose_f64, lib), Cint, (DevPtr, Int64, Int64, Int64, DevPtr, Int64, Ptr{Cvoid}), src, lds, rows, cols, dst, ldd, stream))

@@ -185,6 +185,11 @@ SIGNATURES = {
     "pmt_sparse_blocks_build": (_ci, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp]),
     "pmt_sparse_pack_vector_blocks_f64": (_ci, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _ci, _vp, _i64, _vp, _ci, _vp, _vp, _vp]),
     "pmt_sparse_assemble_blocks_f64": (_ci, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _ci, _vp, _ci, _vp, _vp, _vp]),
+    "pmt_sparse_gram_count": (_ci, [_i64, _i64, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "pmt_sparse_gram_order": (_ci, [_i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
+    "pmt_sparse_gram_runs": (_ci, [_vp, _i64, _i64, _vp, C.POINTER(_i64), _vp, C.POINTER(_i64)]),
+    "pmt_sparse_gram_f64": (_ci, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _ci,
+                                  _ci, _vp, _vp, _vp, _vp, _vp]),
     "pmt_batch_lsq_slab_doubles": (_i64, [_i64, _i64]),
     "pmt_batch_lsq_coeffs_f64": (_ci, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _ci, _vp, _i64, _vp]),
     "pmt_batch_expand_f64": (_ci, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -511,6 +511,7 @@ class DSpMat(DV):
         colptr = np.ascontiguousarray(csc.indptr, dtype=np.int64) + 1            # Julia 1-based
         rowval = np.ascontiguousarray(csc.indices, dtype=np.int64) + 1
         self.indptr, self.indices = csc.indptr.copy(), csc.indices.copy()
+        self._gram = None                                                         # gram_tables(): built on demand
         self.perm = np.empty(self.nnz, dtype=np.int64)
         self.term_row = np.empty(self.nnz, dtype=np.int64)
         self.term_col = np.empty(self.nnz, dtype=np.int64)
@@ -549,6 +550,76 @@ class DSpMat(DV):
     def same_pattern(self, csc):
         return csc.shape == (self.rows, self.cols) and np.array_equal(csc.indptr, self.indptr) and np.array_equal(csc.indices, self.indices)
 
+    def canonical_format(self):
+        """rows strictly ascending within every column (no duplicate entries): what the Gram tables need"""
+        if self.nnz < 2:
+            return True
+        asc = np.diff(self.indices) > 0
+        starts = np.asarray(self.indptr[1:-1], dtype=np.int64)
+        starts = starts[(starts > 0) & (starts < self.nnz)]
+        asc[starts - 1] = True                                # (the step from one column's last entry to the next one's first)
+        return bool(asc.all())
+
+    GRAM_RUN_PRODUCTS = 2048        # products of one workgroup run (csrc/sparse_gram.hip: SG_CAP)
+
+    def gram_tables(self, ctx):
+        """The symbolic phase of dot(r, r), r = C*x (+|-) d (csrc/sparse_gram.hip), once per pattern and only when a Gram consumer asks
+        (moi._Record._compile_sparse_gram): counts, host tables and their device copies."""
+        if self._gram is None:
+            self._gram = SparseGramTables(ctx, self.rows, self.cols, self.indptr, self.indices, self.GRAM_RUN_PRODUCTS)
+        return self._gram
+
+
+class SparseGramTables:
+    """Host tables of pmt_sparse_gram_count / _order / _runs for one CSC pattern (0-based indptr / indices) and, with a context, their device
+    copies: which pairs of columns share a row (pair_j, pair_k, sorted), the product list (prod: nzval positions, rows ascending within a
+    segment), the cut into workgroup runs, the non-empty columns (lin_col), their first entries (lin_seg) and the cut of the linear terms (lin_runs,
+    lin_long: the columns of 64 entries or more, as positions in lin_col)."""
+
+    def __init__(self, ctx, rows, cols, indptr, indices, cap):
+        vp = C.c_void_p
+        colptr = np.ascontiguousarray(indptr, dtype=np.int64) + 1                # Julia 1-based
+        rowval = np.ascontiguousarray(indices, dtype=np.int64) + 1
+        nq, nprod, nlin, nruns, nlong = (C.c_int64() for _ in range(5))
+        _lib.call("pmt_sparse_gram_count", rows, cols, colptr.ctypes.data_as(vp), rowval.ctypes.data_as(vp), C.byref(nq), C.byref(nprod))
+        self.nq, self.nprod = nq.value, nprod.value
+        if self.nprod >= 2 ** 31:
+            raise ArgumentError("dot(r, r) of a sparse residual: nprod = %d products (the sum of L(L+1)/2 over the rows' lengths L), 2^31 or more; "
+                                "at that fill-in hold the matrix in a dense Parameter: the dense Gram node is the right tool" % self.nprod)
+        self.pair_j, self.pair_k = np.zeros(self.nq, dtype=np.uint32), np.zeros(self.nq, dtype=np.uint32)
+        self.seg_ptr = np.zeros(self.nq + 1, dtype=np.int64)
+        self.prod = np.zeros((self.nprod, 2), dtype=np.uint32)
+        lin_col = np.zeros(cols, dtype=np.uint32)
+        _lib.call("pmt_sparse_gram_order", rows, cols, colptr.ctypes.data_as(vp), rowval.ctypes.data_as(vp), self.nq, self.nprod,
+                  self.pair_j.ctypes.data_as(vp), self.pair_k.ctypes.data_as(vp), self.seg_ptr.ctypes.data_as(vp), self.prod.ctypes.data_as(vp),
+                  lin_col.ctypes.data_as(vp), C.byref(nlin))
+        self.nlin = nlin.value
+        self.lin_col = lin_col[:self.nlin].copy()
+        _lib.call("pmt_sparse_gram_runs", self.seg_ptr.ctypes.data_as(vp), self.nq, int(cap), None, C.byref(nruns), None, C.byref(nlong))
+        self.runs, self.long_seg = np.zeros(2 * nruns.value, dtype=np.int64), np.zeros(nlong.value, dtype=np.int64)
+        _lib.call("pmt_sparse_gram_runs", self.seg_ptr.ctypes.data_as(vp), self.nq, int(cap), self.runs.ctypes.data_as(vp), C.byref(nruns),
+                  self.long_seg.ctypes.data_as(vp), C.byref(nlong))
+        self.nruns, self.nlong = nruns.value, nlong.value
+        # the linear terms, cut the same way: the non-empty columns lie back to back in CSC storage, so their first entries are a segment table
+        self.rowidx0 = np.ascontiguousarray(indices, dtype=np.uint32)
+        self.lin_seg = np.append(np.asarray(indptr, dtype=np.int64)[self.lin_col], np.int64(len(self.rowidx0)))
+        _lib.call("pmt_sparse_gram_runs", self.lin_seg.ctypes.data_as(vp), self.nlin, int(cap), None, C.byref(nruns), None, C.byref(nlong))
+        self.lin_runs, self.lin_long = np.zeros(2 * nruns.value, dtype=np.int64), np.zeros(nlong.value, dtype=np.int64)
+        _lib.call("pmt_sparse_gram_runs", self.lin_seg.ctypes.data_as(vp), self.nlin, int(cap), self.lin_runs.ctypes.data_as(vp), C.byref(nruns),
+                  self.lin_long.ctypes.data_as(vp), C.byref(nlong))
+        self.nlin_runs, self.nlin_long = nruns.value, nlong.value
+        self.dev = None
+        if ctx is not None:
+            self.dev = {k: ctx.upload_new(getattr(self, k)) for k in self.TABLES}
+
+    TABLES = ("prod", "seg_ptr", "pair_j", "pair_k", "runs", "long_seg", "lin_seg", "rowidx0", "lin_col", "lin_runs", "lin_long")
+
+    def call_args(self, rows, address=None):
+        """the pattern's arguments of pmt_sparse_gram_f64, between nzval and xvar (`address`: table name -> pointer; default: the device copies)"""
+        a = address or (lambda k: P(self.dev[k]))
+        return (a("prod"), a("seg_ptr"), a("pair_j"), a("pair_k"), self.nq, a("runs"), self.nruns, a("long_seg"), self.nlong,
+                a("lin_seg"), a("rowidx0"), a("lin_col"), self.nlin, a("lin_runs"), self.nlin_runs, a("lin_long"), self.nlin_long, int(rows))
+
 
 class DSparseAff(DAffVec):
     """C*x (+|-) d for a sparse C kept implicit; terms exist for the structural non-zeros only, in row-major order."""
@@ -580,6 +651,14 @@ class DSparseAff(DAffVec):
 
     def uniform(self):
         return False
+
+    def gram_operand(self):
+        """dot(r, r) of this residual has the canonical sparse form (csrc/sparse_gram.hip): x strictly increasing, a canonical-format
+        pattern, 32-bit positions"""
+        return self.xvars.strictly_increasing() and self.spmat.narrow and self.spmat.canonical_format()
+
+    def gram_tables(self):
+        return self.spmat.gram_tables(self.ctx)
 
     def require_terms(self):
         if not self.need_terms:
@@ -641,5 +720,5 @@ def fetch_f64(ctx, ptr, n):
     return out
 
 
-__all__ = ["DeviceContext", "DV", "DNum", "DVec", "DMat", "DVars", "DLinVec", "DAffVec", "DDenseAff", "DStackedAff", "DVarsAff", "DSpMat", "DSparseAff", "DAff", "DQuad",
+__all__ = ["DeviceContext", "DV", "DNum", "DVec", "DMat", "DVars", "DLinVec", "DAffVec", "DDenseAff", "DStackedAff", "DVarsAff", "DSpMat", "DSparseAff", "SparseGramTables", "DAff", "DQuad",
            "fetch_terms", "fetch_f64", "P", "LT", "QT", "VAT", "ArgumentError"]

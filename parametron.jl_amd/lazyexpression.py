@@ -648,6 +648,12 @@ def _rule_dot(model, ctx, x, y):                                                
             c.call("pmt_vecdot_affs_vars_f64", n, P(X.terms), X.row_len, P(X.consts), P(v.buf), 0, None, P(out.quad), P(out.lin))
         return DeviceNode(model, "vecdot!", ins, out, emit)
     if isinstance(dx, DAffVec) and isinstance(dy, DAffVec):                      # :702-709 over :548-576 (HOT LOOP 3)
+        if dx is dy and isinstance(dx, DSparseAff) and dx.gram_operand():
+            # dot(r, r), r = C*x (+|-) d with a sparse C: the canonical sparse objective (moi.quad_plan, csrc/sparse_gram.hip) reads the
+            # pattern's product list; the residual has ragged rows and therefore no literal form (_NoLiteralQuad)
+            lens = np.diff(dx.row_ptr)
+            out = _NoLiteralQuad(ctx, int(np.sum(lens * lens)), int(2 * np.sum(lens)))
+            return _with_lsq(DeviceNode(model, "vecdot!", ins, out, lambda c: None), [LsqTerm("block", r=dx)], bare=True)
         if not (dx.uniform() and dy.uniform()):
             raise ArgumentError("dot of two Vector{AffineFunction} needs rows of equal length on the device")
         nx, ny = dx.row_len, dy.row_len
@@ -671,6 +677,19 @@ def _rule_dot(model, ctx, x, y):                                                
             return _with_lsq(node, [LsqTerm("diag", xvars=dx.xvars, vec=dx.vec, sign=dx.sign)])          # dot(x (+|-) v, x (+|-) v)
         return node
     raise ArgumentError("dot(%s, %s) is not supported on the device" % (kind_of(dx), kind_of(dy)))
+
+
+class _NoLiteralQuad(DQuad):
+    """The deferred dest of dot(r, r) over a sparse residual: only the canonical objective consumes it.  Any literal consumer — expr(), a sum
+    with other terms, quadratic_mode="literal" — gets the error the literal rule gives for ragged rows.  (Next step: sums such as
+    dot(r, r) + lam * dot(x, x) over a sparse block, which need a combine over the sparse term list.)"""
+
+    def __init__(self, ctx, nq, nl):
+        super().__init__(ctx, nq, nl, alloc=False)
+
+    def materialize(self):
+        raise ArgumentError("dot of two Vector{AffineFunction} needs rows of equal length on the device (a sparse residual has no literal form: "
+                            "dot(r, r) alone is the canonical sparse objective; a sum or scaling over it is not built yet)")
 
 
 class _LazyRowTimesMatrix:

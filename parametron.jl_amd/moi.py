@@ -177,7 +177,7 @@ def _form_args(q, varmap_buf, alpha):                                    # the l
 
 class _Record:
     """Common part of Objective and Constraint (src/moi_interop.jl:113-129, 141-166)."""
-    mode = property(lambda self: self.plan.mode)                          # "literal" / "canonical" / "canonical-csc" / "-form" / "-sum" / "-groups"
+    mode = property(lambda self: self.plan.mode)                          # "literal" / "canonical" / "canonical-csc" / "-form" / "-sum" / "-groups" / "-sparse"
     lsq_terms = property(lambda self: self.plan.terms)                    # the LsqTerm list a "canonical-sum" record combines, or None
 
     def _setup(self, model, expr):
@@ -426,7 +426,25 @@ class _Record:
         return emit
 
     # the quadratic forms by plan.mode (quad_plan)
-    _QUAD_FORMS = {"literal": _compile_literal, "canonical": _compile_gram, "canonical-csc": _compile_gram, "canonical-form": _compile_form,
+    def _compile_sparse_gram(self, ctx, varmap_buf, handoff_varmap):
+        """dot(r, r), r = C*x (+|-) d with a sparse C (plan.gram, a DSparseAff): pmt_sparse_gram_f64 streams the pattern's product list
+        (DSpMat.gram_tables, built here once) and writes the canonical MOI function — one quadratic term per pair of columns sharing a row,
+        one linear term per non-empty column.  The index fields are static: they are written into the host arrays here, where the
+        hand-off's generic route finds them before the first update; the kernel rewrites them through varmap_buf at every call, so the
+        record follows the optimizer's index map like the dense forms."""
+        r = self.plan.gram
+        T = r.gram_tables()
+        self.f = f = ScalarQuadraticFunction(T.nlin, T.nq, alloc=ctx.pinned_array)
+        x = r.xvars.vars if handoff_varmap is None else np.asarray(handoff_varmap, dtype=np.int64)[r.xvars.vars - 1]
+        f.quadratic_terms["row"], f.quadratic_terms["col"], f.quadratic_terms["coeff"] = x[T.pair_j], x[T.pair_k], 0.0
+        f.affine_terms["var"], f.affine_terms["coeff"] = x[T.lin_col], 0.0
+        dq, dl, dc = self._twin(ctx, f.quadratic_terms, 24 * T.nq), self._twin(ctx, f.affine_terms, 16 * T.nlin), self._twin(ctx, self._cbuf, 8)
+        self.dev = {"quad": dq, "lin": dl, "const": dc}
+        vec = r.vec.buf if r.vec is not None else None
+        return lambda c: c.call("pmt_sparse_gram_f64", P(r.spmat.buf), *T.call_args(r.rows), P(r.xvars.buf), P(vec), r.sign if vec else 0, 1,
+                                P(varmap_buf), P(dq), P(dl), P(dc))
+
+    _QUAD_FORMS = {"canonical-sparse": _compile_sparse_gram, "literal": _compile_literal, "canonical": _compile_gram, "canonical-csc": _compile_gram, "canonical-form": _compile_form,
                    "canonical-sum": _compile_lsq_sum, "canonical-groups": _compile_groups}
 
     # ---- Vector{AffineFunction}
@@ -582,6 +600,8 @@ def _lsq_sum_combines(terms):
     holds at most PMT_LSQ_MAX_RUNS runs of positions)."""
     from . import _lib
     blocks = [t for t in terms or () if t.kind in ("block", "form")]
+    if any(isinstance(t.r, DSparseAff) for t in blocks):              # a sparse block in a sum: not built yet (the literal path then refuses it)
+        return False
     if len(terms or ()) > _lib.PMT_LSQ_MAX_TERMS or not 1 <= len(blocks) <= _lib.PMT_LSQ_MAX_BLOCKS or not blocks[0].r.xvars.strictly_increasing():
         return False
     x = blocks[0].r.xvars
@@ -661,10 +681,14 @@ def quad_plan(terms, bare, kind, nq, is_objective, quadratic_mode, small, handof
     """The QuadPlan of a record over a node described by (terms, bare) = DeviceNode.(lsq_sum, lsq_bare); no mode unless kind == "quad".  `nq`:
     the terms of its literal expansion; `small`: Model._small; `varmap`: the optimizer's index map when it is fixed before the plan is recorded
     (handoff "device" / "host_csc").  Host data only: nothing is allocated, no stacked matrix is asked for.  First match wins."""
+    one = terms[0] if bare and kind == "quad" else None
+    block = one.r if one is not None and one.kind == "block" else None
+    if isinstance(block, DSparseAff) and (quadratic_mode == "literal" or handoff == "host_csc"):
+        raise ArgumentError("dot(r, r) of a sparse residual C*x (+|-) d has the canonical sparse form only: %s is not available for it "
+                            "(use quadratic_mode 'auto' or 'canonical' with handoff 'moi' or 'device')"
+                            % ("quadratic_mode='literal'" if quadratic_mode == "literal" else "handoff='host_csc'"))
     if kind != "quad" or quadratic_mode == "literal":
         return QuadPlan("literal" if kind == "quad" else None)
-    one = terms[0] if bare else None
-    block = one.r if bare and one.kind == "block" else None
 
     def ordered(x):                       # x keeps its order under the index map fixed early
         return handoff in ("device", "host_csc") and bool(np.all(np.diff(varmap[x.vars - 1]) > 0))
@@ -673,6 +697,10 @@ def quad_plan(terms, bare, kind, nq, is_objective, quadratic_mode, small, handof
     # dot(r, r), r = A*x (+|-) b over a strictly increasing x: the Gram node, in any record and any model — asked for, or ("auto") above 2^24 terms
     if isinstance(block, DDenseAff) and block.xvars.strictly_increasing() and (quadratic_mode == "canonical" or nq > (1 << 24)):
         return gram_plan(block)
+    # dot(r, r), r = C*x (+|-) d with a sparse C: the sparse Gram node, in "auto" too (a ragged residual has no literal alternative), for the MOI
+    # boundary and the device hand-off, in small models and beyond
+    if isinstance(block, DSparseAff):
+        return QuadPlan("canonical-sparse", gram=block)
     if quadratic_mode == "auto":
         return QuadPlan("literal")
     if not small:
