@@ -200,3 +200,72 @@ def run_sum_wave(values, skip_empty):
                 lanes[i] = other if lanes[i] is None else lanes[i] + other
         off //= 2
     return lanes[0]
+
+
+class Plan:
+    """a plan through the C ABI (include/parametron_hip.h): `with plan:` records what is called on plan.rec; update() replays it"""
+
+    def __init__(self):
+        lib()
+        self.plan = C.c_void_p()
+        call("pmt_plan_create", 0, stream(), C.byref(self.plan))
+        self.rec = C.c_void_p(lib().pmt_plan_recording_stream(self.plan))
+
+    def __enter__(self):
+        call("pmt_plan_begin_record", self.plan)
+        return self
+
+    def __exit__(self, *a):
+        call("pmt_plan_end_record", self.plan)
+
+    def fused(self):
+        gr, n, ln = C.c_int(), C.c_int(), C.c_int64()
+        call("pmt_plan_fused", self.plan, C.byref(gr), C.byref(n), C.byref(ln))
+        return gr.value, n.value, ln.value
+
+    def update(self):
+        call("pmt_plan_update", self.plan)
+
+    def fusion(self, on):
+        call("pmt_plan_set_fusion", self.plan, 1 if on else 0)
+
+    def close(self):
+        torch.cuda.synchronize()
+        call("pmt_plan_destroy", self.plan)
+
+
+GUARD_WORDS = 4
+POISON_WORD = -7                                                   # what empty_terms fills with; empty_f64 fills with NaN
+
+
+class Guarded:
+    """An output of `nwords` 8-byte words that a kernel owns, inside a larger poisoned buffer: GUARD_WORDS words in front of it and behind it
+    (-7 for term words, NaN for doubles, as empty_terms / empty_f64).  shift = 0 puts its first word on a 16-byte boundary, shift = 1 one
+    8-byte word behind one.  check(want) compares the WHOLE buffer image bit for bit: `want` is the expected content of the owned words
+    (leading-dimension padding inside it holds the poison, see padding()), the guards must still hold the poison."""
+
+    def __init__(self, nwords, doubles=False, shift=0):
+        self.n, self.doubles, self.off = int(nwords), doubles, GUARD_WORDS + shift
+        total = self.off + self.n + GUARD_WORDS
+        self.buf = empty_f64(total) if doubles else torch.full((total,), POISON_WORD, dtype=torch.int64, device=DEV)
+        assert (self.buf.data_ptr() + 8 * self.off) % 16 == 8 * shift
+
+    def ptr(self):
+        return C.c_void_p(self.buf.data_ptr() + 8 * self.off)
+
+    def padding(self, shape):
+        """an array of `shape` holding this buffer's poison, for the caller to place the expected values in"""
+        return np.full(shape, np.nan) if self.doubles else np.full(shape, POISON_WORD, dtype=np.int64)
+
+    def check(self, want, what=""):
+        want = np.ascontiguousarray(want)
+        assert want.nbytes == 8 * self.n, (what, want.nbytes, 8 * self.n)
+        torch.cuda.synchronize()
+        got = self.buf.cpu().numpy().view(np.int64)
+        image = self.padding(len(got)).view(np.int64)
+        image[self.off:self.off + self.n] = want.reshape(-1).view(np.int64)
+        if not np.array_equal(got, image):
+            bad = np.flatnonzero(got != image)
+            k = int(bad[0])
+            where = "front guard" if k < self.off else ("back guard" if k >= self.off + self.n else "owned word %d of %d" % (k - self.off, self.n))
+            raise AssertionError("%s: %d words differ, the first at %s: got %#018x, want %#018x" % (what, len(bad), where, int(got[k]) % 2 ** 64, int(image[k]) % 2 ** 64))

@@ -16,36 +16,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 
-class Plan:
-    def __init__(self):
-        import gpu_util as g
-        g.lib()
-        self.g = g
-        self.plan = C.c_void_p()
-        g.call("pmt_plan_create", 0, g.stream(), C.byref(self.plan))
-        self.rec = C.c_void_p(g.lib().pmt_plan_recording_stream(self.plan))
-
-    def __enter__(self):
-        self.g.call("pmt_plan_begin_record", self.plan)
-        return self
-
-    def __exit__(self, *a):
-        self.g.call("pmt_plan_end_record", self.plan)
-
-    def fused(self):
-        gr, n, ln = C.c_int(), C.c_int(), C.c_int64()
-        self.g.call("pmt_plan_fused", self.plan, C.byref(gr), C.byref(n), C.byref(ln))
-        return gr.value, n.value, ln.value
-
-    def update(self):
-        self.g.call("pmt_plan_update", self.plan)
-
-    def fusion(self, on):
-        self.g.call("pmt_plan_set_fusion", self.plan, 1 if on else 0)
-
-    def close(self):
-        torch.cuda.synchronize()
-        self.g.call("pmt_plan_destroy", self.plan)
+from gpu_util import Plan  # noqa: E402
 
 
 def test_config1_update_is_one_launch_and_matches_golden_and_oracle():
