@@ -362,13 +362,17 @@ static int fork_side(SideStream *side, hipStream_t s) {
     PMT_HIP_CHECK(hipStreamWaitEvent(side->stream, side->fork, 0));
     return PMT_OK;
 }
+// ... which a fused or one-launch node needs only in a replay that puts work on the side stream (SideStream::side_work).  In a tape of
+// lane-0 entries alone (config 2: the node, then the constraint pack) the event behind the node orders nothing, and the runtime still
+// holds the next launch on `s` back for it: 7.5 us between the node and the pack (profiles/r14_item_boundaries.txt)
+static bool forks_in_replay(const SideStream *side) { return side && side->in_replay && side->side_work; }
 
 // Fused: the diagonal tiles, q and c'c in ONE pass over A (gram_tall.hip), then the strictly upper tiles in ONE ranged launch of the stream-K
 // kernel (SKArgs::strict; the partials of both share the workspace in stream order) — no side stream, no separate reductions
 static int fused_node(const GramArgs &g, SideStream *side, hipStream_t s) {
     int rc = launch_gram_tall(g.A, g.lda, g.rows, g.cols, g.xvar, g.b, g.sign, g.moi, g.varmap, g.out_quad, g.out_csc, g.alpha, g.out_lin,
                               g.out_const, g.workspace, s);
-    if (!rc && side && side->in_replay) rc = fork_side(side, s);          // (the strictly upper tiles then run beside those entries)
+    if (!rc && forks_in_replay(side)) rc = fork_side(side, s);          // (the strictly upper tiles then run beside those entries)
     const int64_t nt = cdiv(g.cols, ST);
     if (!rc && nt > 1)
         rc = launch_gram_sk(g.A, g.lda, g.rows, g.cols, g.xvar, g.varmap, g.moi, g.out_quad, g.out_csc, g.alpha, g.workspace, 0, 0, nt * (nt - 1) / 2,
@@ -382,7 +386,7 @@ static int mid_node(const GramArgs &g, SideStream *side, hipStream_t s) {
                 "quad_gram: no auxiliary state for this stream");
     int rc = launch_gram_mid(g.A, g.lda, g.rows, g.cols, g.xvar, g.b, g.sign, g.moi, g.varmap, g.out_quad, g.out_csc, g.alpha, g.out_lin,
                              g.out_const, g.workspace, reinterpret_cast<unsigned *>(static_cast<char *>(side->counters) + MID_OFFSET), s);
-    return !rc && side->in_replay ? fork_side(side, s) : rc;
+    return !rc && forks_in_replay(side) ? fork_side(side, s) : rc;
 }
 
 // StreamK: the contraction on `s`, q = 2 A'c and c'c on the side stream; staged: stage by stage (deliver_plan), releasing band groups
@@ -391,6 +395,7 @@ static int stream_k_node(const GramArgs &g, bool staged, const DeliverPlan &d, S
     // the MFMA-bound contraction owns the main stream; join before returning control of `s`.  Legal under stream capture.
     hipStream_t s2 = side ? side->stream : s;
     if (side) { if (int rc = fork_side(side, s)) return rc; }
+    if (side && side->in_replay) side->side_work = true;          // (a fused or one-launch node later in the tape forks as before)
     const int64_t rows = g.rows, cols = g.cols;
     int rc = PMT_OK;
     double *scratch = g.workspace ? reinterpret_cast<double *>(static_cast<char *>(g.workspace) + gram_sk_workspace_bytes(rows, cols)) : nullptr;

@@ -61,14 +61,32 @@
 #endif
 
 #ifdef PMT_MID_TRACE
-// debugging aid (tools/mid_trace.py): 100 MHz wall-clock stamps of the phases of every workgroup
+// debugging aid (tools/mid_trace.py): 100 MHz wall-clock stamps of the phases of every workgroup (of its LAST item where it walks several)
 __device__ unsigned long long g_mid_trace[1024 * 8];
-#define MID_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x < 1024) g_mid_trace[blockIdx.x * 8 + (k)] = wall_clock64(); } while (0)
+// ... and (tools/mid_walk_trace.py) per workgroup of the persistent walk, summed over its items in eight words of LDS behind the kernel's
+// own (mid_walk_note) and written out when it leaves: [0] items, [1] main loops, [2] stamp 1 -> 3 / 5 (the waves' sums, the count, a fold), [3] epilogues,
+// [4] from one item's last store to the next one's start, [5] the first item's start, [6] the last item's end, [7] the time it left
+__device__ unsigned long long g_mid_walk[1024 * 8];
+#define MID_TRACE_WORDS 8
+__device__ __forceinline__ void mid_walk_note(unsigned long long *w, int k, unsigned long long t) {
+    if (k == 0) { if (w[0]) w[4] += t - w[7]; else w[5] = t; w[0] += 1; }
+    else if (k == 1) w[1] += t - w[7];
+    else if (k == 3 || k == 5) { w[2] += t - w[7]; w[6] = t; }          // (3: a split tile's chunk that is not the last to arrive ends here)
+    else if (k == 6) { w[3] += t - w[7]; w[6] = t; }
+    else return;
+    w[7] = t;
+}
+#define MID_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x < 1024) { const unsigned long long t_ = wall_clock64(); g_mid_trace[blockIdx.x * 8 + (k)] = t_; \
+                          mid_walk_note(reinterpret_cast<unsigned long long *>(sh + MSH), (k), t_); } } while (0)
 extern "C" int pmt_mid_trace_read(unsigned long long *host) {
     return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_mid_trace), sizeof(unsigned long long) * 1024 * 8) == hipSuccess ? 0 : 1;
 }
+extern "C" int pmt_mid_walk_read(unsigned long long *host) {
+    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_mid_walk), sizeof(unsigned long long) * 1024 * 8) == hipSuccess ? 0 : 1;
+}
 #else
 #define MID_STAMP(k) do { } while (0)
+#define MID_TRACE_WORDS 0
 #endif
 
 namespace pmt {
@@ -299,15 +317,18 @@ __device__ __forceinline__ void mid_compute(double *__restrict__ rot, const f64x
 //   * loads in the scalar-base form (the lane offset passes through an empty asm: nothing to hoist).
 // Every accumulator sees the same operations in the same order as in mid_compute (x before y of each group): the same bits.
 #define MID_SB() __builtin_amdgcn_sched_barrier(0)
+// The reloads take TWO scalar bases, one for the four A-side operands and one for the four B-side ones: both g.A + next_row0 inside an
+// item; in the round that ends an item of the persistent walk, the bases of the NEXT item's tile (mid_body) — the lane offsets of two
+// whole panels differ by a multiple of the pitch, so the redirect is a scalar select and the stream keeps its instructions.
 template <bool DIAG>
-__device__ __forceinline__ void mid_step(const MidArgs &g, double *__restrict__ rot, int64_t next_row0, unsigned (&voff)[DIAG ? 4 : 8],
-                                         f64x2 (&buf)[DIAG ? 4 : 8], f64x2 &cb, int sign, int lane, double (&acc)[MACC], double (&qacc)[4]) {
+__device__ __forceinline__ void mid_step(const MidArgs &g, double *__restrict__ rot, int64_t next_row0, const char *base_a, const char *base_b,
+                                         unsigned (&voff)[DIAG ? 4 : 8], f64x2 (&buf)[DIAG ? 4 : 8], f64x2 &cb, int sign, int lane,
+                                         double (&acc)[MACC], double (&qacc)[4]) {
     constexpr int BO = DIAG ? 0 : 4;
     const int lm = lane & 15, lrow = lane & 48, lk = lane >> 4;
-    const char *base = reinterpret_cast<const char *>(g.A + next_row0);
     auto reload = [&](int t) {
         asm volatile("" : "+v"(voff[t]));
-        buf[t] = *reinterpret_cast<const f64x2 *>(base + voff[t]);
+        buf[t] = *reinterpret_cast<const f64x2 *>((t < 4 ? base_a : base_b) + voff[t]);
     };
     f64x2 bv[4][4];
 #pragma unroll
@@ -581,10 +602,41 @@ __device__ __forceinline__ void mid_fold(const double *p, int count, int64_t str
     }
 }
 
+// What the persistent walk (gram_mid_kernel) knows one item ahead while an item runs; wave-uniform, all false elsewhere.
+struct MidWalk {
+    bool early;                  // the item in hand belongs to the unsplit body: the ticket behind it is drawn under this item's tail
+    unsigned *ticket; int id0;   // ... from this word: id = id0 + 8 * its old value
+    int *slot;                   // ... and travels to the other waves through this word of LDS at the barrier in front of the epilogue
+    int drawn;                   // out: that id
+    bool next_full; int njb, nkb, nrank;      // the item in hand (an unsplit strictly upper tile): two whole panels; its tile and place in the walk
+    bool pre;                    // in: this wave's first PMT_MID_D groups are in buf already (the previous item loaded them); out: the next item's are
+};
+
+// nothing of `buf` is needed from here on: the registers are free up to the next loads (an empty definition, no instruction) — on the
+// paths that never carry loaded groups into the next item (split tiles, diagonal tiles) they do not count against the fold's budget
+template <int N>
+__device__ __forceinline__ void mid_forget(f64x2 (&buf)[PMT_MID_D][N]) {
+#pragma unroll
+    for (int d = 0; d < PMT_MID_D; ++d)
+#pragma unroll
+        for (int t = 0; t < N; ++t) asm volatile("" : "=v"(buf[d][t].x), "=v"(buf[d][t].y));
+}
+
+template <bool DIAG>
+__device__ __forceinline__ auto &mid_buf(f64x2 (&own)[PMT_MID_D][4], f64x2 (&walk)[PMT_MID_D][8]) {
+    if constexpr (DIAG) return own; else return walk;
+}
+
+// `pbuf`: the operand registers of the strictly upper tiles live in the kernel — in the persistent walk they carry the next item's first
+// groups from one item into the next (wk.pre)
 template <bool DIAG, bool FAST>
-__device__ __forceinline__ void mid_body(const MidArgs &g, double *sh, int tid, int jb, int kb, int chunk, int nchunk, int gpc, int first_wg, unsigned *counter) {
+__device__ __forceinline__ void mid_body(const MidArgs &g, double *sh, int tid, int jb, int kb, int chunk, int nchunk, int gpc, int first_wg, unsigned *counter,
+                                         MidWalk &wk, f64x2 (&pbuf)[PMT_MID_D][8]) {
     constexpr int NG = DIAG ? 4 : 8;
     constexpr int D = PMT_MID_D;
+    // (what depends on the thread alone is worked out again per item: kept across the walk's loop, with the operand registers now living
+    // there too, these values no longer fit the register file)
+    asm volatile("" : "+v"(tid));
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lm = lane & 15, lk = lane >> 4;
@@ -605,11 +657,29 @@ __device__ __forceinline__ void mid_body(const MidArgs &g, double *sh, int tid, 
 #pragma unroll
     for (int t = 0; t < NG; ++t) voff[t] = (unsigned)((min((t < 4 ? cj0 : ck0) + 16 * (t & 3) + lm, g.cols - 1) * g.lda + 2 * lk) * 8);
     double *rot = sh + wave * 512;
-    f64x2 buf[D][NG], cb[D];
+    f64x2 dbuf[D][4], cb[D];
+    auto &buf = mid_buf<DIAG>(dbuf, pbuf);
     auto row_of = [&](int s) { return (int64_t)(g0 + 4 * min(s, max(nfast - 1, 0))) * 8; };
+    // The persistent walk: the last whole round of this item loads the first D groups of the item in hand instead of repeating the last
+    // group.  Both items are unsplit strictly upper tiles of whole panels, so the next item gives this wave the same groups g0, g0 + 4, ..
+    // (nfast of them: at least D), and its lane offsets are these plus (its first column - this one's) * pitch, per side: every address
+    // is one the next item's own first loads would read.  No leftover group and no ragged one, which would need buf[] behind the loop.
+    const bool pre = !DIAG && wk.pre;
+    bool pf = false;
+    if (!DIAG && FAST) pf = wk.early && wk.next_full && nchunk == 1 && !ragged && nfast > 0 && nfast % D == 0 && (int64_t)(kb + 1) * MT <= g.cols;
+    const int ahead_at = __builtin_amdgcn_readfirstlane(pf ? nfast - D : -1);          // (a scalar: the loop compares it without a vector instruction)
+    const int64_t shift_a = pf ? ((int64_t)wk.njb * MT - cj0) * g.lda * 8 : 0, shift_b = pf ? ((int64_t)wk.nkb * MT - ck0) * g.lda * 8 : 0;
     if (nfast > 0) {
+        if (!pre) {
+            // (group by group, as the loop issues them: the loop's vmcnt waits are the stricter of what this order and the loop's own
+            // demand — with the groups' loads interleaved here, every round waited for all but one load of the group behind)
 #pragma unroll
-        for (int d = 0; d < D; ++d) mid_load<DIAG, FAST>(g, row_of(d), lane, cj0, ck0, voff, buf[d], cb[d]);
+            for (int d = 0; d < D; ++d) {
+                __builtin_amdgcn_sched_barrier(0);
+                mid_load<DIAG, FAST>(g, row_of(d), lane, cj0, ck0, voff, buf[d], cb[d]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
         // FAST: the pinned stream; mid_compute + mid_load with scheduling barriers between the phases, which it replaced there (37.3 -> 34.3 us
         // at 4096 x 512, 1250 -> 1189 at 65536 x 1024 — profiles/r06_gram_mid.txt), still serve the bounds-checked path and the leftovers
         if (FAST) {
@@ -617,8 +687,13 @@ __device__ __forceinline__ void mid_body(const MidArgs &g, double *sh, int tid, 
             // loads": the number of loads in flight must not depend on the path); the loads beyond the last group repeat the last group
             int s0 = 0;
             for (; s0 + D <= nfast; s0 += D) {
+                const bool ahead = s0 == ahead_at;
 #pragma unroll
-                for (int d = 0; d < D; ++d) mid_step<DIAG>(g, rot, row_of(s0 + d + D), voff, buf[d], cb[d], g.sign, lane, acc, qacc);
+                for (int d = 0; d < D; ++d) {
+                    const int64_t row = ahead ? row_of(d) : row_of(s0 + d + D);
+                    const char *base = reinterpret_cast<const char *>(g.A + row);
+                    mid_step<DIAG>(g, rot, row, base + (ahead ? shift_a : 0), base + (ahead ? shift_b : 0), voff, buf[d], cb[d], g.sign, lane, acc, qacc);
+                }
             }
 #pragma unroll
             for (int d = 0; d < D - 1; ++d)
@@ -639,6 +714,11 @@ __device__ __forceinline__ void mid_body(const MidArgs &g, double *sh, int tid, 
     }
 
     MID_STAMP(1);
+    wk.pre = pf;
+    // the ticket behind the item in hand: asked for here, where only the tail's LDS traffic and the epilogue's stores follow it (behind
+    // this item's loads, the next item's included); looked at in front of the epilogue
+    unsigned drawn = 0;
+    if (!DIAG && wk.early && tid == 0) drawn = __hip_atomic_fetch_add(wk.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     unsigned *flag = reinterpret_cast<unsigned *>(sh + MFLAG);
     double *w = g.ws + (int64_t)(first_wg + chunk) * MSTRIDE;
     __syncthreads();                                               // every wave is done with its rotation piece
@@ -660,7 +740,7 @@ __device__ __forceinline__ void mid_body(const MidArgs &g, double *sh, int tid, 
         if (tid == 0) *flag = __hip_atomic_fetch_add(c1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __syncthreads();
         MID_STAMP(3);
-        if (*flag != (unsigned)(n1 - 1)) return;                   // (workgroup-uniform) not the last one of this tile / group
+        if (*flag != (unsigned)(n1 - 1)) { mid_forget(buf); return; }          // (workgroup-uniform) not the last one of this tile / group
 #if PMT_MID_FORMAL
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 #endif
@@ -681,7 +761,7 @@ __device__ __forceinline__ void mid_body(const MidArgs &g, double *sh, int tid, 
             if (tid == 0) *flag = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __syncthreads();
             const int ng = (nchunk + MFG - 1) / MFG;
-            if (*flag != (unsigned)(ng - 1)) return;
+            if (*flag != (unsigned)(ng - 1)) { mid_forget(buf); return; }
 #if PMT_MID_FORMAL
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 #endif
@@ -699,8 +779,11 @@ __device__ __forceinline__ void mid_body(const MidArgs &g, double *sh, int tid, 
             sh[row * MPITCH + col] = sum[u];
         }
         if (DIAG && tid < MT) sh[MT * MPITCH + tid] = qs;
+        mid_forget(buf);
     }
+    if (!DIAG && wk.early && tid == 0) *wk.slot = wk.id0 + 8 * (int)drawn;
     __syncthreads();
+    if (!DIAG && wk.early) wk.drawn = *wk.slot;
     MID_STAMP(5);
     mid_epilogue(g, sh, tid, jb, kb);
 #ifdef PMT_MID_TRACE
@@ -743,13 +826,14 @@ __device__ __forceinline__ void mid_tile_of(int t, int nb, int &jb, int &kb) {
 }
 
 // one work item of the launch: (tile, chunk) number `id`, or the constant's (the last one)
-template <bool FAST>
-__device__ __forceinline__ void mid_item(const MidArgs &g, double *sh, int tid, int id) {
+struct MidItem { int kind, jb, kb, chunk, nch, gpc, first, rank; };          // kind: 0 a strictly upper tile, 1 a diagonal one, 2 the constant
+__device__ __forceinline__ MidItem mid_decode(const MidArgs &g, int id) {
     // XCD-aware order: workgroup ids go round-robin over the 8 XCDs (id % 8), each with its own 4 MB L2.  The (chunk, tile) list is walked
     // CHUNK-major and cut into 8 contiguous pieces, one per XCD: the 32 workgroups an XCD runs at a time work on the same rows of A and
     // on neighbouring tiles (shared 64-column panels), so a matrix larger than one L2 is still read mostly out of L2 — numbered tile-major
     // (id = tile * S + chunk) every XCD touched every row chunk of every panel and 4096 x 1024 ran out of the Infinity Cache at 1.76 us per
     // 8-row group instead of 1.15 (profiles/r06_gram_mid.txt).
+    MidItem it = {2, 0, 0, 0, 1, 0, 0, 0};
     const int nbody = g.n_off - g.n_tail, wbody = nbody * g.s_off, noff = wbody + g.n_tail * g.s_tail;
     if (id < noff) {
         // body tiles (ranks 0 .. nbody - 1 of the walk) in s_off chunks, then the tail tiles in s_tail chunks: chunk-major inside each part
@@ -765,17 +849,29 @@ __device__ __forceinline__ void mid_item(const MidArgs &g, double *sh, int tid, 
             while (t >= kb) { t -= kb; ++kb; }                     // strictly upper tiles, column by column: (0,1), (0,2), (1,2), (0,3), ..
             jb = t;
         }
-        const int first = tail ? wbody + (rank - nbody) * g.s_tail : rank * g.s_off;
-        mid_body<false, FAST>(g, sh, tid, jb, kb, chunk, nch, tail ? g.gpc_tail : g.gpc_off, first, g.counters + rank * MCNT);
-        return;
+        it.kind = 0; it.jb = jb; it.kb = kb; it.chunk = chunk; it.nch = nch; it.gpc = tail ? g.gpc_tail : g.gpc_off;
+        it.first = tail ? wbody + (rank - nbody) * g.s_tail : rank * g.s_off;
+        it.rank = rank;
+        return it;
     }
     if (id < noff + g.nb * g.s_diag) {
         const int k = g.xcd ? mid_xcd_rank(id, noff, g.nb * g.s_diag) : ((id - noff) % g.s_diag) * g.nb + (id - noff) / g.s_diag;
         const int chunk = k / g.nb, jb = k - chunk * g.nb;
-        mid_body<true, FAST>(g, sh, tid, jb, jb, chunk, g.s_diag, g.gpc_diag, noff + jb * g.s_diag, g.counters + (g.n_off + jb) * MCNT);
+        it.kind = 1; it.jb = jb; it.kb = jb; it.chunk = chunk; it.nch = g.s_diag; it.gpc = g.gpc_diag; it.first = noff + jb * g.s_diag; it.rank = g.n_off + jb;
+    }
+    return it;
+}
+
+template <bool FAST>
+__device__ __forceinline__ void mid_item(const MidArgs &g, double *sh, int tid, const MidItem &it, MidWalk &wk, f64x2 (&pbuf)[PMT_MID_D][8]) {
+    if (it.kind == 0) {
+        mid_body<false, FAST>(g, sh, tid, it.jb, it.kb, it.chunk, it.nch, it.gpc, it.first, g.counters + it.rank * MCNT, wk, pbuf);
         return;
     }
-    mid_constant(g, sh, tid);
+    wk.pre = false;
+    if (it.kind == 1) mid_body<true, FAST>(g, sh, tid, it.jb, it.kb, it.chunk, it.nch, it.gpc, it.first, g.counters + it.rank * MCNT, wk, pbuf);
+    else mid_constant(g, sh, tid);
+    mid_forget(pbuf);
 }
 
 // A launch of more than PMT_MID_G work items runs PERSISTENT (round 6c): PMT_MID_G workgroups, each walking items until none is left,
@@ -783,23 +879,65 @@ __device__ __forceinline__ void mid_item(const MidArgs &g, double *sh, int tid, 
 // next: tools/mid_trace.py, 8 times per CU at config 2); in a loop the next item's loads go out while the stores of the last drain.  The
 // items keep their XCD: a workgroup with blockIdx % 8 = x takes the ids x, x + 8, x + 16, .. in order through ticket word x (what the
 // hardware's round-robin over the XCDs gives a launch of one workgroup per item).  Nobody waits for anybody; the last workgroup to leave
-// re-arms the tickets.
+// re-arms the tickets.  (Workgroups of an XCD that has run dry taking the other XCDs' items: measured, 7 us slower at config 2 —
+// profiles/r14_item_boundaries.txt.)
+// On the fast load path, in the unsplit body (s_off = 1: config 2's 2016 tiles) a workgroup holds ONE ticket in hand: the item after the
+// one it runs is known while that one's main loop runs, so the loop's last round loads the next item's first groups (mid_body) and the
+// ticket behind it is drawn under the tail — between two items stands one barrier instead of a ticket's round trip between two barriers
+// and the first loads' latency.  The look-ahead stops with the body: from the first id in hand that lies in the split tails or the
+// diagonal chunks on, a workgroup draws on demand, so nobody sits on a short item while others run dry.
 template <bool FAST>
 __global__ __launch_bounds__(256, PMT_MID_WPS) void gram_mid_kernel(MidArgs g) {
-    __shared__ double sh[MSH];
-    __shared__ int next_id;
+    __shared__ double sh[MSH + MID_TRACE_WORDS];
+    __shared__ int next_id, ahead_id;
     const int tid = threadIdx.x;
     const int x = blockIdx.x & 7, per = gridDim.x >> 3;
-    int id = blockIdx.x;
+#ifdef PMT_MID_TRACE
+    if (tid == 0) for (int i = 0; i < MID_TRACE_WORDS; ++i) reinterpret_cast<unsigned long long *>(sh + MSH)[i] = 0;
+#endif
+    f64x2 pbuf[PMT_MID_D][8];
+    MidWalk wk = {};
+    wk.ticket = g.tickets + x; wk.id0 = x + 8 * per; wk.slot = &ahead_id;
+    const int wbody = (g.n_off - g.n_tail) * g.s_off;
+    const bool look = FAST && g.persist && g.s_off == 1;
+    int id = blockIdx.x, hand = -1;                                // `hand`: the id behind `id`, once drawn
+    if (look) {
+        if (tid == 0) next_id = wk.id0 + 8 * (int)__hip_atomic_fetch_add(wk.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        hand = next_id;
+    }
+    MidItem cur = mid_decode(g, id);
     for (;;) {
-        mid_item<FAST>(g, sh, tid, id);
+        wk.early = hand >= 0 && hand < wbody;                      // (ids ascend: id is a body item as well; s_off = 1: both are unsplit)
+        wk.next_full = false;
+        if (wk.early) {
+            const MidItem nx = mid_decode(g, hand);
+            wk.next_full = (int64_t)(nx.kb + 1) * MT <= g.cols;
+            wk.njb = nx.jb; wk.nkb = nx.kb; wk.nrank = nx.rank;
+        }
+        mid_item<FAST>(g, sh, tid, cur, wk, pbuf);
         if (!g.persist) return;                                    // (one workgroup per item)
         __syncthreads();                                           // the item's last LDS reads, and next_id's last readers
-        if (tid == 0) next_id = x + 8 * (per + (int)__hip_atomic_fetch_add(g.tickets + x, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        __syncthreads();
-        id = next_id;
+        if (wk.early) {
+            id = hand; hand = wk.drawn;
+            cur.jb = wk.njb; cur.kb = wk.nkb; cur.first = cur.rank = wk.nrank;          // (an unsplit body item like `cur`: kind, chunk, nch, gpc stay)
+            continue;
+        }
+        if (hand >= 0) { id = hand; hand = -1; }
+        else {
+            if (tid == 0) next_id = wk.id0 + 8 * (int)__hip_atomic_fetch_add(wk.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __syncthreads();
+            id = next_id;
+        }
         if (id >= g.total) break;
+        cur = mid_decode(g, id);
     }
+#ifdef PMT_MID_TRACE
+    if (tid == 0 && blockIdx.x < 1024) {
+        for (int i = 0; i < 7; ++i) g_mid_walk[blockIdx.x * 8 + i] = reinterpret_cast<unsigned long long *>(sh + MSH)[i];
+        g_mid_walk[blockIdx.x * 8 + 7] = wall_clock64();
+    }
+#endif
     if (tid == 0) {
         const unsigned gone = __hip_atomic_fetch_add(g.tickets + 8, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (gone == gridDim.x - 1) {

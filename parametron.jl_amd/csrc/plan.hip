@@ -775,11 +775,11 @@ static int replay(pmt_plan *plan, hipStream_t s) {
     // copies of the previous re-evaluation that are still on the fetch stream read buffers this one is about to overwrite
     if (!plan->fetch_events.empty())
         if (int rc = pmt::fetch_fence(s)) return rc;
-    pmt::replay_begin(s);
-    struct End { hipStream_t s; int rc = PMT_OK; bool done = false; int finish() { if (!done) { done = true; rc = pmt::replay_end(s); } return rc; } ~End() { finish(); } } end{s};
-    hipStream_t side = nullptr;
     bool any = false;
     for (char l : plan->exec_lanes) any |= (l != 0);
+    pmt::replay_begin(s, any);
+    struct End { hipStream_t s; int rc = PMT_OK; bool done = false; int finish() { if (!done) { done = true; rc = pmt::replay_end(s); } return rc; } ~End() { finish(); } } end{s};
+    hipStream_t side = nullptr;
     if (any && (side = pmt::side_stream_of(s))) {
         if (!plan->lane_fork) {
             PMT_HIP_CHECK(hipEventCreateWithFlags(&plan->lane_fork, hipEventDisableTiming));

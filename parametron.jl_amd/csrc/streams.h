@@ -27,6 +27,7 @@ struct SideStream {
     std::vector<std::pair<dma::Engine *, dma::Signal>> dma_pending;     // completion signals of copy-engine transfers in flight
     std::vector<std::shared_ptr<void>> keepalive;                        // ... and the owners of their signals (an immediate call's go with the call)
     bool in_replay = false;                                              // a plan's tape is being replayed: P's transfers are submitted at its end
+    bool side_work = false;                                              // ... and it puts work on `stream`: side-lane entries, or a stream-K node's reductions
     std::vector<std::function<int()>> deferred;
 };
 constexpr int ERR_COURIER = 1, ERR_PAIR_FOLD = 2;
@@ -47,7 +48,7 @@ void release_side_stream(hipStream_t s);
 int fetch_async(hipStream_t s, hipStream_t after, hipEvent_t order_event, void *host_dst, const void *device_src, size_t bytes, FetchState *st, FetchRect r);
 int fetch_fence(hipStream_t s);
 int fetch_synchronize(hipStream_t s);
-void replay_begin(hipStream_t s);
+void replay_begin(hipStream_t s, bool side_work);      // side_work: the tape has side-lane entries (plan.hip: replay)
 int replay_end(hipStream_t s);
 // at replay time: run `f` on `s` behind the work a plan's replay has deferred to its end on `s`, or now
 int gram_after_deferred(hipStream_t s, std::function<int()> f);

@@ -211,16 +211,17 @@ int fetch_fence(hipStream_t s) {
 }
 
 // a plan's replay brackets its tape with these: transfers that should queue up behind the tape's own are submitted by replay_end
-void replay_begin(hipStream_t s) {
+void replay_begin(hipStream_t s, bool side_work) {
 #ifdef PMT_TUNING
     g_replay_t0 = host_us();
 #endif
-    if (SideStream *ss = find_side(s)) ss->in_replay = true;
+    if (SideStream *ss = find_side(s)) { ss->in_replay = true; ss->side_work = side_work; }
 }
 int replay_end(hipStream_t s) {
     SideStream *ss = find_side(s);
     if (!ss) return PMT_OK;
     ss->in_replay = false;
+    ss->side_work = false;
     int rc = PMT_OK;
     for (auto &f : ss->deferred) { const int r = f(); if (r && !rc) rc = r; }
     ss->deferred.clear();
