@@ -791,6 +791,33 @@ int64_t pmt_plan_tape_length(const pmt_plan *plan);
  *   pmt_plan_fused       number of fused runs, tape entries they replace, and launches-or-entries one replay executes */
 int pmt_plan_set_fusion(pmt_plan *plan, int on);
 int pmt_plan_fused(const pmt_plan *plan, int *groups, int *nodes, int64_t *exec_length);
+/* RIDERS.  The one-launch form of pmt_quad_gram_f64 / _csc (2049 .. 4096 columns and the wide shapes below; csrc/gram_mid.hip) runs, from
+ * 512 work items on, as 256 persistent workgroups that hold every CU until they leave, and a workgroup's last item ends tens of
+ * microseconds before the launch does.  pmt_plan_end_record lets dense constraint packs of the tape (pmt_affine_pack_vector_f64 with rows,
+ * cols > 0) RIDE in such a node that delivers nothing to the host: a workgroup whose Gram items have run out draws the packs' tiles — the
+ * stand-alone kernel's own tile body, so the pack's output is bit-identical — and the pack's entry leaves the replay.  Who rides:
+ *   (a) the packs of the unbroken run of packs directly behind the node on the plan's own lane, and
+ *   (b) side-lane packs (pmt_plan_set_lane 1) anywhere in the tape, as long as the caller has put nothing of its own on the side stream
+ *       (pmt_plan_commit_lane(1), pmt_plan_lane_stream): from the first such call on they stay on the side stream, which alone orders them,
+ * whose reads and writes are independent, by byte range, of the node's writes (and the node's reads of their writes), of the other riders
+ * and, for (a), of what stays between them and the node; for (b) of every other entry that is not on the plan's own lane (an entry
+ * whose ranges the plan does not know, such as a recorded fetch, counts as dependent).  At most 8 riders per node and 256 MB of
+ * algorithmic bytes (32 per matrix entry) in all — measured beside a 4096 x 4096 node: 64 and 256 MB ride 12 us per step faster than
+ * alone, 512 MB only 3-4 us, within the noise; a persistent workgroup is one per CU where the stand-alone pack runs eight, so larger
+ * packs stay alone.  Immediate calls never have riders;
+ * pmt_plan_set_fusion(plan, 0) turns riders off with the fused runs; a captured graph keeps them.
+ *   pmt_plan_riders       packs that ride in this plan's nodes, and their tiles
+ *   pmt_plan_rider_check  the decision alone, a pure host function: tape[0 .. n) describes the entries (kind 1: a one-launch node, 2: a dense
+ *                         vector pack, 0: anything else / unknown ranges; the lane; the shape; up to PMT_RIDER_RANGES byte ranges
+ *                         [begin, end) read and written, begin == end: none), `node` is the index of the node; rides[i] = 1 where entry i rides */
+#define PMT_RIDER_RANGES 5
+typedef struct pmt_rider_entry {
+    int32_t kind, lane;
+    int64_t rows, cols;
+    uint64_t reads[PMT_RIDER_RANGES][2], writes[PMT_RIDER_RANGES][2];
+} pmt_rider_entry;
+int pmt_plan_riders(const pmt_plan *plan, int *riders, int64_t *tiles);
+int pmt_plan_rider_check(const pmt_rider_entry *tape, int64_t n, int64_t node, int *rides, int *riders, int64_t *tiles);
 /* Inside a fused run a workgroup barrier stands only in front of a node that touches what an earlier node since the last barrier wrote
  * (or writes what one read): independent nodes — the Parameter callbacks; the objective's chain and a constraint's — share a PHASE.
  * Number of phases over all fused runs (README Example 1: 7 entries, 3 phases). */

@@ -75,6 +75,12 @@ function fused(plan::Plan)
     check(ccall((:pmt_plan_fused, lib), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Cint}, Ref{Int64}), plan.handle, g, n, len))
     Int(g[]), Int(n[]), len[]
 end
+"(constraint packs that ride in the plan's one-launch Gram nodes, their tiles)"
+function riders(plan::Plan)
+    n = Ref{Cint}(0); tiles = Ref{Int64}(0)
+    check(ccall((:pmt_plan_riders, lib), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Int64}), plan.handle, n, tiles))
+    Int(n[]), tiles[]
+end
 "while recording: lane 1 = the following calls only read Parameter values and are independent of the rest of the tape (side lane), 0 = back"
 set_lane!(plan::Plan, lane::Integer) = check(ccall((:pmt_plan_set_lane, lib), Cint, (Ptr{Cvoid}, Cint), plan.handle, lane))
 "One update!(model) worth of kernels (src/model.jl:132-143): replays the tape, no allocation."

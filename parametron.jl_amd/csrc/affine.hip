@@ -11,7 +11,7 @@
 // or 1 KiB-chunks of the 1.5 KiB row segment (24-byte VectorAffineTerm, assembled as 16-byte chunks so
 // that all stores are global_store_dwordx4).  Algorithmic bytes: 8 read + 16 (LT) / 24 (VAT) written
 // per matrix entry.
-#include "common.h"
+#include "affine_tile.h"
 
 namespace pmt {
 
@@ -20,24 +20,6 @@ namespace pmt {
 // objective's contraction, which has streamed ~1 GB through the cache since the block was last touched: it is always cold there, and the
 // policy takes the in-step launch of config 2's 512 x 4096 block from 15.4 to ~13.8 us.  Small blocks and the LinearTerm form keep plain loads.
 constexpr int64_t NTL_MIN_BYTES = 8 << 20;
-
-constexpr int TILE = 64;
-constexpr int PITCH = TILE + 1;
-
-typedef unsigned long long u64;
-typedef u64 u64x2 __attribute__((ext_vector_type(2)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ u64 f2u(double x) { return (u64)__double_as_longlong(x); }
-
-template <bool NT>
-__device__ __forceinline__ void store16(u64x2 *p, u64x2 v) {
-    if (NT) __builtin_nontemporal_store(v, p); else *p = v;
-}
-template <bool NT>
-__device__ __forceinline__ void store8(u64 *p, u64 v) {
-    if (NT) __builtin_nontemporal_store(v, p); else *p = v;
-}
 
 // MODE 0: LinearTerm output   MODE 1: VectorAffineTerm output
 // TR: rows per tile (64, or 32 for blocks that would otherwise give fewer than ~4 workgroups per CU: the 512 x 4096 constraint block
@@ -57,91 +39,9 @@ __global__ __launch_bounds__(256) void affine_tile_kernel(
     // its own slot (plain stores — atomics of a thousand workgroups on one word serialise and triple the launch)
     const unsigned wg = blockIdx.y * gridDim.x + blockIdx.x;
     if (stamps && t == 0 && wg < stamp_cap) stamps[2 * wg] = (u64)wall_clock64();
-    const int lane = t & 63;
-    const int wave = t >> 6;
-    const int64_t c0 = (int64_t)blockIdx.x * TILE;
-    const int64_t r0 = (int64_t)blockIdx.y * TR;
-    const int nr = (int)min((int64_t)TR, rows - r0);
-    const int nc = (int)min((int64_t)TILE, cols - c0);
-    const bool full = (nr == TR) && (nc == TILE);
-
-    // ---- load phase: column-major A tile -> LDS tile[row][col]
-    if (full && vec_in) {
-        constexpr int TPC = TR / 2;        // threads per column (16-byte pieces of a column segment)
-        constexpr int CPI = 256 / TPC;     // columns per iteration
-        const int cg = t / TPC;            // column within the group
-        const int lr = (t % TPC) * 2;      // row pair
-        const double *base = A + (c0 + cg) * lda + r0 + lr;
-#pragma unroll
-        for (int it = 0; it < TILE / CPI; ++it) {
-            const f64x2 *src = reinterpret_cast<const f64x2 *>(base + (int64_t)it * CPI * lda);
-            f64x2 v = NTL ? __builtin_nontemporal_load(src) : *src;
-            const int c = it * CPI + cg;
-            tile[lr * PITCH + c] = v.x;
-            tile[(lr + 1) * PITCH + c] = v.y;
-        }
-    } else {
-        const int r = t & 63;
-        for (int c = t >> 6; c < nc; c += 4)
-            if (r < nr) tile[r * PITCH + c] = A[(c0 + c) * lda + r0 + r];
-    }
-    if (t < nc) {
-        const int64_t v = xvar[c0 + t];
-        vmx[t] = (u64)(MODE == 1 ? map_var(varmap, v) : v);
-    }
-    // constants: one column of blocks writes 0.0 (+|-) b[row]
-    if (blockIdx.x == 0 && t < nr && out_consts)
-        out_consts[r0 + t] = signed_const(b ? b[r0 + t] : 0.0, b ? sign : 0);
-    __syncthreads();
-
-    // ---- store phase
-    if (MODE == 0) {
-        // 16 B per term: one wave store = 64 terms = 1 KiB contiguous
-        if (lane < nc) {
-            const u64 var = vmx[lane];
-            for (int r = wave; r < nr; r += 4) {
-                u64x2 v;
-                v.x = f2u(tile[r * PITCH + lane]);
-                v.y = var;
-                store16<NT>(reinterpret_cast<u64x2 *>(out + ((r0 + r) * cols + c0 + lane) * 2), v);
-            }
-        }
-    } else {
-        if (full && vec_out) {
-            // rows in pairs: 3 full-wave 16-byte stores per pair (row segment = 192 qwords = 96 chunks)
-            for (int rp = wave * 2; rp < TR; rp += 8) {
-#pragma unroll
-                for (int s = 0; s < 3; ++s) {
-                    int r, chunk;
-                    if (s == 0) { r = rp; chunk = lane; }
-                    else if (s == 1) { r = rp + (lane >> 5); chunk = 64 + (lane & 31); }
-                    else { r = rp + 1; chunk = lane; }
-                    const int q0 = chunk * 2;
-                    const u64 rowidx = (u64)(row_offset + r0 + r + 1);
-                    u64 w[2];
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        const int q = q0 + h;
-                        const int term = q / 3;
-                        const int f = q - term * 3;
-                        w[h] = (f == 0) ? rowidx : (f == 1 ? f2u(tile[r * PITCH + term]) : vmx[term]);
-                    }
-                    u64x2 v; v.x = w[0]; v.y = w[1];
-                    store16<NT>(reinterpret_cast<u64x2 *>(out + ((r0 + r) * cols + c0) * 3 + q0), v);
-                }
-            }
-        } else {
-            if (lane < nc) {
-                const u64 var = vmx[lane];
-                for (int r = wave; r < nr; r += 4) {
-                    u64 *p = out + ((r0 + r) * cols + c0 + lane) * 3;
-                    store8<NT>(p, (u64)(row_offset + r0 + r + 1));
-                    store8<NT>(p + 1, f2u(tile[r * PITCH + lane]));
-                    store8<NT>(p + 2, var);
-                }
-            }
-        }
-    }
+    // (the tile itself: affine_tile.h, shared with the riders of the one-launch Gram node)
+    affine_tile_body<MODE, NT, TR, NTL>(A, lda, rows, cols, xvar, b, sign, varmap, row_offset, out, out_consts, vec_in, vec_out,
+                                        (int)blockIdx.x, (int)blockIdx.y, t, tile, vmx);
     if (stamps) {                    // ... and the latest workgroup end, behind this workgroup's stores
         __syncthreads();
         if (t == 0 && wg < stamp_cap) {
@@ -293,6 +193,11 @@ static bool env_nt() {
 static u64 *g_stamps = nullptr;
 static unsigned g_stamp_cap = 0;
 
+// small blocks: 32-row tiles, twice the workgroups (see the kernel's comment); ~1024 = 4 per CU is where 64-row tiles start to fill the chip
+static bool affine_small_tiles(int64_t rows, int64_t cols) { return cdiv(cols, TILE) * cdiv(rows, TILE) < 1024 && rows > 32; }
+// the MOI pack of a block this large reads its matrix with the nontemporal policy (NTL_MIN_BYTES)
+static bool affine_cold(int64_t rows, int64_t cols) { return rows * cols * (int64_t)sizeof(double) >= NTL_MIN_BYTES; }
+
 template <int MODE>
 static int launch_affine(const double *A, int64_t lda, int64_t rows, int64_t cols, const int64_t *xvar, const double *b, int sign,
                          const int64_t *varmap, int64_t row_offset, void *out_terms, double *out_consts, hipStream_t s) {
@@ -301,9 +206,8 @@ static int launch_affine(const double *A, int64_t lda, int64_t rows, int64_t col
     const int vec_out = ((reinterpret_cast<uintptr_t>(out_terms) & 15) == 0 && (cols & 1) == 0) ? 1 : 0;
     const char *name = MODE == 0 ? "affine_tile_kernel<LT>" : "affine_tile_kernel<VAT>";
     u64 *out = reinterpret_cast<u64 *>(out_terms);
-    // small blocks: 32-row tiles, twice the workgroups (see the kernel's comment); ~1024 = 4 per CU is where 64-row tiles start to fill the chip
-    const bool small = cdiv(cols, TILE) * cdiv(rows, TILE) < 1024 && rows > 32;
-    const bool ntl = MODE == 1 && rows * cols * (int64_t)sizeof(double) >= NTL_MIN_BYTES;
+    const bool small = affine_small_tiles(rows, cols);
+    const bool ntl = MODE == 1 && affine_cold(rows, cols);
     u64 *stamps = MODE == 1 ? g_stamps : nullptr;
 #define AFFINE_LAUNCH(NTV, TRV, NTLV)                                                                                                    \
     PMT_LAUNCH_NAMED(name, (affine_tile_kernel<MODE, NTV, TRV, NTLV>), dim3((unsigned)cdiv(cols, TILE), (unsigned)cdiv(rows, TRV)), dim3(256), 0, s, A, \
@@ -318,6 +222,29 @@ static int launch_affine(const double *A, int64_t lda, int64_t rows, int64_t col
     else { if (small) AFFINE_LAUNCH(false, 32, false); else AFFINE_LAUNCH(false, 64, false); }
 #undef AFFINE_LAUNCH
     return check_launch("affine_tile_kernel");
+}
+
+// the pack as a rider of the one-launch Gram node (affine_tile.h): what launch_affine<1> would choose for it
+int64_t affine_rider_tiles(int64_t rows, int64_t cols) {
+    if (rows <= 0 || cols <= 0) return 0;
+    return cdiv(cols, TILE) * cdiv(rows, affine_small_tiles(rows, cols) ? 32 : 64);
+}
+bool affine_rider(const SmallNode &nd, AffineRider *r) {
+    const int64_t lda = nd.d[0], rows = nd.d[1], cols = nd.d[2];
+    if (nd.op != SOP_AFFINE_VAT || rows <= 0 || cols <= 0) return false;
+    r->A = static_cast<const double *>(nd.in[0]); r->lda = lda; r->rows = rows; r->cols = cols;
+    r->xvar = static_cast<const int64_t *>(nd.in[1]); r->b = static_cast<const double *>(nd.in[2]);
+    r->varmap = static_cast<const int64_t *>(nd.in[3]); r->row_offset = nd.d[3];
+    r->out = static_cast<u64 *>(nd.out[0]); r->out_consts = static_cast<double *>(nd.out[1]);
+    r->sign = nd.sign;
+    r->vec_in = ((reinterpret_cast<uintptr_t>(r->A) & 15) == 0 && (lda & 1) == 0) ? 1 : 0;
+    r->vec_out = ((reinterpret_cast<uintptr_t>(r->out) & 15) == 0 && (cols & 1) == 0) ? 1 : 0;
+    r->tr = affine_small_tiles(rows, cols) ? 32 : 64;
+    r->ntl = affine_cold(rows, cols) ? 1 : 0;
+    r->nt = (r->ntl || env_nt()) ? 1 : 0;
+    r->tiles_x = (int)cdiv(cols, TILE);
+    r->first_tile = 0;
+    return true;
 }
 
 }  // namespace pmt

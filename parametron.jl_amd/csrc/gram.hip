@@ -385,7 +385,8 @@ static int mid_node(const GramArgs &g, SideStream *side, hipStream_t s) {
     PMT_REQUIRE(side && side->counters && (size_t)gram_mid_counters(g.cols) * sizeof(unsigned) <= MID_COUNTER_BYTES, PMT_STATE_ERROR,
                 "quad_gram: no auxiliary state for this stream");
     int rc = launch_gram_mid(g.A, g.lda, g.rows, g.cols, g.xvar, g.b, g.sign, g.moi, g.varmap, g.out_quad, g.out_csc, g.alpha, g.out_lin,
-                             g.out_const, g.workspace, reinterpret_cast<unsigned *>(static_cast<char *>(side->counters) + MID_OFFSET), s);
+                             g.out_const, g.workspace, reinterpret_cast<unsigned *>(static_cast<char *>(side->counters) + MID_OFFSET),
+                             side->mid_riders, side->mid_nriders, side->mid_rider_tiles, s);
     return !rc && forks_in_replay(side) ? fork_side(side, s) : rc;
 }
 
@@ -478,7 +479,7 @@ static int gram_node(const GramArgs &g, void *stream, double *host = nullptr, in
         dplan.sig = std::make_shared<DeliverSignals>();
         mark_no_graph(stream);
     }
-    return dispatch(stream, [=](hipStream_t s) -> int {
+    Launch node = [=](hipStream_t s) -> int {
         SideStream *side = side_stream(s);
         const bool deliver = dplan.host != nullptr;
         if (deliver) { if (int rc = deliver_arm(dplan, side, s)) return rc; }
@@ -488,7 +489,13 @@ static int gram_node(const GramArgs &g, void *stream, double *host = nullptr, in
         if (!rc && deliver) rc = release_group(dplan, side, 0, s);
         if (!rc && deliver) rc = deliver_submit(dplan, side);
         return rc;
-    });
+    };
+    // a recorded one-launch node that delivers nothing: the plan may let constraint packs ride in it (plan.hip)
+    if (form == GramForm::Mid && !host && cols > 0)
+        return dispatch_mid(stream, std::move(node), MidNote{g.A, g.lda, rows, cols, (g.b && g.sign) ? g.b : nullptr, g.xvar, g.moi ? g.varmap : nullptr,
+                                                              g.out_quad, g.out_csc, g.out_lin, g.out_const, g.workspace,
+                                                              pmt_quad_gram_workspace_bytes(rows, cols)});
+    return dispatch(stream, std::move(node));
 }
 
 }  // namespace pmt

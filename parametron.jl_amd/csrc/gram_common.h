@@ -202,7 +202,22 @@ size_t gram_mid_workspace_bytes(int64_t rows, int64_t cols);
 int gram_mid_counters(int64_t cols);
 int launch_gram_mid(const double *A, int64_t lda, int64_t rows, int64_t cols, const int64_t *xvar, const double *b, int sign, int moi,
                     const int64_t *varmap, pmt_quadratic_term *out_quad, double *out_csc, double alpha, pmt_linear_term *out_lin,
-                    double *out_const, void *workspace, unsigned *counters, hipStream_t s);
+                    double *out_const, void *workspace, unsigned *counters, const void *riders, int nriders, int rider_tiles, hipStream_t s);
+bool gram_mid_persistent(int64_t rows, int64_t cols);          // the shape runs as PMT_MID_G persistent workgroups (the form that takes riders)
+// What a recorded one-launch node that delivers nothing to the host tells its plan, which decides who rides in it (plan.hip): its operands;
+// the plan derives the byte ranges the node reads (A, b, xvar, varmap) and writes (out_quad / out_csc, out_lin, out_const, workspace)
+struct MidNote {
+    const double *A; int64_t lda, rows, cols; const double *b; const int64_t *xvar, *varmap;
+    const void *out_quad, *out_csc, *out_lin, *out_const, *workspace; size_t workspace_bytes;
+};
+int dispatch_mid(void *stream, Launch launch, const MidNote &note);
+// the riders of one node: at most this many packs, of at most this many algorithmic bytes (32 per entry) in all — a persistent workgroup
+// is one workgroup per CU where the stand-alone pack runs eight, so a pack much larger than the node's idle tail is faster alone
+#ifndef PMT_MID_RIDER_MB
+#define PMT_MID_RIDER_MB 256       // measured: profiles/r15_gram_riders.txt, section 5 (a measurement build raises it)
+#endif
+constexpr int MID_MAX_RIDERS = 8;
+constexpr int64_t PMT_MID_RIDER_BYTES = (int64_t)PMT_MID_RIDER_MB << 20;
 int launch_gram_mid_constant(const double *b, int sign, int64_t rows, double *out_const, hipStream_t s);
 int check_strictly_increasing(const int64_t *xvar_dev, int64_t n, void *stream);
 void mark_no_graph(void *stream);

@@ -21,6 +21,7 @@
 //     restated bit for bit by tests/gpu_util.py.
 // Summation order of a coefficient (fixed by (rows, cols) alone): wave w of chunk c adds the 8-row groups c gpc + w, + 4, .. in MFMA k
 // order (rows 2 k, 2 k + 1 of a group in contraction slot k); waves (0 + 2) + (1 + 3); chunks in ascending order.
+#include "affine_tile.h"
 #include "gram_common.h"
 
 #ifndef PMT_MID_WPS
@@ -67,6 +68,8 @@ __device__ unsigned long long g_mid_trace[1024 * 8];
 // own (mid_walk_note) and written out when it leaves: [0] items, [1] main loops, [2] stamp 1 -> 3 / 5 (the waves' sums, the count, a fold), [3] epilogues,
 // [4] from one item's last store to the next one's start, [5] the first item's start, [6] the last item's end, [7] the time it left
 __device__ unsigned long long g_mid_walk[1024 * 8];
+// ... and of its rider tiles: [0] how many it drew, [1] the time its last rider store had left
+__device__ unsigned long long g_mid_riders[1024 * 2];
 #define MID_TRACE_WORDS 8
 __device__ __forceinline__ void mid_walk_note(unsigned long long *w, int k, unsigned long long t) {
     if (k == 0) { if (w[0]) w[4] += t - w[7]; else w[5] = t; w[0] += 1; }
@@ -83,6 +86,9 @@ extern "C" int pmt_mid_trace_read(unsigned long long *host) {
 }
 extern "C" int pmt_mid_walk_read(unsigned long long *host) {
     return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_mid_walk), sizeof(unsigned long long) * 1024 * 8) == hipSuccess ? 0 : 1;
+}
+extern "C" int pmt_mid_riders_read(unsigned long long *host) {
+    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_mid_riders), sizeof(unsigned long long) * 1024 * 2) == hipSuccess ? 0 : 1;
 }
 #else
 #define MID_STAMP(k) do { } while (0)
@@ -116,7 +122,9 @@ struct MidArgs {
     unsigned *counters;                      // one per tile, zero between launches (the last arriver re-arms its tile's)
     int xcd;                                 // workgroup ids in the XCD-aware order (gram_mid_kernel)
     int persist, total;                      // PMT_MID_G persistent workgroups walk the `total` work items (gram_mid_kernel)
-    unsigned *tickets;                       // 8 per-XCD tickets + the count of workgroups that have left; zero between launches
+    unsigned *tickets;                       // 8 per-XCD tickets + the count of workgroups that have left + the riders' ticket; zero between launches
+    const AffineRider *riders;               // constraint packs whose tiles the persistent workgroups draw once their items have run out
+    int nriders, rider_tiles;                // (a plan's table, plan.hip; null / 0: nobody rides) ... and the tiles of all of them
 };
 
 struct MidPlan { int nb, n_off, s_off, s_diag, gpc_off, gpc_diag, n_tail, s_tail, gpc_tail, wgs; };
@@ -874,6 +882,28 @@ __device__ __forceinline__ void mid_item(const MidArgs &g, double *sh, int tid, 
     mid_forget(pbuf);
 }
 
+// One tile of a RIDER: a dense MOI constraint pack recorded beside the node (plan.hip) whose tiles the persistent workgroups draw from
+// ticket word 9 once their XCD's Gram items have run out — a workgroup's last item ends 27 us (median, config 2) before the launch does,
+// and nothing else can use its CU until it leaves.  The tile is affine_tile_kernel's own body (affine_tile.h) in the front of `sh`;
+// what depends on the thread comes from a fresh thread id, so nothing of it is live across the Gram items.
+__device__ __forceinline__ void mid_rider_tile(const AffineRider &r, int local, double *sh) {
+    int t;
+    asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"((int)threadIdx.x));
+    const int by = local / r.tiles_x, bx = local - by * r.tiles_x;
+    double *tile = sh;
+    u64 *vmx = reinterpret_cast<u64 *>(sh + TILE * PITCH);
+#define MID_RIDE(NTV, TRV, NTLV)                                                                                                         \
+    affine_tile_body<1, NTV, TRV, NTLV>(r.A, r.lda, r.rows, r.cols, r.xvar, r.b, r.sign, r.varmap, r.row_offset, r.out, r.out_consts,   \
+                                        r.vec_in, r.vec_out, bx, by, t, tile, vmx)
+    if (r.ntl) { if (r.tr == 32) MID_RIDE(true, 32, true); else MID_RIDE(true, 64, true); }
+#ifdef PMT_TUNING
+    else if (!r.nt) { if (r.tr == 32) MID_RIDE(false, 32, false); else MID_RIDE(false, 64, false); }
+#endif
+    else { if (r.tr == 32) MID_RIDE(true, 32, false); else MID_RIDE(true, 64, false); }
+#undef MID_RIDE
+}
+static_assert(TILE * PITCH + TILE <= MQBUF, "a rider's tile and its variable-map row live in the front of the kernel's LDS");
+
 // A launch of more than PMT_MID_G work items runs PERSISTENT (round 6c): PMT_MID_G workgroups, each walking items until none is left,
 // instead of one workgroup per item — between two workgroups on a CU lay 2.5 us (the first one's stores drain, the dispatcher starts the
 // next: tools/mid_trace.py, 8 times per CU at config 2); in a loop the next item's loads go out while the stores of the last drain.  The
@@ -886,6 +916,8 @@ __device__ __forceinline__ void mid_item(const MidArgs &g, double *sh, int tid, 
 // ticket behind it is drawn under the tail — between two items stands one barrier instead of a ticket's round trip between two barriers
 // and the first loads' latency.  The look-ahead stops with the body: from the first id in hand that lies in the split tails or the
 // diagonal chunks on, a workgroup draws on demand, so nobody sits on a short item while others run dry.
+// A workgroup whose ticket has run dry then draws RIDER tiles (mid_rider_tile) until those are exhausted too, and leaves: Gram items
+// always come first; the launch of one workgroup per item takes no riders.
 template <bool FAST>
 __global__ __launch_bounds__(256, PMT_MID_WPS) void gram_mid_kernel(MidArgs g) {
     __shared__ double sh[MSH + MID_TRACE_WORDS];
@@ -932,6 +964,25 @@ __global__ __launch_bounds__(256, PMT_MID_WPS) void gram_mid_kernel(MidArgs g) {
         if (id >= g.total) break;
         cur = mid_decode(g, id);
     }
+    if (g.rider_tiles > 0) {
+        int mine = 0;
+        for (;;) {
+            __syncthreads();                                       // next_id's last readers; the last tile's LDS reads
+            if (tid == 0) next_id = (int)__hip_atomic_fetch_add(g.tickets + 9, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __syncthreads();
+            const int rt = __builtin_amdgcn_readfirstlane(next_id);
+            if (rt >= g.rider_tiles) break;
+            int k = 0;
+            while (k + 1 < g.nriders && rt >= g.riders[k + 1].first_tile) ++k;
+            mid_rider_tile(g.riders[k], rt - g.riders[k].first_tile, sh);
+            ++mine;
+        }
+#ifdef PMT_MID_TRACE
+        __builtin_amdgcn_s_waitcnt(0);
+        if (tid == 0 && blockIdx.x < 1024) { g_mid_riders[blockIdx.x * 2] = (unsigned long long)mine; g_mid_riders[blockIdx.x * 2 + 1] = wall_clock64(); }
+#endif
+        (void)mine;                                                // (read by the trace build only)
+    }
 #ifdef PMT_MID_TRACE
     if (tid == 0 && blockIdx.x < 1024) {
         for (int i = 0; i < 7; ++i) g_mid_walk[blockIdx.x * 8 + i] = reinterpret_cast<unsigned long long *>(sh + MSH)[i];
@@ -942,7 +993,7 @@ __global__ __launch_bounds__(256, PMT_MID_WPS) void gram_mid_kernel(MidArgs g) {
         const unsigned gone = __hip_atomic_fetch_add(g.tickets + 8, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (gone == gridDim.x - 1) {
 #pragma unroll
-            for (int i = 0; i < 9; ++i) __hip_atomic_store(g.tickets + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int i = 0; i < 10; ++i) __hip_atomic_store(g.tickets + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }
@@ -964,12 +1015,13 @@ size_t gram_mid_workspace_bytes(int64_t rows, int64_t cols) {
     const MidPlan p = mid_plan(rows, cols);
     return sizeof(double) * (size_t)p.wgs * MSTRIDE;
 }
+bool gram_mid_persistent(int64_t rows, int64_t cols) { return cols > 0 && rows > 0 && mid_plan(rows, cols).wgs >= 2 * PMT_MID_G; }
 int gram_mid_counters(int64_t cols) { const int nb = (int)cdiv(cols, MT); return MCNT * (nb * (nb + 1) / 2) + 16; }      // (+ the tickets)
 
 // the whole node in one launch; `counters`: gram_mid_counters(cols) zeroed words owned by the calling stream (streams.h: SideStream)
 int launch_gram_mid(const double *A, int64_t lda, int64_t rows, int64_t cols, const int64_t *xvar, const double *b, int sign, int moi,
                     const int64_t *varmap, pmt_quadratic_term *out_quad, double *out_csc, double alpha, pmt_linear_term *out_lin,
-                    double *out_const, void *workspace, unsigned *counters, hipStream_t s) {
+                    double *out_const, void *workspace, unsigned *counters, const void *riders, int nriders, int rider_tiles, hipStream_t s) {
     if (!workspace || !counters) return fail(PMT_INVALID_ARGUMENT, "quad_gram: workspace required");
     const MidPlan p = mid_plan(rows, cols);
     MidArgs g;
@@ -985,6 +1037,9 @@ int launch_gram_mid(const double *A, int64_t lda, int64_t rows, int64_t cols, co
     g.total = p.wgs;
     g.persist = p.wgs >= 2 * PMT_MID_G;
     g.tickets = counters + gram_mid_counters(cols) - 16;
+    // riders (a plan's table, gram.hip: mid_node) travel with the persistent form only: plan.hip lets nobody ride another
+    const bool ride = g.persist && riders && nriders > 0 && rider_tiles > 0;
+    g.riders = ride ? static_cast<const AffineRider *>(riders) : nullptr; g.nriders = ride ? nriders : 0; g.rider_tiles = ride ? rider_tiles : 0;
     const unsigned grid = g.persist ? (unsigned)PMT_MID_G : (unsigned)p.wgs;
     if (fast) PMT_LAUNCH_NAMED("gram_mid_kernel", (gram_mid_kernel<true>), dim3(grid), dim3(256), 0, s, g);
     else PMT_LAUNCH_NAMED("gram_mid_kernel", (gram_mid_kernel<false>), dim3(grid), dim3(256), 0, s, g);

@@ -17,6 +17,7 @@
 
 #include <memory>
 
+#include "affine_tile.h"
 #include "streams.h"
 
 namespace pmt {
@@ -41,6 +42,12 @@ struct pmt_plan {
     std::vector<char> exec_lanes;
     std::vector<int> node_of;         // per tape entry: index into `nodes`, or -1 (an entry only its closure can execute)
     std::vector<pmt::SmallNode> nodes;
+    std::unordered_map<size_t, pmt::MidNote> mid_notes;      // tape index -> what a recorded one-launch Gram node told about itself (riders)
+    int riders = 0; int64_t rider_tiles = 0;                  // what rides in this plan's one-launch nodes (pmt_plan_riders)
+    bool lane1_riders = false;                                // ... side-lane entries among them
+    // something outside the tape has been put on the side stream (pmt_plan_commit_lane(1), pmt_plan_lane_stream): a side-lane entry may
+    // read it, and only the side stream orders the two — such a plan's side-lane entries stay where they are
+    bool side_external = false;
     bool fusion = true;
     int fused_groups = 0, fused_nodes = 0, fused_phases = 0, fused_workgroups = 0;
     int *barrier_error = nullptr;            // page-locked word a run on several workgroups stores 1 into when its grid barrier times out
@@ -198,6 +205,16 @@ int dispatch(void *stream, Launch launch) {
         }
     }
     return launch(reinterpret_cast<hipStream_t>(stream));
+}
+
+int dispatch_mid(void *stream, Launch launch, const MidNote &note) {
+    pmt_plan *plan = recording_plan(stream);
+    if (plan && plan->recording) {
+        if (int rc = dispatch(stream, std::move(launch))) return rc;
+        plan->mid_notes[plan->tape.size() - 1] = note;
+        return PMT_OK;
+    }
+    return dispatch(stream, std::move(launch));
 }
 
 int dispatch(void *stream, Launch launch, const SmallNode &node) {
@@ -454,6 +471,19 @@ extern "C" int pmt_plan_fetch_2d(pmt_plan *plan, void *host_dst, size_t dst_pitc
     return PMT_OK;
 }
 
+// The caller starts to put work of its own on the plan's side stream (a commit, a Parameter callback): from here on only that stream
+// orders such work against the side-lane entries that read it, so side-lane packs no longer ride in a node on the plan's stream
+static int build_exec(pmt_plan *plan);
+static int side_stream_goes_external(pmt_plan *plan) {
+    if (plan->side_external) return PMT_OK;
+    plan->side_external = true;
+    if (!plan->lane1_riders) return PMT_OK;
+    PMT_REQUIRE(!plan->graph_exec, PMT_STATE_ERROR, "plan: side-lane packs ride in the captured graph's Gram node; use the side stream before pmt_plan_instantiate_graph");
+    PMT_HIP_CHECK(hipSetDevice(plan->device));
+    PMT_HIP_CHECK(hipStreamSynchronize(plan->stream));
+    return build_exec(plan);
+}
+
 // ---- staged uploads: host-updated Parameters without the serial PCIe copy (src/parameter.jl:88,101-102) ------------
 // The reference's `Parameter(model, val=buf)` is a host buffer the user overwrites between solves; update!() reads it when the Parameter
 // is evaluated.  Uploading it on the plan's stream puts the PCIe copy serially in front of the kernels (config 2 with host-updated A, b,
@@ -545,7 +575,7 @@ extern "C" int pmt_plan_commit_lane(pmt_plan *plan, int lane) {
     PMT_REQUIRE(plan, PMT_INVALID_ARGUMENT, "plan_commit_lane: null plan");
     PMT_REQUIRE(lane == 0 || lane == 1, PMT_INVALID_ARGUMENT, "plan_commit_lane: lane must be 0 or 1");
     plan->commit_lane = lane;
-    return PMT_OK;
+    return lane ? side_stream_goes_external(plan) : PMT_OK;
 }
 
 extern "C" int pmt_plan_staging_consumed(pmt_plan *plan) {
@@ -651,12 +681,143 @@ static int build_exec(pmt_plan *plan) {
     return PMT_OK;
 }
 
+// ---- riders: constraint packs that run inside a one-launch Gram node (gram_mid.hip) -------------------------------------------------------
+static bool ranges_meet(const uint64_t (*a)[2], const uint64_t (*b)[2]) {
+    for (int i = 0; i < PMT_RIDER_RANGES; ++i)
+        for (int j = 0; j < PMT_RIDER_RANGES; ++j)
+            if (a[i][0] < a[i][1] && b[j][0] < b[j][1] && a[i][0] < b[j][1] && b[j][0] < a[i][1]) return true;
+    return false;
+}
+// either order of the two gives the same memory: neither writes what the other reads or writes (an entry of unknown ranges never is)
+static bool rider_independent(const pmt_rider_entry &a, const pmt_rider_entry &b) {
+    if (a.kind == 0 || b.kind == 0) return false;
+    return !ranges_meet(a.writes, b.writes) && !ranges_meet(a.writes, b.reads) && !ranges_meet(a.reads, b.writes);
+}
+
+extern "C" int pmt_plan_rider_check(const pmt_rider_entry *tape, int64_t n, int64_t node, int *rides, int *riders, int64_t *tiles) {
+    PMT_REQUIRE(tape && rides && n >= 0 && node >= 0 && node < n && tape[node].kind == 1, PMT_INVALID_ARGUMENT, "plan_rider_check: bad argument");
+    for (int64_t i = 0; i < n; ++i) rides[i] = 0;
+    int count = 0;
+    int64_t bytes = 0, ntiles = 0;
+    const pmt_rider_entry &nd = tape[node];
+    const bool persistent = pmt::gram_mid_persistent(nd.rows, nd.cols);          // (the form of one workgroup per item takes no riders)
+    bool run = true;
+    for (int64_t i = 0; persistent && i < n; ++i) {
+        const pmt_rider_entry &e = tape[i];
+        if (i == node) continue;
+        const bool side = e.lane == 1;
+        if (!side) {
+            // the plan's own lane: the unbroken run of packs directly behind the node
+            if (e.lane != 0 || i < node || !run) continue;
+            if (e.kind != 2) { run = false; continue; }
+        }
+        if (e.kind != 2 || e.rows <= 0 || e.cols <= 0 || count == pmt::MID_MAX_RIDERS) continue;
+        if (e.rows > pmt::PMT_MID_RIDER_BYTES / 32 / e.cols || bytes + 32 * e.rows * e.cols > pmt::PMT_MID_RIDER_BYTES) continue;
+        bool ok = rider_independent(e, nd);
+        for (int64_t k = 0; ok && k < n; ++k) {
+            if (k == i || k == node) continue;
+            // the other riders; what stays between the node and a pack of the run; for a side-lane pack, whatever else is not on the plan's
+            // own lane (its neighbours on the side stream, in front of it and behind it)
+            const bool matters = rides[k] || (side ? tape[k].lane != 0 : (tape[k].lane == 0 && k > node && k < i));
+            if (matters && !rider_independent(e, tape[k])) ok = false;
+        }
+        if (!ok) continue;
+        rides[i] = 1;
+        count += 1;
+        bytes += 32 * e.rows * e.cols;
+        ntiles += pmt::affine_rider_tiles(e.rows, e.cols);
+    }
+    if (riders) *riders = count;
+    if (tiles) *tiles = ntiles;
+    return PMT_OK;
+}
+
+extern "C" int pmt_plan_riders(const pmt_plan *plan, int *riders, int64_t *tiles) {
+    PMT_REQUIRE(plan, PMT_INVALID_ARGUMENT, "plan_riders: null plan");
+    if (riders) *riders = plan->riders;
+    if (tiles) *tiles = plan->rider_tiles;
+    return PMT_OK;
+}
+
+static void set_range(uint64_t (&r)[2], const void *p, size_t bytes) {
+    r[0] = reinterpret_cast<uintptr_t>(p); r[1] = p ? r[0] + bytes : r[0];
+}
+// the largest variable index of `n` device words (the extent of the variable map an entry reads); < 0: could not be read
+static int64_t max_index(const int64_t *xvar_dev, int64_t n, bool increasing) {
+    if (n <= 0 || !xvar_dev) return 0;
+    std::vector<int64_t> h((size_t)(increasing ? 1 : n));
+    if (hipMemcpy(h.data(), increasing ? xvar_dev + n - 1 : xvar_dev, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return -1; }
+    return std::max<int64_t>(0, *std::max_element(h.begin(), h.end()));
+}
+
+// per tape entry: the index of the one-launch node it rides in, or -1; the byte ranges come from the entries' recorded operands (setup, not
+// the solve path: the variable indices are static, gram.hip: check_strictly_increasing, and are read back once for the maps' extents)
+static std::vector<int64_t> choose_riders(pmt_plan *plan) {
+    const size_t n = plan->tape.size();
+    std::vector<int64_t> host(n, -1);
+    if (!plan->fusion || plan->mid_notes.empty()) return host;
+    std::vector<pmt_rider_entry> entries(n);
+    bool packs = false;
+    for (size_t i = 0; i < n; ++i) {
+        pmt_rider_entry &e = entries[i];
+        memset(&e, 0, sizeof e);
+        e.lane = plan->lanes[i];
+        if (plan->node_of[i] < 0 || (e.lane == 1 && plan->side_external)) continue;
+        const pmt::SmallNode &nd = plan->nodes[(size_t)plan->node_of[i]];
+        if (nd.op != pmt::SOP_AFFINE_VAT || nd.d[1] <= 0 || nd.d[2] <= 0) continue;
+        e.kind = 2; e.rows = nd.d[1]; e.cols = nd.d[2];
+        packs = true;
+    }
+    if (!packs) return host;
+    if (hipStreamSynchronize(plan->stream) != hipSuccess) { (void)hipGetLastError(); return host; }      // (the indices may still be on their way)
+    for (size_t i = 0; i < n; ++i) {
+        pmt_rider_entry &e = entries[i];
+        if (e.kind != 2) continue;
+        const pmt::SmallNode &nd = plan->nodes[(size_t)plan->node_of[i]];
+        const int64_t lda = nd.d[0], vmax = nd.in[3] ? max_index(static_cast<const int64_t *>(nd.in[1]), e.cols, false) : 0;
+        if (vmax < 0) { e.kind = 0; continue; }
+        set_range(e.reads[0], nd.in[0], sizeof(double) * (size_t)((e.cols - 1) * lda + e.rows));
+        set_range(e.reads[1], nd.in[1], sizeof(int64_t) * (size_t)e.cols);
+        set_range(e.reads[2], nd.in[2], sizeof(double) * (size_t)e.rows);
+        set_range(e.reads[3], nd.in[3], sizeof(int64_t) * (size_t)vmax);
+        set_range(e.writes[0], nd.out[0], sizeof(pmt::VAT) * (size_t)(e.rows * e.cols));
+        set_range(e.writes[1], nd.out[1], sizeof(double) * (size_t)e.rows);
+    }
+    std::vector<int> rides(n);
+    for (size_t i = 0; i < n; ++i) {
+        auto it = plan->mid_notes.find(i);
+        if (it == plan->mid_notes.end()) continue;
+        const pmt::MidNote &m = it->second;
+        const int64_t vmax = m.varmap ? max_index(m.xvar, m.cols, true) : 0;
+        if (vmax < 0) continue;
+        pmt_rider_entry &e = entries[i];
+        const size_t nq = (size_t)(m.cols * (m.cols + 1) / 2);
+        e.kind = 1; e.rows = m.rows; e.cols = m.cols;
+        set_range(e.reads[0], m.A, sizeof(double) * (size_t)((m.cols - 1) * m.lda + m.rows));
+        set_range(e.reads[1], m.b, sizeof(double) * (size_t)m.rows);
+        set_range(e.reads[2], m.xvar, sizeof(int64_t) * (size_t)m.cols);
+        set_range(e.reads[3], m.varmap, sizeof(int64_t) * (size_t)vmax);
+        set_range(e.writes[0], m.out_quad, sizeof(pmt::QT) * nq);
+        set_range(e.writes[1], m.out_csc, sizeof(double) * nq);
+        set_range(e.writes[2], m.out_lin, sizeof(pmt::LT) * (size_t)m.cols);
+        set_range(e.writes[3], m.out_const, sizeof(double));
+        set_range(e.writes[4], m.workspace, m.workspace_bytes);
+        if (pmt_plan_rider_check(entries.data(), (int64_t)n, (int64_t)i, rides.data(), nullptr, nullptr)) continue;
+        for (size_t k = 0; k < n; ++k)
+            if (rides[k]) { host[k] = (int64_t)i; entries[k].kind = 0; }          // (it has left its place: nothing moves across it any more)
+        e.kind = 0;
+    }
+    return host;
+}
+
 static int build_exec_into(pmt_plan *plan, std::vector<pmt::Launch> &out_exec, std::vector<char> &out_lanes, std::vector<std::pair<void *, size_t>> &tables) {
     plan->fused_groups = 0; plan->fused_nodes = 0; plan->fused_phases = 0; plan->fused_workgroups = 0;
+    plan->riders = 0; plan->rider_tiles = 0; plan->lane1_riders = false;
     const int wg_limit = multi_workgroup_limit(plan);
     const size_t n = plan->tape.size();
+    const std::vector<int64_t> host = choose_riders(plan);
     auto small = [&](size_t i) {
-        return plan->fusion && plan->node_of[i] >= 0 && plan->lanes[i] == 0 && plan->nodes[(size_t)plan->node_of[i]].work <= pmt::SMALL_NODE_WORK_MAX;
+        return host[i] < 0 && plan->fusion && plan->node_of[i] >= 0 && plan->lanes[i] == 0 && plan->nodes[(size_t)plan->node_of[i]].work <= pmt::SMALL_NODE_WORK_MAX;
     };
     for (size_t i = 0; i < n;) {
         size_t j = i;
@@ -672,7 +833,39 @@ static int build_exec_into(pmt_plan *plan, std::vector<pmt::Launch> &out_exec, s
             ++j;
         }
         if (j - i < 2) {
-            out_exec.push_back(plan->tape[i]);
+            if (host[i] >= 0) { ++i; continue; }                  // a rider: it runs inside its node's launch
+            pmt::Launch entry = plan->tape[i];
+            std::vector<pmt::AffineRider> riders;
+            for (size_t k = 0; k < n; ++k) {
+                pmt::AffineRider r;
+                if (host[k] != (int64_t)i || !pmt::affine_rider(plan->nodes[(size_t)plan->node_of[k]], &r)) continue;
+                r.first_tile = riders.empty() ? 0 : riders.back().first_tile + (int)pmt::affine_rider_tiles(riders.back().rows, riders.back().cols);
+                riders.push_back(r);
+                plan->lane1_riders |= plan->lanes[k] == 1;
+            }
+            if (!riders.empty()) {
+                // the node with its riders: their table (plan-owned device memory, written here once) travels to the node's launch through
+                // the stream's record (gram.hip: mid_node)
+                const int count = (int)riders.size();
+                const int ntiles = riders.back().first_tile + (int)pmt::affine_rider_tiles(riders.back().rows, riders.back().cols);
+                const size_t table_bytes = sizeof(pmt::AffineRider) * riders.size();
+                void *table = nullptr;
+                hipError_t e = hipMalloc(&table, table_bytes);
+                if (e != hipSuccess) { (void)hipGetLastError(); return fail(PMT_OUT_OF_MEMORY, std::string("hipMalloc: ") + hipGetErrorString(e)); }
+                tables.emplace_back(table, table_bytes);
+                PMT_HIP_CHECK(hipMemcpy(table, riders.data(), table_bytes, hipMemcpyHostToDevice));
+                pmt::Launch node = entry;
+                entry = [=](hipStream_t s) {
+                    pmt::SideStream *ss = pmt::side_stream(s);
+                    if (ss) { ss->mid_riders = table; ss->mid_nriders = count; ss->mid_rider_tiles = ntiles; }
+                    const int rc = node(s);
+                    if (ss) { ss->mid_riders = nullptr; ss->mid_nriders = 0; ss->mid_rider_tiles = 0; }
+                    return rc;
+                };
+                plan->riders += count;
+                plan->rider_tiles += ntiles;
+            }
+            out_exec.push_back(std::move(entry));
             out_lanes.push_back(plan->lanes[i]);
             ++i;
             continue;
@@ -892,7 +1085,7 @@ extern "C" int pmt_plan_lane_stream(pmt_plan *plan, int lane, void **out_stream)
     hipStream_t s = lane == 0 ? plan->stream : pmt::side_stream_of(plan->stream);
     PMT_REQUIRE(s || lane == 0, PMT_STATE_ERROR, "plan_lane_stream: the plan's stream has no side stream");
     *out_stream = s;
-    return PMT_OK;
+    return lane ? side_stream_goes_external(plan) : PMT_OK;
 }
 
 extern "C" int pmt_plan_update(pmt_plan *plan) {

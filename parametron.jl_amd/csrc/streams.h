@@ -29,6 +29,9 @@ struct SideStream {
     bool in_replay = false;                                              // a plan's tape is being replayed: P's transfers are submitted at its end
     bool side_work = false;                                              // ... and it puts work on `stream`: side-lane entries, or a stream-K node's reductions
     std::vector<std::function<int()>> deferred;
+    // the riders of the NEXT one-launch Gram node on this stream: set and cleared around the node by its plan's exec entry (plan.hip), passed
+    // on by mid_node (gram.hip); a device table of AffineRider (affine_tile.h), its length, the tiles of all of them
+    const void *mid_riders = nullptr; int mid_nriders = 0, mid_rider_tiles = 0;
 };
 constexpr int ERR_COURIER = 1, ERR_PAIR_FOLD = 2;
 // layout of `counters`: [MAXGROUPS x u64 unused][MAXGROUPS x i64 courier flags (armed = 1)][u32 courier done][u32 unused]
