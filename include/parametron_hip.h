@@ -581,6 +581,75 @@ int pmt_sparse_gram_f64(const double *nzval, const void *prod, const int64_t *se
                         int sign, int moi, const int64_t *varmap, pmt_quadratic_term *out_quad, pmt_linear_term *out_lin, double *out_const,
                         void *stream);
 
+/* A WEIGHTED SUM over sparse least-squares blocks and simple terms over one strictly increasing Variable vector x (n columns) as one
+ * canonical MOI function: dot(r, r) + lam*dot(x, x), w1*dot(r1, r1) + w2*dot(r2, r2), dot(r, r) + dot(c, x) + s, 2.0*dot(r, r) ..  The
+ * function is the reference's literal function (add! / mul! of the terms' functions, src/functions.jl:452-461, :578) minus the structural
+ * zeros, canonicalize!d (:381-386), then the MOI copy (src/moi_interop.jl:45-62).  `terms` is a HOST array of `nterms`
+ * (1 .. PMT_LSQ_MAX_TERMS) pmt_sparse_lsq_term descriptors in expression order, of the kinds of pmt_lsq_term:
+ *   PMT_LSQ_BLOCK     dot(r_b, r_b), r_b = C_b*x (+|-) d_b, C_b sparse: `quad`, `lin`, `constant` are the block's MOI-form outputs of
+ *                     pmt_sparse_gram_f64 (moi = 1, the same varmap: coefficients already doubled), left in scratch lists of the block's
+ *                     own nq_b / nlin_b terms; `quad_at` / `lin_at` its gather tables (below).  1 .. PMT_LSQ_MAX_BLOCKS blocks; patterns and
+ *                     row counts may differ between blocks.
+ *   PMT_LSQ_DIAG      dot(x, x) (vec NULL, sign 0) or dot(x (+|-) v, x (+|-) v) (vec = v, sign = +1 | -1)
+ *   PMT_LSQ_LINEAR    dot(c, x) (vec = c)
+ *   PMT_LSQ_CONSTANT  a scalar: *vec (a scalar Parameter), or 1.0 when vec is NULL (a number folded into `scale`)
+ * A diagonal or linear term lies over all of x (`pos` NULL, nvec = n) or over a strictly increasing part of it: `pos` is then a device
+ * table over the positions 0 .. n-1 giving the index into the term's vector (nvec entries), or -1 for a position the term does not list.
+ * Every term is weighted by W = scale * (*weight), or scale when weight is NULL.
+ * STRUCTURE (from the patterns alone; terms exist even when a coefficient is 0.0, as in the bare node):
+ *   quadratic pairs   the sorted union, by (j, k) with j <= k, of the blocks' pair sets and of (j, j) for every position j that some
+ *                     diagonal term lists
+ *   linear columns    the sorted union of the blocks' non-empty columns, the positions listed by diagonal terms with a v, and the positions
+ *                     listed by linear terms
+ * COEFFICIENTS, every operation in the order written, no contraction into fma; a position or pair a term does not hold gets nothing from
+ * it (no + 0.0), the first contributor starts the chain (no 0.0 +):
+ *   quad[(j,k)]  W_b*Q_b[(j,k)] over the blocks holding the pair, in block order (c = c + W_b*Q_b); on the diagonal, when a diagonal term
+ *                lists j, then + D_j,  D_j = ((2*W_d1) + (2*W_d2)) + .. over the diagonal terms that list j, in order; D_j alone when no
+ *                block holds the pair
+ *   lin[j]       W_b*L_b[j] over the blocks that have column j, in block order; then + W_t*(2*(0.0 (+|-) v[p])) over the diagonal terms
+ *                with v that list j, in order; then + W_t*c[p] over the linear terms that list j, in order
+ *   constant     W_b*cc_b in block order; then W_t*S_t for every diagonal term with v, S_t the sum of v^2 over the term's own vector: 256
+ *                chains (chain t adds entries t, t + 256, .. in order), then the halving tree — S_d's order in pmt_quad_gram_sum_f64; then
+ *                W_t*(*vec or 1.0) for the scalar constants, in expression order
+ * The row, column and variable words go through varmap at every call, and the whole 24- or 16-byte struct is written every time, every
+ * output term exactly once: the output may be host-visible memory.  One launch (csrc/sparse_gram_sum.hip): workgroup 0 the constant, then
+ * one workgroup per PMT_SPARSE_SUM_WG_TERMS output quadratic terms (the structs go through LDS and leave as 16-byte stores per wave; an
+ * output base that is 8 mod 16 is fine), then one per PMT_SPARSE_SUM_WG_TERMS output linear terms.
+ * SYMBOLIC PHASE, host, once per term list: pmt_sparse_gram_sum_merge merges the blocks' sorted lists (pair_j[b], pair_k[b], nq[b] and
+ * lin_col[b], nlin[b] of pmt_sparse_gram_order, HOST arrays of `nblocks` pointers / counts in block order) with the column lists of the
+ * diagonal and linear terms — term_kind[t] (PMT_LSQ_*), term_has_vec[t] (a diagonal term's v), term_cols[t] / term_ncols[t] as in
+ * pmt_quad_gram_sum_sub_f64 (NULL: all of x) for each of the nterms terms in expression order; the blocks among them number nblocks.
+ * Linear in the input (the lists are sorted: each output pair looks at the at most nine list heads, no comparison sort).  With every output array
+ * NULL it returns the counts *out_nq / *out_nlin only; otherwise it also writes out_pair_j / out_pair_k (out_nq entries), out_lin_col
+ * (out_nlin), per block quad_at[b] (out_nq entries: the index of the output pair in the block's own list, or 0xFFFFFFFF when the block
+ * has no such pair) and lin_at[b] (out_nlin entries, likewise), and per term with a column list term_pos[t] (n entries of int32: the `pos`
+ * table above).  Unsorted lists are PMT_INVALID_ARGUMENT, positions outside 0 .. n-1 PMT_DIMENSION_MISMATCH, nblocks outside
+ * 1 .. PMT_LSQ_MAX_BLOCKS or nterms outside 1 .. PMT_LSQ_MAX_TERMS PMT_INVALID_ARGUMENT — all checked before anything is written.
+ * pmt_sparse_gram_sum_f64 rejects null pointers, negative counts, bad signs and term / block counts out of range before any device call. */
+#define PMT_SPARSE_SUM_WG_TERMS 256
+typedef struct {
+    int32_t kind;                     /* PMT_LSQ_* */
+    int32_t sign;                     /* PMT_LSQ_DIAG with vec: +1 for x + v, -1 for x - v; otherwise 0 */
+    double scale;                     /* host factor of the weight */
+    const double *weight;             /* device scalar factor of the weight, or NULL */
+    const pmt_quadratic_term *quad;   /* PMT_LSQ_BLOCK: the block's quadratic terms (nq_b) */
+    const pmt_linear_term *lin;       /* PMT_LSQ_BLOCK: the block's linear terms (nlin_b) */
+    const double *constant;           /* PMT_LSQ_BLOCK: the block's constant */
+    const uint32_t *quad_at;          /* PMT_LSQ_BLOCK: per output quadratic term, its index in `quad` or 0xFFFFFFFF */
+    const uint32_t *lin_at;           /* PMT_LSQ_BLOCK: per output linear term, its index in `lin` or 0xFFFFFFFF */
+    const double *vec;                /* PMT_LSQ_DIAG: v or NULL; PMT_LSQ_LINEAR: c; PMT_LSQ_CONSTANT: the scalar or NULL */
+    const int32_t *pos;               /* PMT_LSQ_DIAG / PMT_LSQ_LINEAR over part of x: per position its index in vec or -1; NULL: all of x */
+    int64_t nvec;                     /* PMT_LSQ_DIAG / PMT_LSQ_LINEAR: the number of positions the term lists (the length of vec) */
+} pmt_sparse_lsq_term;
+int pmt_sparse_gram_sum_merge(int64_t n, int nblocks, const uint32_t *const *host_pair_j, const uint32_t *const *host_pair_k,
+                              const int64_t *host_nq, const uint32_t *const *host_lin_col, const int64_t *host_nlin, int nterms,
+                              const int32_t *term_kind, const int32_t *term_has_vec, const int64_t *const *term_cols,
+                              const int64_t *term_ncols, int64_t *out_nq, int64_t *out_nlin, uint32_t *out_pair_j, uint32_t *out_pair_k,
+                              uint32_t *out_lin_col, uint32_t *const *quad_at, uint32_t *const *lin_at, int32_t *const *term_pos);
+int pmt_sparse_gram_sum_f64(int64_t n, const pmt_sparse_lsq_term *terms, int nterms, const uint32_t *pair_j, const uint32_t *pair_k,
+                            int64_t nq, const uint32_t *lin_col, int64_t nlin, const int64_t *xvar, const int64_t *varmap,
+                            pmt_quadratic_term *out_quad, pmt_linear_term *out_lin, double *out_const, void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * Batched independent QPs (BASELINE config 4).  In the reference a batch is many independent Models (src/model.jl:1-22); all
  * instances share one structure, so per re-evaluation only coefficients are produced: one slab of

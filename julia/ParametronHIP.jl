@@ -322,6 +322,59 @@ sparse_gram!(out_quad::DevPtr, out_lin::DevPtr, out_const::DevPtr, nzval::DevPtr
                 nzval, prod, seg_ptr, pair_j, pair_k, nq, runs, nruns, long_seg, nlong, lin_seg, rowidx0, lin_col, nlin, lin_runs, nlin_runs, lin_long,
                 nlin_long, rows, xvar, d, sign, moi, varmap, out_quad, out_lin, out_const, stream))
 
+"""
+the symbolic merge of a weighted sum over sparse blocks (csrc/sparse_gram_sum.hip): `plans` are the blocks' sparse_gram_plan results in
+block order, `kinds` / `has_vec` / `cols` describe the nterms terms in expression order (cols[t]: 0-based positions in x, or `nothing`
+for all of x).  Returns the merged pairs and columns, the blocks' gather tables and the position tables of the terms with a list.
+"""
+function sparse_gram_sum_plan(n::Integer, plans, kinds::Vector{Int32}, has_vec::Vector{Int32}, cols)
+    K, nt = length(plans), length(kinds)
+    pj, pk, lc = [p.pair_j for p in plans], [p.pair_k for p in plans], [p.lin_col for p in plans]
+    nqs, nls = Int64[p.nq for p in plans], Int64[p.nlin for p in plans]
+    lists = [c === nothing ? nothing : Vector{Int64}(c) for c in cols]
+    keep = [c === nothing ? nothing : (isempty(c) ? Int64[0] : c) for c in lists]
+    ncols = Int64[c === nothing ? 0 : length(c) for c in lists]
+    ptrs(v) = Ptr{Cvoid}[a === nothing ? C_NULL : Ptr{Cvoid}(pointer(a)) for a in v]
+    nq, nlin = Ref{Int64}(0), Ref{Int64}(0)
+    arg(a) = a === nothing ? C_NULL : a
+    tabs(v) = v === nothing ? C_NULL : ptrs(v)
+    merge(opj, opk, olc, qat, lat, pos) = GC.@preserve pj pk lc keep qat lat pos check(ccall((:pmt_sparse_gram_sum_merge, lib), Cint,
+        (Int64, Cint, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Int64}, Ptr{Ptr{Cvoid}}, Ptr{Int64}, Cint, Ptr{Int32}, Ptr{Int32}, Ptr{Ptr{Cvoid}}, Ptr{Int64},
+         Ref{Int64}, Ref{Int64}, Ptr{UInt32}, Ptr{UInt32}, Ptr{UInt32}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}, Ptr{Ptr{Cvoid}}),
+        n, K, ptrs(pj), ptrs(pk), nqs, ptrs(lc), nls, nt, kinds, has_vec, ptrs(keep), ncols, nq, nlin,
+        arg(opj), arg(opk), arg(olc), tabs(qat), tabs(lat), tabs(pos)))
+    merge(nothing, nothing, nothing, nothing, nothing, nothing)
+    opj, opk, olc = zeros(UInt32, max(nq[], 1)), zeros(UInt32, max(nq[], 1)), zeros(UInt32, max(nlin[], 1))
+    qat, lat = [zeros(UInt32, max(nq[], 1)) for _ in 1:K], [zeros(UInt32, max(nlin[], 1)) for _ in 1:K]
+    pos = [c === nothing ? nothing : fill(Int32(-1), max(n, 1)) for c in lists]
+    merge(opj, opk, olc, qat, lat, pos)
+    (nq = nq[], nlin = nlin[], pair_j = opj, pair_k = opk, lin_col = olc, quad_at = qat, lin_at = lat, term_pos = pos)
+end
+
+"pmt_sparse_lsq_term: one term of the weighted sum sparse_gram_sum! combines (pointers are device addresses or C_NULL)"
+struct SparseLsqTerm
+    kind::Int32
+    sign::Int32
+    scale::Float64
+    weight::DevPtr
+    quad::DevPtr
+    lin::DevPtr
+    constant::DevPtr
+    quad_at::DevPtr
+    lin_at::DevPtr
+    vec::DevPtr
+    pos::DevPtr
+    nvec::Int64
+end
+
+"the canonical MOI function of a weighted sum over sparse blocks (csrc/sparse_gram_sum.hip): every block's sparse_gram! (moi = 1) has
+written its scratch lists; `terms` is a host Vector{SparseLsqTerm} in expression order, the tables those of sparse_gram_sum_plan as device copies"
+sparse_gram_sum!(out_quad::DevPtr, out_lin::DevPtr, out_const::DevPtr, n, terms::Vector{SparseLsqTerm}, pair_j::DevPtr, pair_k::DevPtr, nq,
+                 lin_col::DevPtr, nlin, xvar::DevPtr, varmap::DevPtr, stream) =
+    check(ccall((:pmt_sparse_gram_sum_f64, lib), Cint,
+                (Int64, Ptr{SparseLsqTerm}, Cint, DevPtr, DevPtr, Int64, DevPtr, Int64, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
+                n, terms, length(terms), pair_j, pair_k, nq, lin_col, nlin, xvar, varmap, out_quad, out_lin, out_const, stream))
+
 "dst (cols x rows, leading dimension ldd) = transpose of src (rows x cols, leading dimension lds) — the adjoint rule, src/lazyexpression.jl:206-217"
 transpose!(dst::DevPtr, ldd, src::DevPtr, lds, rows, cols, stream) =
     check(ccall((:pmt_transpose_f64, lib), Cint, (DevPtr, Int64, Int64, Int64, DevPtr, Int64, Ptr{Cvoid}), src, lds, rows, cols, dst, ldd, stream))

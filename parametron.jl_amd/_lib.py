@@ -20,6 +20,7 @@ PMT_OK, PMT_DIMENSION_MISMATCH, PMT_INVALID_ARGUMENT, PMT_HIP_ERROR, PMT_STATE_E
 PMT_LSQ_BLOCK, PMT_LSQ_DIAG, PMT_LSQ_LINEAR, PMT_LSQ_CONSTANT = 1, 2, 3, 4
 PMT_LSQ_MAX_TERMS, PMT_LSQ_MAX_BLOCKS, PMT_LSQ_MAX_RUNS = 32, 8, 64
 PMT_QUAD_MAX_GROUPS = 8
+PMT_SPARSE_SUM_WG_TERMS = 256                                    # output terms per workgroup of pmt_sparse_gram_sum_f64
 STACK_COLUMN = np.dtype([("src", "<u8"), ("sign", "<i8")])       # pmt_stack_column
 
 
@@ -32,6 +33,24 @@ class LsqTerm(C.Structure):
 def lsq_terms(terms):
     """host array of pmt_lsq_term from dicts {kind, sign, scale, weight, values, lin, constant, vec} (missing fields: 0 / None)"""
     arr = (LsqTerm * max(len(terms), 1))()
+    for i, t in enumerate(terms):
+        for k, v in t.items():
+            setattr(arr[i], k, v)
+        if "scale" not in t:
+            arr[i].scale = 1.0
+    return arr
+
+
+class SparseLsqTerm(C.Structure):
+    """pmt_sparse_lsq_term: one term of the weighted sum pmt_sparse_gram_sum_f64 combines (pointers are device addresses, or None)."""
+    _fields_ = [("kind", C.c_int32), ("sign", C.c_int32), ("scale", C.c_double), ("weight", C.c_void_p), ("quad", C.c_void_p),
+                ("lin", C.c_void_p), ("constant", C.c_void_p), ("quad_at", C.c_void_p), ("lin_at", C.c_void_p), ("vec", C.c_void_p),
+                ("pos", C.c_void_p), ("nvec", C.c_int64)]
+
+
+def sparse_lsq_terms(terms):
+    """host array of pmt_sparse_lsq_term from dicts of its fields (missing fields: 0 / None, scale 1.0)"""
+    arr = (SparseLsqTerm * max(len(terms), 1))()
     for i, t in enumerate(terms):
         for k, v in t.items():
             setattr(arr[i], k, v)
@@ -190,6 +209,9 @@ SIGNATURES = {
     "pmt_sparse_gram_runs": (_ci, [_vp, _i64, _i64, _vp, C.POINTER(_i64), _vp, C.POINTER(_i64)]),
     "pmt_sparse_gram_f64": (_ci, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _ci,
                                   _ci, _vp, _vp, _vp, _vp, _vp]),
+    "pmt_sparse_gram_sum_merge": (_ci, [_i64, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), _vp, _vp, _vp, _vp,
+                                        _vp, _vp]),
+    "pmt_sparse_gram_sum_f64": (_ci, [_i64, _vp, _ci, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pmt_batch_lsq_slab_doubles": (_i64, [_i64, _i64]),
     "pmt_batch_lsq_coeffs_f64": (_ci, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _ci, _vp, _i64, _vp]),
     "pmt_batch_expand_f64": (_ci, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -621,6 +621,52 @@ class SparseGramTables:
                 a("lin_seg"), a("rowidx0"), a("lin_col"), self.nlin, a("lin_runs"), self.nlin_runs, a("lin_long"), self.nlin_long, int(rows))
 
 
+class SparseSumTables:
+    """Host tables of pmt_sparse_gram_sum_merge for one weighted sum over sparse blocks (include/parametron_hip.h, pmt_sparse_gram_sum_f64)
+    and, with a context, their device copies — built once per record.  `blocks`: the SparseGramTables of the blocks in block order (what is
+    read: pair_j, pair_k, nq, lin_col, nlin); `terms`: per term in expression order (kind, has_vec, cols) with kind a PMT_LSQ_* value and
+    cols the term's positions in x (None: all of x; blocks and constants: None).
+      nq, pair_j, pair_k     the merged quadratic pairs;  nlin, lin_col: the merged linear columns
+      quad_at[b], lin_at[b]  per block, the gather tables over the output terms (0xFFFFFFFF: the block has no such term)
+      term_pos[t]            per term with a column list, the int32 table over 0 .. n-1 (index into the term's vector, or -1)"""
+
+    def __init__(self, ctx, n, blocks, terms):
+        vp = C.c_void_p
+        K, nt = len(blocks), len(terms)
+        ptrs = lambda arrs: (vp * max(len(arrs), 1))(*[a.ctypes.data if a is not None else None for a in arrs])        # noqa: E731
+        pj = [np.ascontiguousarray(T.pair_j, dtype=np.uint32) for T in blocks]
+        pk = [np.ascontiguousarray(T.pair_k, dtype=np.uint32) for T in blocks]
+        lc = [np.ascontiguousarray(T.lin_col, dtype=np.uint32) for T in blocks]
+        nqs = np.array([T.nq for T in blocks], dtype=np.int64)
+        nls = np.array([T.nlin for T in blocks], dtype=np.int64)
+        kinds = np.array([t[0] for t in terms], dtype=np.int32)
+        has_vec = np.array([1 if t[1] else 0 for t in terms], dtype=np.int32)
+        cols = [np.ascontiguousarray(t[2], dtype=np.int64) if t[2] is not None else None for t in terms]
+        ncols = np.array([len(c) if c is not None else 0 for c in cols], dtype=np.int64)
+        # (an empty list still counts as a list: a non-null pointer)
+        keep = [np.zeros(1, dtype=np.int64) if c is not None and len(c) == 0 else c for c in cols]
+        head = (int(n), K, ptrs(pj), ptrs(pk), nqs.ctypes.data_as(vp), ptrs(lc), nls.ctypes.data_as(vp), nt, kinds.ctypes.data_as(vp),
+                has_vec.ctypes.data_as(vp), ptrs(keep), ncols.ctypes.data_as(vp))
+        nq, nlin = C.c_int64(), C.c_int64()
+        _lib.call("pmt_sparse_gram_sum_merge", *head, C.byref(nq), C.byref(nlin), None, None, None, None, None, None)
+        self.n, self.nq, self.nlin = int(n), nq.value, nlin.value
+        self.pair_j, self.pair_k = np.zeros(max(self.nq, 1), dtype=np.uint32), np.zeros(max(self.nq, 1), dtype=np.uint32)
+        self.lin_col = np.zeros(max(self.nlin, 1), dtype=np.uint32)
+        self.quad_at = [np.zeros(max(self.nq, 1), dtype=np.uint32) for _ in range(K)]
+        self.lin_at = [np.zeros(max(self.nlin, 1), dtype=np.uint32) for _ in range(K)]
+        self.term_pos = {t: np.full(max(int(n), 1), -1, dtype=np.int32) for t, c in enumerate(cols) if c is not None}
+        pos = [self.term_pos.get(t) for t in range(nt)]
+        _lib.call("pmt_sparse_gram_sum_merge", *head, C.byref(nq), C.byref(nlin), self.pair_j.ctypes.data_as(vp), self.pair_k.ctypes.data_as(vp),
+                  self.lin_col.ctypes.data_as(vp), ptrs(self.quad_at), ptrs(self.lin_at), ptrs(pos))
+        self.pair_j, self.pair_k, self.lin_col = self.pair_j[:self.nq], self.pair_k[:self.nq], self.lin_col[:self.nlin]
+        self.quad_at, self.lin_at = [a[:self.nq] for a in self.quad_at], [a[:self.nlin] for a in self.lin_at]
+        self.dev = None
+        if ctx is not None:
+            self.dev = {"pair_j": ctx.upload_new(self.pair_j), "pair_k": ctx.upload_new(self.pair_k), "lin_col": ctx.upload_new(self.lin_col),
+                        "quad_at": [ctx.upload_new(a) for a in self.quad_at], "lin_at": [ctx.upload_new(a) for a in self.lin_at],
+                        "term_pos": {t: ctx.upload_new(a) for t, a in self.term_pos.items()}}
+
+
 class DSparseAff(DAffVec):
     """C*x (+|-) d for a sparse C kept implicit; terms exist for the structural non-zeros only, in row-major order."""
 
@@ -720,5 +766,5 @@ def fetch_f64(ctx, ptr, n):
     return out
 
 
-__all__ = ["DeviceContext", "DV", "DNum", "DVec", "DMat", "DVars", "DLinVec", "DAffVec", "DDenseAff", "DStackedAff", "DVarsAff", "DSpMat", "DSparseAff", "SparseGramTables", "DAff", "DQuad",
+__all__ = ["DeviceContext", "DV", "DNum", "DVec", "DMat", "DVars", "DLinVec", "DAffVec", "DDenseAff", "DStackedAff", "DVarsAff", "DSpMat", "DSparseAff", "SparseGramTables", "SparseSumTables", "DAff", "DQuad",
            "fetch_terms", "fetch_f64", "P", "LT", "QT", "VAT", "ArgumentError"]

@@ -680,16 +680,18 @@ def _rule_dot(model, ctx, x, y):                                                
 
 
 class _NoLiteralQuad(DQuad):
-    """The deferred dest of dot(r, r) over a sparse residual: only the canonical objective consumes it.  Any literal consumer — expr(), a sum
-    with other terms, quadratic_mode="literal" — gets the error the literal rule gives for ragged rows.  (Next step: sums such as
-    dot(r, r) + lam * dot(x, x) over a sparse block, which need a combine over the sparse term list.)"""
+    """The deferred dest of dot(r, r) over a sparse residual: only the canonical records consume it — the bare node ("canonical-sparse") and
+    weighted sums over such blocks, diagonal, linear and constant terms over the same x ("canonical-sparse-sum", moi.quad_plan).  Any
+    literal consumer — expr(), a sum the sparse combine does not take (a dense block beside it, another x), quadratic_mode="literal" —
+    gets the error the literal rule gives for ragged rows."""
 
     def __init__(self, ctx, nq, nl):
         super().__init__(ctx, nq, nl, alloc=False)
 
     def materialize(self):
         raise ArgumentError("dot of two Vector{AffineFunction} needs rows of equal length on the device (a sparse residual has no literal form: "
-                            "dot(r, r) alone is the canonical sparse objective; a sum or scaling over it is not built yet)")
+                            "dot(r, r) and weighted sums of such blocks with dot(x, x), dot(x - v, x - v), dot(c, x) and scalar terms over the same x "
+                            "have the canonical sparse form, with quadratic_mode 'auto' or 'canonical' and handoff 'moi' or 'device')")
 
 
 class _LazyRowTimesMatrix:
@@ -741,15 +743,16 @@ class LsqTerm:
       'diag'      dot(x, x), or dot(x (+|-) v, x (+|-) v) with v a vector Parameter (xvars, vec, sign)
       'linear'    dot(c, x) / dot(x, c) with c a vector Parameter (xvars, vec)
       'constant'  a number (folded into scale) or a scalar Parameter (value)
-    weighted by scale (+-1 times Python numbers) times at most one scalar Parameter (param: its DNum, read on the device at run time)."""
-    __slots__ = ("kind", "scale", "param", "r", "xvars", "vec", "sign", "value")
+    weighted by scale (+-1 times Python numbers) times at most one scalar Parameter (param: its DNum, read on the device at run time).
+    host_scaled: a 'diag' term read from a host-evaluated number * dot(u, u) — only the sparse combine takes such a term (moi.quad_plan)."""
+    __slots__ = ("kind", "scale", "param", "r", "xvars", "vec", "sign", "value", "host_scaled")
 
-    def __init__(self, kind, scale=1.0, param=None, r=None, xvars=None, vec=None, sign=0, value=None):
+    def __init__(self, kind, scale=1.0, param=None, r=None, xvars=None, vec=None, sign=0, value=None, host_scaled=False):
         self.kind, self.scale, self.param = kind, float(scale), param
-        self.r, self.xvars, self.vec, self.sign, self.value = r, xvars, vec, sign, value
+        self.r, self.xvars, self.vec, self.sign, self.value, self.host_scaled = r, xvars, vec, sign, value, host_scaled
 
     def scaled(self, s, param=None):
-        t = LsqTerm(self.kind, self.scale * s, param or self.param, self.r, self.xvars, self.vec, self.sign, self.value)
+        t = LsqTerm(self.kind, self.scale * s, param or self.param, self.r, self.xvars, self.vec, self.sign, self.value, self.host_scaled)
         return t
 
     def __repr__(self):
@@ -777,6 +780,9 @@ def _lsq_of(arg, dv):
         q = arg.quadratic
         if q and not arg.affine.linear and arg.affine.constant == 0 and all(t.coeff == 1.0 and t.rowvar.index == t.colvar.index for t in q):
             return [LsqTerm("diag", xvars=_IndexVars([t.rowvar.index for t in q]))]
+        # number * dot(u, u), multiplied on the host too: sum_i s * u_i * u_i — one diagonal term of weight s
+        if q and not arg.affine.linear and arg.affine.constant == 0 and all(t.coeff == q[0].coeff and t.rowvar.index == t.colvar.index for t in q):
+            return [LsqTerm("diag", scale=q[0].coeff, xvars=_IndexVars([t.rowvar.index for t in q]), host_scaled=True)]
         return None
     if isinstance(dv, DNum):
         return [LsqTerm("constant", scale=float(arg))] if _isnum(arg) else [LsqTerm("constant", value=dv)]

@@ -177,7 +177,7 @@ def _form_args(q, varmap_buf, alpha):                                    # the l
 
 class _Record:
     """Common part of Objective and Constraint (src/moi_interop.jl:113-129, 141-166)."""
-    mode = property(lambda self: self.plan.mode)                          # "literal" / "canonical" / "canonical-csc" / "-form" / "-sum" / "-groups" / "-sparse"
+    mode = property(lambda self: self.plan.mode)                          # "literal" / "canonical" / "canonical-csc" / "-form" / "-sum" / "-groups" / "-sparse" / "-sparse-sum"
     lsq_terms = property(lambda self: self.plan.terms)                    # the LsqTerm list a "canonical-sum" record combines, or None
 
     def _setup(self, model, expr):
@@ -444,7 +444,61 @@ class _Record:
         return lambda c: c.call("pmt_sparse_gram_f64", P(r.spmat.buf), *T.call_args(r.rows), P(r.xvars.buf), P(vec), r.sign if vec else 0, 1,
                                 P(varmap_buf), P(dq), P(dl), P(dc))
 
-    _QUAD_FORMS = {"canonical-sparse": _compile_sparse_gram, "literal": _compile_literal, "canonical": _compile_gram, "canonical-csc": _compile_gram, "canonical-form": _compile_form,
+    def _compile_sparse_sum(self, ctx, varmap_buf, handoff_varmap):
+        """A weighted sum over sparse least-squares blocks, diagonal, linear and constant terms over one x (plan.terms; quad_plan:
+        _sparse_sum_combines): every block by the unchanged pmt_sparse_gram_f64 (moi = 1) into its own scratch term lists, then ONE
+        pmt_sparse_gram_sum_f64 weights and adds them through the gather tables of the symbolic merge (device.SparseSumTables, built here
+        once) and writes every term of the MOI buffers once — also straight into the page-locked host arrays of a small model.  The index
+        fields are static: written into the host arrays here through the hand-off's map, as _compile_sparse_gram does; the kernel rewrites
+        them through varmap_buf at every call."""
+        from . import _lib
+        from .device import SparseSumTables
+        terms = self.plan.terms
+        blocks = [t for t in terms if t.kind == "block"]
+        xv = blocks[0].r.xvars
+        n = len(xv.vars)
+        kind = {"block": _lib.PMT_LSQ_BLOCK, "diag": _lib.PMT_LSQ_DIAG, "linear": _lib.PMT_LSQ_LINEAR, "constant": _lib.PMT_LSQ_CONSTANT}
+        lists = [np.searchsorted(xv.vars, t.xvars.vars).astype(np.int64) if t.kind in ("diag", "linear") and not np.array_equal(t.xvars.vars, xv.vars)
+                 else None for t in terms]
+        Ts = [t.r.gram_tables() for t in blocks]
+        S = SparseSumTables(ctx, n, Ts, [(kind[t.kind], t.kind == "diag" and t.vec is not None, p) for t, p in zip(terms, lists)])
+        self.f = f = ScalarQuadraticFunction(S.nlin, S.nq, alloc=ctx.pinned_array)
+        x = xv.vars if handoff_varmap is None else np.asarray(handoff_varmap, dtype=np.int64)[xv.vars - 1]
+        f.quadratic_terms["row"], f.quadratic_terms["col"], f.quadratic_terms["coeff"] = x[S.pair_j], x[S.pair_k], 0.0
+        f.affine_terms["var"], f.affine_terms["coeff"] = x[S.lin_col], 0.0
+        dq, dl, dc = self._twin(ctx, f.quadratic_terms, 24 * S.nq), self._twin(ctx, f.affine_terms, 16 * S.nlin), self._twin(ctx, self._cbuf, 8)
+        self.dev = {"quad": dq, "lin": dl, "const": dc}
+        # per block: the scratch lists pmt_sparse_gram_f64 writes (its own nq / nlin terms, its constant)
+        parts = [(ctx.alloc(24 * max(T.nq, 1)), ctx.alloc(16 * max(T.nlin, 1)), ctx.alloc(8)) for T in Ts]
+        desc, k = [], 0
+        for i, t in enumerate(terms):
+            d = {"kind": kind[t.kind], "scale": t.scale, "weight": t.param.buf if t.param is not None else None}
+            if t.kind == "block":
+                d["quad"], d["lin"], d["constant"] = parts[k]
+                d["quad_at"], d["lin_at"] = S.dev["quad_at"][k], S.dev["lin_at"][k]
+                k += 1
+            elif t.kind in ("diag", "linear"):
+                d["vec"] = t.vec.buf if t.vec is not None else None
+                d["sign"] = t.sign if t.kind == "diag" and t.vec is not None else 0
+                d["pos"] = S.dev["term_pos"].get(i)
+                d["nvec"] = len(t.xvars.vars)
+            elif t.value is not None:
+                d["vec"] = t.value.buf
+            desc.append(d)
+        arr = _lib.sparse_lsq_terms(desc)
+        self._sub_args.append((S, arr))                                     # (the entry reads the descriptors when the call is recorded)
+
+        def emit(c):
+            for t, T, part in zip(blocks, Ts, parts):
+                r = t.r
+                vec = r.vec.buf if r.vec is not None else None
+                c.call("pmt_sparse_gram_f64", P(r.spmat.buf), *T.call_args(r.rows), P(r.xvars.buf), P(vec), r.sign if vec else 0, 1,
+                       P(varmap_buf), P(part[0]), P(part[1]), P(part[2]))
+            c.call("pmt_sparse_gram_sum_f64", n, C.addressof(arr), len(desc), P(S.dev["pair_j"]), P(S.dev["pair_k"]), S.nq, P(S.dev["lin_col"]),
+                   S.nlin, P(xv.buf), P(varmap_buf), P(dq), P(dl), P(dc))
+        return emit
+
+    _QUAD_FORMS = {"canonical-sparse": _compile_sparse_gram, "canonical-sparse-sum": _compile_sparse_sum, "literal": _compile_literal, "canonical": _compile_gram, "canonical-csc": _compile_gram, "canonical-form": _compile_form,
                    "canonical-sum": _compile_lsq_sum, "canonical-groups": _compile_groups}
 
     # ---- Vector{AffineFunction}
@@ -600,7 +654,9 @@ def _lsq_sum_combines(terms):
     holds at most PMT_LSQ_MAX_RUNS runs of positions)."""
     from . import _lib
     blocks = [t for t in terms or () if t.kind in ("block", "form")]
-    if any(isinstance(t.r, DSparseAff) for t in blocks):              # a sparse block in a sum: not built yet (the literal path then refuses it)
+    if any(isinstance(t.r, DSparseAff) for t in blocks):              # a sparse block: the dense combine cannot take it (_sparse_sum_combines)
+        return False
+    if any(t.host_scaled for t in terms or ()):                        # number * dot(u, u) multiplied on the host: the literal path, as before
         return False
     if len(terms or ()) > _lib.PMT_LSQ_MAX_TERMS or not 1 <= len(blocks) <= _lib.PMT_LSQ_MAX_BLOCKS or not blocks[0].r.xvars.strictly_increasing():
         return False
@@ -617,6 +673,31 @@ def _lsq_sum_combines(terms):
                 return False
             runs += _lib.column_runs(pos)
     return runs <= _lib.PMT_LSQ_MAX_RUNS
+
+
+def _sparse_sum_combines(terms):
+    """Whether pmt_sparse_gram_sum_f64 can combine this LsqTerm list: 1 .. PMT_LSQ_MAX_BLOCKS blocks, every one a sparse Gram operand
+    (DSparseAff.gram_operand) — no dense block, no form beside them —, at most PMT_LSQ_MAX_TERMS terms, every block over the same strictly
+    increasing x, every diagonal / linear term over x or a strictly increasing part of it (_lsq_sum_combines' subset rule; the positions
+    are held in tables, so there is no limit on their runs)."""
+    from . import _lib
+    terms = terms or ()
+    blocks = [t for t in terms if t.kind in ("block", "form")]
+    if not 1 <= len(blocks) <= _lib.PMT_LSQ_MAX_BLOCKS or len(terms) > _lib.PMT_LSQ_MAX_TERMS:
+        return False
+    if not all(t.kind == "block" and isinstance(t.r, DSparseAff) and t.r.gram_operand() for t in blocks):
+        return False
+    x = blocks[0].r.xvars.vars
+    for t in terms:
+        if t.kind == "block":
+            if not np.array_equal(t.r.xvars.vars, x):
+                return False
+        elif t.xvars is not None and not np.array_equal(t.xvars.vars, x):
+            v = t.xvars.vars
+            pos = np.searchsorted(x, v)
+            if not (len(v) and np.all(np.diff(v) > 0) and np.all(pos < len(x)) and np.array_equal(x[np.minimum(pos, len(x) - 1)], v)):
+                return False
+    return True
 
 
 # A sum over disjoint Variable vectors whose literal function is smaller than this keeps the literal expansion + canonicalize: such models
@@ -677,10 +758,11 @@ class QuadPlan:
         return [r for r in [self.gram] + [t.r for ts in lists for t in ts] if r is not None]
 
 
-def quad_plan(terms, bare, kind, nq, is_objective, quadratic_mode, small, handoff, varmap=None):
+def quad_plan(terms, bare, kind, nq, is_objective, quadratic_mode, small, handoff, varmap=None, sparse_sums=False):
     """The QuadPlan of a record over a node described by (terms, bare) = DeviceNode.(lsq_sum, lsq_bare); no mode unless kind == "quad".  `nq`:
     the terms of its literal expansion; `small`: Model._small; `varmap`: the optimizer's index map when it is fixed before the plan is recorded
-    (handoff "device" / "host_csc").  Host data only: nothing is allocated, no stacked matrix is asked for.  First match wins."""
+    (handoff "device" / "host_csc"); `sparse_sums`: weighted sums over sparse blocks take the sparse combine (Model passes True).  Host data
+    only: nothing is allocated, no stacked matrix is asked for.  First match wins."""
     one = terms[0] if bare and kind == "quad" else None
     block = one.r if one is not None and one.kind == "block" else None
     if isinstance(block, DSparseAff) and (quadratic_mode == "literal" or handoff == "host_csc"):
@@ -701,6 +783,10 @@ def quad_plan(terms, bare, kind, nq, is_objective, quadratic_mode, small, handof
     # boundary and the device hand-off, in small models and beyond
     if isinstance(block, DSparseAff):
         return QuadPlan("canonical-sparse", gram=block)
+    # a weighted sum over sparse blocks, diagonal, linear and constant terms over one x: the blocks' sparse Gram nodes combined through
+    # the merged pattern — like the bare node in "auto" too, for both boundaries, in small models and beyond, objective or constraint
+    if sparse_sums and not bare and handoff in ("moi", "device") and _sparse_sum_combines(terms):
+        return QuadPlan("canonical-sparse-sum", terms=terms)
     if quadratic_mode == "auto":
         return QuadPlan("literal")
     if not small:
