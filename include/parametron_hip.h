@@ -657,7 +657,16 @@ int pmt_sparse_gram_sum_f64(int64_t n, const pmt_sparse_lsq_term *terms, int nte
  *     [ Q: n(n+1)/2 | q: n | const: 1 | C: m*n row-major | d-consts: m ],
  * = the coefficients of the canonical MOI objective of residual . residual (Appendix A.3) and of the constraint block
  * C*x (+|-) d (Appendix A.4).  Inputs are instance-major: A[B][r*n] column-major, b[B][r], C[B][m*n] column-major, d[B][m].
- * pmt_batch_expand_f64 rebuilds the full MOI term buffers (with indices through xvar / varmap) of ONE instance from its slab.
+ * Instance i's slab starts at out + i * out_stride (out_stride >= the slab length; the words between two slabs are not written).
+ * Q is 2 A'A on the row-major upper triangle, q is 2 A'c with c = 0.0 (+|-) b, const is c'c summed left to right, the d-consts are
+ * 0.0 (+|-) d.  Edge cases, each a complete slab:
+ *   sign_b == 0   no constants in the residual: q and const are +0.0; sign_d == 0: the d-consts are +0.0 (b / d must still be valid)
+ *   r == 0        no rows: Q, q and const are +0.0
+ *   m == 0        no constraint block: the slab is [Q | q | const]
+ *   n == 0        no variables: the slab is [const | d-consts]
+ * pmt_batch_expand_f64 rebuilds the full MOI term buffers (with indices through xvar / varmap) of ONE instance from its slab: indices
+ * and layout as pmt_quad_gram_f64 / pmt_affine_pack_vector_f64 produce them for that instance alone, Q and q equal to rounding (the
+ * single-instance node sums in an order of its own), the constant and the constraint block bit for bit.
  * ------------------------------------------------------------------------------------- */
 int64_t pmt_batch_lsq_slab_doubles(int64_t n, int64_t m);
 int pmt_batch_lsq_coeffs_f64(const double *A, const double *b, const double *C, const double *d, int64_t B, int64_t n, int64_t r,

@@ -5,8 +5,9 @@
 //     [ Q: n(n+1)/2 | q: n | const: 1 | C: m*n row-major | d-consts: m ]
 // where Q/q/const are the canonical objective coefficients of residual . residual (MOI form) and C / d-consts
 // the coefficients / constants of the constraint block C*x (+|-) d (Appendix A.4).  pmt_batch_expand_f64 turns one instance's slab
-// into the full MOI term buffers (coefficient + indices) — byte-identical to what pmt_quad_gram_f64 / pmt_affine_pack_vector_f64
-// produce for that instance alone.
+// into the full MOI term buffers (coefficient + indices): indices and layout identical to what pmt_quad_gram_f64 /
+// pmt_affine_pack_vector_f64 produce for that instance alone, the Q and q coefficients equal to rounding (the single-instance node of such
+// shapes is the fused or the one-launch form, with a summation order of its own), the constant and the constraint block bit for bit.
 #include "common.h"
 
 namespace pmt {
@@ -97,10 +98,9 @@ extern "C" int pmt_batch_lsq_coeffs_f64(const double *A, const double *b, const 
             // small instances: the whole slab of an instance from one persistent workgroup (batch_small.hip)
             return launch_batch_small(A, r, r, n, r * n, b, r, sign_b, B, out, out_stride, Cm, m, d, sign_d, s);
         }
-        if (n > 0) {
-            int rc = launch_batch_gram(A, r, r, n, r * n, b, r, sign_b, B, out, out + nq, out + nq + n, out_stride, s);
-            if (rc) return rc;
-        }
+        // (n == 0: the slab is [c'c | d-consts]; launch_batch_gram then runs its constant kernel alone)
+        int rc = launch_batch_gram(A, r, r, n, r * n, b, r, sign_b, B, out, out + nq, out + nq + n, out_stride, s);
+        if (rc) return rc;
         if (m > 0 && n > 0) {
             for (int64_t i0 = 0; i0 < B; i0 += 65535) {
                 const unsigned nb = (unsigned)std::min<int64_t>(65535, B - i0);

@@ -25,7 +25,9 @@
 // kernel; loads and stores in the SAME wave also wait for each other (one in-order counter).  Separated, each stream has the whole phase.
 // The kernel runs at the chip's power limit: 0.39 ms without the HBM reads at 2.39 GHz, 0.46 ms with them at 1.97 GHz, the same ~1.0 M
 // cycles either way (profiles/r02_batch_small.txt).
-// Q uses the MFMA lane mapping and k order of gram_sk.hip: bit-identical to pmt_quad_gram_f64 on the same instance.
+// Q uses the MFMA lane mapping and k order of gram_sk.hip.  Against pmt_quad_gram_f64 on the same instance: indices and layout identical, Q and q
+// equal to rounding (the single-instance node of these shapes is the fused or the one-launch form, which sums in another order), the constant
+// and the constraint block bit for bit.
 #include <type_traits>
 
 #include "common.h"

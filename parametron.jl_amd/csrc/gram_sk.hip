@@ -368,7 +368,7 @@ int launch_batch_gram(const double *A, int64_t lda, int64_t rows, int64_t cols, 
     bg.ntiles = (int)cdiv(cols, ST);
     bg.vec_in = ((reinterpret_cast<uintptr_t>(A) & 15) == 0 && (lda & 1) == 0 && (strideA & 1) == 0) ? 1 : 0;
     const int T = bg.ntiles * (bg.ntiles + 1) / 2;
-    for (int64_t i0 = 0; i0 < B; i0 += 65535) {                 // gridDim.y limit
+    for (int64_t i0 = 0; i0 < B && cols > 0; i0 += 65535) {     // gridDim.y limit; without columns both grids are empty: the constant alone
         const unsigned nb = (unsigned)std::min<int64_t>(65535, B - i0);
         BatchGramArgs part = bg;
         part.A = A + i0 * strideA; part.out = out_q + i0 * out_stride;
