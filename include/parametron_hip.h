@@ -650,6 +650,46 @@ int pmt_sparse_gram_sum_f64(int64_t n, const pmt_sparse_lsq_term *terms, int nte
                             int64_t nq, const uint32_t *lin_col, int64_t nlin, const int64_t *xvar, const int64_t *varmap,
                             pmt_quadratic_term *out_quad, pmt_linear_term *out_lin, double *out_const, void *stream);
 
+/* Sparse quadratic form: transpose(x) * Q * x with Q an n x n fixed-pattern CSC matrix (only nzval changes between calls) and x = n
+ * DISTINCT variables in strictly increasing order, as the canonical MOI function.  The function is the reference's literal one minus the
+ * structural zeros: bilinearmul! (src/functions.jl:840-858) emitting a term (Q[r,c], x_r, x_c) for the STORED entries only,
+ * canonicalize! (:381-386), then the MOI copy (src/moi_interop.jl:45-62):
+ *   quadratic terms  one per unordered pair {j, k}, j <= k, for which Q[j,k] or Q[k,j] is stored, sorted by (j, k); nq terms.  A term
+ *                    exists even when its coefficient is 0.0.  The coefficient is
+ *                      Q[j,k] + Q[k,j]   when both are stored: the sum of two numbers, defined bit for bit as in pmt_quad_form_f64;
+ *                      the stored value  UNCHANGED when only one of them is stored (no + 0.0: -0.0 stays -0.0);
+ *                      2*Q[j,j]          on the diagonal with moi = 1 (moi_interop.jl:58), Q[j,j] with moi = 0.
+ *                    The index words are always (vm[xvar[j]], vm[xvar[k]]) with j <= k (moi = 0: xvar[j], xvar[k], varmap not read).  This
+ *                    is one deliberate departure from the reference, whose canonicalize! leaves a lone term's two variables in stored
+ *                    order (src/util.jl:18-19 compares the ordered pair, the term itself is kept): a lone lower-triangle entry Q[k,j]
+ *                    keeps (x_k, x_j) there — the same monomial.
+ *   linear terms     none
+ *   constant         0.0
+ * Symbolic phase, host, once per pattern (colptr / rowval 1-based as for pmt_sparse_gram_*; linear in nnz + n, no comparison sort: the
+ * transpose pattern of the upper part by a counting pass, then row j of the upper part and column j of the lower part walked together):
+ *   pmt_sparse_form_count -> nq
+ *   pmt_sparse_form_order -> pair_j[nq], pair_k[nq] (0-based positions, sorted by (j, k)); src_a[nq]: the position in nzval of Q[j,k] (row j,
+ *                            column k) or 0xFFFFFFFF; src_b[nq]: the position of Q[k,j] or 0xFFFFFFFF.  On the diagonal src_a is the entry
+ *                            and src_b is 0xFFFFFFFF.  Never are both 0xFFFFFFFF.  nq is that of _count.
+ *   a 0-based or non-monotone colptr, rows that do not ascend strictly within a column and null pointers are PMT_INVALID_ARGUMENT; a row
+ *   outside 1 .. n, n < 0 or n >= 2^31, 2^32 - 1 or more non-zeros and an nq that is not that of _count are PMT_DIMENSION_MISMATCH — all
+ *   checked before anything is written.
+ * Per call, pmt_sparse_form_f64: ONE launch (csrc/sparse_form.hip), one workgroup per PMT_SPARSE_SUM_WG_TERMS output terms, one term per
+ * thread.  The four table words are read coalesced; one or two values are gathered from nzval, each only where its source word is not
+ * 0xFFFFFFFF; the add or the doubling above, no fma.  The 24-byte structs go through LDS and leave as 16-byte stores per wave; an output
+ * base that is 8 mod 16 is fine.  The whole struct is rewritten at every call — the index words through varmap — every output term
+ * exactly once, nothing beyond nq terms: the output may be host-visible memory.  *out_const = 0.0 when out_const is given.  nq = 0 is a
+ * valid call (the constant only, or nothing).  No atomics, no wait between workgroups, no workspace.  The gathers are in range only because
+ * pmt_sparse_form_order produced the tables: the kernel does not check them.  Null pointers (with nq > 0), a negative nq, moi outside
+ * {0, 1} and moi without varmap are PMT_INVALID_ARGUMENT before any device call.  Algorithmic bytes: 16 nq (tables) + 24 nq (terms) + 8 per
+ * value gathered. */
+int pmt_sparse_form_count(int64_t n, const int64_t *host_colptr, const int64_t *host_rowval, int64_t *nq);
+int pmt_sparse_form_order(int64_t n, const int64_t *host_colptr, const int64_t *host_rowval, int64_t nq, uint32_t *host_pair_j,
+                          uint32_t *host_pair_k, uint32_t *host_src_a, uint32_t *host_src_b);
+int pmt_sparse_form_f64(const double *nzval, const uint32_t *src_a, const uint32_t *src_b, const uint32_t *pair_j, const uint32_t *pair_k,
+                        int64_t nq, const int64_t *xvar, int moi, const int64_t *varmap, pmt_quadratic_term *out_quad, double *out_const,
+                        void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * Batched independent QPs (BASELINE config 4).  In the reference a batch is many independent Models (src/model.jl:1-22); all
  * instances share one structure, so per re-evaluation only coefficients are produced: one slab of

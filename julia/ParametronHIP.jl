@@ -375,6 +375,27 @@ sparse_gram_sum!(out_quad::DevPtr, out_lin::DevPtr, out_const::DevPtr, n, terms:
                 (Int64, Ptr{SparseLsqTerm}, Cint, DevPtr, DevPtr, Int64, DevPtr, Int64, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
                 n, terms, length(terms), pair_j, pair_k, nq, lin_col, nlin, xvar, varmap, out_quad, out_lin, out_const, stream))
 
+"symbolic phase of the sparse quadratic form transpose(x)*Q*x (host, once per pattern): the unordered pairs {j, k}, j <= k, with Q[j,k] or
+Q[k,j] stored, sorted by (j, k), and per pair the positions in nzval of Q[j,k] (src_a) and Q[k,j] (src_b), 0xFFFFFFFF where not stored"
+function sparse_form_plan(Q::SparseMatrixCSC{Float64,Int64})
+    n = size(Q, 1)
+    size(Q, 2) == n || throw(DimensionMismatch("sparse_form_plan: Q must be square"))
+    nq = Ref{Int64}(0)
+    check(ccall((:pmt_sparse_form_count, lib), Cint, (Int64, Ptr{Int64}, Ptr{Int64}, Ref{Int64}), n, Q.colptr, Q.rowval, nq))
+    pj, pk, sa, sb = (zeros(UInt32, max(nq[], 1)) for _ in 1:4)
+    check(ccall((:pmt_sparse_form_order, lib), Cint, (Int64, Ptr{Int64}, Ptr{Int64}, Int64, Ptr{UInt32}, Ptr{UInt32}, Ptr{UInt32}, Ptr{UInt32}),
+                n, Q.colptr, Q.rowval, nq[], pj, pk, sa, sb))
+    (nq = nq[], pair_j = pj, pair_k = pk, src_a = sa, src_b = sb)
+end
+
+"the canonical MOI function of transpose(x)*Q*x with a sparse Q (csrc/sparse_form.hip): the tables of sparse_form_plan as device copies;
+nq quadratic terms, no linear terms, `out_const` (or C_NULL) receives 0.0"
+sparse_form!(out_quad::DevPtr, out_const::DevPtr, nzval::DevPtr, src_a::DevPtr, src_b::DevPtr, pair_j::DevPtr, pair_k::DevPtr, nq, xvar::DevPtr, moi,
+             varmap::DevPtr, stream) =
+    check(ccall((:pmt_sparse_form_f64, lib), Cint,
+                (DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, Int64, DevPtr, Cint, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
+                nzval, src_a, src_b, pair_j, pair_k, nq, xvar, moi, varmap, out_quad, out_const, stream))
+
 "dst (cols x rows, leading dimension ldd) = transpose of src (rows x cols, leading dimension lds) — the adjoint rule, src/lazyexpression.jl:206-217"
 transpose!(dst::DevPtr, ldd, src::DevPtr, lds, rows, cols, stream) =
     check(ccall((:pmt_transpose_f64, lib), Cint, (DevPtr, Int64, Int64, Int64, DevPtr, Int64, Ptr{Cvoid}), src, lds, rows, cols, dst, ldd, stream))

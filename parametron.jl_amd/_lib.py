@@ -212,7 +212,10 @@ SIGNATURES = {
     "pmt_sparse_gram_sum_merge": (_ci, [_i64, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64), _vp, _vp, _vp, _vp,
                                         _vp, _vp]),
     "pmt_sparse_gram_sum_f64": (_ci, [_i64, _vp, _ci, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "pmt_batch_lsq_slab_doubles": (_i64, [_i64, _i64]),
+    "pmt_sparse_form_count": (_ci, [_i64, _vp, _vp, C.POINTER(_i64)]),
+    "pmt_sparse_form_order": (_ci, [_i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "pmt_sparse_form_f64": (_ci, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _ci, _vp, _vp, _vp, _vp]),
+    "pmt_batch_lsq_slab_doubles":(_i64, [_i64, _i64]),
     "pmt_batch_lsq_coeffs_f64": (_ci, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _ci, _vp, _i64, _vp]),
     "pmt_batch_expand_f64": (_ci, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pmt_comm_unique_id": (_ci, [_vp]),

@@ -512,6 +512,7 @@ class DSpMat(DV):
         rowval = np.ascontiguousarray(csc.indices, dtype=np.int64) + 1
         self.indptr, self.indices = csc.indptr.copy(), csc.indices.copy()
         self._gram = None                                                         # gram_tables(): built on demand
+        self._form = None                                                         # form_tables(): built on demand
         self.perm = np.empty(self.nnz, dtype=np.int64)
         self.term_row = np.empty(self.nnz, dtype=np.int64)
         self.term_col = np.empty(self.nnz, dtype=np.int64)
@@ -568,6 +569,42 @@ class DSpMat(DV):
         if self._gram is None:
             self._gram = SparseGramTables(ctx, self.rows, self.cols, self.indptr, self.indices, self.GRAM_RUN_PRODUCTS)
         return self._gram
+
+    def form_tables(self, ctx):
+        """The symbolic phase of transpose(x)*Q*x with this matrix as Q (csrc/sparse_form.hip), once per pattern and only when a consumer
+        asks (moi._Record._compile_sparse_form / _compile_sparse_sum): host tables and their device copies.  The device copies stay with
+        this layer: the kernel's gathers are in range only because pmt_sparse_form_order produced the tables."""
+        if self._form is None:
+            self._form = SparseFormTables(ctx, self.rows, self.indptr, self.indices)
+        return self._form
+
+
+class SparseFormTables:
+    """Host tables of pmt_sparse_form_count / _order for one square CSC pattern (0-based indptr / indices) and, with a context, their device
+    copies: the unordered pairs {j, k}, j <= k, with Q[j,k] or Q[k,j] stored (pair_j, pair_k, sorted) and per pair the positions in nzval of
+    Q[j,k] (src_a) and Q[k,j] (src_b), 0xFFFFFFFF where not stored.  nlin = 0 with an empty lin_col: SparseSumTables reads these tables as
+    a block's (a form has no linear terms)."""
+
+    TABLES = ("pair_j", "pair_k", "src_a", "src_b")
+
+    def __init__(self, ctx, n, indptr, indices):
+        vp = C.c_void_p
+        colptr = np.ascontiguousarray(indptr, dtype=np.int64) + 1                # Julia 1-based
+        rowval = np.ascontiguousarray(indices, dtype=np.int64) + 1
+        nq = C.c_int64()
+        _lib.call("pmt_sparse_form_count", int(n), colptr.ctypes.data_as(vp), rowval.ctypes.data_as(vp), C.byref(nq))
+        self.n, self.nq = int(n), nq.value
+        self.pair_j, self.pair_k, self.src_a, self.src_b = (np.zeros(self.nq, dtype=np.uint32) for _ in range(4))
+        _lib.call("pmt_sparse_form_order", int(n), colptr.ctypes.data_as(vp), rowval.ctypes.data_as(vp), self.nq,
+                  *[getattr(self, k).ctypes.data_as(vp) if self.nq else None for k in self.TABLES])
+        self.nlin, self.lin_col = 0, np.zeros(0, dtype=np.uint32)
+        self.dev = None
+        if ctx is not None:
+            self.dev = {k: ctx.upload_new(getattr(self, k)) for k in self.TABLES}
+
+    def call_args(self):
+        """the pattern's arguments of pmt_sparse_form_f64, between nzval and xvar"""
+        return tuple(P(self.dev[k]) for k in ("src_a", "src_b", "pair_j", "pair_k")) + (self.nq,)
 
 
 class SparseGramTables:
@@ -766,5 +803,5 @@ def fetch_f64(ctx, ptr, n):
     return out
 
 
-__all__ = ["DeviceContext", "DV", "DNum", "DVec", "DMat", "DVars", "DLinVec", "DAffVec", "DDenseAff", "DStackedAff", "DVarsAff", "DSpMat", "DSparseAff", "SparseGramTables", "SparseSumTables", "DAff", "DQuad",
+__all__ = ["DeviceContext", "DV", "DNum", "DVec", "DMat", "DVars", "DLinVec", "DAffVec", "DDenseAff", "DStackedAff", "DVarsAff", "DSpMat", "DSparseAff", "SparseGramTables", "SparseFormTables", "SparseSumTables", "DAff", "DQuad",
            "fetch_terms", "fetch_f64", "P", "LT", "QT", "VAT", "ArgumentError"]

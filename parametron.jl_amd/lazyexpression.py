@@ -683,15 +683,22 @@ class _NoLiteralQuad(DQuad):
     """The deferred dest of dot(r, r) over a sparse residual: only the canonical records consume it — the bare node ("canonical-sparse") and
     weighted sums over such blocks, diagonal, linear and constant terms over the same x ("canonical-sparse-sum", moi.quad_plan).  Any
     literal consumer — expr(), a sum the sparse combine does not take (a dense block beside it, another x), quadratic_mode="literal" —
-    gets the error the literal rule gives for ragged rows."""
+    gets the error the literal rule gives for ragged rows.  `form`: the dest of transpose(x)*Q*x with a sparse Q instead ("canonical-sparse-form",
+    and a block of "canonical-sparse-sum"): the literal builder reads a dense matrix, so the same consumers and no others."""
 
-    def __init__(self, ctx, nq, nl):
+    def __init__(self, ctx, nq, nl, form=False):
         super().__init__(ctx, nq, nl, alloc=False)
+        self.form = form
 
     def materialize(self):
+        if self.form:
+            raise ArgumentError("transpose(x) * Q * x with a sparse Q has no literal form (the literal builder walks a dense matrix): the form, "
+                                "and weighted sums of it with sparse blocks dot(r, r), other sparse forms, dot(x, x), dot(x - v, x - v), dot(c, x) and "
+                                "scalar terms over the same x, have the canonical sparse form, with quadratic_mode 'auto' or 'canonical' and "
+                                "handoff 'moi' or 'device'; a dense block or a dense form beside it, or another x, has none")
         raise ArgumentError("dot of two Vector{AffineFunction} needs rows of equal length on the device (a sparse residual has no literal form: "
-                            "dot(r, r) and weighted sums of such blocks with dot(x, x), dot(x - v, x - v), dot(c, x) and scalar terms over the same x "
-                            "have the canonical sparse form, with quadratic_mode 'auto' or 'canonical' and handoff 'moi' or 'device')")
+                            "dot(r, r) and weighted sums of such blocks with sparse forms transpose(x)*Q*x, dot(x, x), dot(x - v, x - v), dot(c, x) and "
+                            "scalar terms over the same x have the canonical sparse form, with quadratic_mode 'auto' or 'canonical' and handoff 'moi' or 'device')")
 
 
 class _LazyRowTimesMatrix:
@@ -714,8 +721,42 @@ class QuadForm:
         self.mat, self.xvars = mat, xvars
 
 
+class SparseQuadForm:
+    """transpose(x) * Q * x with Q a sparse square matrix Parameter (its DSpMat: fixed pattern, nzval on the device) and x ONE Variable vector
+    in strictly increasing order: what the canonical node pmt_sparse_form_f64 reads (the r of an LsqTerm 'form'; moi.quad_plan tells it from
+    the dense QuadForm by its type)."""
+
+    def __init__(self, ctx, spmat, xvars):
+        self.ctx, self.spmat, self.xvars = ctx, spmat, xvars
+
+    def form_tables(self):
+        return self.spmat.form_tables(self.ctx)
+
+
+def _rule_sparse_bilinear(model, ctx, x, Q, y, dx, dQ, dy):
+    """transpose(x) * Q * x with a sparse Q: the canonical sparse form only (moi.quad_plan, csrc/sparse_form.hip).  The literal builder walks a
+    dense matrix (pmt_bilinear_f64), so there is no literal form (_NoLiteralQuad)."""
+    if (dQ.rows, dQ.cols) != (dx.n, dy.n):
+        raise DimensionMismatch("bilinearmul!: size(Q) != (length(x), length(y))")   # src/functions.jl:845
+    what = "transpose(x) * Q * y with a sparse Q has the canonical sparse form only, which needs "
+    if not isinstance(Q, Parameter):
+        raise ArgumentError(what + "Q to be a Parameter (a fixed-pattern sparse matrix)")
+    if not np.array_equal(dx.vars, dy.vars):
+        raise ArgumentError(what + "y to be the same Variable vector as x")
+    if not dx.strictly_increasing():
+        raise ArgumentError(what + "x to be distinct Variables in strictly increasing order (x is unsorted or repeats a Variable)")
+    if not (dQ.narrow and dQ.canonical_format()):
+        raise ArgumentError(what + "a canonical CSC pattern: rows strictly ascending within every column, no duplicate entries, fewer than "
+                            "2^32 non-zeros")
+    out = _NoLiteralQuad(ctx, dQ.nnz, 0, form=True)
+    node = DeviceNode(model, "bilinearmul!", _inputs(x, Q, y), out, lambda c: None)
+    return _with_lsq(node, [LsqTerm("form", r=SparseQuadForm(ctx, dQ, dx))], bare=True)
+
+
 def _rule_bilinear(model, ctx, x, Q, y):                                         # rule :219-226, builder :840-858
     dx, dQ, dy = _dv(ctx, x), _dv(ctx, Q), _dv(ctx, y)
+    if isinstance(dx, DVars) and isinstance(dy, DVars) and isinstance(dQ, DSpMat):
+        return _rule_sparse_bilinear(model, ctx, x, Q, y, dx, dQ, dy)
     if not (isinstance(dx, DVars) and isinstance(dy, DVars) and isinstance(dQ, DMat)):
         raise ArgumentError("transpose(x) * Q * y needs Variable vectors and a matrix")
     if (dQ.rows, dQ.cols) != (dx.n, dy.n):
@@ -739,7 +780,8 @@ def _rule_bilinear(model, ctx, x, Q, y):                                        
 class LsqTerm:
     """One term of a scalar node read as a weighted sum (DeviceNode.lsq_sum; moi.quad_plan chooses the record's canonical form from it):
       'block'     dot(r, r) / transpose(r)*r, r = A*x (+|-) b a Gram operand (r: its DDenseAff, or the DStackedAff of a stacked residual)
-      'form'      transpose(x) * Q * x, Q a matrix Parameter (r: its QuadForm); stands where a block stands in the combine
+      'form'      transpose(x) * Q * x, Q a matrix Parameter (r: its QuadForm; a sparse Q: its SparseQuadForm); stands where a block stands in
+                  the combine (a SparseQuadForm: where a sparse block stands in the sparse combine)
       'diag'      dot(x, x), or dot(x (+|-) v, x (+|-) v) with v a vector Parameter (xvars, vec, sign)
       'linear'    dot(c, x) / dot(x, c) with c a vector Parameter (xvars, vec)
       'constant'  a number (folded into scale) or a scalar Parameter (value)
@@ -1132,7 +1174,7 @@ def lazy(f, *args):
             return _rule_matvec(model, ctx, a, b)
         if ka == "spmat" and kb == "varvec":
             return _rule_spmatvec(model, ctx, a, b)
-        if ka == "tvarvec" and kb == "mat":
+        if ka == "tvarvec" and kb in ("mat", "spmat"):
             return _LazyRowTimesMatrix(model, a.parent, b)
         if ka == "rowmat":
             x, Q = (a.x, a.Q)

@@ -13,7 +13,7 @@ import numpy as np
 from ._lib import LT, QT, VAT, ArgumentError, DimensionMismatch, ErrorException
 from .device import DAff, DAffVec, DDenseAff, DQuad, DSparseAff, DStackedAff, DVarsAff, P
 from .functions import AffineFunction, LinearTerm, QuadraticFunction, QuadraticTerm, Variable, _isnum
-from .lazyexpression import DeviceNode, kind_of
+from .lazyexpression import DeviceNode, QuadForm, SparseQuadForm, kind_of
 
 MIN_SENSE, MAX_SENSE = "MIN_SENSE", "MAX_SENSE"
 
@@ -177,7 +177,7 @@ def _form_args(q, varmap_buf, alpha):                                    # the l
 
 class _Record:
     """Common part of Objective and Constraint (src/moi_interop.jl:113-129, 141-166)."""
-    mode = property(lambda self: self.plan.mode)                          # "literal" / "canonical" / "canonical-csc" / "-form" / "-sum" / "-groups" / "-sparse" / "-sparse-sum"
+    mode = property(lambda self: self.plan.mode)                          # "literal" / "canonical" / "canonical-csc" / "-form" / "-sum" / "-groups" / "-sparse" / "-sparse-form" / "-sparse-sum"
     lsq_terms = property(lambda self: self.plan.terms)                    # the LsqTerm list a "canonical-sum" record combines, or None
 
     def _setup(self, model, expr):
@@ -444,23 +444,41 @@ class _Record:
         return lambda c: c.call("pmt_sparse_gram_f64", P(r.spmat.buf), *T.call_args(r.rows), P(r.xvars.buf), P(vec), r.sign if vec else 0, 1,
                                 P(varmap_buf), P(dq), P(dl), P(dc))
 
+    def _compile_sparse_form(self, ctx, varmap_buf, handoff_varmap):
+        """transpose(x) * Q * x with a sparse Q (plan.form, a SparseQuadForm), the counterpart of _compile_sparse_gram: pmt_sparse_form_f64
+        streams the pattern's pair and source tables (DSpMat.form_tables, built here once) and writes the canonical MOI function — one
+        quadratic term per unordered pair with a stored entry, no linear terms, constant 0.0.  The index fields are static: written into the
+        host arrays here through the hand-off's map, where the generic route finds them; the kernel rewrites them through varmap_buf."""
+        form = self.plan.form
+        T = form.form_tables()
+        self.f = f = ScalarQuadraticFunction(0, T.nq, alloc=ctx.pinned_array)
+        x = form.xvars.vars if handoff_varmap is None else np.asarray(handoff_varmap, dtype=np.int64)[form.xvars.vars - 1]
+        f.quadratic_terms["row"], f.quadratic_terms["col"], f.quadratic_terms["coeff"] = x[T.pair_j], x[T.pair_k], 0.0
+        dq, dl, dc = self._twin(ctx, f.quadratic_terms, 24 * T.nq), self._twin(ctx, f.affine_terms, 0), self._twin(ctx, self._cbuf, 8)
+        self.dev = {"quad": dq, "lin": dl, "const": dc}                   # ("lin": no terms; the hand-off's generic route asks for the key)
+        return lambda c: c.call("pmt_sparse_form_f64", P(form.spmat.buf), *T.call_args(), P(form.xvars.buf), 1, P(varmap_buf), P(dq), P(dc))
+
     def _compile_sparse_sum(self, ctx, varmap_buf, handoff_varmap):
         """A weighted sum over sparse least-squares blocks, diagonal, linear and constant terms over one x (plan.terms; quad_plan:
         _sparse_sum_combines): every block by the unchanged pmt_sparse_gram_f64 (moi = 1) into its own scratch term lists, then ONE
         pmt_sparse_gram_sum_f64 weights and adds them through the gather tables of the symbolic merge (device.SparseSumTables, built here
         once) and writes every term of the MOI buffers once — also straight into the page-locked host arrays of a small model.  The index
         fields are static: written into the host arrays here through the hand-off's map, as _compile_sparse_gram does; the kernel rewrites
-        them through varmap_buf at every call."""
+        them through varmap_buf at every call.  A sparse form transpose(x)*Q*x among the blocks (LsqTerm 'form', a SparseQuadForm) is written
+        by pmt_sparse_form_f64 (moi = 1) into a scratch quad list and constant word of its own and described to the unchanged combine as a
+        block without linear terms: a 16-byte dummy `lin`, the all-0xFFFFFFFF `lin_at` the merge writes for nlin_b = 0."""
         from . import _lib
         from .device import SparseSumTables
         terms = self.plan.terms
-        blocks = [t for t in terms if t.kind == "block"]
+        blocks = [t for t in terms if t.kind in ("block", "form")]
         xv = blocks[0].r.xvars
         n = len(xv.vars)
-        kind = {"block": _lib.PMT_LSQ_BLOCK, "diag": _lib.PMT_LSQ_DIAG, "linear": _lib.PMT_LSQ_LINEAR, "constant": _lib.PMT_LSQ_CONSTANT}
+        # a sparse form stands where a block stands: its own scratch quad list and constant word (pmt_sparse_form_f64, moi = 1), no linear terms
+        kind = {"block": _lib.PMT_LSQ_BLOCK, "form": _lib.PMT_LSQ_BLOCK, "diag": _lib.PMT_LSQ_DIAG, "linear": _lib.PMT_LSQ_LINEAR,
+                "constant": _lib.PMT_LSQ_CONSTANT}
         lists = [np.searchsorted(xv.vars, t.xvars.vars).astype(np.int64) if t.kind in ("diag", "linear") and not np.array_equal(t.xvars.vars, xv.vars)
                  else None for t in terms]
-        Ts = [t.r.gram_tables() for t in blocks]
+        Ts = [t.r.form_tables() if t.kind == "form" else t.r.gram_tables() for t in blocks]
         S = SparseSumTables(ctx, n, Ts, [(kind[t.kind], t.kind == "diag" and t.vec is not None, p) for t, p in zip(terms, lists)])
         self.f = f = ScalarQuadraticFunction(S.nlin, S.nq, alloc=ctx.pinned_array)
         x = xv.vars if handoff_varmap is None else np.asarray(handoff_varmap, dtype=np.int64)[xv.vars - 1]
@@ -473,8 +491,8 @@ class _Record:
         desc, k = [], 0
         for i, t in enumerate(terms):
             d = {"kind": kind[t.kind], "scale": t.scale, "weight": t.param.buf if t.param is not None else None}
-            if t.kind == "block":
-                d["quad"], d["lin"], d["constant"] = parts[k]
+            if t.kind in ("block", "form"):
+                d["quad"], d["lin"], d["constant"] = parts[k]             # (a form's lin: a dummy allocation; its lin_at is all 0xFFFFFFFF)
                 d["quad_at"], d["lin_at"] = S.dev["quad_at"][k], S.dev["lin_at"][k]
                 k += 1
             elif t.kind in ("diag", "linear"):
@@ -491,6 +509,9 @@ class _Record:
         def emit(c):
             for t, T, part in zip(blocks, Ts, parts):
                 r = t.r
+                if t.kind == "form":
+                    c.call("pmt_sparse_form_f64", P(r.spmat.buf), *T.call_args(), P(r.xvars.buf), 1, P(varmap_buf), P(part[0]), P(part[2]))
+                    continue
                 vec = r.vec.buf if r.vec is not None else None
                 c.call("pmt_sparse_gram_f64", P(r.spmat.buf), *T.call_args(r.rows), P(r.xvars.buf), P(vec), r.sign if vec else 0, 1,
                        P(varmap_buf), P(part[0]), P(part[1]), P(part[2]))
@@ -498,7 +519,7 @@ class _Record:
                    S.nlin, P(xv.buf), P(varmap_buf), P(dq), P(dl), P(dc))
         return emit
 
-    _QUAD_FORMS = {"canonical-sparse": _compile_sparse_gram, "canonical-sparse-sum": _compile_sparse_sum, "literal": _compile_literal, "canonical": _compile_gram, "canonical-csc": _compile_gram, "canonical-form": _compile_form,
+    _QUAD_FORMS = {"canonical-sparse": _compile_sparse_gram, "canonical-sparse-form": _compile_sparse_form, "canonical-sparse-sum": _compile_sparse_sum, "literal": _compile_literal, "canonical": _compile_gram, "canonical-csc": _compile_gram, "canonical-form": _compile_form,
                    "canonical-sum": _compile_lsq_sum, "canonical-groups": _compile_groups}
 
     # ---- Vector{AffineFunction}
@@ -654,7 +675,7 @@ def _lsq_sum_combines(terms):
     holds at most PMT_LSQ_MAX_RUNS runs of positions)."""
     from . import _lib
     blocks = [t for t in terms or () if t.kind in ("block", "form")]
-    if any(isinstance(t.r, DSparseAff) for t in blocks):              # a sparse block: the dense combine cannot take it (_sparse_sum_combines)
+    if any(isinstance(t.r, (DSparseAff, SparseQuadForm)) for t in blocks):   # a sparse block or form: the dense combine cannot take it (_sparse_sum_combines)
         return False
     if any(t.host_scaled for t in terms or ()):                        # number * dot(u, u) multiplied on the host: the literal path, as before
         return False
@@ -675,9 +696,15 @@ def _lsq_sum_combines(terms):
     return runs <= _lib.PMT_LSQ_MAX_RUNS
 
 
+def _sparse_form_term(t):
+    """the LsqTerm is transpose(x)*Q*x with a sparse Q (lazyexpression._rule_bilinear made it only for a strictly increasing x and a canonical pattern)"""
+    return t is not None and t.kind == "form" and isinstance(t.r, SparseQuadForm)
+
+
 def _sparse_sum_combines(terms):
     """Whether pmt_sparse_gram_sum_f64 can combine this LsqTerm list: 1 .. PMT_LSQ_MAX_BLOCKS blocks, every one a sparse Gram operand
-    (DSparseAff.gram_operand) — no dense block, no form beside them —, at most PMT_LSQ_MAX_TERMS terms, every block over the same strictly
+    (DSparseAff.gram_operand) or a sparse form transpose(x)*Q*x (SparseQuadForm: it stands where a block stands and counts among them) — no
+    dense block, no dense form beside them —, at most PMT_LSQ_MAX_TERMS terms, every block over the same strictly
     increasing x, every diagonal / linear term over x or a strictly increasing part of it (_lsq_sum_combines' subset rule; the positions
     are held in tables, so there is no limit on their runs)."""
     from . import _lib
@@ -685,11 +712,11 @@ def _sparse_sum_combines(terms):
     blocks = [t for t in terms if t.kind in ("block", "form")]
     if not 1 <= len(blocks) <= _lib.PMT_LSQ_MAX_BLOCKS or len(terms) > _lib.PMT_LSQ_MAX_TERMS:
         return False
-    if not all(t.kind == "block" and isinstance(t.r, DSparseAff) and t.r.gram_operand() for t in blocks):
+    if not all(_sparse_form_term(t) or (t.kind == "block" and isinstance(t.r, DSparseAff) and t.r.gram_operand()) for t in blocks):
         return False
     x = blocks[0].r.xvars.vars
     for t in terms:
-        if t.kind == "block":
+        if t.kind in ("block", "form"):
             if not np.array_equal(t.r.xvars.vars, x):
                 return False
         elif t.xvars is not None and not np.array_equal(t.xvars.vars, x):
@@ -769,6 +796,11 @@ def quad_plan(terms, bare, kind, nq, is_objective, quadratic_mode, small, handof
         raise ArgumentError("dot(r, r) of a sparse residual C*x (+|-) d has the canonical sparse form only: %s is not available for it "
                             "(use quadratic_mode 'auto' or 'canonical' with handoff 'moi' or 'device')"
                             % ("quadratic_mode='literal'" if quadratic_mode == "literal" else "handoff='host_csc'"))
+    sform = one.r if _sparse_form_term(one) else None
+    if sform is not None and (quadratic_mode == "literal" or handoff == "host_csc"):
+        raise ArgumentError("transpose(x) * Q * x with a sparse Q has the canonical sparse form only: %s is not available for it "
+                            "(use quadratic_mode 'auto' or 'canonical' with handoff 'moi' or 'device')"
+                            % ("quadratic_mode='literal'" if quadratic_mode == "literal" else "handoff='host_csc'"))
     if kind != "quad" or quadratic_mode == "literal":
         return QuadPlan("literal" if kind == "quad" else None)
 
@@ -783,6 +815,10 @@ def quad_plan(terms, bare, kind, nq, is_objective, quadratic_mode, small, handof
     # boundary and the device hand-off, in small models and beyond
     if isinstance(block, DSparseAff):
         return QuadPlan("canonical-sparse", gram=block)
+    # transpose(x) * Q * x with a sparse Q: the sparse form node, under exactly the bare sparse block's conditions (the literal builder walks
+    # a dense matrix: no literal alternative either)
+    if sform is not None:
+        return QuadPlan("canonical-sparse-form", form=sform)
     # a weighted sum over sparse blocks, diagonal, linear and constant terms over one x: the blocks' sparse Gram nodes combined through
     # the merged pattern — like the bare node in "auto" too, for both boundaries, in small models and beyond, objective or constraint
     if sparse_sums and not bare and handoff in ("moi", "device") and _sparse_sum_combines(terms):
@@ -795,7 +831,7 @@ def quad_plan(terms, bare, kind, nq, is_objective, quadratic_mode, small, handof
             return gram_plan(block)
         # transpose(x) * Q * x alone (lazyexpression._rule_bilinear): the canonical node reads Q itself — MOI terms, or P's CSC values for
         # the device hand-off when x keeps its order under the optimizer's index map
-        if is_objective and bare and one.kind == "form" and (handoff == "moi" or (handoff == "device" and ordered(one.r.xvars))):
+        if is_objective and bare and one.kind == "form" and isinstance(one.r, QuadForm) and (handoff == "moi" or (handoff == "device" and ordered(one.r.xvars))):
             return QuadPlan("canonical-form", form=one.r)
         # a weighted sum of least-squares blocks over one x: combined from the blocks' Gram nodes — the MOI boundary of a model beyond the small plan only
         if is_objective and handoff == "moi" and not bare and _lsq_sum_combines(terms):
