@@ -326,6 +326,34 @@ int pmt_quad_gram_sum_sub_f64(int64_t cols, const pmt_lsq_term *terms, int nterm
 int pmt_quad_form_f64(const double *Q, int64_t ldq, int64_t n, const int64_t *xvar, int moi, const int64_t *varmap, double alpha,
                       pmt_quadratic_term *out_quad, double *out_P_values, pmt_linear_term *out_lin, double *out_const, void *stream);
 
+/* The tracking cost transpose(x (+|-) v) * Q * (x (+|-) v) as its canonical function, for the Q and x of pmt_quad_form_f64 and v a vector of
+ * n numbers: matvecmul! over the affine vector (src/functions.jl:800-822), vecdot! (:702-709 over :548-576: n^2 quadratic and n(n+1) linear
+ * terms), canonicalize! (:381-386) and the MOI copy (src/moi_interop.jl:45-62) in one pass over Q and two short launches.  With
+ * c_j = 0.0 + v_j (sign +1) or 0.0 - v_j (sign -1) — the constants of pmt_vars_addsub_f64 and of a PMT_LSQ_DIAG term — the function is
+ * the plain form's quadratic part plus lin = (Q + Q')c and the constant c'Qc = 0.5 * c'lin:
+ *   out_quad, out_P_values   word for word what pmt_quad_form_f64 writes for the same Q, xvar, moi, varmap and alpha.
+ *   out_lin[j] = (lin_j, vm[xvar[j]]) (moi == 0: native indices), *out_const = the constant; the same in both index modes.
+ * The arithmetic is fixed — plain multiplies and adds, no fma, independent of launch geometry, timing and streams:
+ *   S[j,k]   = Q[j,k] + Q[k,j] for j != k (the rounded sum the quadratic term holds, bitwise symmetric), S[j,j] = 2*Q[j,j];
+ *   P[B][j]  = ((S[j,k0]*c_k0 + S[j,k0+1]*c_{k0+1}) + ..) + S[j,k1]*c_k1 over column block B = columns k0 = 64 B .. k1 = min(64 B + 63, n-1),
+ *              ascending, the first product starting the chain (no 0.0 +);
+ *   lin_j    = ((P[0][j] + P[1][j]) + ..) + P[nb-1][j], nb = ceil(n / 64) blocks in order;
+ *   constant = 0.5 * T, T = sum_j c_j*lin_j in S_d's order of pmt_quad_gram_sum_f64: 256 chains (chain t adds j = t, t + 256, .. in order
+ *              onto 0.0), then the halving tree (t += t + 128, t + 64, ..).
+ * The outputs stand wherever a least-squares block's stand in pmt_quad_gram_sum_f64 / _sum_sub_f64, like the plain form's.  `workspace`
+ * (device, pmt_quad_form_shift_workspace_bytes(n) = 8 * (ceil(n/64) + 1) * n bytes, host arithmetic) holds P and, in its last row, the
+ * products c_j*lin_j (written only when out_const is given); every entry is written once per call
+ * before it is read, so it needs no zeroing.  At least one of out_quad / out_P_values; out_lin and out_const are optional.  A null Q, xvar,
+ * v or workspace, a sign other than +-1, n < 1 (or beyond 2^21), ldq < n, moi != 0 without a varmap: PMT_INVALID_ARGUMENT before any device
+ * call.  Three launches behind each other on the stream (csrc/form.hip): the tile kernel of the plain form, whose workgroup (J, K) also adds
+ * the chains of its rows and, off the diagonal, of its columns from the S it holds in LDS; one thread per j adds the blocks, stores the
+ * linear term and leaves c_j*lin_j; one workgroup adds those n products into the constant (only when out_const is given).  Stream order
+ * alone orders them: no workgroup waits for another, no floating-point atomics. */
+int64_t pmt_quad_form_shift_workspace_bytes(int64_t n);
+int pmt_quad_form_shift_f64(const double *Q, int64_t ldq, int64_t n, const int64_t *xvar, const double *v, int sign, int moi,
+                            const int64_t *varmap, double alpha, pmt_quadratic_term *out_quad, double *out_P_values,
+                            pmt_linear_term *out_lin, double *out_const, void *workspace, void *stream);
+
 /* A sum whose least-squares blocks and forms lie over 2 .. PMT_QUAD_MAX_GROUPS pairwise DISJOINT, strictly increasing Variable vectors
  * (transpose(x)*Q*x + transpose(u)*R*u; dot(r1, r1) + w*dot(r2, r2) with r1 over x and r2 over u) as one canonical MOI function.  No pair
  * (j, k) is shared between two groups, so canonicalize! (src/functions.jl:381-386) combines nothing across them.  With z the sorted union

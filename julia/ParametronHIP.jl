@@ -180,6 +180,15 @@ quad_form!(out_quad, out_P_values, out_lin, out_const, Q, ldq, n, xvar, moi, var
                 (DevPtr, Int64, Int64, DevPtr, Cint, DevPtr, Cdouble, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
                 Q, ldq, n, xvar, moi, varmap, alpha, out_quad, out_P_values, out_lin, out_const, stream))
 
+"transpose(x ± v) * Q * (x ± v) as its canonical function (matvecmul! src/functions.jl:800-822, vecdot! :702-709 over :548-576, canonicalize!
+ :381-386, MOI copy src/moi_interop.jl:45-62): quad_form!'s quadratic part, lin = (Q + Q')c and the constant c'Qc with c = 0.0 ± v, in the
+ order include/parametron_hip.h fixes; `workspace`: quad_form_shift_workspace_bytes(n) device bytes, no zeroing"
+quad_form_shift!(out_quad, out_P_values, out_lin, out_const, Q, ldq, n, xvar, v, sign, moi, varmap, alpha, workspace, stream) =
+    check(ccall((:pmt_quad_form_shift_f64, lib), Cint,
+                (DevPtr, Int64, Int64, DevPtr, DevPtr, Cint, Cint, DevPtr, Cdouble, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
+                Q, ldq, n, xvar, v, sign, moi, varmap, alpha, out_quad, out_P_values, out_lin, out_const, workspace, stream))
+quad_form_shift_workspace_bytes(n) = ccall((:pmt_quad_form_shift_workspace_bytes, lib), Int64, (Int64,), n)
+
 "rows of the groups' canonical functions (an arena, src_quad / src_lin) placed in the function over the sorted union of their disjoint
  variable sets: device tables row_src (nrows), row_dst (nrows + 1) in 8-byte words, lin_src (nlin) — include/parametron_hip.h"
 quad_groups_gather!(out_quad, out_lin, src_quad, row_src, row_dst, nrows, nterms, src_lin, lin_src, nlin, stream) =

@@ -164,6 +164,8 @@ SIGNATURES = {
     "pmt_quad_gram_sum_sub_f64": (_ci, [_i64, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pmt_affine_stack_columns_f64": (_ci, [_vp, _i64, _i64, _vp, _i64, _vp]),
     "pmt_quad_form_f64": (_ci, [_vp, _i64, _i64, _vp, _ci, _vp, _f64, _vp, _vp, _vp, _vp, _vp]),
+    "pmt_quad_form_shift_workspace_bytes": (_i64, [_i64]),
+    "pmt_quad_form_shift_f64": (_ci, [_vp, _i64, _i64, _vp, _vp, _ci, _ci, _vp, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pmt_quad_groups_gather_f64": (_ci, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
     "pmt_quad_groups_constant_f64": (_ci, [_vp, _ci, _vp, _vp]),
     "pmt_fetch_synchronize": (_ci, [_vp]),

@@ -481,7 +481,24 @@ def _rule_spmatvec(model, ctx, A, x):
     return DeviceNode(model, "matvecmul!", _inputs(A, x), out, lambda c: _emit_sparse_terms(c, out))
 
 
-def _rule_matvec(model, ctx, A, x):
+class _DeferredMatVec(DAffVec):
+    """A * e for e a Vector{AffineFunction}, as the inner node of transpose(e) * A * e (_rule_bilinear): the rows * cols * row_len
+    LinearTerms exist only once a literal consumer asks (`materialized`, from the consumer's prepare) — a canonical record reads A itself."""
+
+    def __init__(self, ctx, rows, row_len, operand):
+        super().__init__(ctx, rows, row_len=row_len, alloc=False)
+        self.operand = operand
+
+    def materialized(self):
+        if self.terms is None:
+            self.operand.materialized()
+            self.terms = self.ctx.alloc(16 * max(self.nterms, 1))
+            self.consts = self.ctx.alloc(8 * max(self.rows, 1))
+        return self
+
+
+def _rule_matvec(model, ctx, A, x, defer=False):
+    """`defer`: an affine operand's product keeps its buffers unallocated until a literal consumer asks (_DeferredMatVec)"""
     dA, dx = _dv(ctx, A), _dv(ctx, x)
     if dA.cols != _vec_len(dx):
         raise DimensionMismatch("matvecmul!: size(A, 2) != length(x)")          # src/functions.jl:781
@@ -491,6 +508,16 @@ def _rule_matvec(model, ctx, A, x):
         def emit(c):
             if out.need_terms:
                 c.call("pmt_affine_assemble_f64", P(dA.buf), dA.lda, dA.rows, dA.cols, P(dx.buf), None, 0, P(out.terms), P(out.consts))
+        return DeviceNode(model, "matvecmul!", _inputs(A, x), out, emit)
+    if isinstance(dx, DAffVec) and defer:                                        # builder :800-822, on demand
+        if not dx.uniform():
+            raise ArgumentError("matrix * Vector{AffineFunction} needs rows of equal length on the device")
+        out = _DeferredMatVec(ctx, dA.rows, dA.cols * dx.row_len, dx)
+
+        def emit(c):
+            if out.terms is None:
+                return                                                           # no literal consumer: nothing reads the product
+            c.call("pmt_matvecmul_affs_f64", P(dA.buf), dA.lda, dA.rows, dA.cols, P(dx.terms), dx.row_len, P(dx.consts), P(out.terms), P(out.consts))
         return DeviceNode(model, "matvecmul!", _inputs(A, x), out, emit)
     if isinstance(dx, DAffVec):                                                  # builder :800-822
         X = dx.materialized()
@@ -672,8 +699,7 @@ def _rule_dot(model, ctx, x, y):                                                
         if dx is dy and isinstance(dx, (DDenseAff, DStackedAff)):
             # dot(r, r): a Gram operand — a stacked r once the model asks for its stacked matrix (moi.quad_plan, Model.initialize)
             return _with_lsq(node, [LsqTerm("block", r=dx)], bare=True)
-        if isinstance(dx, DVarsAff) and isinstance(dy, DVarsAff) and np.array_equal(dx.xvars.vars, dy.xvars.vars) and dx.sign == dy.sign and \
-                dx.vec is not None and dy.vec is not None and dx.vec.buf == dy.vec.buf:
+        if _same_shifted_vector(dx, dy):
             return _with_lsq(node, [LsqTerm("diag", xvars=dx.xvars, vec=dx.vec, sign=dx.sign)])          # dot(x (+|-) v, x (+|-) v)
         return node
     raise ArgumentError("dot(%s, %s) is not supported on the device" % (kind_of(dx), kind_of(dy)))
@@ -715,10 +741,11 @@ class _LazyRowTimesMatrix:
 
 class QuadForm:
     """transpose(x) * Q * x with Q a dense square matrix Parameter on the device and x ONE Variable vector in strictly increasing order: what
-    the canonical node pmt_quad_form_f64 reads (the r of an LsqTerm 'form')."""
+    the canonical node pmt_quad_form_f64 reads (the r of an LsqTerm 'form').  With `vec` (a vector Parameter's DVec) and `sign` (+1 | -1) the
+    shifted form transpose(x (+|-) v) * Q * (x (+|-) v), the node pmt_quad_form_shift_f64; None, 0: the plain form."""
 
-    def __init__(self, mat, xvars):
-        self.mat, self.xvars = mat, xvars
+    def __init__(self, mat, xvars, vec=None, sign=0):
+        self.mat, self.xvars, self.vec, self.sign = mat, xvars, vec, sign
 
 
 class SparseQuadForm:
@@ -753,8 +780,32 @@ def _rule_sparse_bilinear(model, ctx, x, Q, y, dx, dQ, dy):
     return _with_lsq(node, [LsqTerm("form", r=SparseQuadForm(ctx, dQ, dx))], bare=True)
 
 
+def _same_shifted_vector(dx, dy):
+    """both sides are x (+|-) v with equal Variables, the same vector buffer and the same sign (the test of dot(x (+|-) v, x (+|-) v), _rule_dot)"""
+    return isinstance(dx, DVarsAff) and isinstance(dy, DVarsAff) and np.array_equal(dx.xvars.vars, dy.xvars.vars) and dx.sign == dy.sign and \
+        dx.vec is not None and dy.vec is not None and dx.vec.buf == dy.vec.buf
+
+
+def _rule_shifted_bilinear(model, ctx, x, Q, y, dx, dQ, dy):
+    """transpose(x) * Q * y with x or y a shifted Variable vector x (+|-) v and a dense Q.  The literal function is dot(x, Q*y) built by the
+    rules of that spelling (matvecmul! over the affine vector src/functions.jl:800-822, vecdot! :702-709): the same record, bit for bit, with
+    buffers only once a literal consumer asks.  transpose(e) * Q * e over ONE e = x (+|-) v, x strictly increasing, Q a matrix Parameter, is
+    the tracking cost: the canonical objective reads Q and v themselves (moi.py, pmt_quad_form_shift_f64).  Every other mix is literal only."""
+    if (dQ.rows, dQ.cols) != (_vec_len(dx), _vec_len(dy)):
+        raise DimensionMismatch("bilinearmul!: size(Q) != (length(x), length(y))")   # src/functions.jl:845
+    if isinstance(dQ, DSpMat):
+        raise ArgumentError("transpose(x) * Q * y with a sparse Q has the canonical sparse form only, which needs x and y to be Variable "
+                            "vectors: a shifted vector x (+|-) v beside a sparse Q is not supported (a dense Q Parameter takes it)")
+    node = _rule_dot(model, ctx, x, _rule_matvec(model, ctx, Q, y, defer=True))
+    if isinstance(Q, Parameter) and _same_shifted_vector(dx, dy) and dx.rows >= 1 and dx.xvars.strictly_increasing():
+        return _with_lsq(node, [LsqTerm("form", r=QuadForm(dQ, dx.xvars, dx.vec, dx.sign))], bare=True)
+    return node
+
+
 def _rule_bilinear(model, ctx, x, Q, y):                                         # rule :219-226, builder :840-858
     dx, dQ, dy = _dv(ctx, x), _dv(ctx, Q), _dv(ctx, y)
+    if all(isinstance(d, (DVars, DVarsAff)) for d in (dx, dy)) and not all(isinstance(d, DVars) for d in (dx, dy)) and isinstance(dQ, (DMat, DSpMat)):
+        return _rule_shifted_bilinear(model, ctx, x, Q, y, dx, dQ, dy)
     if isinstance(dx, DVars) and isinstance(dy, DVars) and isinstance(dQ, DSpMat):
         return _rule_sparse_bilinear(model, ctx, x, Q, y, dx, dQ, dy)
     if not (isinstance(dx, DVars) and isinstance(dy, DVars) and isinstance(dQ, DMat)):
@@ -781,7 +832,8 @@ class LsqTerm:
     """One term of a scalar node read as a weighted sum (DeviceNode.lsq_sum; moi.quad_plan chooses the record's canonical form from it):
       'block'     dot(r, r) / transpose(r)*r, r = A*x (+|-) b a Gram operand (r: its DDenseAff, or the DStackedAff of a stacked residual)
       'form'      transpose(x) * Q * x, Q a matrix Parameter (r: its QuadForm; a sparse Q: its SparseQuadForm); stands where a block stands in
-                  the combine (a SparseQuadForm: where a sparse block stands in the sparse combine)
+                  the combine (a SparseQuadForm: where a sparse block stands in the sparse combine).  A QuadForm with vec / sign: the
+                  shifted form transpose(x (+|-) v) * Q * (x (+|-) v), a block with a non-zero affine part
       'diag'      dot(x, x), or dot(x (+|-) v, x (+|-) v) with v a vector Parameter (xvars, vec, sign)
       'linear'    dot(c, x) / dot(x, c) with c a vector Parameter (xvars, vec)
       'constant'  a number (folded into scale) or a scalar Parameter (value)
@@ -1134,6 +1186,11 @@ def _source_parameters(args):
     return out
 
 
+def _is_shifted_row(a):
+    """transpose(x (+|-) v) of a shifted Variable vector: the only affine row a matrix may follow (_rule_bilinear)"""
+    return isinstance(a, Transpose) and isinstance(a.parent, DeviceNode) and isinstance(a.parent.out, DVarsAff)
+
+
 def lazy(f, *args):
     """optimize_toplevel(LazyExpression(f, args...)) — src/lazyexpression.jl:184-193."""
     if not any(_is_lazy(a) or isinstance(a, _LazyRowTimesMatrix) or (isinstance(a, Transpose) and _is_lazy(a.parent)) for a in args):
@@ -1166,7 +1223,7 @@ def lazy(f, *args):
         return DerivedParameter(recompute, _source_parameters(args), model)
     ctx = model.device()
     if f == "*":
-        if len(args) == 3 and kinds[0] == "tvarvec":
+        if len(args) == 3 and kinds[0] in ("tvarvec", "taffvec"):                # (bilinear(r, Q, r) over a residual: the rule's refusal)
             return _rule_bilinear(model, ctx, args[0].parent, args[1], args[2])
         a, b = args
         ka, kb = kinds
@@ -1174,7 +1231,7 @@ def lazy(f, *args):
             return _rule_matvec(model, ctx, a, b)
         if ka == "spmat" and kb == "varvec":
             return _rule_spmatvec(model, ctx, a, b)
-        if ka == "tvarvec" and kb in ("mat", "spmat"):
+        if (ka == "tvarvec" or _is_shifted_row(a)) and kb in ("mat", "spmat"):
             return _LazyRowTimesMatrix(model, a.parent, b)
         if ka == "rowmat":
             x, Q = (a.x, a.Q)

@@ -171,8 +171,23 @@ def _gram_workspace(ctx, g):
     return ctx.alloc(max(16, int(ctx.lib.pmt_quad_gram_workspace_bytes(_gram_rows(g), g.mat.cols))))
 
 
-def _form_args(q, varmap_buf, alpha):                                    # the leading arguments of pmt_quad_form_f64
+def _form_args(q, varmap_buf, alpha):                                    # the leading arguments of pmt_quad_form_f64 / _shift_f64
+    if q.vec is not None:
+        return (P(q.mat.buf), q.mat.lda, q.mat.cols, P(q.xvars.buf), P(q.vec.buf), q.sign, 1, P(varmap_buf), alpha)
     return (P(q.mat.buf), q.mat.lda, q.mat.cols, P(q.xvars.buf), 1, P(varmap_buf), alpha)
+
+
+def _form_call(c, q, varmap_buf, alpha, outs, ws):
+    """the form node's call: pmt_quad_form_f64, or pmt_quad_form_shift_f64 with its workspace `ws` for a shifted form (q.vec)"""
+    if q.vec is not None:
+        c.call("pmt_quad_form_shift_f64", *_form_args(q, varmap_buf, alpha), *outs, P(ws))
+    else:
+        c.call("pmt_quad_form_f64", *_form_args(q, varmap_buf, alpha), *outs)
+
+
+def _form_workspace(ctx, q):
+    """the partial sums of a shifted form's linear part (allocated at compile: update! allocates nothing); a plain form has none"""
+    return ctx.alloc(max(16, int(ctx.lib.pmt_quad_form_shift_workspace_bytes(q.mat.cols)))) if q.vec is not None else None
 
 
 class _Record:
@@ -306,10 +321,17 @@ class _Record:
 
     def _compile_form(self, ctx, varmap_buf, handoff_varmap):
         """transpose(x) * Q * x alone (plan.form): pmt_quad_form_f64 reads the Parameter matrix and writes the canonical
-        MOI function — n(n+1)/2 quadratic terms, no linear terms, constant 0.0 — or, for the device hand-off, the CSC values of P."""
+        MOI function — n(n+1)/2 quadratic terms, no linear terms, constant 0.0 — or, for the device hand-off, the CSC values of P.
+        A shifted form transpose(x (+|-) v) * Q * (x (+|-) v) (MOI boundary only, quad_plan): pmt_quad_form_shift_f64 writes the same
+        quadratic terms, n linear terms and the constant."""
         form = self.plan.form
         n = form.mat.cols
         nq = n * (n + 1) // 2
+        if form.vec is not None:
+            self.f = ScalarQuadraticFunction(n, nq, alloc=ctx.pinned_array)
+            dq, dl, dc, ws = ctx.alloc(24 * nq), ctx.alloc(16 * n), ctx.alloc(8), _form_workspace(ctx, form)
+            self.dev = {"quad": dq, "lin": dl, "const": dc}
+            return lambda c: _form_call(c, form, varmap_buf, 1.0, (P(dq), None, P(dl), P(dc)), ws)
         if handoff_varmap is not None:
             self.f = ScalarQuadraticFunction(n, 0, alloc=ctx.pinned_array)
             dp, dl, dc = ctx.alloc(8 * nq), ctx.alloc(16 * n), ctx.alloc(8)
@@ -342,7 +364,7 @@ class _Record:
         g1 = blocks[0].r
         n = g1.mat.cols
         nq = n * (n + 1) // 2
-        ws = [_gram_workspace(ctx, t.r) if t.kind == "block" else None for t in blocks]
+        ws = [_gram_workspace(ctx, t.r) if t.kind == "block" else _form_workspace(ctx, t.r) for t in blocks]
         # per block 2..K: its CSC values, linear terms and constant
         parts = [(ctx.alloc(8 * max(nq, 1)), ctx.alloc(16 * max(n, 1)), ctx.alloc(8)) for _ in blocks[1:]]
         desc, k = [], 0
@@ -376,7 +398,7 @@ class _Record:
         def emit_block(c, t, w, first, part):
             if t.kind == "form":
                 outs = (P(dq), None, P(dl), P(dc)) if first else (None, P(part[0]), P(part[1]), P(part[2]))
-                c.call("pmt_quad_form_f64", *_form_args(t.r, varmap_buf, 1.0), *outs)
+                _form_call(c, t.r, varmap_buf, 1.0, outs, w)
             elif first:
                 c.call("pmt_quad_gram_f64", *_gram_args(t.r), 1, P(varmap_buf), P(dq), P(dl), P(dc), P(w))
             else:
@@ -830,8 +852,10 @@ def quad_plan(terms, bare, kind, nq, is_objective, quadratic_mode, small, handof
         if isinstance(block, DStackedAff) and block.xvars.strictly_increasing():
             return gram_plan(block)
         # transpose(x) * Q * x alone (lazyexpression._rule_bilinear): the canonical node reads Q itself — MOI terms, or P's CSC values for
-        # the device hand-off when x keeps its order under the optimizer's index map
-        if is_objective and bare and one.kind == "form" and isinstance(one.r, QuadForm) and (handoff == "moi" or (handoff == "device" and ordered(one.r.xvars))):
+        # the device hand-off when x keeps its order under the optimizer's index map.  A shifted form transpose(x (+|-) v) * Q * (x (+|-) v): the
+        # MOI boundary only (the CSC shortcut has no place for its linear part q yet: the literal function + canonicalize! as any other quadratic)
+        if is_objective and bare and one.kind == "form" and isinstance(one.r, QuadForm) and \
+                (handoff == "moi" or (handoff == "device" and one.r.vec is None and ordered(one.r.xvars))):
             return QuadPlan("canonical-form", form=one.r)
         # a weighted sum of least-squares blocks over one x: combined from the blocks' Gram nodes — the MOI boundary of a model beyond the small plan only
         if is_objective and handoff == "moi" and not bare and _lsq_sum_combines(terms):
