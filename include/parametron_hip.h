@@ -743,6 +743,31 @@ int pmt_batch_expand_f64(const double *slab, int64_t n, int64_t m, const int64_t
                          pmt_quadratic_term *out_quad, pmt_linear_term *out_lin, double *out_const,
                          pmt_vector_affine_term *out_vat, double *out_vconsts, void *stream);
 
+/* The batch whose objective is the tracking cost transpose(x (+|-) p_i) * Q_i * (x (+|-) p_i) — every instance with a weight matrix and a
+ * reference of its own — over the constraint block C_i*x (+|-) d_i: one slab per instance at out + i * out_stride, in the layout above
+ * (pmt_batch_lsq_slab_doubles(n, m) doubles; out_stride >= that; the words between two slabs are never written), so pmt_batch_expand_f64,
+ * pmt_batch_allgather_f64 and the chunk arithmetic take it as it is.  Inputs are instance-major: Q[B][n*n] column-major with leading
+ * dimension n (it need not be symmetric), p[B][n], C[B][m*n] column-major, d[B][m].  The contents are fixed bit for bit — plain multiplies
+ * and adds, no fma, independent of B, of the instance's position, of launch geometry and timing:
+ *   Q section   at tri(j,k) = j*n - j*(j-1)/2 + k - j: S[j,k] = Q[j,k] + Q[k,j] for j < k, 2*Q[j,j] on the diagonal — the moi = 1 coefficients
+ *               of pmt_quad_form_f64.
+ *   q, const    sign_p = +-1, c = 0.0 (+|-) p: q[j] = lin_j and const = 0.5 * T in the order fixed above for pmt_quad_form_shift_f64, word
+ *               for word: P[Bk][j] = ((S[j,k0]*c_k0 + S[j,k0+1]*c_{k0+1}) + ..) + S[j,k1]*c_k1 over column block Bk = columns k0 = 64 Bk ..
+ *               k1 = min(64 Bk + 63, n-1), the first product starting the chain; lin_j = ((P[0][j] + P[1][j]) + ..) + P[nb-1][j], the
+ *               nb = ceil(n / 64) blocks in order; T = sum_j c_j*lin_j by 256 chains onto 0.0 (n <= 256: chain t holds 0.0 + c_t*lin_t),
+ *               then the halving tree (t += t + 128, t + 64, ..).  The slab equals what that node writes for the instance alone.
+ *               sign_p == 0: q and const are +0.0 and p may be NULL — the plain form, pmt_quad_form_f64 with out_lin / out_const.
+ *   C, d-consts as pmt_batch_lsq_coeffs_f64: C row-major, 0.0 (+|-) d, +0.0 with sign_d == 0 (d must still be valid).
+ * Edge cases, each a complete slab: m == 0: [Q | q | const]; n == 0: [+0.0 | d-consts]; B == 0: PMT_OK without a launch, whatever the
+ * pointers.  A negative dimension, n > PMT_BATCH_FORM_MAX_N or out_stride below the slab length: PMT_DIMENSION_MISMATCH; a sign outside
+ * {-1, 0, 1} or a null pointer where data is needed: PMT_INVALID_ARGUMENT — all before any device call.  One launch (csrc/batch_form.hip):
+ * one workgroup per instance walks its 64 x 64 tile pairs as pmt_quad_form_shift_f64's tile kernel does and keeps the chains P in LDS
+ * where that node has its workspace; no workspace, no atomics, no workgroup waits for another.  Algorithmic bytes per instance:
+ * 8 (n^2 + n + m n + m) read, 8 L written. */
+#define PMT_BATCH_FORM_MAX_N 256
+int pmt_batch_form_coeffs_f64(const double *Q, const double *p, const double *C, const double *d, int64_t B, int64_t n, int64_t m, int sign_p,
+                              int sign_d, double *out, int64_t out_stride, void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * Device-side Parameter update callbacks for synthetic inputs (counter-based):
  * dst[i] = scale * U[0,1)(seed, i)   — the analogue of `Parameter(rand!, zeros(n, n), model)` README.md:36-43

@@ -589,6 +589,14 @@ batch_step!(comm::Ptr{Cvoid}, A::DevPtr, b::DevPtr, C::DevPtr, d::DevPtr, per_ra
                 (Ptr{Cvoid}, DevPtr, DevPtr, DevPtr, DevPtr, Int64, Int64, Int64, Int64, Cint, Cint, DevPtr, DevPtr, Int64, Int64, Ptr{Cvoid}),
                 comm, A, b, C, d, per_rank, n, r, m, -1, -1, local_slabs, gathered, stride, chunk, stream))
 
+"one slab [Q | q | const | C | d-consts] per instance for the batch of tracking costs transpose(x ± p_i) * Q_i * (x ± p_i) over C_i*x ± d_i
+ (n <= 256): instance-major Q (column-major, need not be symmetric), p, C, d; the layout of the least-squares batch, the Q / q / const of
+ quad_form_shift! for the instance alone bit for bit; sign_p == 0: the plain form"
+batch_form_coeffs!(out::DevPtr, out_stride, Q::DevPtr, p::DevPtr, C::DevPtr, d::DevPtr, B, n, m, sign_p, sign_d, stream) =
+    check(ccall((:pmt_batch_form_coeffs_f64, lib), Cint,
+                (DevPtr, DevPtr, DevPtr, DevPtr, Int64, Int64, Int64, Cint, Cint, DevPtr, Int64, Ptr{Cvoid}),
+                Q, p, C, d, B, n, m, sign_p, sign_d, out, out_stride, stream))
+
 "the same callback RECORDED with its seed in a host word (`Ref{UInt64}`, kept alive by the caller): every replay draws the stream of the
 seed the word holds then — `seed[] += 1000` before `update!(plan)` is the whole callback"
 device_uniform_dyn!(dst::DevPtr, rows, cols, lda, seed::Ref{UInt64}, scale, stream) =

@@ -162,6 +162,54 @@ class BatchLSQ:
                   self.m, -1, -1, self._p(self.local), self._p(self.gathered), self.L, int(chunk), self.stream)
 
 
+class BatchTracking:
+    """Device-resident batch of tracking costs transpose(x - p_i) * Q_i * (x - p_i) over C_i*x == d_i (many small MPC instances, each with a
+    weight matrix and a reference of its own): Q[B][n x n], p[B][n], C[B][m x n], d[B][m] generated by the counter-based stream with GLOBAL
+    element offsets, so instance k holds the same data whatever the sharding.  One launch of pmt_batch_form_coeffs_f64 writes the slabs, in
+    the layout of BatchLSQ's — slab_layout, gather_slabs and pmt_batch_expand_f64 apply as they are.  There is no pipelined exchange for
+    this objective (pmt_batch_step_f64 computes the least-squares slabs): step() is compute() and one all-gather."""
+
+    SEEDS = {"Q": 201, "p": 202, "C": 203, "d": 204}
+
+    def __init__(self, torch, total, n, m, rank=0, world=1, device=None):
+        _lib.require_gpu()
+        self.torch, self.total, self.n, self.m, self.rank, self.world = torch, total, n, m, rank, world
+        self.lo, self.hi = shard_range(total, rank, world)
+        self.B = self.hi - self.lo
+        dev = device or torch.device("cuda", torch.cuda.current_device())
+        f64 = torch.float64
+        self.Q = torch.empty(self.B * n * n, dtype=f64, device=dev)
+        self.p = torch.empty(self.B * n, dtype=f64, device=dev)
+        self.Cm = torch.empty(self.B * m * n, dtype=f64, device=dev)
+        self.d = torch.empty(self.B * m, dtype=f64, device=dev)
+        self.offsets, self.L = slab_layout(n, m)
+        self.local = torch.empty((self.B, self.L), dtype=f64, device=dev)
+        self.gathered = torch.empty((total, self.L), dtype=f64, device=dev) if world > 1 else self.local
+        self.stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        self.regenerate(0)
+
+    _p = staticmethod(BatchLSQ._p)
+
+    def regenerate(self, epoch):
+        """device-side Parameter callbacks (↔ rand! in README.md:36-43), one stream per Parameter and epoch"""
+        n, m = self.n, self.m
+        for name, buf, per, scale in (("Q", self.Q, n * n, 1.0), ("p", self.p, n, 1.0), ("C", self.Cm, m * n, 1.0), ("d", self.d, m, 2.0)):
+            _lib.call("pmt_fill_uniform_offset_f64", self._p(buf), self.B * per, C.c_uint64(self.SEEDS[name] + 1000 * epoch),
+                      C.c_uint64(self.lo * per), scale, self.stream)
+
+    def compute(self):
+        _lib.call("pmt_batch_form_coeffs_f64", self._p(self.Q), self._p(self.p), self._p(self.Cm), self._p(self.d), self.B, self.n, self.m,
+                  -1, -1, self._p(self.local), self.L, self.stream)
+
+    def gather(self, dist):
+        if self.world > 1:
+            gather_slabs(dist, self.local, self.gathered)
+
+    def step(self, dist):
+        self.compute()
+        self.gather(dist)
+
+
 TOTAL, N, R, M = 8192, 128, 128, 16        # BASELINE config 4 (m is not stated there: 16, SURVEY.md section 8d)
 
 
