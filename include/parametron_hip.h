@@ -768,6 +768,44 @@ int pmt_batch_expand_f64(const double *slab, int64_t n, int64_t m, const int64_t
 int pmt_batch_form_coeffs_f64(const double *Q, const double *p, const double *C, const double *d, int64_t B, int64_t n, int64_t m, int sign_p,
                               int sign_d, double *out, int64_t out_stride, void *stream);
 
+/* Horizon stage costs: a sum of T >= 1 stages over pairwise DISJOINT, strictly increasing Variable vectors x_t as one canonical MOI function
+ * from one launch — J = sum_t transpose(x_t - r_t)*Q*(x_t - r_t) + transpose(u_t)*R*u_t, what a model-predictive controller writes.  Stage t
+ * is transpose(x_t (+|-) v_t) * Q_t * (x_t (+|-) v_t) (sign = +-1), or the plain form transpose(x_t) * Q_t * x_t (sign == 0, vec may be NULL);
+ * many stages may name the same Q.  No pair (j, k) is shared between two stages, so canonicalize! (src/functions.jl:381-386) combines
+ * nothing across them.  The caller builds a DEVICE array of descriptors once; indices go through the varmap (moi = 1, alpha = 1.0):
+ *   quadratic terms  stage t writes its n(n+1)/2 terms at out_quad + quad_at, row j holding its columns k >= j at tri(j,k) = j*n - j*(j-1)/2 + k - j;
+ *                    every word equals what pmt_quad_form_f64 / pmt_quad_form_shift_f64 writes for that stage alone with the same Q, xvar,
+ *                    varmap, moi = 1 and alpha = 1.0.  quad_at may be odd: an address 8 mod 16.
+ *   linear terms     stage t writes n terms at out_lin + lin_at: (lin_j, vm[xvar[j]]), lin_j in the order fixed above for
+ *                    pmt_quad_form_shift_f64 (64-column chains, the first product starting the chain, then the blocks in order), word for
+ *                    word; a plain stage writes (0.0, vm[xvar[j]]).
+ *   constant         stage_consts[t] = 0.5 * T_t, T_t = sum_j c_j*lin_j in that node's chain-then-tree order (n <= 256: chain j holds
+ *                    0.0 + c_j*lin_j); a plain stage contributes +0.0.  *out_const = the sum of stage_consts in S_d's order of
+ *                    pmt_quad_gram_sum_f64: 256 chains (chain c adds the stages c, c + 256, .. in order onto 0.0), then the halving tree
+ *                    (c += c + 128, c + 64, ..) — a short second launch of one workgroup, ordered by the stream alone.
+ * Plain multiplies and adds, no fma, no floating-point atomics, no workgroup waits for another; the results do not depend on T, on the
+ * stage's position in the table, on launch geometry or on timing.  Every output word is written exactly once per call, nothing outside the
+ * stages' slices is written, and stage_consts (device, T doubles) is written before it is read: it needs no zeroing.
+ * pmt_quad_stages_check is host arithmetic over a HOST copy of the table (no device call): a null Q or xvar, a sign outside {-1, 0, 1}, a
+ * NULL vec with sign != 0 (or a null table with T > 0): PMT_INVALID_ARGUMENT; n outside 1 .. PMT_QUAD_STAGES_MAX_N, ldq < n, T < 0, a slice
+ * leaving [0, nterms) / [0, nlin), slices that overlap: PMT_DIMENSION_MISMATCH.  pmt_quad_stages_f64 itself rejects null pointers
+ * (PMT_INVALID_ARGUMENT) and T < 0 (PMT_DIMENSION_MISMATCH) before any device call; T == 0 writes *out_const = 0.0 only.  The kernel reads
+ * the table on the device and does NOT check it again: pass a table only after pmt_quad_stages_check accepted its host copy.
+ * Persistent workgroups of 256 threads, three per CU, grid = min(T, 3 CUs), workgroup g taking the stages g, g + G, ..; a stage is walked as
+ * pmt_batch_form_coeffs_f64 walks an instance, with the chains in LDS (csrc/quad_stages.hip).  Algorithmic bytes: 24 per quadratic and 16 per
+ * linear term written; every distinct Q once, the vectors and the table read. */
+#define PMT_QUAD_STAGES_MAX_N 256
+typedef struct {
+    const double *Q; int64_t ldq;      /* n columns of ldq doubles; many stages may name the same Q */
+    const int64_t *xvar;               /* n model-variable indices, strictly increasing */
+    const double *vec;                 /* v_t, or NULL with sign == 0 */
+    int32_t n, sign;                   /* 1 .. PMT_QUAD_STAGES_MAX_N; -1 | 0 | +1 */
+    int64_t quad_at, lin_at;           /* first quadratic / linear term of the stage in out_quad / out_lin */
+} pmt_quad_stage;                      /* 56 bytes, no padding (static_assert in csrc/quad_stages.hip) */
+int pmt_quad_stages_check(const pmt_quad_stage *host_stages, int64_t T, int64_t nterms, int64_t nlin);
+int pmt_quad_stages_f64(const pmt_quad_stage *stages, int64_t T, const int64_t *varmap, pmt_quadratic_term *out_quad,
+                        pmt_linear_term *out_lin, double *stage_consts, double *out_const, void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * Device-side Parameter update callbacks for synthetic inputs (counter-based):
  * dst[i] = scale * U[0,1)(seed, i)   — the analogue of `Parameter(rand!, zeros(n, n), model)` README.md:36-43

@@ -200,6 +200,30 @@ quad_groups_gather!(out_quad, out_lin, src_quad, row_src, row_dst, nrows, nterms
 quad_groups_constant!(out_const, group_consts, ngroups, stream) =
     check(ccall((:pmt_quad_groups_constant_f64, lib), Cint, (DevPtr, Cint, DevPtr, Ptr{Cvoid}), group_consts, ngroups, out_const, stream))
 
+"pmt_quad_stage (include/parametron_hip.h): one stage transpose(x_t (+|-) v_t) * Q * (x_t (+|-) v_t) of pmt_quad_stages_f64 — device
+ addresses (vec C_NULL with sign 0), n in 1 .. 256, and the stage's first quadratic / linear term in the outputs; 56 bytes, no padding"
+struct QuadStage
+    Q::DevPtr
+    ldq::Int64
+    xvar::DevPtr
+    vec::DevPtr
+    n::Int32
+    sign::Int32
+    quad_at::Int64
+    lin_at::Int64
+end
+const QUAD_STAGES_MAX_N = 256
+
+"host arithmetic over a host Vector{QuadStage}: pointers, signs, sizes, and slices inside [0, nterms) / [0, nlin) that do not overlap"
+quad_stages_check(stages::Vector{QuadStage}, nterms, nlin) =
+    check(ccall((:pmt_quad_stages_check, lib), Cint, (Ptr{QuadStage}, Int64, Int64, Int64), stages, length(stages), nterms, nlin))
+
+"a horizon of T stage costs over pairwise disjoint Variable vectors as one canonical MOI function from one launch: `stages` is the DEVICE copy
+ of a table quad_stages_check accepted (the kernel does not check it again); stage_consts: T device doubles"
+quad_stages!(out_quad, out_lin, stage_consts, out_const, stages::DevPtr, T, varmap, stream) =
+    check(ccall((:pmt_quad_stages_f64, lib), Cint, (DevPtr, Int64, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
+                stages, T, varmap, out_quad, out_lin, stage_consts, out_const, stream))
+
 "structure of a solver matrix from 1-based (row, col) indices (host, once): perm, seg_ptr, colptr, rowval (0-based), nnz"
 function csc_order(rows::Vector{Int64}, cols::Vector{Int64}, nrows, ncols; upper::Bool=false)
     n = length(rows)

@@ -59,6 +59,24 @@ def sparse_lsq_terms(terms):
     return arr
 
 
+PMT_QUAD_STAGES_MAX_N = 256
+
+
+class QuadStage(C.Structure):
+    """pmt_quad_stage: one stage of pmt_quad_stages_f64 (pointers are device addresses; vec None with sign 0)."""
+    _fields_ = [("Q", C.c_void_p), ("ldq", C.c_int64), ("xvar", C.c_void_p), ("vec", C.c_void_p), ("n", C.c_int32), ("sign", C.c_int32),
+                ("quad_at", C.c_int64), ("lin_at", C.c_int64)]
+
+
+def quad_stages(stages):
+    """host array of pmt_quad_stage from dicts of its fields (missing fields: 0 / None)"""
+    arr = (QuadStage * max(len(stages), 1))()
+    for i, t in enumerate(stages):
+        for k, v in t.items():
+            setattr(arr[i], k, v)
+    return arr
+
+
 def stack_table(srcs, signs):
     """host image of the pmt_stack_column table of pmt_affine_stack_columns_f64: column c is signs[c] * (the column at device address
     srcs[c]).  The entry point reads the table on the device only, so the signs are checked here."""
@@ -111,7 +129,8 @@ class GroupsLayout:
         self.lin_src = self.src_lin[owner] + local
         self.nterms, self.nlin = int(self.row_dst[-1]) // 3, len(self.z)
         self.ordered = int(np.count_nonzero(np.diff(owner))) == len(sets) - 1
-        first = np.array([int(np.flatnonzero(owner == g)[0]) for g in range(len(sets))], dtype=np.int64)
+        first = np.full(len(sets), len(owner), dtype=np.int64)                             # every group's first variable in z: one pass
+        np.minimum.at(first, owner, np.arange(len(owner), dtype=np.int64))
         self.dst_quad, self.dst_lin = self.row_dst[first] // 3, first
 
 
@@ -221,6 +240,8 @@ SIGNATURES = {
     "pmt_batch_lsq_coeffs_f64": (_ci, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _ci, _vp, _i64, _vp]),
     "pmt_batch_expand_f64": (_ci, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pmt_batch_form_coeffs_f64": (_ci, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _ci, _ci, _vp, _i64, _vp]),
+    "pmt_quad_stages_check": (_ci, [_vp, _i64, _i64, _i64]),
+    "pmt_quad_stages_f64": (_ci, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pmt_comm_unique_id": (_ci, [_vp]),
     "pmt_comm_init_rank": (_ci, [_ci, _ci, _vp, _ci, C.POINTER(_vp)]),
     "pmt_comm_destroy": (_ci, [_vp]),

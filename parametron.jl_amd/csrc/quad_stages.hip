@@ -1,0 +1,319 @@
+// Horizon stage costs: sum_t transpose(x_t (+|-) v_t) * Q_t * (x_t (+|-) v_t) over T pairwise disjoint Variable vectors as ONE canonical MOI
+// function, from one launch (pmt_quad_stages_f64).  What a model-predictive controller writes: T = 10 .. a few hundred stages, two or three
+// weight matrices shared by all of them, one reference vector per stage.  In the reference every stage is matvecmul! over the affine vector
+// (src/functions.jl:800-822) and vecdot! (:702-709 over :548-576) — bilinearmul! (:840-858) for a plain stage —, the stages are added with
+// add! (:244), and canonicalize! (:381-386) and the MOI copy (src/moi_interop.jl:45-62) follow; no pair (j, k) is shared between two stages.
+//
+// One workgroup of 256 threads per stage, persistent: workgroup g takes the stages g, g + G, .. of a device table of descriptors
+// (pmt_quad_stage).  No workgroup waits for another, no atomics, no workspace.  A stage is walked exactly as batch_form_kernel
+// (batch_form.hip) walks an instance: the 64 x 64 tile pairs (J <= K), both source tiles read along their columns with every load of a tile
+// issued before the first value is looked at, the transpose-add through an LDS tile of pitch 65 doubles, one thread per row adding the row
+// chains and — off the diagonal — one per column the column chains into P[B][j] in LDS (n <= 256); after the last tile one thread per j adds
+// the blocks in order, the 256-entry tree gives the stage's constant.  Summation order and operations are those include/parametron_hip.h
+// fixes for pmt_quad_form_shift_f64, so a stage's slice equals what that node writes for the stage alone, bit for bit.
+// What is new against that kernel:
+//   - Q is named by the descriptor (column-major, leading dimension ldq) and shared by many stages: behind the first stages it comes from L2
+//     and the launch is bound by its writes;
+//   - the stage's index words vm[xvar[j]] are fetched once into LDS (2 KB) — asked for at the top of the stage, looked up through the varmap
+//     behind the first tile's loads, read by the epilogues;
+//   - the epilogue writes 24-byte term structs row by row and 16-byte linear terms through wave_write_words (common.h), as quad_form_tile
+//     (form.hip) and sparse_form_kernel do: a slice starts at any 8-byte address.
+// The stages' constants go to stage_consts[t]; a second launch of one workgroup, ordered by the stream alone, adds them in S_d's order.
+// LDS: 33280 (tile) + 8192 (P) + 2048 (c) + 2048 (tree) + 2048 (index words) + 2048 (lin) = 49664 bytes: three workgroups per CU.
+#include <algorithm>
+#include <vector>
+
+#include "common.h"
+
+namespace pmt {
+
+namespace {
+
+constexpr int QS_TILE = 64;
+constexpr int QS_THREADS = 256;
+constexpr int QS_MAX_N = 256;
+constexpr int QS_MAX_NB = QS_MAX_N / QS_TILE;
+constexpr int QS_WG_PER_CU = 3;
+static_assert(QS_MAX_N == PMT_QUAD_STAGES_MAX_N, "the header's bound is the kernel's");
+static_assert(QS_MAX_N <= QS_THREADS, "one thread per j adds the blocks; the tree takes one product per thread");
+static_assert(sizeof(pmt_quad_stage) == 56, "pmt_quad_stage: 56 bytes, no padding (the ctypes and Julia mirrors)");
+
+struct QuadStagesArgs {
+    const pmt_quad_stage *stages; int64_t T;
+    const int64_t *varmap;
+    QT *quad; LT *lin;
+    double *consts, *cst;
+};
+
+__device__ __forceinline__ int64_t qs_tri_pos(int64_t n, int64_t j, int64_t k) { return j * n - (j * (j - 1)) / 2 + (k - j); }
+
+// ((s(0)*c(0) + s(1)*c(1)) + ..) + s(len-1)*c(len-1): the first product starts the chain.  The operands of eight steps are read from LDS
+// together; the order of the additions is the chain's.
+template <typename FS, typename FC>
+__device__ __forceinline__ double qs_chain(int len, FS s, FC c) {
+    double acc = s(0) * c(0);
+    int k = 1;
+    for (; k + 8 <= len; k += 8) {
+        double a[8], b[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { a[i] = s(k + i); b[i] = c(k + i); }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { const double pr = a[i] * b[i]; acc = acc + pr; }
+    }
+    for (; k < len; ++k) acc = acc + s(k) * c(k);
+    return acc;
+}
+
+// Every element of v is in its register here: loads issued above this point are not moved below it or into a branch.
+__device__ __forceinline__ void qs_landed(double (&v)[16]) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) asm volatile("" : "+v"(v[i]));
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(QS_THREADS) void quad_stages_kernel(QuadStagesArgs g) {
+    typedef unsigned long long u64w;
+    __shared__ double tile[QS_TILE][QS_TILE + 1];
+    __shared__ double part[QS_MAX_NB][QS_MAX_N];          // P[B][j]
+    __shared__ double cvec[QS_MAX_N];
+    __shared__ double red[QS_THREADS];
+    __shared__ int64_t var[QS_MAX_N];                     // vm[xvar[j]]
+    __shared__ double linv[QS_MAX_N];
+    const int tid = threadIdx.x;
+    const int64_t *__restrict__ varmap = g.varmap;
+
+    for (int64_t t = blockIdx.x; t < g.T; t += gridDim.x) {
+        const pmt_quad_stage d = g.stages[t];
+        const int n = d.n, nt = (n + QS_TILE - 1) / QS_TILE;
+        const int64_t ldq = d.ldq;
+        const double *__restrict__ Q = d.Q;
+        const bool shift = d.sign != 0;
+        QT *__restrict__ oq = g.quad + d.quad_at;
+        // v and the index words are asked for now and looked at behind the first tile's loads: no round trip of their own in front of the
+        // tiles (every thread loads, thread t >= n the last entry again)
+        const int ct = tid < n ? tid : n - 1;
+        double pv = 0.0;
+        if (shift) pv = d.vec[ct];
+        int64_t xv = d.xvar[ct];
+        bool pending = true;
+
+        for (int bj = 0; bj < nt; ++bj) {
+            for (int bk = bj; bk < nt; ++bk) {
+                const bool diagonal = bk == bj;
+                // (the lane's coordinates are made opaque per tile: derived from loop invariants, the compiler otherwise keeps every address
+                // and predicate of the unrolled body below alive across the whole stage loop)
+                int lane = tid & 63, wave = tid >> 6;
+                asm volatile("" : "+v"(lane), "+v"(wave));
+                const int j0 = bj * QS_TILE, k0 = bk * QS_TILE;
+                // lower[i] = Q[k0 + lane, j0 + wave + 4 i] (k on the lanes); upper[i] = Q[j0 + lane, k0 + wave + 4 i] (j on the lanes)
+                // Out-of-range entries are 0.0: the load goes to the stage's last row / column instead and is dropped, so no load is
+                // conditional.  All loads of a tile are issued before the first value is looked at (qs_landed).
+                double lower[16], upper[16];
+                const int rk = k0 + lane, rj = j0 + lane;
+                const int ork = rk < n ? rk : n - 1, orj = rj < n ? rj : n - 1;
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int c = j0 + wave + 4 * i;
+                    lower[i] = Q[ork + (int64_t)(c < n ? c : n - 1) * ldq];
+                }
+                if (!diagonal) {
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        const int c = k0 + wave + 4 * i;
+                        upper[i] = Q[orj + (int64_t)(c < n ? c : n - 1) * ldq];
+                    }
+                    qs_landed(upper);
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) upper[i] = (rj < n && k0 + wave + 4 * i < n) ? upper[i] : 0.0;
+                }
+                qs_landed(lower);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) lower[i] = (rk < n && j0 + wave + 4 * i < n) ? lower[i] : 0.0;
+                if (diagonal) {
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) upper[i] = lower[i];
+                }
+                if (pending) {                          // c = 0.0 (+|-) v and the index words; read behind this tile's barriers
+                    asm volatile("" : "+v"(pv), "+v"(xv));      // (looked at here, not in front of the loads)
+                    if (tid < n) {
+                        var[tid] = varmap[xv - 1];
+                        if (shift) cvec[tid] = signed_const(pv, d.sign);
+                    }
+                    pending = false;
+                }
+                // tile[kk][jj] = Q[j0 + jj, k0 + kk]
+#pragma unroll
+                for (int i = 0; i < 16; ++i) tile[wave + 4 * i][lane] = upper[i];
+                __syncthreads();
+                // s(jj = wave + 4 i, kk = lane) = Q[j,k] + Q[k,j]; the diagonal keeps Q[j,j] (doubled where it is used)
+                double s[16];
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int jj = wave + 4 * i;
+                    const double a = tile[lane][jj];
+                    s[i] = (diagonal && jj == lane) ? a : a + lower[i];
+                }
+                __syncthreads();
+                // tile[jj][kk] = s
+#pragma unroll
+                for (int i = 0; i < 16; ++i) tile[wave + 4 * i][lane] = s[i];
+                __syncthreads();
+                const int kw = n - k0 < QS_TILE ? n - k0 : QS_TILE, jw = n - j0 < QS_TILE ? n - j0 : QS_TILE;
+                if (shift) {
+                    // plain multiplies and adds, ascending, the first product starting the chain
+                    if (wave == 0 && lane < jw) {
+                        part[bk][j0 + lane] = qs_chain(kw, [&](int kk) { const double a = tile[lane][kk]; return (diagonal && kk == lane) ? 2 * a : a; },
+                                                       [&](int kk) { return cvec[k0 + kk]; });
+                    } else if (wave == 1 && !diagonal && lane < kw) {
+                        part[bj][k0 + lane] = qs_chain(jw, [&](int jj) { return tile[jj][lane]; }, [&](int jj) { return cvec[j0 + jj]; });
+                    }
+                }
+                // the quadratic terms: row j holds its columns k >= j; this tile's piece of it, a wave per row segment, 16-byte stores
+                const int ke = k0 + kw;
+                for (int r = 0; r < 16; ++r) {
+                    const int jj = wave * 16 + r, j = j0 + jj;
+                    if (j >= n) break;
+                    const int ks = k0 > j ? k0 : j;
+                    if (ke <= ks) continue;
+                    const int off = ks - k0;
+                    const u64w rowvar = (u64w)var[j];
+                    wave_write_words<3>(reinterpret_cast<u64w *>(oq + qs_tri_pos(n, j, ks)), ke - ks, lane, [&](int q) -> u64w {
+                        const int e = q / 3, f = q - 3 * e;
+                        if (f == 1) return rowvar;
+                        if (f == 2) return (u64w)var[k0 + off + e];
+                        const double v = tile[jj][off + e];
+                        return (u64w)__double_as_longlong((diagonal && e == 0) ? 2 * v : v);      // the row's first term is its diagonal term
+                    });
+                }
+                __syncthreads();
+            }
+        }
+
+        // lin_j = ((P[0][j] + P[1][j]) + ..) + P[nb-1][j]; T_t by 256 chains onto 0.0 (n <= 256: one product each), then the halving tree
+        double prod = 0.0;
+        if (tid < n) {
+            double lin = 0.0;
+            if (shift) {
+                lin = part[0][tid];
+                for (int b = 1; b < nt; ++b) lin = lin + part[b][tid];
+                prod = cvec[tid] * lin;
+            }
+            linv[tid] = lin;
+        }
+        double chain = 0.0;
+        if (shift && tid < n) chain = chain + prod;
+        red[tid] = chain;
+        __syncthreads();
+        {
+            // the linear terms: wave w writes the terms 64 w .. of the stage's slice
+            const int lane = tid & 63, w0 = (tid >> 6) * 64;
+            if (w0 < n) {
+                const int cnt = n - w0 < 64 ? n - w0 : 64;
+                wave_write_words<2>(reinterpret_cast<u64w *>(g.lin + d.lin_at + w0), cnt, lane, [&](int q) -> u64w {
+                    const int e = w0 + (q >> 1);
+                    return (q & 1) ? (u64w)var[e] : (u64w)__double_as_longlong(linv[e]);
+                });
+            }
+        }
+        for (int h = QS_THREADS / 2; h > 0; h >>= 1) {
+            if (tid < h) red[tid] = red[tid] + red[tid + h];
+            __syncthreads();
+        }
+        if (tid == 0) g.consts[t] = shift ? 0.5 * red[0] : 0.0;
+        __syncthreads();                                  // the next stage reuses cvec, part, red, var and linv
+    }
+}
+
+// Behind quad_stages_kernel on the stream: one workgroup adds the T stage constants in S_d's order (gram_sum.hip: 256 chains onto 0.0,
+// chain c taking the stages c, c + 256, .. in order, then the halving tree).  T == 0 gives 0.0.
+__global__ __launch_bounds__(QS_THREADS) void quad_stages_const_kernel(QuadStagesArgs g) {
+    __shared__ double red[QS_THREADS];
+    const int tid = threadIdx.x;
+    const double *__restrict__ c = g.consts;
+    double s = 0.0;
+    for (int64_t t = tid; t < g.T; t += QS_THREADS) s = s + c[t];
+    red[tid] = s;
+    __syncthreads();
+    for (int h = QS_THREADS / 2; h > 0; h >>= 1) {
+        if (tid < h) red[tid] = red[tid] + red[tid + h];
+        __syncthreads();
+    }
+    if (tid == 0) *g.cst = red[0];
+}
+
+static int qs_cu_count() {
+    static int cus[16] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) { (void)hipGetLastError(); return 256; }
+    if (!cus[dev]) {
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) { (void)hipGetLastError(); v = 256; }
+        cus[dev] = v;
+    }
+    return cus[dev];
+}
+
+// slices [at, at + len) of the stages, sorted by their start, stay inside [0, total) and do not overlap
+static bool qs_slices_ok(std::vector<std::pair<int64_t, int64_t>> &s, int64_t total) {
+    std::sort(s.begin(), s.end());
+    int64_t end = 0;
+    for (const auto &p : s) {
+        if (p.first < end || p.second > total - p.first) return false;
+        end = p.first + p.second;
+    }
+    return true;
+}
+
+}  // namespace pmt
+
+using namespace pmt;
+
+extern "C" int pmt_quad_stages_check(const pmt_quad_stage *host_stages, int64_t T, int64_t nterms, int64_t nlin) {
+    PMT_REQUIRE(T >= 0, PMT_DIMENSION_MISMATCH, "quad_stages: negative stage count");
+    PMT_REQUIRE(nterms >= 0 && nlin >= 0, PMT_DIMENSION_MISMATCH, "quad_stages: negative term count");
+    if (T == 0) return PMT_OK;
+    PMT_REQUIRE(host_stages, PMT_INVALID_ARGUMENT, "quad_stages: null stage table");
+    std::vector<std::pair<int64_t, int64_t>> quad, lin;
+    quad.reserve((size_t)T);
+    lin.reserve((size_t)T);
+    for (int64_t t = 0; t < T; ++t) {
+        const pmt_quad_stage &d = host_stages[t];
+        const std::string at = " (stage " + std::to_string(t) + ")";
+        PMT_REQUIRE(d.Q, PMT_INVALID_ARGUMENT, "quad_stages: null matrix" + at);
+        PMT_REQUIRE(d.xvar, PMT_INVALID_ARGUMENT, "quad_stages: null variable indices" + at);
+        PMT_REQUIRE(d.sign >= -1 && d.sign <= 1, PMT_INVALID_ARGUMENT, "quad_stages: sign must be -1, 0 or +1" + at);
+        PMT_REQUIRE(d.sign == 0 || d.vec, PMT_INVALID_ARGUMENT, "quad_stages: a shifted stage without its vector" + at);
+        PMT_REQUIRE(d.n >= 1 && d.n <= QS_MAX_N, PMT_DIMENSION_MISMATCH, "quad_stages: n outside 1 .. 256" + at);
+        PMT_REQUIRE(d.ldq >= d.n, PMT_DIMENSION_MISMATCH, "quad_stages: ldq < n" + at);
+        PMT_REQUIRE(d.quad_at >= 0 && d.lin_at >= 0, PMT_DIMENSION_MISMATCH, "quad_stages: a slice starts below 0" + at);
+        quad.emplace_back(d.quad_at, (int64_t)d.n * (d.n + 1) / 2);
+        lin.emplace_back(d.lin_at, (int64_t)d.n);
+    }
+    PMT_REQUIRE(qs_slices_ok(quad, nterms), PMT_DIMENSION_MISMATCH, "quad_stages: quadratic slices overlap or leave [0, nterms)");
+    PMT_REQUIRE(qs_slices_ok(lin, nlin), PMT_DIMENSION_MISMATCH, "quad_stages: linear slices overlap or leave [0, nlin)");
+    return PMT_OK;
+}
+
+extern "C" int pmt_quad_stages_f64(const pmt_quad_stage *stages, int64_t T, const int64_t *varmap, pmt_quadratic_term *out_quad,
+                                   pmt_linear_term *out_lin, double *stage_consts, double *out_const, void *stream) {
+    PMT_REQUIRE(T >= 0, PMT_DIMENSION_MISMATCH, "quad_stages: negative stage count");
+    PMT_REQUIRE(out_const, PMT_INVALID_ARGUMENT, "quad_stages: null constant");
+    PMT_REQUIRE(T == 0 || (stages && varmap && out_quad && out_lin && stage_consts), PMT_INVALID_ARGUMENT, "quad_stages: null pointer");
+    QuadStagesArgs g;
+    g.stages = stages; g.T = T;
+    g.varmap = varmap;
+    g.quad = out_quad; g.lin = out_lin;
+    g.consts = stage_consts; g.cst = out_const;
+    return dispatch(stream, [=](hipStream_t s) {
+        if (T > 0) {
+            // three workgroups per CU stay resident (LDS); each walks the stages blockIdx.x, blockIdx.x + G, ..
+            const dim3 grid((unsigned)std::min<int64_t>(T, (int64_t)QS_WG_PER_CU * qs_cu_count()));
+            PMT_LAUNCH(quad_stages_kernel, grid, dim3(QS_THREADS), 0, s, g);
+            const int rc = check_launch("quad_stages_kernel");
+            if (rc != PMT_OK) return rc;
+        }
+        PMT_LAUNCH(quad_stages_const_kernel, dim3(1), dim3(QS_THREADS), 0, s, g);
+        return check_launch("quad_stages_const_kernel");
+    });
+}

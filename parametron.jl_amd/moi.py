@@ -192,7 +192,7 @@ def _form_workspace(ctx, q):
 
 class _Record:
     """Common part of Objective and Constraint (src/moi_interop.jl:113-129, 141-166)."""
-    mode = property(lambda self: self.plan.mode)                          # "literal" / "canonical" / "canonical-csc" / "-form" / "-sum" / "-groups" / "-sparse" / "-sparse-form" / "-sparse-sum"
+    mode = property(lambda self: self.plan.mode)                          # "literal" / "canonical" / "canonical-csc" / "-form" / "-sum" / "-groups" / "-stages" / "-sparse" / "-sparse-form" / "-sparse-sum"
     lsq_terms = property(lambda self: self.plan.terms)                    # the LsqTerm list a "canonical-sum" record combines, or None
 
     def _setup(self, model, expr):
@@ -447,6 +447,41 @@ class _Record:
             c.call("pmt_quad_groups_constant_f64", P(consts), G, P(dc))
         return emit
 
+    def _compile_stages(self, ctx, varmap_buf, handoff_varmap):
+        """The objective as a sum of horizon stages — dense forms, plain or shifted, of weight 1 over pairwise disjoint Variable vectors, more
+        of them than "canonical-groups" holds (plan.stages): ONE pmt_quad_stages_f64 writes every stage's canonical function from a device
+        table of descriptors built, checked (pmt_quad_stages_check) and uploaded here once — straight into the stages' slices of the MOI
+        buffers when their variables are consecutive in the sorted union z, into an arena otherwise, from where the unchanged
+        pmt_quad_groups_gather_f64 places the rows, as _compile_groups does.  The stages' constants are added by the call's own second
+        launch.  update! allocates nothing and makes one call, or two with the gather."""
+        from . import _lib
+        stages = self.plan.stages
+        lay = _lib.GroupsLayout([q.xvars.vars for q in stages])
+        T, n, nq = len(stages), lay.nlin, lay.nterms
+        self.f = ScalarQuadraticFunction(n, nq, alloc=ctx.pinned_array)
+        dq, dl, dc, consts = ctx.alloc(24 * nq), ctx.alloc(16 * n), ctx.alloc(8), ctx.alloc(8 * T)
+        self.dev = {"quad": dq, "lin": dl, "const": dc}
+        self.groups_ordered = lay.ordered
+        if lay.ordered:
+            bq, bl, oq, ol = dq, dl, lay.dst_quad, lay.dst_lin
+        else:
+            bq, bl, oq, ol = ctx.alloc(24 * nq), ctx.alloc(16 * n), lay.src_quad, lay.src_lin
+            tables = [ctx.alloc(8 * len(t)) for t in (lay.row_src, lay.row_dst, lay.lin_src)]
+            for buf, t in zip(tables, (lay.row_src, lay.row_dst, lay.lin_src)):
+                ctx.upload(buf, t)
+        arr = _lib.quad_stages([{"Q": q.mat.buf, "ldq": q.mat.lda, "xvar": q.xvars.buf, "vec": q.vec.buf if q.vec is not None else None,
+                                 "n": q.mat.cols, "sign": q.sign if q.vec is not None else 0, "quad_at": int(oq[k]), "lin_at": int(ol[k])}
+                                for k, q in enumerate(stages)])
+        _lib.call("pmt_quad_stages_check", C.addressof(arr), T, nq, n)
+        table = ctx.alloc(C.sizeof(arr))
+        ctx.upload(table, np.frombuffer(arr, dtype=np.uint8).copy())
+
+        def emit(c):
+            c.call("pmt_quad_stages_f64", P(table), T, P(varmap_buf), P(bq), P(bl), P(consts), P(dc))
+            if not lay.ordered:
+                c.call("pmt_quad_groups_gather_f64", P(bq), P(tables[0]), P(tables[1]), n, nq, P(bl), P(tables[2]), n, P(dq), P(dl))
+        return emit
+
     # the quadratic forms by plan.mode (quad_plan)
     def _compile_sparse_gram(self, ctx, varmap_buf, handoff_varmap):
         """dot(r, r), r = C*x (+|-) d with a sparse C (plan.gram, a DSparseAff): pmt_sparse_gram_f64 streams the pattern's product list
@@ -542,7 +577,7 @@ class _Record:
         return emit
 
     _QUAD_FORMS = {"canonical-sparse": _compile_sparse_gram, "canonical-sparse-form": _compile_sparse_form, "canonical-sparse-sum": _compile_sparse_sum, "literal": _compile_literal, "canonical": _compile_gram, "canonical-csc": _compile_gram, "canonical-form": _compile_form,
-                   "canonical-sum": _compile_lsq_sum, "canonical-groups": _compile_groups}
+                   "canonical-sum": _compile_lsq_sum, "canonical-groups": _compile_groups, "canonical-stages": _compile_stages}
 
     # ---- Vector{AffineFunction}
     def _compile_vector(self, ctx, varmap_buf, handoff_varmap):
@@ -791,12 +826,34 @@ def _lsq_groups(terms):
     return groups if all(_lsq_sum_combines(g.terms) for g in groups) else None
 
 
+def _lsq_stages(terms):
+    """The QuadForms of an LsqTerm list that is a horizon of stage costs, or None: more than PMT_QUAD_MAX_GROUPS terms, every one a dense
+    form transpose(x_t)*Q*x_t or transpose(x_t (+|-) v_t)*Q*(x_t (+|-) v_t) of weight exactly 1 (no scale, no Parameter factor) over a
+    strictly increasing vector of 1 .. PMT_QUAD_STAGES_MAX_N variables, the vectors pairwise disjoint, and at least two stages reading the
+    same weight matrix (the device mirror of one matrix Parameter) — the horizon's shape; nine unrelated forms keep the literal path."""
+    from . import _lib
+    terms = terms or ()
+    if len(terms) <= _lib.PMT_QUAD_MAX_GROUPS:
+        return None
+    for t in terms:
+        if not (t.kind == "form" and isinstance(t.r, QuadForm) and t.scale == 1.0 and t.param is None and not t.host_scaled):
+            return None
+        v = t.r.xvars.vars
+        if not 1 <= len(v) <= _lib.PMT_QUAD_STAGES_MAX_N or t.r.mat.cols != len(v) or np.any(np.diff(v) <= 0):
+            return None
+    z = np.concatenate([t.r.xvars.vars for t in terms])
+    if len(np.unique(z)) != len(z) or len({id(t.r.mat) for t in terms}) == len(terms):
+        return None
+    return [t.r for t in terms]
+
+
 class QuadPlan:
     """How a quadratic record reaches its MOI function (quad_plan decides; Model.initialize and _Record.compile execute): the mode and what it
-    reads — the operand r of dot(r, r) (`gram`), the QuadForm (`form`), the LsqTerm list (`terms`) or the QuadGroups of a sum over disjoint
-    Variable vectors (`groups`); `canonicalize`: through canonicalize! first."""
-    def __init__(self, mode, gram=None, form=None, terms=None, canonicalize=False, groups=None):
+    reads — the operand r of dot(r, r) (`gram`), the QuadForm (`form`), the LsqTerm list (`terms`), the QuadGroups of a sum over disjoint
+    Variable vectors (`groups`) or the QuadForms of a horizon of stage costs (`stages`); `canonicalize`: through canonicalize! first."""
+    def __init__(self, mode, gram=None, form=None, terms=None, canonicalize=False, groups=None, stages=None):
         self.mode, self.gram, self.form, self.terms, self.canonicalize, self.groups = mode, gram, form, terms, canonicalize, groups
+        self.stages = stages
         # the MOI copy is the canonical least-squares node, bare or the weighted sum of such nodes (model.lane_order: side lane, small-plan order)
         self.gram_record = mode in ("canonical", "canonical-csc", "canonical-sum") or \
             (mode == "canonical-groups" and any(t.kind == "block" for g in groups for t in g.terms))
@@ -804,7 +861,7 @@ class QuadPlan:
     def operands(self):
         """what the plan's kernels read: the Gram operand, the forms and blocks of its term lists (Model.initialize: their stacked matrices)"""
         lists = [self.terms or ()] + [g.terms for g in self.groups or ()]
-        return [r for r in [self.gram] + [t.r for ts in lists for t in ts] if r is not None]
+        return [r for r in [self.gram] + [t.r for ts in lists for t in ts] + list(self.stages or ()) if r is not None]
 
 
 def quad_plan(terms, bare, kind, nq, is_objective, quadratic_mode, small, handoff, varmap=None, sparse_sums=False):
@@ -866,6 +923,11 @@ def quad_plan(terms, bare, kind, nq, is_objective, quadratic_mode, small, handof
             groups = _lsq_groups(terms)
             if groups:
                 return QuadPlan("canonical-groups", groups=groups)
+            # a horizon of stage costs — more disjoint vectors than the groups hold, every term a dense form of weight 1, plain or
+            # shifted, two or more of them reading one weight matrix: all stages from one launch (pmt_quad_stages_f64)
+            stages = _lsq_stages(terms)
+            if stages:
+                return QuadPlan("canonical-stages", stages=stages)
     # anything else: the literal function through the generic device canonicalize! (sorted, duplicates combined) before the MOI copy
     return QuadPlan("literal", canonicalize=True)
 
