@@ -216,6 +216,13 @@ size_t pmt_quad_gram_workspace_bytes(int64_t rows, int64_t cols);
  * (tests/gpu_util.py restates every order bit for bit.)
  * Every order is within (rows / 2048 + 2048) * eps / 2 relative of the exact sum for same-signed terms: far inside the 1e-12 parity bar. */
 int pmt_quad_gram_constant_order(int64_t rows, int64_t cols, int *order, int *groups, int *stage_rows);
+/* Pure host query beside it: does the one-launch form of an undelivered plain call defer its tiles (gram_mid.hip: MidWalk — a finished
+ * tile's sums and stores run inside the next tile's main loop)?  *plan: the shape runs the persistent walk over an unsplit body of at
+ * least two tiles per workgroup, so tiles can be deferred; *whole_rounds (may be null): the row count (a multiple of 64) also gives every
+ * wave whole rounds, so with 16-byte aligned operands and an even pitch the call runs the deferring build of the kernel and every body
+ * tile of two whole 64-column panels but a workgroup's last IS deferred.  Both 0 for shapes of the other forms.
+ * The results do not depend on it (the sums add the same operands level by level); tests use it to know which path they exercise. */
+int pmt_quad_gram_mid_defers(int64_t rows, int64_t cols, int *plan, int *whole_rounds);
 int pmt_quad_gram_f64(const double *A, int64_t lda, int64_t rows, int64_t cols,
                       const int64_t *xvar, const double *b, int sign,
                       int moi, const int64_t *varmap,

@@ -511,6 +511,14 @@ extern "C" int pmt_quad_gram_constant_order(int64_t rows, int64_t cols, int *ord
     return PMT_OK;
 }
 
+extern "C" int pmt_quad_gram_mid_defers(int64_t rows, int64_t cols, int *plan, int *whole_rounds) {
+    PMT_REQUIRE(rows >= 0 && cols >= 0 && plan, PMT_INVALID_ARGUMENT, "quad_gram_mid_defers: bad argument");
+    bool whole = false;
+    const bool can = gram_form(rows, cols, true, false) == GramForm::Mid && gram_mid_defers(rows, cols, &whole);
+    *plan = can ? 1 : 0; if (whole_rounds) *whole_rounds = (can && whole) ? 1 : 0;
+    return PMT_OK;
+}
+
 extern "C" size_t pmt_quad_gram_workspace_bytes(int64_t rows, int64_t cols) {
     // The most that a form the shape takes across call kinds (plain or CSC, delivered; a tiny node none) needs, and never less than the
     // stream-K node's need — its partial tiles (which the fused form's strict launch shares), the chunk sums of q, the chains of c'c.

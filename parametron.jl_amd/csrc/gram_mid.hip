@@ -20,7 +20,10 @@
 //   * c'c is one more workgroup of the same launch, in the order pmt_quad_gram_constant_order reports as 5 (gram_sk.hip: sk_lin_role),
 //     restated bit for bit by tests/gpu_util.py.
 // Summation order of a coefficient (fixed by (rows, cols) alone): wave w of chunk c adds the 8-row groups c gpc + w, + 4, .. in MFMA k
-// order (rows 2 k, 2 k + 1 of a group in contraction slot k); waves (0 + 2) + (1 + 3); chunks in ascending order.
+// order (rows 2 k, 2 k + 1 of a group in contraction slot k); waves (0 + 2) + (1 + 3); chunks in ascending order.  The waves' sums are
+// added in one of two places — by halving behind the item's loop (mid_tail), or, for a DEFERRED tile of the persistent walk, row by row
+// inside the next item's loop from the four raw partials in LDS (mid_wo_op: (p0 + p2) + (p1 + p3)) — each level the same two operands,
+// so the same bits; pmt_quad_gram_mid_defers tells which shapes defer (profiles/r20_deferred_tile.txt).
 #include "affine_tile.h"
 #include "gram_common.h"
 
@@ -35,6 +38,9 @@
 #endif
 #ifndef PMT_MID_D
 #define PMT_MID_D 2                // iterations (8-row groups) in flight per wave (pinned stream, mid_step: 2 33.6 us at 4096 x 512, 3 34.0, 4 35.4; 4096 x 1024 97.7 / 100.3 / 103.7)
+#endif
+#ifndef PMT_MID_WO_RPS
+#define PMT_MID_WO_RPS 2           // rows of a deferred tile that a wave writes out per 8-row group of the next item's loop (mid_wo_op: 1 and 2 the same step time at config 2, 1.0637 / 1.0645 ms against the parent's 1.0748; 4 spills 7 registers)
 #endif
 #ifndef PMT_MID_GROUP_US
 #define PMT_MID_GROUP_US 1.15      // the cost model's time of one 8-row group per wave (mid_plan)
@@ -65,7 +71,8 @@
 // debugging aid (tools/mid_trace.py): 100 MHz wall-clock stamps of the phases of every workgroup (of its LAST item where it walks several)
 __device__ unsigned long long g_mid_trace[1024 * 8];
 // ... and (tools/mid_walk_trace.py) per workgroup of the persistent walk, summed over its items in eight words of LDS behind the kernel's
-// own (mid_walk_note) and written out when it leaves: [0] items, [1] main loops, [2] stamp 1 -> 3 / 5 (the waves' sums, the count, a fold), [3] epilogues,
+// own (mid_walk_note) and written out when it leaves: [0] items, [1] main loops (a deferred tile's write-out inside), [2] stamp 1 -> 3 / 5 (the waves'
+// sums, the count, a fold; of a deferring item: the hand-off), [3] epilogues (none of a deferring item),
 // [4] from one item's last store to the next one's start, [5] the first item's start, [6] the last item's end, [7] the time it left
 __device__ unsigned long long g_mid_walk[1024 * 8];
 // ... and of its rider tiles: [0] how many it drew, [1] the time its last rider store had left
@@ -80,7 +87,7 @@ __device__ __forceinline__ void mid_walk_note(unsigned long long *w, int k, unsi
     w[7] = t;
 }
 #define MID_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x < 1024) { const unsigned long long t_ = wall_clock64(); g_mid_trace[blockIdx.x * 8 + (k)] = t_; \
-                          mid_walk_note(reinterpret_cast<unsigned long long *>(sh + MSH), (k), t_); } } while (0)
+                          mid_walk_note(reinterpret_cast<unsigned long long *>(sh + MSH_AT), (k), t_); } } while (0)
 extern "C" int pmt_mid_trace_read(unsigned long long *host) {
     return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_mid_trace), sizeof(unsigned long long) * 1024 * 8) == hipSuccess ? 0 : 1;
 }
@@ -105,9 +112,30 @@ constexpr int MPITCH = MT + 1;
 constexpr int MFG = 8;                       // chunks per group of a two-level fold (mid_body)
 constexpr int MCNT = 16;                     // counter words per tile: [0] the tile's, [1 + group] the groups' (at most 64 chunks)
 constexpr int MQBUF = 4 * 2048;              // LDS (doubles): [0, 8192) rotation pieces / the waves' exchange pieces / the finished tile + q + row descriptors;
-constexpr int MFLAG = MQBUF + 4 * MT;        // the waves' q (4 x 64); the count's old value; the tile's variable maps (2 x 64)
-constexpr int MMAPS = MFLAG + 8;
-constexpr int MSH = MMAPS + 2 * MT;          // 68.7 KB per workgroup
+// A DEFERRED tile (mid_body: hand-off) waits in LDS while the next item's loop runs: the four waves' raw accumulators, [wave][a][lane]
+// with a pitch of MDP doubles per a.  A row of the write-out (mid_wo_op) reads 16 different a, four neighbouring lanes each: a pitch of
+// 68 = 4 (mod 32) puts the 8 a of a half-wave on 8 different groups of four 8-byte banks (64 dwords: the bank modulus of ds_read_b64).
+// The region starts behind the rotation pieces (4 x 4 KB, which the next item's loop uses) and overlaps the exchange pieces and the
+// finished tile of the immediate path, which never runs with a tile pending (MidWalk).
+constexpr int MDP = 68;
+constexpr int MDPART = MACC * MDP;           // doubles of a wave's deferred partial
+constexpr int MDEF = 4 * 512;                // the deferred partials: behind the rotation pieces
+constexpr int MAREA = 4 * MT;                // a map area of the deferring form: the tile's variable maps (2 x 64) and a deferred tile's row descriptors (64 x (address of the row's first term, row variable))
+// The kernel is built twice on the fast load path (gram_mid_kernel<FAST, DF>).  DF = false is the kernel without deferred tiles, kept
+// instruction for instruction what it was before there were any (tools/isa_diff.py against the commit before: whatever is new stands
+// under `if constexpr (DF)`, the loop's text and the order of the declarations around it included — the register allocation of both
+// builds follows them): the larger LDS allocation alone cost the single-round shapes 0.4 .. 0.7 us per launch, a changed decode and loop
+// as much again (profiles/r20_deferred_tile.txt).  Only the launches that defer (launch_gram_mid) take the other one.
+template <bool DF> struct MidLds {
+    static constexpr int QW = DF ? MDEF + 4 * MDPART : MQBUF;      // the waves' q (4 x 64)
+    static constexpr int FLAG = QW + 4 * MT;                        // the count's old value
+    static constexpr int MAPS = FLAG + 8;                           // the tile's variable maps (2 x 64); DF: two areas, alternating from one deferred tile to the next (MidWalk::par)
+    static constexpr int SH = MAPS + (DF ? 2 * MAREA : 2 * MT);
+};
+// 16 KB of rotation pieces + 4 x 64 x 68 x 8 B = 136 KB of partials + 2 KB (q) + 64 B + 2 x 2 KB = 158.1 KB of the CU's 160 KB (by its
+// registers the kernel runs one workgroup per CU either way)
+static_assert(MDEF + 4 * MDPART >= MQBUF, "the immediate path's exchange pieces and finished tile lie inside the rotation pieces + partials");
+static_assert((MidLds<true>::SH + MID_TRACE_WORDS) * 8 + 16 <= 160 * 1024, "the kernel's LDS: one workgroup within the 160 KB of a gfx950 CU");
 
 struct MidArgs {
     const double *A; int64_t lda, rows, cols;
@@ -314,6 +342,68 @@ __device__ __forceinline__ void mid_compute(double *__restrict__ rot, const f64x
     }
 }
 
+// The write-out of a DEFERRED tile (mid_body: hand-off): an unsplit strictly upper tile of two whole panels, so every row is 64 doubled
+// terms that start at the tile's first column.  Rows are dealt as in mid_epilogue — row 4 i + wave, a lane per term — and a wave's 16 rows
+// are taken MWO_RPS per step (an 8-row group of the next item's loop), in the order i = 4 (step's rows) + b: the rows of one step share
+// b = (row >> 2) & 3 and with it the lanes' offsets into the partials.  Per row: the row's descriptor (one broadcast read), the four
+// waves' partials of the lane's entry, (p0 + p2) + (p1 + p3) — what the halving of mid_tail adds, level by level the same two operands —
+// doubled, the column's variable, three 8-byte stores to scalar row base + 24 * lane.  Every operation is one mid_wo_op(n): the loop
+// (mid_step<false, true>) puts each behind an MFMA of its own; mid_wo_run issues what is left of a tile without a loop around it.
+// What is wave-uniform (step, wave, area, the row's address) is scalar; what depends on the lane comes from a fresh thread id.
+constexpr int MWO_RPS = PMT_MID_WO_RPS;            // rows per step and wave
+constexpr int MWO_STEPS = 16 / MWO_RPS;            // steps per tile
+constexpr int MWO_ROW_OPS = 13;
+constexpr int MWO_OPS = 2 + MWO_ROW_OPS * MWO_RPS;
+static_assert(4 % MWO_RPS == 0, "the rows of a step share b");
+static_assert(MWO_OPS <= 16 + 92, "a step's free places: 16 MFMAs of phase 0, 92 of phase 1");
+struct MidWoAt { double *sh; int q, wave, pmo; };          // the pending tile's next step, this wave, the tile's map area: all scalar
+struct MidWo { const double *rb; unsigned so; u64 dsc[2], m; double p[4]; u64 dst; };
+__device__ __forceinline__ int mid_fresh_lane() {
+    int t;
+    asm volatile("v_mov_b32 %0, %1" : "=v"(t) : "v"((int)threadIdx.x));
+    return t & 63;
+}
+__device__ __forceinline__ void mid_wo_op(int n, MidWo &r, const MidWoAt &at) {
+    const int i0 = at.q * MWO_RPS, b = i0 >> 2, tm0 = i0 & 3;
+    if (n == 0) {
+        // entry (row, lane) of the tile is accumulator a = 16 tm + 4 (lane >> 4) + (((lane >> 2) - b) & 3) of lane 16 wave + 4 b + (lane & 3) (mid_pos)
+        const int lane = mid_fresh_lane();
+        r.rb = at.sh + MDEF + ((lane >> 4) * 4 + (((lane >> 2) - b) & 3)) * MDP + (lane & 3) + tm0 * 16 * MDP + at.wave * 16 + b * 4;
+        return;
+    }
+    if (n == 1) { r.so = 24u * (unsigned)mid_fresh_lane(); return; }
+    const int e = (n - 2) / MWO_ROW_OPS, o = (n - 2) % MWO_ROW_OPS;
+    const int row = 16 * (tm0 + e) + 4 * b + at.wave;
+    if (o == 0) {
+        const u64 *d = reinterpret_cast<const u64 *>(at.sh + at.pmo + 2 * MT) + 2 * row;
+        r.dsc[0] = d[0]; r.dsc[1] = d[1];
+    } else if (o <= 4) r.p[o - 1] = r.rb[(o - 1) * MDPART + e * 16 * MDP];
+    else if (o == 5) r.m = reinterpret_cast<const u64 *>(at.sh + at.pmo)[mid_fresh_lane()];
+    else if (o == 6) {
+        const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)r.dsc[0]), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(r.dsc[0] >> 32));
+        r.dst = (u64)hi << 32 | lo;
+    } else if (o == 7) r.p[0] = r.p[0] + r.p[2];
+    else if (o == 8) r.p[1] = r.p[1] + r.p[3];
+    else if (o == 9) r.p[0] = 2 * (r.p[0] + r.p[1]);
+    else {
+        // (an address built from two scalars: named global, or the stores are flat ones, which count as LDS traffic too and after which every wait is for everything)
+        typedef __attribute__((address_space(1))) u64 gu64;
+        gu64 *d = reinterpret_cast<gu64 *>(r.dst + r.so);
+        if (o == 10) d[0] = (u64)__double_as_longlong(r.p[0]);
+        else if (o == 11) d[1] = r.dsc[1];
+        else d[2] = r.m;
+    }
+}
+// what is left of the pending tile, at once (a flush, or the rest of an item with fewer rounds than the write-out needs)
+__device__ __forceinline__ void mid_wo_run(double *sh, int &q, int wave, int pmo) {
+    for (; q < MWO_STEPS; ++q) {
+        MidWo r;
+        const MidWoAt at = {sh, q, wave, pmo};
+#pragma unroll
+        for (int n = 0; n < MWO_OPS; ++n) mid_wo_op(n, r, at);
+    }
+}
+
 // One 8-row group AND the loads of the group D further on, as ONE pinned instruction stream (the FAST load path).  The
 // workgroup has one wave per SIMD: whatever is not an MFMA stands in the wave's only issue stream.  mid_compute + mid_load put the 16 LDS
 // operations of a group in one run in front of the MFMAs and its 8 loads (with a 64-bit vector add each: the compiler hoists the zero
@@ -328,10 +418,15 @@ __device__ __forceinline__ void mid_compute(double *__restrict__ rot, const f64x
 // The reloads take TWO scalar bases, one for the four A-side operands and one for the four B-side ones: both g.A + next_row0 inside an
 // item; in the round that ends an item of the persistent walk, the bases of the NEXT item's tile (mid_body) — the lane offsets of two
 // whole panels differ by a multiple of the pitch, so the redirect is a scalar select and the stream keeps its instructions.
-template <bool DIAG>
+// WO: the step also carries one step of a deferred tile's write-out (mid_wo_op), one operation behind each MFMA that has nothing behind it
+// yet — the same 128 MFMAs, 16 LDS operations and 8 loads in the same places.
+template <bool DIAG, bool WO = false>
 __device__ __forceinline__ void mid_step(const MidArgs &g, double *__restrict__ rot, int64_t next_row0, const char *base_a, const char *base_b,
                                          unsigned (&voff)[DIAG ? 4 : 8], f64x2 (&buf)[DIAG ? 4 : 8], f64x2 &cb, int sign, int lane,
-                                         double (&acc)[MACC], double (&qacc)[4]) {
+                                         double (&acc)[MACC], double (&qacc)[4], const MidWoAt &wo = MidWoAt()) {
+    static_assert(!(DIAG && WO), "only a strictly upper tile's loop carries a write-out");
+    MidWo wr;
+    int wn = 0;                                      // write-out operations issued
     constexpr int BO = DIAG ? 0 : 4;
     const int lm = lane & 15, lrow = lane & 48, lk = lane >> 4;
     auto reload = [&](int t) {
@@ -360,6 +455,7 @@ __device__ __forceinline__ void mid_step(const MidArgs &g, double *__restrict__ 
                 const int a = (tm * 4 + c) * 4;
                 acc[a] = __builtin_amdgcn_mfma_f64_4x4x4f64(pass ? buf[tm].y : buf[tm].x, pass ? bv[c][0].y : bv[c][0].x, acc[a], 0, 0, 0);
                 if (k < 16) { MID_SB(); lds_op(k); MID_SB(); }
+                else if constexpr (WO) { if (wn < MWO_OPS) { MID_SB(); mid_wo_op(wn, wr, wo); MID_SB(); ++wn; } }
                 ++k;
             }
     if (DIAG) {
@@ -387,6 +483,7 @@ __device__ __forceinline__ void mid_step(const MidArgs &g, double *__restrict__ 
                     const int a = (tm * 4 + c) * 4 + r;
                     acc[a] = __builtin_amdgcn_mfma_f64_4x4x4f64(pass ? buf[tm].y : buf[tm].x, pass ? bv[c][r].y : bv[c][r].x, acc[a], 0, 0, 0);
                     if (!DIAG && nb < 4) { MID_SB(); reload(4 + nb); MID_SB(); ++nb; }
+                    else if constexpr (WO) { if (wn < MWO_OPS) { MID_SB(); mid_wo_op(wn, wr, wo); MID_SB(); ++wn; } }
                 }
         MID_SB();
         reload(tm);
@@ -405,8 +502,8 @@ __device__ __forceinline__ void mid_pos(int lane, int a, int &row, int &col) {
 
 // the mapped variable indices of the tile's 64 columns / 64 rows, gathered at the TOP of the workgroup's life (two dependent loads that
 // would otherwise stand in the tail of the tile's last arriver); the barriers of the wave sums order them before the epilogue
-__device__ __forceinline__ void mid_maps(const MidArgs &g, double *sh, int tid, int jb, int kb) {
-    u64 *cmap = reinterpret_cast<u64 *>(sh + MMAPS);
+__device__ __forceinline__ void mid_maps(const MidArgs &g, double *sh, int tid, int jb, int kb, int mo) {
+    u64 *cmap = reinterpret_cast<u64 *>(sh + mo);
     if (tid >= 2 * MT || (!g.out_quad && jb != kb)) return;
     const int64_t i = (tid < MT ? (int64_t)kb * MT + tid : (int64_t)jb * MT + tid - MT);
     const int64_t v = i < g.cols ? g.xvar[i] : 1;
@@ -415,12 +512,12 @@ __device__ __forceinline__ void mid_maps(const MidArgs &g, double *sh, int tid, 
 
 // The finished tile (sh[row * MPITCH + col], q of a diagonal tile in sh[MT * MPITCH ..]) -> terms.  Row j of the tile's entries
 // k = max(j, k0) .. are consecutive QuadraticTerms of the canonical upper triangle: one wave per row, 16-byte chunks.
-__device__ __forceinline__ void mid_epilogue(const MidArgs &g, double *sh, int tid, int jb, int kb) {
+__device__ __forceinline__ void mid_epilogue(const MidArgs &g, double *sh, int tid, int jb, int kb, int mo) {
     const int wave = tid >> 6, lane = tid & 63;
     const int64_t n = g.cols, j0 = (int64_t)jb * MT, k0 = (int64_t)kb * MT;
     double *tile = sh;
     const double *qfin = sh + MT * MPITCH;
-    const u64 *cmap = reinterpret_cast<const u64 *>(sh + MMAPS);          // (mid_maps, at the top of the kernel)
+    const u64 *cmap = reinterpret_cast<const u64 *>(sh + mo);             // (mid_maps, at the top of the item; mo: the item's map area)
     const u64 *rmap = cmap + MT;
     if (g.out_csc) {
         const int64_t j = j0 + lane;
@@ -521,7 +618,7 @@ __device__ __forceinline__ double mid_get(const double *p) {
 // the same bits whichever side added (a + b = b + a).  Two waves summing everything for the others took 2.5 us of the workgroup's tail
 // (accumulator moves + adds in one issue stream, tools/mid_trace.py); here every wave moves 48 and adds 48.  The owned quarter then goes
 // to the workspace (a split tile) or into the finished tile in LDS; q of a diagonal tile is added by wave 0 (lane = column).
-template <bool DIAG, int W>
+template <bool DIAG, int W, bool DF>
 __device__ __forceinline__ void mid_tail(const MidArgs &g, double *sh, int lane, double (&acc)[MACC], const double (&qacc)[4], int nchunk, double *w) {
     constexpr int KEEP1 = (W >> 1) * 32, GIVE1 = 32 - KEEP1, KEEP2 = KEEP1 + (W & 1) * 16, GIVE2 = KEEP1 + 16 - (W & 1) * 16;
     double *mine = sh + W * 2048;
@@ -533,7 +630,7 @@ __device__ __forceinline__ void mid_tail(const MidArgs &g, double *sh, int lane,
         if (mid_used(DIAG, GIVE1 + a)) { f64x2 v; v.x = acc[GIVE1 + a]; v.y = acc[GIVE1 + a + 1]; *reinterpret_cast<f64x2 *>(mine + (a * 32 + lane) * 2) = v; }
     if (DIAG && qlane) {
 #pragma unroll
-        for (int t = 0; t < 4; ++t) sh[MQBUF + W * MT + 16 * t + qcol] = qacc[t];
+        for (int t = 0; t < 4; ++t) sh[MidLds<DF>::QW + W * MT + 16 * t + qcol] = qacc[t];
     }
     __syncthreads();
 #pragma unroll
@@ -543,7 +640,7 @@ __device__ __forceinline__ void mid_tail(const MidArgs &g, double *sh, int lane,
             acc[KEEP1 + a] = acc[KEEP1 + a] + v.x; acc[KEEP1 + a + 1] = acc[KEEP1 + a + 1] + v.y;
         }
     double qsum = 0.0;
-    if (DIAG && W == 0) qsum = (sh[MQBUF + lane] + sh[MQBUF + 2 * MT + lane]) + (sh[MQBUF + MT + lane] + sh[MQBUF + 3 * MT + lane]);
+    if (DIAG && W == 0) qsum = (sh[MidLds<DF>::QW + lane] + sh[MidLds<DF>::QW + 2 * MT + lane]) + (sh[MidLds<DF>::QW + MT + lane] + sh[MidLds<DF>::QW + 3 * MT + lane]);
     __syncthreads();
 #pragma unroll
     for (int a = 0; a < 16; a += 2)
@@ -618,6 +715,16 @@ struct MidWalk {
     int drawn;                   // out: that id
     bool next_full; int njb, nkb, nrank;      // the item in hand (an unsplit strictly upper tile): two whole panels; its tile and place in the walk
     bool pre;                    // in: this wave's first PMT_MID_D groups are in buf already (the previous item loaded them); out: the next item's are
+    // The deferred tile.  An item that prefetches on every wave (mid_body: defer) does not add and write its tile behind its loop: the
+    // waves leave their raw accumulators in LDS (the hand-off) and the tile is added and written inside the first rounds of the NEXT
+    // item's loop.  INVARIANT: while a tile is pending (woq < MWO_STEPS) nothing but the rotation pieces, the other map area and the next
+    // hand-off (behind its barrier) touches LDS.  The item behind a deferring one is the body tile it held in hand, so a tile is only
+    // ever pending at the top of a strictly upper item: that item either defers too or writes the pending tile out before anything else
+    // (mid_body: mid_wo_run).  A workgroup's last body item holds no body tile in hand and does not defer, so nothing is pending in front
+    // of a diagonal chunk, the constant, a rider tile or the end of the kernel: no path leaves or reuses the partials or the areas.
+    int woq;                     // the pending tile's next write-out step; MWO_STEPS: none pending
+    int par;                     // the map area of the item that runs (0 / 1); a pending tile's is the other one
+    bool deferred;               // out: the item left its tile pending (no barrier needed behind it)
 };
 
 // nothing of `buf` is needed from here on: the registers are free up to the next loads (an empty definition, no instruction) — on the
@@ -637,7 +744,7 @@ __device__ __forceinline__ auto &mid_buf(f64x2 (&own)[PMT_MID_D][4], f64x2 (&wal
 
 // `pbuf`: the operand registers of the strictly upper tiles live in the kernel — in the persistent walk they carry the next item's first
 // groups from one item into the next (wk.pre)
-template <bool DIAG, bool FAST>
+template <bool DIAG, bool FAST, bool DF>
 __device__ __forceinline__ void mid_body(const MidArgs &g, double *sh, int tid, int jb, int kb, int chunk, int nchunk, int gpc, int first_wg, unsigned *counter,
                                          MidWalk &wk, f64x2 (&pbuf)[PMT_MID_D][8]) {
     constexpr int NG = DIAG ? 4 : 8;
@@ -656,8 +763,12 @@ __device__ __forceinline__ void mid_body(const MidArgs &g, double *sh, int tid, 
     const bool ragged = FAST && (g.rows & 7) && my > 0 && g0 + 4 * (my - 1) == ngroups - 1;
     const int nfast = ragged ? my - 1 : my;
 
+    static_assert(FAST || !DF, "tiles are deferred on the fast load path only");
+    constexpr int MSH_AT = MidLds<DF>::SH;
+    (void)MSH_AT;                                                  // (read by the trace build only)
     MID_STAMP(0);
-    mid_maps(g, sh, tid, jb, kb);
+    const int mo = MidLds<DF>::MAPS + (DF ? wk.par * MAREA : 0), pmo = MidLds<DF>::MAPS + (wk.par ^ 1) * MAREA;
+    mid_maps(g, sh, tid, jb, kb, mo);
     double acc[MACC], qacc[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int a = 0; a < MACC; ++a) acc[a] = 0.0;
@@ -675,6 +786,19 @@ __device__ __forceinline__ void mid_body(const MidArgs &g, double *sh, int tid, 
     const bool pre = !DIAG && wk.pre;
     bool pf = false;
     if (!DIAG && FAST) pf = wk.early && wk.next_full && nchunk == 1 && !ragged && nfast > 0 && nfast % D == 0 && (int64_t)(kb + 1) * MT <= g.cols;
+    // In the deferring build the item DEFERS its tile (MidWalk) where it prefetches.  The launch chose the build (launch_gram_mid) for
+    // rows a multiple of 32 D, an unsplit body and a call that writes terms and nothing else: a body item then has whole rounds on all
+    // four waves, none ragged — `pf` is the same on every wave, the choice is the workgroup's, and what is left of it at run time is the
+    // item in hand (a body tile of a whole panel) and this item's own last panel.  An item that does not defer writes a pending tile out
+    // before it touches LDS (its loop and the barrier behind it stand between that and its own tail's LDS writes).
+    bool defer = false;
+    if constexpr (DF) {
+        // (the ticket in hand came through LDS: stated uniform here, the step counter and the loops that test it stay scalar)
+        defer = __builtin_amdgcn_readfirstlane((int)pf) != 0;
+        if (!defer) mid_wo_run(sh, wk.woq, wave, pmo);
+    }
+    bool late = false;                                             // the ticket was drawn in front of the loop's last round ...
+    unsigned drawn_late = 0;                                       // ... this one
     const int ahead_at = __builtin_amdgcn_readfirstlane(pf ? nfast - D : -1);          // (a scalar: the loop compares it without a vector instruction)
     const int64_t shift_a = pf ? ((int64_t)wk.njb * MT - cj0) * g.lda * 8 : 0, shift_b = pf ? ((int64_t)wk.nkb * MT - ck0) * g.lda * 8 : 0;
     if (nfast > 0) {
@@ -694,13 +818,45 @@ __device__ __forceinline__ void mid_body(const MidArgs &g, double *sh, int tid, 
             // whole rounds of D groups as one branch-free block (a branch inside it and the compiler's vmcnt waits fall back to "all
             // loads": the number of loads in flight must not depend on the path); the loads beyond the last group repeat the last group
             int s0 = 0;
-            for (; s0 + D <= nfast; s0 += D) {
+            if constexpr (!DIAG && DF) {
+                // the first rounds of an item behind a deferred tile: the same rounds with the tile's write-out in them, a step per group
+                // (loops of their own: the steady rounds below keep their instruction stream and their waits)
+                static_assert(MWO_STEPS % D == 0, "whole rounds of write-out steps");
+                for (; s0 + D <= nfast && wk.woq < MWO_STEPS; s0 += D, wk.woq += D) {
+                    const bool ahead = s0 == ahead_at;
+#pragma unroll
+                    for (int d = 0; d < D; ++d) {
+                        const int64_t row = ahead ? (int64_t)(g0 + 4 * d) * 8 : row_of(s0 + d + D);          // (ahead: at least D groups, row_of(d) without its clamp)
+                        const char *base = reinterpret_cast<const char *>(g.A + row);
+                        const MidWoAt at = {sh, wk.woq + d, wave, pmo};
+                        mid_step<DIAG, true>(g, rot, row, base + (ahead ? shift_a : 0), base + (ahead ? shift_b : 0), voff, buf[d], cb[d], g.sign, lane, acc, qacc, at);
+                    }
+                }
+            }
+            // A deferring item draws the ticket behind the item in hand in front of its LAST round, where that is a steady one: the
+            // hand-off is a few hundred clocks of LDS traffic, not the tail that hid the ticket's round trip, and the round is a copy
+            // of its own behind the loop — straight-line, so its waits count the one more operation in flight, and the loop keeps its text.
+            if constexpr (DF) late = defer && s0 + D <= nfast;
+            for (; s0 + D <= nfast - (late ? D : 0); s0 += D) {
                 const bool ahead = s0 == ahead_at;
 #pragma unroll
                 for (int d = 0; d < D; ++d) {
-                    const int64_t row = ahead ? row_of(d) : row_of(s0 + d + D);
+                    // (DF, ahead: at least D groups, row_of(d) without its clamp — with the clamp the deferring build's round held vector instructions)
+                    const int64_t row = ahead ? (DF ? (int64_t)(g0 + 4 * d) * 8 : row_of(d)) : row_of(s0 + d + D);
                     const char *base = reinterpret_cast<const char *>(g.A + row);
                     mid_step<DIAG>(g, rot, row, base + (ahead ? shift_a : 0), base + (ahead ? shift_b : 0), voff, buf[d], cb[d], g.sign, lane, acc, qacc);
+                }
+            }
+            if constexpr (DF) {
+                if (late) {
+                    // (as a wrapping increment: an atomic add the compiler turns into a wave reduction whose result it waits for on the spot)
+                    if (tid == 0) drawn_late = __builtin_amdgcn_atomic_inc32(wk.ticket, ~0u, __ATOMIC_RELAXED, "agent");
+#pragma unroll
+                    for (int d = 0; d < D; ++d) {          // (the last round: ahead, the next item's first groups)
+                        const char *base = reinterpret_cast<const char *>(g.A + (int64_t)(g0 + 4 * d) * 8);
+                        mid_step<DIAG>(g, rot, (int64_t)(g0 + 4 * d) * 8, base + shift_a, base + shift_b, voff, buf[d], cb[d], g.sign, lane, acc, qacc);
+                    }
+                    s0 += D;
                 }
             }
 #pragma unroll
@@ -721,19 +877,48 @@ __device__ __forceinline__ void mid_body(const MidArgs &g, double *sh, int tid, 
         mid_compute<DIAG>(rot, buf[0], cb[0], g.sign, lane, acc, qacc);
     }
 
+    if constexpr (DF) wk.deferred = false;
+    if constexpr (!DIAG && DF) {
+        if (defer) {
+            // The HAND-OFF.  What the loop's rounds did not take of the tile before this one goes out first; then a barrier (every wave's
+            // last read of the pending partials and descriptors), the raw accumulators and this tile's descriptors, a barrier — and the
+            // next item's loop starts, its first groups in registers.  The ticket travels as it does in front of the epilogue.
+            mid_wo_run(sh, wk.woq, wave, pmo);
+            MID_STAMP(1);
+            wk.pre = pf;
+            unsigned drawn = drawn_late;
+            if (!late && tid == 0) drawn = __hip_atomic_fetch_add(wk.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __syncthreads();
+            double *mine = sh + MDEF + wave * MDPART + lane;
+#pragma unroll
+            for (int a = 0; a < MACC; ++a) mine[a * MDP] = acc[a];
+            if (tid < MT) {
+                const int64_t n = g.cols, j = cj0 + tid;
+                u64 *desc = reinterpret_cast<u64 *>(sh + mo + 2 * MT);
+                desc[2 * tid] = (u64)(reinterpret_cast<u64 *>(g.out_quad) + (u64)(j * n - (j * (j - 1)) / 2 + (ck0 - j)) * 3);
+                desc[2 * tid + 1] = reinterpret_cast<const u64 *>(sh + mo)[MT + tid];
+            }
+            if (tid == 0) *wk.slot = wk.id0 + 8 * (int)drawn;
+            __syncthreads();
+            wk.drawn = *wk.slot;
+            wk.woq = 0; wk.par ^= 1; wk.deferred = true;
+            MID_STAMP(5);
+            return;
+        }
+    }
     MID_STAMP(1);
     wk.pre = pf;
     // the ticket behind the item in hand: asked for here, where only the tail's LDS traffic and the epilogue's stores follow it (behind
     // this item's loads, the next item's included); looked at in front of the epilogue
     unsigned drawn = 0;
     if (!DIAG && wk.early && tid == 0) drawn = __hip_atomic_fetch_add(wk.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    unsigned *flag = reinterpret_cast<unsigned *>(sh + MFLAG);
+    unsigned *flag = reinterpret_cast<unsigned *>(sh + MidLds<DF>::FLAG);
     double *w = g.ws + (int64_t)(first_wg + chunk) * MSTRIDE;
     __syncthreads();                                               // every wave is done with its rotation piece
-    if (wave == 0) mid_tail<DIAG, 0>(g, sh, lane, acc, qacc, nchunk, w);
-    else if (wave == 1) mid_tail<DIAG, 1>(g, sh, lane, acc, qacc, nchunk, w);
-    else if (wave == 2) mid_tail<DIAG, 2>(g, sh, lane, acc, qacc, nchunk, w);
-    else mid_tail<DIAG, 3>(g, sh, lane, acc, qacc, nchunk, w);
+    if (wave == 0) mid_tail<DIAG, 0, DF>(g, sh, lane, acc, qacc, nchunk, w);
+    else if (wave == 1) mid_tail<DIAG, 1, DF>(g, sh, lane, acc, qacc, nchunk, w);
+    else if (wave == 2) mid_tail<DIAG, 2, DF>(g, sh, lane, acc, qacc, nchunk, w);
+    else mid_tail<DIAG, 3, DF>(g, sh, lane, acc, qacc, nchunk, w);
     MID_STAMP(2);
     if (nchunk > 1) {
         // One level up to MFG chunks: the tile's last arriver adds them all.  Beyond (few tiles, tall: 65536 x 256 is 10 tiles of 29 chunks —
@@ -793,7 +978,7 @@ __device__ __forceinline__ void mid_body(const MidArgs &g, double *sh, int tid, 
     __syncthreads();
     if (!DIAG && wk.early) wk.drawn = *wk.slot;
     MID_STAMP(5);
-    mid_epilogue(g, sh, tid, jb, kb);
+    mid_epilogue(g, sh, tid, jb, kb, mo);
 #ifdef PMT_MID_TRACE
     __builtin_amdgcn_s_waitcnt(0);
     MID_STAMP(6);
@@ -815,26 +1000,49 @@ __device__ __forceinline__ int mid_xcd_rank(int id, int base, int n) {
 // Strictly upper tile number t -> (jb, kb) in SUPER-TILE order (round 6c): 8 x 8 blocks of tiles, column by column; inside a block row by
 // row (on the diagonal: column by column).  32 consecutive tiles — what an XCD runs at a time — are then 4 row panels x 8 column panels
 // (12 panels through its L2) instead of one column panel with 32 row panels (33): config 2 moved 4.39 GB per launch over the fabric.
+// COLS (the deferring build only, where the decode stands alone between two items in the waves' one issue stream: 1.9 -> 1.2 us per item,
+// profiles/r20_deferred_tile.txt): a column of blocks at a time, the same order; every other build keeps the walk block by block.
+template <bool COLS>
 __device__ __forceinline__ void mid_tile_of(int t, int nb, int &jb, int &kb) {
     constexpr int SB = PMT_MID_SB;
     const int nsb = (nb + SB - 1) / SB;
-    for (int K = 0; K < nsb; ++K) {
-        const int wK = min(SB, nb - SB * K);
-        for (int J = 0; J <= K; ++J) {
-            const int cnt = J < K ? SB * wK : wK * (wK - 1) / 2;
+    if constexpr (!COLS) {
+        for (int K = 0; K < nsb; ++K) {
+            const int wK = min(SB, nb - SB * K);
+            for (int J = 0; J <= K; ++J) {
+                const int cnt = J < K ? SB * wK : wK * (wK - 1) / 2;
+                if (t >= cnt) { t -= cnt; continue; }
+                if (J < K) { jb = SB * J + t / wK; kb = SB * K + t % wK; return; }
+                int kk = 1;
+                while (t >= kk) { t -= kk; ++kk; }
+                jb = SB * K + t; kb = SB * K + kk;
+                return;
+            }
+        }
+        jb = 0; kb = 1;
+    } else {
+        for (int K = 0; K < nsb; ++K) {
+            const int wK = min(SB, nb - SB * K);
+            const int above = K * SB * wK, cnt = above + wK * (wK - 1) / 2;          // the K blocks above the diagonal one, and the column
             if (t >= cnt) { t -= cnt; continue; }
-            if (J < K) { jb = SB * J + t / wK; kb = SB * K + t % wK; return; }
+            if (t < above) {
+                if (wK == SB) { jb = t / SB; kb = SB * K + t % SB; }                  // (block J = t / SB^2, row t % SB^2 / SB of it: SB J + that row is t / SB)
+                else { const int J = t / (SB * wK), u = t - J * SB * wK; jb = SB * J + u / wK; kb = SB * K + u % wK; }
+                return;
+            }
+            t -= above;
             int kk = 1;
             while (t >= kk) { t -= kk; ++kk; }
             jb = SB * K + t; kb = SB * K + kk;
             return;
         }
+        jb = 0; kb = 1;
     }
-    jb = 0; kb = 1;
 }
 
 // one work item of the launch: (tile, chunk) number `id`, or the constant's (the last one)
 struct MidItem { int kind, jb, kb, chunk, nch, gpc, first, rank; };          // kind: 0 a strictly upper tile, 1 a diagonal one, 2 the constant
+template <bool COLS>
 __device__ __forceinline__ MidItem mid_decode(const MidArgs &g, int id) {
     // XCD-aware order: workgroup ids go round-robin over the 8 XCDs (id % 8), each with its own 4 MB L2.  The (chunk, tile) list is walked
     // CHUNK-major and cut into 8 contiguous pieces, one per XCD: the 32 workgroups an XCD runs at a time work on the same rows of A and
@@ -851,7 +1059,7 @@ __device__ __forceinline__ MidItem mid_decode(const MidArgs &g, int id) {
         const int chunk = k / ntile;
         const int rank = (tail ? nbody : 0) + (k - chunk * ntile);          // the tile's place in the walk: its workspace slots and its counters
         int t = rank, jb, kb;
-        if (g.xcd) mid_tile_of(t, g.nb, jb, kb);
+        if (g.xcd) mid_tile_of<COLS>(t, g.nb, jb, kb);
         else {
             kb = 1;
             while (t >= kb) { t -= kb; ++kb; }                     // strictly upper tiles, column by column: (0,1), (0,2), (1,2), (0,3), ..
@@ -870,15 +1078,16 @@ __device__ __forceinline__ MidItem mid_decode(const MidArgs &g, int id) {
     return it;
 }
 
-template <bool FAST>
+template <bool FAST, bool DF>
 __device__ __forceinline__ void mid_item(const MidArgs &g, double *sh, int tid, const MidItem &it, MidWalk &wk, f64x2 (&pbuf)[PMT_MID_D][8]) {
     if (it.kind == 0) {
-        mid_body<false, FAST>(g, sh, tid, it.jb, it.kb, it.chunk, it.nch, it.gpc, it.first, g.counters + it.rank * MCNT, wk, pbuf);
+        mid_body<false, FAST, DF>(g, sh, tid, it.jb, it.kb, it.chunk, it.nch, it.gpc, it.first, g.counters + it.rank * MCNT, wk, pbuf);
         return;
     }
     wk.pre = false;
-    if (it.kind == 1) mid_body<true, FAST>(g, sh, tid, it.jb, it.kb, it.chunk, it.nch, it.gpc, it.first, g.counters + it.rank * MCNT, wk, pbuf);
-    else mid_constant(g, sh, tid);
+    if constexpr (DF) wk.deferred = false;
+    if (it.kind == 1) mid_body<true, FAST, DF>(g, sh, tid, it.jb, it.kb, it.chunk, it.nch, it.gpc, it.first, g.counters + it.rank * MCNT, wk, pbuf);
+    else mid_constant(g, sh, tid);          // (nothing is pending: the item behind a deferring one is a body tile, MidWalk)
     mid_forget(pbuf);
 }
 
@@ -916,20 +1125,24 @@ static_assert(TILE * PITCH + TILE <= MQBUF, "a rider's tile and its variable-map
 // ticket behind it is drawn under the tail — between two items stands one barrier instead of a ticket's round trip between two barriers
 // and the first loads' latency.  The look-ahead stops with the body: from the first id in hand that lies in the split tails or the
 // diagonal chunks on, a workgroup draws on demand, so nobody sits on a short item while others run dry.
+// Round 20: such an item also DEFERS its tile (MidWalk, mid_body: hand-off) — the waves' sums, the doubling and the stores of a finished
+// tile run inside the first rounds of the next item's loop instead of behind its own.
 // A workgroup whose ticket has run dry then draws RIDER tiles (mid_rider_tile) until those are exhausted too, and leaves: Gram items
 // always come first; the launch of one workgroup per item takes no riders.
-template <bool FAST>
+template <bool FAST, bool DF>
 __global__ __launch_bounds__(256, PMT_MID_WPS) void gram_mid_kernel(MidArgs g) {
-    __shared__ double sh[MSH + MID_TRACE_WORDS];
+    constexpr int MSH_AT = MidLds<DF>::SH;
+    __shared__ double sh[MSH_AT + MID_TRACE_WORDS];
     __shared__ int next_id, ahead_id;
     const int tid = threadIdx.x;
     const int x = blockIdx.x & 7, per = gridDim.x >> 3;
 #ifdef PMT_MID_TRACE
-    if (tid == 0) for (int i = 0; i < MID_TRACE_WORDS; ++i) reinterpret_cast<unsigned long long *>(sh + MSH)[i] = 0;
+    if (tid == 0) for (int i = 0; i < MID_TRACE_WORDS; ++i) reinterpret_cast<unsigned long long *>(sh + MSH_AT)[i] = 0;
 #endif
     f64x2 pbuf[PMT_MID_D][8];
     MidWalk wk = {};
     wk.ticket = g.tickets + x; wk.id0 = x + 8 * per; wk.slot = &ahead_id;
+    if constexpr (DF) wk.woq = MWO_STEPS;
     const int wbody = (g.n_off - g.n_tail) * g.s_off;
     const bool look = FAST && g.persist && g.s_off == 1;
     int id = blockIdx.x, hand = -1;                                // `hand`: the id behind `id`, once drawn
@@ -938,18 +1151,18 @@ __global__ __launch_bounds__(256, PMT_MID_WPS) void gram_mid_kernel(MidArgs g) {
         __syncthreads();
         hand = next_id;
     }
-    MidItem cur = mid_decode(g, id);
+    MidItem cur = mid_decode<DF>(g, id);
     for (;;) {
         wk.early = hand >= 0 && hand < wbody;                      // (ids ascend: id is a body item as well; s_off = 1: both are unsplit)
         wk.next_full = false;
         if (wk.early) {
-            const MidItem nx = mid_decode(g, hand);
+            const MidItem nx = mid_decode<DF>(g, hand);
             wk.next_full = (int64_t)(nx.kb + 1) * MT <= g.cols;
             wk.njb = nx.jb; wk.nkb = nx.kb; wk.nrank = nx.rank;
         }
-        mid_item<FAST>(g, sh, tid, cur, wk, pbuf);
+        mid_item<FAST, DF>(g, sh, tid, cur, wk, pbuf);
         if (!g.persist) return;                                    // (one workgroup per item)
-        __syncthreads();                                           // the item's last LDS reads, and next_id's last readers
+        if (!DF || !wk.deferred) __syncthreads();                         // the item's last LDS reads, and next_id's last readers (a deferred tile: the hand-off's barriers)
         if (wk.early) {
             id = hand; hand = wk.drawn;
             cur.jb = wk.njb; cur.kb = wk.nkb; cur.first = cur.rank = wk.nrank;          // (an unsplit body item like `cur`: kind, chunk, nch, gpc stay)
@@ -962,8 +1175,9 @@ __global__ __launch_bounds__(256, PMT_MID_WPS) void gram_mid_kernel(MidArgs g) {
             id = next_id;
         }
         if (id >= g.total) break;
-        cur = mid_decode(g, id);
+        cur = mid_decode<DF>(g, id);
     }
+    // (nothing is pending here, MidWalk: a workgroup's last body item does not defer — the riders and the end of the walk need no write-out)
     if (g.rider_tiles > 0) {
         int mine = 0;
         for (;;) {
@@ -985,7 +1199,7 @@ __global__ __launch_bounds__(256, PMT_MID_WPS) void gram_mid_kernel(MidArgs g) {
     }
 #ifdef PMT_MID_TRACE
     if (tid == 0 && blockIdx.x < 1024) {
-        for (int i = 0; i < 7; ++i) g_mid_walk[blockIdx.x * 8 + i] = reinterpret_cast<unsigned long long *>(sh + MSH)[i];
+        for (int i = 0; i < 7; ++i) g_mid_walk[blockIdx.x * 8 + i] = reinterpret_cast<unsigned long long *>(sh + MSH_AT)[i];
         g_mid_walk[blockIdx.x * 8 + 7] = wall_clock64();
     }
 #endif
@@ -1016,6 +1230,21 @@ size_t gram_mid_workspace_bytes(int64_t rows, int64_t cols) {
     return sizeof(double) * (size_t)p.wgs * MSTRIDE;
 }
 bool gram_mid_persistent(int64_t rows, int64_t cols) { return cols > 0 && rows > 0 && mid_plan(rows, cols).wgs >= 2 * PMT_MID_G; }
+// The shape's plan lets tiles be deferred (MidWalk): the persistent walk over an unsplit body.  *whole_rounds: the row count gives every
+// wave whole rounds of 8-row groups (rows a multiple of 32 PMT_MID_D), so on the fast load path the launch takes the deferring build
+// (gram_mid_kernel<true, true>) and every body tile of two whole panels but a workgroup's last is deferred; otherwise the launch is the
+// build without deferred tiles and every item takes the immediate path.
+static bool mid_plan_defers(const MidPlan &p) {          // (two body tiles per workgroup: with one, nothing is ever pending)
+    return p.wgs >= 2 * PMT_MID_G && p.s_off == 1 && p.n_off - p.n_tail >= 2 * PMT_MID_G;
+}
+static bool mid_rows_defer(int64_t rows) { return rows % (32 * PMT_MID_D) == 0; }
+bool gram_mid_defers(int64_t rows, int64_t cols, bool *whole_rounds) {
+    if (whole_rounds) *whole_rounds = false;
+    if (cols <= 0 || rows <= 0) return false;
+    const bool can = mid_plan_defers(mid_plan(rows, cols));
+    if (whole_rounds) *whole_rounds = can && mid_rows_defer(rows);
+    return can;
+}
 int gram_mid_counters(int64_t cols) { const int nb = (int)cdiv(cols, MT); return MCNT * (nb * (nb + 1) / 2) + 16; }      // (+ the tickets)
 
 // the whole node in one launch; `counters`: gram_mid_counters(cols) zeroed words owned by the calling stream (streams.h: SideStream)
@@ -1041,8 +1270,12 @@ int launch_gram_mid(const double *A, int64_t lda, int64_t rows, int64_t cols, co
     const bool ride = g.persist && riders && nriders > 0 && rider_tiles > 0;
     g.riders = ride ? static_cast<const AffineRider *>(riders) : nullptr; g.nriders = ride ? nriders : 0; g.rider_tiles = ride ? rider_tiles : 0;
     const unsigned grid = g.persist ? (unsigned)PMT_MID_G : (unsigned)p.wgs;
-    if (fast) PMT_LAUNCH_NAMED("gram_mid_kernel", (gram_mid_kernel<true>), dim3(grid), dim3(256), 0, s, g);
-    else PMT_LAUNCH_NAMED("gram_mid_kernel", (gram_mid_kernel<false>), dim3(grid), dim3(256), 0, s, g);
+    // the deferring form where tiles will be deferred (gram_mid_defers + what the call adds: the fast load path, terms and nothing else)
+    const bool df = fast && mid_plan_defers(p) && mid_rows_defer(rows) && out_quad && !out_csc;
+    // (instantiated in this order, the builds without deferred tiles are kernels 1 and 2 of the file as in the parent: tools/isa_diff.py)
+    if (fast && !df) PMT_LAUNCH_NAMED("gram_mid_kernel", (gram_mid_kernel<true, false>), dim3(grid), dim3(256), 0, s, g);
+    else if (!fast) PMT_LAUNCH_NAMED("gram_mid_kernel", (gram_mid_kernel<false, false>), dim3(grid), dim3(256), 0, s, g);
+    else PMT_LAUNCH_NAMED("gram_mid_kernel", (gram_mid_kernel<true, true>), dim3(grid), dim3(256), 0, s, g);
     return check_launch("gram_mid_kernel");
 }
 

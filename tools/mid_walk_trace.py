@@ -74,7 +74,8 @@ for rep in range(5):          # five more launches, each read on its own
     total = us(end - start)
     per = lambda k: us(t[:, k].sum()) / items.sum()
     print("launch %d: %d workgroups, %d items, first start -> last store %.1f us" % (rep, len(t), int(items.sum()), total))
-    print("  per item: main loop %.2f us, sums / count / fold %.2f, epilogue %.2f, last store -> next start %.2f" % (per(1), per(2), per(3), us(t[:, 4].sum()) / max(1.0, (items - 1).sum())))
+    # (a deferring item, gram_mid.hip: MidWalk: its hand-off counts as "sums", it has no epilogue, and the write-out of the tile before it is inside its main loop)
+    print("  per item: main loop %.2f us, sums / count / fold / hand-off %.2f, epilogue %.2f, last store or hand-off -> next start %.2f" % (per(1), per(2), per(3), us(t[:, 4].sum()) / max(1.0, (items - 1).sum())))
     busy = us(t[:, 1] + t[:, 2] + t[:, 3] + t[:, 4])
     print("  per workgroup: in main loops %.1f us (median), elsewhere %.1f; items %d .. %d" % (np.median(us(t[:, 1])), np.median(busy - us(t[:, 1])), items.min(), items.max()))
     idle = us(end - t[:, 6])
