@@ -813,6 +813,50 @@ int pmt_quad_stages_check(const pmt_quad_stage *host_stages, int64_t T, int64_t 
 int pmt_quad_stages_f64(const pmt_quad_stage *stages, int64_t T, const int64_t *varmap, pmt_quadratic_term *out_quad,
                         pmt_linear_term *out_lin, double *stage_consts, double *out_const, void *stream);
 
+/* The batch of horizons: B independent instances (src/model.jl:1-22), each the whole horizon above with weights and references of its own,
+ *   J_i = sum_{t<T} transpose(x_t (+|-) r_{i,t})*Q_i*(x_t (+|-) r_{i,t}) + transpose(u_t (+|-) v_{i,t})*R_i*(u_t (+|-) v_{i,t})
+ * over the instance's variables z = [x_0; u_0; x_1; u_1; ..], n = T*(nx + nu), subject to the constraint block C_i*z (+|-) d_i.  Per instance
+ * this replaces, stage by stage, matvecmul! over the affine vector (src/functions.jl:800-822) and vecdot! (:702-709 over :548-576), the add!
+ * of the stages (:244), canonicalize! (:381-386) and the MOI copies (src/moi_interop.jl:45-81), coefficients only.  Q_i and R_i are shared by
+ * the instance's T stages, so its slab of pmt_batch_horizon_slab_doubles(T, nx, nu, m) doubles at out + i * out_stride holds each once:
+ *     [ SQ: nx(nx+1)/2 | SR: nu(nu+1)/2 | q: n | const: 1 | C: m*n row-major | d-consts: m ]
+ * (out_stride >= that length; the words between two slabs are never written).  Inputs are instance-major: Q[B][nx*nx] and R[B][nu*nu]
+ * column-major with leading dimension nx / nu (they need not be symmetric), r[B][T*nx] and v[B][T*nu] stage-major, C[B][m*n] column-major,
+ * d[B][m].  The contents are fixed bit for bit — plain multiplies and adds, no fma, no floating-point atomics, no workgroup waits for
+ * another; independent of B, of the instance's position, of launch geometry and timing:
+ *   SQ, SR      the moi = 1 coefficients of pmt_quad_form_f64 for Q_i / R_i at tri(j,k) = j*nd - j*(j-1)/2 + k - j (nd = nx / nu): S[j,k] =
+ *               M[j,k] + M[k,j] for j < k, 2*M[j,j] on the diagonal — the Q section of pmt_batch_form_coeffs_f64.
+ *   q           in z order: the nx words of stage x_t are the lin_j of pmt_quad_form_shift_f64 for (Q_i, r_{i,t}, sign_r), the nu words of
+ *               stage u_t those for (R_i, v_{i,t}, sign_v), in that node's order (64-column chains, the first product starting the chain, then
+ *               the nb <= 2 blocks in order).  A sign of 0 is the plain stage: +0.0, and the reference pointer may be NULL.
+ *   const       what pmt_quad_stages_f64 leaves in *out_const for the table [x_0, u_0, x_1, u_1, ..] ([x_0, x_1, ..] with nu == 0): each stage's
+ *               constant 0.5 * T_s in that node's chain-then-tree order (a plain stage: +0.0), the stage constants added in S_d's order — 256
+ *               chains over the stages in z order onto 0.0, then the halving tree.
+ *   C, d-consts as pmt_batch_lsq_coeffs_f64: C row-major, 0.0 (+|-) d, +0.0 with sign_d == 0 (d must still be valid).
+ * Edge cases, each a complete slab: m == 0: [SQ | SR | q | const]; nu == 0: no SR, the stages are x_0, x_1, ..; both signs 0: the plain
+ * horizon, q and const +0.0; B == 0: PMT_OK without a launch, whatever the pointers.  A negative dimension, nx < 1, nx or nu above
+ * PMT_BATCH_HORIZON_MAX_DIM, T outside 1 .. PMT_BATCH_HORIZON_MAX_T or out_stride below the slab length: PMT_DIMENSION_MISMATCH; a sign
+ * outside {-1, 0, 1} or a null pointer where data is needed: PMT_INVALID_ARGUMENT — all before any device call.  One launch, no workspace
+ * (csrc/batch_horizon.hip): persistent workgroups of 256 threads, workgroup g taking the instances g, g + G, ..; a workgroup forms S_Q's
+ * upper 64 x 64 tiles once as pmt_batch_form_coeffs_f64's does and keeps them in LDS (one tile for dims <= 64: three workgroups per CU; three
+ * for dims <= 128: one per CU), writes SQ, runs the T matvecs from LDS with one thread per row (a stage in 16, 32 or 64 lanes of a wave, or
+ * in two waves above 64 rows), then the same for R_i, the constants' tree, C_i and the d-consts.  Algorithmic bytes per instance: 8 (nx^2 + nu^2 + T nx + T nu + m n + m) read, 8 L written.
+ * pmt_batch_horizon_expand_f64 rebuilds ONE instance's MOI buffers from its slab, with xvar the n model variables of z and indices through
+ * the varmap: out_quad (T (nx(nx+1)/2 + nu(nu+1)/2) terms), out_lin (n terms) and *out_const are, word for word, what pmt_quad_stages_f64
+ * writes for the instance's table with the stages laid out one behind the other (quad_at / lin_at cumulative in z order; a plain stage's
+ * linear terms are (0.0, vm[xvar[j]])); out_vat (m*n terms) and out_vconsts (m) are what pmt_batch_expand_f64 writes.  Every output needs
+ * 8-byte alignment only.  The dimension errors above (PMT_DIMENSION_MISMATCH) and a null slab, xvar, varmap or output that a non-zero size
+ * needs (PMT_INVALID_ARGUMENT) come before any device call.  A streaming launch: 8 L bytes read, 24 / 16 / 24 bytes per term written. */
+#define PMT_BATCH_HORIZON_MAX_DIM 128      /* nx, nu */
+#define PMT_BATCH_HORIZON_MAX_T   512
+int64_t pmt_batch_horizon_slab_doubles(int64_t T, int64_t nx, int64_t nu, int64_t m);
+int pmt_batch_horizon_coeffs_f64(const double *Q, const double *R, const double *r, const double *v, const double *C, const double *d,
+                                 int64_t B, int64_t T, int64_t nx, int64_t nu, int64_t m, int sign_r, int sign_v, int sign_d,
+                                 double *out, int64_t out_stride, void *stream);
+int pmt_batch_horizon_expand_f64(const double *slab, int64_t T, int64_t nx, int64_t nu, int64_t m, const int64_t *xvar, const int64_t *varmap,
+                                 pmt_quadratic_term *out_quad, pmt_linear_term *out_lin, double *out_const,
+                                 pmt_vector_affine_term *out_vat, double *out_vconsts, void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * Device-side Parameter update callbacks for synthetic inputs (counter-based):
  * dst[i] = scale * U[0,1)(seed, i)   — the analogue of `Parameter(rand!, zeros(n, n), model)` README.md:36-43

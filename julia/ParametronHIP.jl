@@ -621,6 +621,26 @@ batch_form_coeffs!(out::DevPtr, out_stride, Q::DevPtr, p::DevPtr, C::DevPtr, d::
                 (DevPtr, DevPtr, DevPtr, DevPtr, Int64, Int64, Int64, Cint, Cint, DevPtr, Int64, Ptr{Cvoid}),
                 Q, p, C, d, B, n, m, sign_p, sign_d, out, out_stride, stream))
 
+"doubles of one instance's slab [SQ | SR | q | const | C | d-consts] of the batch of horizons, n = T*(nx + nu)"
+batch_horizon_slab_doubles(T, nx, nu, m) = ccall((:pmt_batch_horizon_slab_doubles, lib), Int64, (Int64, Int64, Int64, Int64), T, nx, nu, m)
+
+"one slab per instance for the batch of horizons sum_t transpose(x_t ± r_t) * Q_i * (x_t ± r_t) + transpose(u_t ± v_t) * R_i * (u_t ± v_t) over
+ C_i*z ± d_i, z = [x_0; u_0; x_1; ..] (nx, nu <= 128, T <= 512): instance-major Q, R (column-major, need not be symmetric), stage-major r, v;
+ SQ / SR / q / const bit for bit what quad_stages! writes for the instance's own table; a sign of 0: plain stages, the reference may be C_NULL"
+batch_horizon_coeffs!(out::DevPtr, out_stride, Q::DevPtr, R::DevPtr, r::DevPtr, v::DevPtr, C::DevPtr, d::DevPtr, B, T, nx, nu, m, sign_r, sign_v,
+                      sign_d, stream) =
+    check(ccall((:pmt_batch_horizon_coeffs_f64, lib), Cint,
+                (DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, Int64, Int64, Int64, Int64, Int64, Cint, Cint, Cint, DevPtr, Int64, Ptr{Cvoid}),
+                Q, R, r, v, C, d, B, T, nx, nu, m, sign_r, sign_v, sign_d, out, out_stride, stream))
+
+"one instance's MOI buffers from its horizon slab: the quadratic / linear terms and the constant of quad_stages! for its table, the
+ constraint block of the least-squares batch's expansion; xvar: the n model variables of z"
+batch_horizon_expand!(slab::DevPtr, T, nx, nu, m, xvar::DevPtr, varmap::DevPtr, out_quad::DevPtr, out_lin::DevPtr, out_const::DevPtr,
+                      out_vat::DevPtr, out_vconsts::DevPtr, stream) =
+    check(ccall((:pmt_batch_horizon_expand_f64, lib), Cint,
+                (DevPtr, Int64, Int64, Int64, Int64, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
+                slab, T, nx, nu, m, xvar, varmap, out_quad, out_lin, out_const, out_vat, out_vconsts, stream))
+
 "the same callback RECORDED with its seed in a host word (`Ref{UInt64}`, kept alive by the caller): every replay draws the stream of the
 seed the word holds then — `seed[] += 1000` before `update!(plan)` is the whole callback"
 device_uniform_dyn!(dst::DevPtr, rows, cols, lda, seed::Ref{UInt64}, scale, stream) =

@@ -241,6 +241,9 @@ SIGNATURES = {
     "pmt_batch_lsq_coeffs_f64": (_ci, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _ci, _vp, _i64, _vp]),
     "pmt_batch_expand_f64": (_ci, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pmt_batch_form_coeffs_f64": (_ci, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _ci, _ci, _vp, _i64, _vp]),
+    "pmt_batch_horizon_slab_doubles": (_i64, [_i64, _i64, _i64, _i64]),
+    "pmt_batch_horizon_coeffs_f64": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _ci, _ci, _ci, _vp, _i64, _vp]),
+    "pmt_batch_horizon_expand_f64": (_ci, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pmt_quad_stages_check": (_ci, [_vp, _i64, _i64, _i64]),
     "pmt_quad_stages_f64": (_ci, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pmt_comm_unique_id": (_ci, [_vp]),

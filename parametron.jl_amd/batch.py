@@ -210,6 +210,82 @@ class BatchTracking:
         self.gather(dist)
 
 
+def horizon_slab_layout(T, nx, nu, m):
+    """Offsets (in doubles) of the sections of one horizon instance's slab [SQ | SR | q | const | C | d-consts] over n = T*(nx + nu)
+    variables, and the slab length (pmt_batch_horizon_slab_doubles)."""
+    n = T * (nx + nu)
+    nqx, nqu = nx * (nx + 1) // 2, nu * (nu + 1) // 2
+    q = nqx + nqu
+    off = {"SQ": 0, "SR": nqx, "q": q, "const": q + n, "C": q + n + 1, "dconst": q + n + 1 + m * n}
+    return off, q + n + 1 + m * n + m
+
+
+class BatchHorizon:
+    """Device-resident batch of MPC horizons sum_t transpose(x_t - r_{i,t}) * Q_i * (x_t - r_{i,t}) + transpose(u_t) * R_i * u_t over
+    C_i*z == d_i, z = [x_0; u_0; x_1; ..] (a fleet of controllers, or of sampled scenarios: every instance with weights and stage references
+    of its own): Q[B][nx x nx], R[B][nu x nu], r[B][T x nx], v[B][T x nu], C[B][m x n], d[B][m] generated by the counter-based stream with
+    GLOBAL element offsets, so instance k holds the same data whatever the sharding.  One launch of pmt_batch_horizon_coeffs_f64 writes the
+    slabs (horizon_slab_layout); gather_slabs takes them as they are; expand() rebuilds one instance's MOI buffers.  There is no pipelined
+    exchange for this objective: step() is compute() and one all-gather."""
+
+    SEEDS = {"Q": 301, "R": 302, "r": 303, "v": 304, "C": 305, "d": 306}
+
+    def __init__(self, torch, total, T, nx, nu, m, rank=0, world=1, device=None):
+        _lib.require_gpu()
+        self.torch, self.total, self.T, self.nx, self.nu, self.m, self.rank, self.world = torch, total, T, nx, nu, m, rank, world
+        self.n = T * (nx + nu)
+        self.lo, self.hi = shard_range(total, rank, world)
+        self.B = self.hi - self.lo
+        dev = device or torch.device("cuda", torch.cuda.current_device())
+        f64 = torch.float64
+        self.per = {"Q": nx * nx, "R": nu * nu, "r": T * nx, "v": T * nu, "C": m * self.n, "d": m}
+        self.Q, self.R, self.r, self.v, self.Cm, self.d = (torch.empty(self.B * self.per[k], dtype=f64, device=dev) for k in "QRrvCd")
+        self.offsets, self.L = horizon_slab_layout(T, nx, nu, m)
+        assert self.L == _lib.load().pmt_batch_horizon_slab_doubles(T, nx, nu, m)
+        self.local = torch.empty((self.B, self.L), dtype=f64, device=dev)
+        self.gathered = torch.empty((total, self.L), dtype=f64, device=dev) if world > 1 else self.local
+        self.stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        self.regenerate(0)
+
+    _p = staticmethod(BatchLSQ._p)
+
+    def regenerate(self, epoch):
+        """device-side Parameter callbacks (↔ rand! in README.md:36-43), one stream per Parameter and epoch"""
+        for name, buf, scale in (("Q", self.Q, 1.0), ("R", self.R, 1.0), ("r", self.r, 1.0), ("v", self.v, 1.0), ("C", self.Cm, 1.0), ("d", self.d, 2.0)):
+            per = self.per[name]
+            _lib.call("pmt_fill_uniform_offset_f64", self._p(buf), self.B * per, C.c_uint64(self.SEEDS[name] + 1000 * epoch),
+                      C.c_uint64(self.lo * per), scale, self.stream)
+
+    def compute(self):
+        """x_t - r_t, u_t as it is, C*z - d"""
+        _lib.call("pmt_batch_horizon_coeffs_f64", self._p(self.Q), self._p(self.R), self._p(self.r), self._p(self.v), self._p(self.Cm),
+                  self._p(self.d), self.B, self.T, self.nx, self.nu, self.m, -1, 0, -1, self._p(self.local), self.L, self.stream)
+
+    def gather(self, dist):
+        if self.world > 1:
+            gather_slabs(dist, self.local, self.gathered)
+
+    def step(self, dist):
+        self.compute()
+        self.gather(dist)
+
+    def expand(self, i, xvar, varmap):
+        """the MOI buffers of local instance i from its slab (pmt_batch_horizon_expand_f64): xvar the n model variables of z, varmap the
+        model-to-optimizer index map, both int64 device tensors -> (quadratic terms as 3 words each, linear terms as 2 words each, the
+        constant, vector-affine terms as 3 words each, their m constants), device tensors"""
+        torch, T, n, m = self.torch, self.T, self.n, self.m
+        nq = T * (self.nx * (self.nx + 1) // 2 + self.nu * (self.nu + 1) // 2)
+        dev = self.local.device
+        quad = torch.empty(3 * nq, dtype=torch.int64, device=dev)
+        lin = torch.empty(2 * n, dtype=torch.int64, device=dev)
+        const = torch.empty(1, dtype=torch.float64, device=dev)
+        vat = torch.empty(max(3 * m * n, 1), dtype=torch.int64, device=dev)
+        vconsts = torch.empty(max(m, 1), dtype=torch.float64, device=dev)
+        _lib.call("pmt_batch_horizon_expand_f64", C.c_void_p(self.local.data_ptr() + 8 * i * self.L), T, self.nx, self.nu, m, self._p(xvar),
+                  self._p(varmap), self._p(quad), self._p(lin), self._p(const), self._p(vat), self._p(vconsts), self.stream)
+        return quad, lin, const, vat[:3 * m * n], vconsts[:m]
+
+
 TOTAL, N, R, M = 8192, 128, 128, 16        # BASELINE config 4 (m is not stated there: 16, SURVEY.md section 8d)
 
 
