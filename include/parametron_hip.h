@@ -813,6 +813,57 @@ int pmt_quad_stages_check(const pmt_quad_stage *host_stages, int64_t T, int64_t 
 int pmt_quad_stages_f64(const pmt_quad_stage *stages, int64_t T, const int64_t *varmap, pmt_quadratic_term *out_quad,
                         pmt_linear_term *out_lin, double *stage_consts, double *out_const, void *stream);
 
+/* Horizon dynamics constraints: the MOI.VectorAffineFunction buffers of T affine records from one launch — x_{t+1} == A*x_t + B*u_t (+ w_t)
+ * for every stage of a horizon, the other half of the model whose objective pmt_quad_stages_f64 writes.  A record is a sum
+ * (+|-)L_1 (+|-) L_2 .. of 1 .. PMT_AFFINE_STAGES_MAX_PARTS leaves of equal row count with terms — a dense product M*v of a column-major
+ * matrix and a Variable vector, or a Variable vector alone — and at most one number vector.  In the reference every product is matvecmul!
+ * (src/functions.jl:775-798), every + / - vecadd! / vecsubtract! (:751-764: copyto! :419-427, add! / subtract! :452-485) and the copy
+ * update!(::MOI.VectorAffineFunction, fs, varmap) (src/moi_interop.jl:64-81).  Two DEVICE tables describe the records; the host builds them once:
+ *   pmt_affine_part   one leaf with terms, in expression order: `mat` (rows x cols, leading dimension ld) over the cols model variables
+ *                     `xvar`, or mat == NULL for a Variable vector (cols == 1, `xvar` has the record's `rows` entries); sign = +1 | -1, the
+ *                     product of the signs on the leaf's way to the root.
+ *   pmt_affine_stage  one record: rows, its parts first_part .. first_part + nparts - 1, row_len = the sum of their cols, its first term
+ *                     (term_offset) and first constant (const_offset) in the outputs, its number vector `vec` with vec_sign = +1 | -1, or
+ *                     NULL with vec_sign == 0.
+ * For stage s, row i, part p starting at term o_p of the row (the cols of the parts before it), column j:
+ *   out_terms[term_offset + i*row_len + o_p + j] = (i + 1,  mat[i + j*ld], with its sign bit flipped when sign == -1,  vm[xvar[j]])
+ *       a Variable-vector part:                    (i + 1,  +1.0 | -1.0,  vm[xvar[i]])                (vm[v] = varmap[v - 1], v itself without a varmap)
+ *   out_consts[const_offset + i] = 0.0 (+|-) vec[i] by vec_sign,  0.0 without a vector
+ * These are the words of pmt_affine_assemble_f64 per product, pmt_affvec_combine_f64 per + / - and pmt_pack_vector_affine_f64 on the same
+ * data: the combine copies part a and multiplies part b by an exact +1 / -1 (-1 flips the sign bit, of a zero too), the pack copies the
+ * coefficients.  The constant: a product's constants are +0.0, a Variable vector has none, and every combine gives ca (+ sb*cb), or 0.0 + sb*cb
+ * without ca; so a number vector that is NOT the leftmost leaf of the whole sum has passed through at least one `0.0 (+|-)` or `+0.0 +` by
+ * the root, which leaves 0.0 (+|-) vec[i] for every input, signed zeros included (NaN payloads are not part of the contract).  A leftmost
+ * number vector enters as itself (a -0.0 entry survives): such a record is not described by these tables.
+ * Every output word is written exactly once per call, nothing outside the stages' slices; no atomics, no workgroup waits for another; the
+ * words do not depend on T, on a stage's position in the table, on launch geometry or on timing.  Persistent workgroups of 256 threads walk
+ * the stages; a matrix part is cut into tiles of 16 rows x 64 columns, read along its columns, transposed through LDS and written row segment by row
+ * segment as 16-byte stores — a segment may start at an address 8 mod 16 (csrc/affine_stages.hip).  Algorithmic bytes: 24 per term and 8
+ * per constant written; every matrix once per stage (from L2 when stages share it), the vectors, index words and tables read.
+ * pmt_affine_stages_check is host arithmetic over HOST copies of the tables (no device call): a null table with T > 0, a null xvar, a part
+ * sign other than +-1, a vec_sign outside {-1, 0, 1}, a vector without a sign or a sign without a vector: PMT_INVALID_ARGUMENT; negative
+ * counts, rows < 1, nparts outside 1 .. PMT_AFFINE_STAGES_MAX_PARTS, parts outside [0, nparts), cols < 1, ld < rows, a Variable-vector part
+ * with cols != 1, row_len not the sum of the parts' cols, or term / constant slices that do not tile [0, nterms) / [0, nconsts) exactly — an
+ * overlap, a gap, a slice past the end: PMT_DIMENSION_MISMATCH.  pmt_affine_stages_f64 itself rejects T < 0 (PMT_DIMENSION_MISMATCH) and,
+ * with T > 0, a null table or output (PMT_INVALID_ARGUMENT) before any device call; varmap may be NULL (the identity); T == 0 writes
+ * nothing.  The kernel reads the tables on the device and does NOT check them again: pass tables only after the check accepted their host copies. */
+#define PMT_AFFINE_STAGES_MAX_PARTS 8
+typedef struct {
+    const double *mat; int64_t ld;     /* rows x cols, column-major; NULL: a Variable vector */
+    const int64_t *xvar;               /* cols model-variable indices (a Variable vector: rows of them) */
+    int32_t cols, sign;                /* terms per row; +1 | -1 */
+} pmt_affine_part;                     /* 32 bytes, no padding (static_assert in csrc/affine_stages.hip) */
+typedef struct {
+    const double *vec;                 /* the number vector, or NULL with vec_sign == 0 */
+    int64_t term_offset, const_offset; /* first term / constant of the stage in out_terms / out_consts */
+    int64_t row_len;                   /* terms per row: the sum of the parts' cols */
+    int32_t rows, first_part, nparts, vec_sign;
+} pmt_affine_stage;                    /* 48 bytes, no padding (static_assert in csrc/affine_stages.hip) */
+int pmt_affine_stages_check(const pmt_affine_stage *host_stages, int64_t T, const pmt_affine_part *host_parts, int64_t nparts,
+                            int64_t nterms, int64_t nconsts);
+int pmt_affine_stages_f64(const pmt_affine_stage *stages, int64_t T, const pmt_affine_part *parts, const int64_t *varmap,
+                          pmt_vector_affine_term *out_terms, double *out_consts, void *stream);
+
 /* The batch of horizons: B independent instances (src/model.jl:1-22), each the whole horizon above with weights and references of its own,
  *   J_i = sum_{t<T} transpose(x_t (+|-) r_{i,t})*Q_i*(x_t (+|-) r_{i,t}) + transpose(u_t (+|-) v_{i,t})*R_i*(u_t (+|-) v_{i,t})
  * over the instance's variables z = [x_0; u_0; x_1; u_1; ..], n = T*(nx + nu), subject to the constraint block C_i*z (+|-) d_i.  Per instance

@@ -224,6 +224,41 @@ quad_stages!(out_quad, out_lin, stage_consts, out_const, stages::DevPtr, T, varm
     check(ccall((:pmt_quad_stages_f64, lib), Cint, (DevPtr, Int64, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
                 stages, T, varmap, out_quad, out_lin, stage_consts, out_const, stream))
 
+"pmt_affine_part (include/parametron_hip.h): one leaf with terms of a record of pmt_affine_stages_f64 — a matrix (column-major, leading
+ dimension ld) over `cols` model variables, or mat C_NULL for a Variable vector (cols 1); sign +1 | -1; 32 bytes, no padding"
+struct AffinePart
+    mat::DevPtr
+    ld::Int64
+    xvar::DevPtr
+    cols::Int32
+    sign::Int32
+end
+
+"pmt_affine_stage: one record — its number vector (C_NULL with vec_sign 0), its first term / constant in the outputs, the terms per row, its
+ rows and its run of parts; 48 bytes, no padding"
+struct AffineStage
+    vec::DevPtr
+    term_offset::Int64
+    const_offset::Int64
+    row_len::Int64
+    rows::Int32
+    first_part::Int32
+    nparts::Int32
+    vec_sign::Int32
+end
+const AFFINE_STAGES_MAX_PARTS = 8
+
+"host arithmetic over host tables: pointers, signs, sizes, row_len = the sum of the parts' cols, slices that tile [0, nterms) / [0, nconsts)"
+affine_stages_check(stages::Vector{AffineStage}, parts::Vector{AffinePart}, nterms, nconsts) =
+    check(ccall((:pmt_affine_stages_check, lib), Cint, (Ptr{AffineStage}, Int64, Ptr{AffinePart}, Int64, Int64, Int64),
+                stages, length(stages), parts, length(parts), nterms, nconsts))
+
+"the MOI.VectorAffineFunction buffers of T affine records (a horizon's dynamics constraints) from one launch: `stages` and `parts` are the
+ DEVICE copies of tables affine_stages_check accepted (the kernel does not check them again)"
+affine_stages!(out_terms, out_consts, stages::DevPtr, T, parts::DevPtr, varmap, stream) =
+    check(ccall((:pmt_affine_stages_f64, lib), Cint, (DevPtr, Int64, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
+                stages, T, parts, varmap, out_terms, out_consts, stream))
+
 "structure of a solver matrix from 1-based (row, col) indices (host, once): perm, seg_ptr, colptr, rowval (0-based), nnz"
 function csc_order(rows::Vector{Int64}, cols::Vector{Int64}, nrows, ncols; upper::Bool=false)
     n = length(rows)

@@ -77,6 +77,38 @@ def quad_stages(stages):
     return arr
 
 
+PMT_AFFINE_STAGES_MAX_PARTS = 8
+
+
+class AffinePart(C.Structure):
+    """pmt_affine_part: one leaf with terms of a record of pmt_affine_stages_f64 (device addresses; mat None: a Variable vector, cols 1)."""
+    _fields_ = [("mat", C.c_void_p), ("ld", C.c_int64), ("xvar", C.c_void_p), ("cols", C.c_int32), ("sign", C.c_int32)]
+
+
+class AffineStage(C.Structure):
+    """pmt_affine_stage: one record of pmt_affine_stages_f64 (vec a device address, or None with vec_sign 0)."""
+    _fields_ = [("vec", C.c_void_p), ("term_offset", C.c_int64), ("const_offset", C.c_int64), ("row_len", C.c_int64), ("rows", C.c_int32),
+                ("first_part", C.c_int32), ("nparts", C.c_int32), ("vec_sign", C.c_int32)]
+
+
+def _struct_array(cls, rows):
+    arr = (cls * max(len(rows), 1))()
+    for i, t in enumerate(rows):
+        for k, v in t.items():
+            setattr(arr[i], k, v)
+    return arr
+
+
+def affine_parts(parts):
+    """host array of pmt_affine_part from dicts of its fields (missing fields: 0 / None)"""
+    return _struct_array(AffinePart, parts)
+
+
+def affine_stages(stages):
+    """host array of pmt_affine_stage from dicts of its fields (missing fields: 0 / None)"""
+    return _struct_array(AffineStage, stages)
+
+
 def stack_table(srcs, signs):
     """host image of the pmt_stack_column table of pmt_affine_stack_columns_f64: column c is signs[c] * (the column at device address
     srcs[c]).  The entry point reads the table on the device only, so the signs are checked here."""
@@ -246,6 +278,8 @@ SIGNATURES = {
     "pmt_batch_horizon_expand_f64": (_ci, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pmt_quad_stages_check": (_ci, [_vp, _i64, _i64, _i64]),
     "pmt_quad_stages_f64": (_ci, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pmt_affine_stages_check": (_ci, [_vp, _i64, _vp, _i64, _i64, _i64]),
+    "pmt_affine_stages_f64": (_ci, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "pmt_comm_unique_id": (_ci, [_vp]),
     "pmt_comm_init_rank": (_ci, [_ci, _ci, _vp, _ci, C.POINTER(_vp)]),
     "pmt_comm_destroy": (_ci, [_vp]),

@@ -589,6 +589,18 @@ def _rule_vec_addsub(model, ctx, a, b, sign):                                   
             if out.mat is not None:
                 c.call("pmt_affine_stack_columns_f64", P(out.table), out.ncols, out.rows, P(out.mat.buf), out.mat.lda)
         return DeviceNode(model, name, _inputs(a, b), out, emit)
+    if _sum_leaves(da, db, 1 if sign > 0 else -1) is not None:
+        # a sum of dense products, Variable vectors and at most one number vector (a horizon's dynamics record, affine_stage_leaves): the
+        # same combine, but its buffers and its operands' exist only once a consumer asks (_DeferredSum) — the record of a stage group
+        # (moi.affine_stage_group) reads the leaves themselves
+        out = _DeferredSum(ctx, len(lens), row_ptr, (da, db, 1 if sign > 0 else -1))
+
+        def emit(c):
+            if out.need_terms:
+                (ta, pa, la, ca), (tb, pb, lb, cb) = out.parts
+                c.call("pmt_affvec_combine_f64", out.rows, P(ta), P(pa), la, P(ca), P(tb), P(pb), lb, P(cb), out.operands[2],
+                       P(out.terms), P(out.row_ptr_buf), out.row_len, P(out.consts))
+        return DeviceNode(model, name, _inputs(a, b), out, emit)
     ta, pa, la, ca = _affvec_parts(da)
     tb, pb, lb, cb = _affvec_parts(db)
     out = DAffVec(ctx, len(lens), row_ptr=row_ptr)
@@ -597,6 +609,97 @@ def _rule_vec_addsub(model, ctx, a, b, sign):                                   
         c.call("pmt_affvec_combine_f64", out.rows, P(ta), P(pa), la, P(ca), P(tb), P(pb), lb, P(cb), 1 if sign > 0 else -1,
                P(out.terms), P(out.row_ptr_buf), out.row_len, P(out.consts))
     return DeviceNode(model, name, _inputs(a, b), out, emit)
+
+
+class _DeferredSum(DAffVec):
+    """a (+|-) b of the generic vecadd! / vecsubtract! path whose leaves are all of the kinds affine_stage_leaves names: like DStackedAff the
+    LinearTerms exist only on demand (`require_terms` / `materialized`: a literal consumer, the record's own MOI copy, expr()), written by
+    today's pmt_affvec_combine_f64 of the two operands, which are materialised with it.  `operands`: (a, b, sb), the combine's arguments."""
+
+    def __init__(self, ctx, rows, row_ptr, operands):
+        super().__init__(ctx, rows, row_ptr=row_ptr, alloc=False)
+        self.operands = operands
+        self.parts = None                 # require_terms: the combine's (terms, row_ptr_buf, row_len, consts) of a and of b
+        self.need_terms = False
+
+    def require_terms(self):
+        if not self.need_terms:
+            self.need_terms = True
+            self.parts = (_affvec_parts(self.operands[0]), _affvec_parts(self.operands[1]))
+            self.terms = self.ctx.alloc(16 * max(self.nterms, 1))
+            self.consts = self.ctx.alloc(8 * max(self.rows, 1))
+        return self
+
+    def materialized(self):
+        return self.require_terms()
+
+
+AFFINE_STAGE_MAX_LEAVES = 8
+
+
+def _append_leaves(dv, sign, out):
+    """the leaves of one operand, each with the product of the signs on its way to the root; False: not a sum of such leaves"""
+    if isinstance(dv, DVars):
+        out.append(("vars", dv, sign))
+    elif isinstance(dv, DVec):
+        out.append(("vec", dv, sign))
+    elif isinstance(dv, DDenseAff):                      # M*v, or the fused M*v (+|-) b
+        if not isinstance(dv.mat, DMat) or not (dv.vec is None or isinstance(dv.vec, DVec)):
+            return False
+        out.append(("mat", dv, sign))
+        if dv.vec is not None:
+            out.append(("vec", dv.vec, sign * dv.sign))
+    elif isinstance(dv, DVarsAff):                       # the fused x (+|-) v
+        if not isinstance(dv.vec, DVec):
+            return False
+        out.append(("vars", dv.xvars, sign))
+        out.append(("vec", dv.vec, sign * dv.sign))
+    elif isinstance(dv, (DStackedAff, _DeferredSum)):    # a vector + / - node: its two operands
+        a, b, sb = dv.operands
+        return _append_leaves(a, sign, out) and _append_leaves(b, sign * sb, out)
+    else:                                                # a scaled leaf, a sparse product, a materialised vector, ..
+        return False
+    return True
+
+
+def _sum_leaves(da, db, sb, root=False):
+    """affine_stage_leaves for the sum da (+|-) db before its node exists.  Below the root of a record the number vector may come first
+    (w - B*u inside x+ - (A*x - (w - B*u))): such a node is deferred like the others, and only a whole record must not start with it."""
+    leaves = []
+    if not (_append_leaves(da, 1, leaves) and _append_leaves(db, sb, leaves)):
+        return None
+    if not 2 <= len(leaves) <= AFFINE_STAGE_MAX_LEAVES or sum(1 for k, _, _ in leaves if k == "vec") > 1 or (root and leaves[0][0] == "vec"):
+        return None
+    rows = _vec_len(da)
+    if any((d.rows if k == "mat" else d.n) != rows for k, d, _ in leaves):
+        return None
+    return leaves
+
+
+def affine_stage_leaves(expr):
+    """The flattened leaf list [(kind, operand, effective sign), ..] in expression order of a constraint record's expression node, or None.
+    Host data only.  kind "mat": a dense product M*v (operand: its DDenseAff — `mat` the matrix Parameter's device mirror, `xvars` the
+    Variable vector); "vars": a Variable vector (DVars); "vec": a number vector (DVec).  The effective sign is the product of the signs on
+    the leaf's way to the root.
+
+    Eligible: a tree of vector + / - nodes (as constraint() builds with lhs - rhs; not an implicit block A*x (+|-) b, x (+|-) v or
+    C*x (+|-) d on its own) with 2 .. 8 leaves, every one of the record's row count, at most one of them a number vector, and that one not
+    the leftmost leaf.  A scaled leaf, a sparse product or any other operand: None.
+
+    Why the number vector must not come first — from pmt_affvec_combine_f64's rule (include/parametron_hip.h): a combine writes
+    [a's terms ; sb * b's terms] and the constant ca (+ sb*cb), 0.0 (+ sb*cb) when a has none.  Terms: a leaf's coefficients are copied or
+    multiplied by exact +-1 at every level, so they arrive as the matrix entries (1.0 for a Variable) with the sign bit flipped iff the
+    effective sign is -1.  Constants: a product's are +0.0 (pmt_affine_assemble_f64 without a vector), a Variable vector has none.  With
+    the number vector w in b's place at its first combine the constant becomes ca + sb*w with ca = +0.0, or 0.0 + sb*w: for every w, -0.0
+    included, that is 0.0 (+|-) w, never -0.0.  Every later level leaves such a value c alone (c + (+-0.0) = c as part a) or turns it
+    into 0.0 + (+-c) (as part b), and 0.0 + -(0.0 + w) = 0.0 - w bit for bit (both +0.0 for a zero w); the fused A*x (+|-) w and x (+|-) w
+    write 0.0 (+|-) w themselves.  So the chain's constant is signed_const(w, effective sign).  As part a of the FIRST combine, though, w
+    enters as itself; it is cleaned only if its subtree later becomes a part b.  Leftmost in the whole record it never does: a -0.0 entry
+    would survive (w + -0.0), where 0.0 (+|-) w gives +0.0."""
+    out = expr.out if isinstance(expr, DeviceNode) else None
+    if not isinstance(out, (DStackedAff, _DeferredSum)):
+        return None
+    return _sum_leaves(*out.operands, root=True)
 
 
 def _stack_parts(dv):

@@ -198,6 +198,7 @@ class Model:
         self._run_slot = []                     # ... and per Parameter its slot in the C model (_create_model_run), or -1: written here
         self._model_run = None                  # _create_model_run: the pmt_model behind _fast_update
         self._fetches_read_parameters = False   # handoff.DeviceQP: host_csc transfers leave straight out of Parameter buffers
+        self._stage_group = None                # _group_affine_stages: the dynamics records written by one launch, or None
         if quadratic_mode not in ("auto", "literal", "canonical"):
             raise ArgumentError("quadratic_mode must be 'auto', 'literal' or 'canonical'")
         if handoff not in ("moi", "device", "host_csc"):
@@ -358,6 +359,7 @@ class Model:
             ctx.upload(self._varmap_buf, self.model_var_to_optimizer if early else ident)
             varmap = self.model_var_to_optimizer if early else None
             self._plan_quadratic_records(varmap)
+            self._group_affine_stages()
             emitters = [r.compile(ctx, self._varmap_buf, varmap) for r in records]
             self._order = schedule([r.expr for r in records])
             for x in self._order:
@@ -396,6 +398,15 @@ class Model:
                 g.require_stack()
             if plan.canonicalize:
                 r.expr = r.expr.canonicalize()
+
+    def _group_affine_stages(self):
+        """the horizon's dynamics records as one launch (moi.affine_stage_group): decided after the records exist and before their
+        emitters are compiled; the grouped records' nodes are never asked for their terms, so the nodes below them emit nothing"""
+        for r in self._records:
+            r.stage_group = None
+        self._stage_group = group = moi.affine_stage_group(self._records, self._small, self.handoff)
+        for r in (group.members if group is not None else ()):
+            r.stage_group = group
 
     def _record_tape(self, ctx, emitters):
         """the tape: Parameter callbacks of a small model, the nodes in the reference's order, the records' MOI copies as lane_order places them"""

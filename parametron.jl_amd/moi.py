@@ -13,7 +13,7 @@ import numpy as np
 from ._lib import LT, QT, VAT, ArgumentError, DimensionMismatch, ErrorException
 from .device import DAff, DAffVec, DDenseAff, DQuad, DSparseAff, DStackedAff, DVarsAff, P
 from .functions import AffineFunction, LinearTerm, QuadraticFunction, QuadraticTerm, Variable, _isnum
-from .lazyexpression import DeviceNode, QuadForm, SparseQuadForm, kind_of
+from .lazyexpression import DeviceNode, QuadForm, SparseQuadForm, affine_stage_leaves, kind_of
 
 MIN_SENSE, MAX_SENSE = "MIN_SENSE", "MAX_SENSE"
 
@@ -200,6 +200,7 @@ class _Record:
         self.expr = expr
         self.isconstant = not isinstance(expr, DeviceNode)                # "it's just a value; not a LazyExpression" (:123)
         self.plan = QuadPlan(None)                                        # a quadratic record's is decided in Model._plan_quadratic_records (quad_plan)
+        self.stage_group = None                                           # Model.initialize: the AffineStageGroup whose one launch writes this record (affine_stage_group)
         self._reset_compiled()
         if self.isconstant:
             self.kind = canonical_function_kind(kind_of(expr))
@@ -238,6 +239,10 @@ class _Record:
         no quadratic term structs at all."""
         self._reset_compiled()
         self._cbuf = ctx.pinned_array(1, np.float64)
+        if self.stage_group is not None:
+            emit = self.stage_group.compile_member(self, ctx, varmap_buf)
+            self.buffers = [(self.f._terms, "terms"), (self.f.constants, "consts")]
+            return emit
         if self.kind == "aff":
             emit = self._compile_affine(ctx, varmap_buf, handoff_varmap)
             self.buffers = [(self.f.terms, "terms"), (self._cbuf, "const")]
@@ -699,6 +704,8 @@ class _Record:
         """(host array, device address) of the entries of `buffers` that need a D2H copy: a key absent from dev has none (P's CSC values are
         written instead of quadratic terms, a bare form has no linear terms, static terms never leave the host), and neither has a twin
         that IS the host array (a small model, _twin)"""
+        if self.stage_group is not None:                                  # the group's two arenas travel with its first member
+            return self.stage_group.copies(self)
         d = self.dev or {}
         return [(host, d[key]) for host, key in self.buffers if key in d and key not in skip and d[key] != host.ctypes.data]
 
@@ -930,6 +937,112 @@ def quad_plan(terms, bare, kind, nq, is_objective, quadratic_mode, small, handof
                 return QuadPlan("canonical-stages", stages=stages)
     # anything else: the literal function through the generic device canonicalize! (sorted, duplicates combined) before the MOI copy
     return QuadPlan("literal", canonicalize=True)
+
+
+# A horizon's dynamics records (x_{t+1} == A*x_t + B*u_t (+ w_t) for every stage) are grouped from this many on: more than "canonical-groups"
+# holds, the objective's own threshold for "canonical-stages" (_lsq_stages), so a horizon model gets both launches or neither.  Measured
+# (tools/affine_stages_probe.py, profiles/r21_affine_stages.txt): at nine records of 10 x (1 + 10 + 4) terms the group is already the faster
+# plan — update! 308 against 361 us under a graph replay, 370 against 626 us as a tape with recorded fetches — and the ratio only grows
+# with T (3.5 x at 100 x (64, 32)); no crossover above the threshold.
+AFFINE_STAGE_MIN_RECORDS = 9
+
+
+class AffineStageGroup:
+    """The vector-affine constraint records one pmt_affine_stages_f64 launch writes (affine_stage_group decides; Model.initialize attaches
+    the group to its members, _Record.compile executes).  `members` in update! order, `leaves` their affine_stage_leaves.  One page-locked
+    arena for all terms and one for all constants, each with a device twin; every member's VectorAffineFunction lies over its slices, so
+    set_constraint_function, .terms, .constants and mapindices! see what they see today.  The first member's emitter makes the call and
+    its copies() are the group's two fetches; the other members emit and fetch nothing.  The tables are built, checked
+    (pmt_affine_stages_check) and uploaded when the first member is compiled: update! allocates nothing."""
+
+    def __init__(self, members, leaves):
+        self.members, self.leaves = members, leaves
+        self.terms_host = self.consts_host = None
+        self.dev = None
+
+    def _layout(self):
+        """the part and stage tables as lists of dicts, the members' slices, (nterms, nconsts)"""
+        parts, stages, slices = [], [], []
+        ta = ca = 0
+        for r, leaves in zip(self.members, self.leaves):
+            rows, first, row_len, vec, vs = r.expr.out.rows, len(parts), 0, None, 0
+            for kind, d, sign in leaves:
+                if kind == "mat":
+                    parts.append({"mat": d.mat.buf, "ld": d.mat.lda, "xvar": d.xvars.buf, "cols": d.mat.cols, "sign": sign})
+                    row_len += d.mat.cols
+                elif kind == "vars":
+                    parts.append({"mat": None, "ld": 0, "xvar": d.buf, "cols": 1, "sign": sign})
+                    row_len += 1
+                else:
+                    vec, vs = d.buf, sign
+            stages.append({"vec": vec, "term_offset": ta, "const_offset": ca, "row_len": row_len, "rows": rows, "first_part": first,
+                           "nparts": len(parts) - first, "vec_sign": vs})
+            slices.append((ta, rows * row_len, ca, rows))
+            ta, ca = ta + rows * row_len, ca + rows
+        return parts, stages, slices, ta, ca
+
+    def _build(self, ctx, varmap_buf):
+        from . import _lib
+        parts, stages, self.slices, nterms, nconsts = self._layout()
+        parr, sarr = _lib.affine_parts(parts), _lib.affine_stages(stages)
+        T = len(stages)
+        _lib.call("pmt_affine_stages_check", C.addressof(sarr), T, C.addressof(parr), len(parts), nterms, nconsts)
+        self.terms_host, self.consts_host = ctx.pinned_array(nterms, VAT), ctx.pinned_array(nconsts, np.float64)
+        dterms, dconsts = ctx.alloc(24 * nterms), ctx.alloc(8 * nconsts)
+        self.dev = {"terms": dterms, "consts": dconsts}
+        stable, ptable = ctx.alloc(C.sizeof(sarr)), ctx.alloc(C.sizeof(parr))
+        ctx.upload(stable, np.frombuffer(sarr, dtype=np.uint8).copy())
+        ctx.upload(ptable, np.frombuffer(parr, dtype=np.uint8).copy())
+        return lambda c: c.call("pmt_affine_stages_f64", P(stable), T, P(ptable), P(varmap_buf), P(dterms), P(dconsts))
+
+    def compile_member(self, r, ctx, varmap_buf):
+        """sets r.f (over the member's arena slices) and r.dev; returns the member's emitter — the launch for the first, nothing for the rest"""
+        k = [i for i, m in enumerate(self.members) if m is r][0]
+        emit = self._build(ctx, varmap_buf) if k == 0 else (lambda c: None)
+        ta, nt, ca, rows = self.slices[k]
+        arena = {np.dtype(VAT): self.terms_host[ta:ta + nt], np.dtype(np.float64): self.consts_host[ca:ca + rows]}
+        r.f = VectorAffineFunction(nt, rows, alloc=lambda n, dtype: arena[np.dtype(dtype)])
+        r.dev = {"terms": self.dev["terms"] + 24 * ta, "consts": self.dev["consts"] + 8 * ca}
+        return emit
+
+    def copies(self, r):
+        if r is not self.members[0] or self.dev is None:
+            return []
+        return [(host, dptr) for host, dptr in ((self.terms_host, self.dev["terms"]), (self.consts_host, self.dev["consts"])) if host.nbytes]
+
+
+def affine_stage_group(records, small, handoff):
+    """The AffineStageGroup of a model's records (`records`: the non-constant records in update! order), or None.  The one decision on
+    the horizon dynamics' path: tests and tools/affine_stages_probe.py replace this function by one that returns None and get the plan
+    every record had before for the same model.
+
+    A record is eligible when it is a vector-affine constraint whose expression flattens (lazyexpression.affine_stage_leaves), whose
+    node nobody else consumes — no other record over the same node, no consumer that asked for its terms — and that has a row.  The
+    eligible records form the group when the model is beyond the small plan, the boundary is the host MOI functions (handoff "moi"),
+    there are at least AFFINE_STAGE_MIN_RECORDS of them and two of them read the same matrix (a horizon's shape: nine unrelated records
+    keep their own chains).  Every other record, interleaved among them or not, keeps its path and its place."""
+    if small or handoff != "moi":
+        return None
+    nodes = [id(r.expr) for r in records]
+    members, leaves = [], []
+    for r in records:
+        if not isinstance(r, Constraint) or r.kind != "affvec" or nodes.count(id(r.expr)) != 1:
+            continue
+        lv = affine_stage_leaves(r.expr)
+        if lv is None or r.expr.out.need_terms or r.expr.out.rows < 1:
+            continue
+        members.append(r)
+        leaves.append(lv)
+    if len(members) < AFFINE_STAGE_MIN_RECORDS:
+        return None
+    readers = {}
+    for k, lv in enumerate(leaves):
+        for kind, d, _ in lv:
+            if kind == "mat":
+                readers.setdefault(id(d.mat), set()).add(k)
+    if not any(len(v) >= 2 for v in readers.values()):
+        return None
+    return AffineStageGroup(members, leaves)
 
 
 class Objective(_Record):                                                 # src/moi_interop.jl:113-137
