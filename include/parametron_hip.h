@@ -812,6 +812,44 @@ typedef struct {
 int pmt_quad_stages_check(const pmt_quad_stage *host_stages, int64_t T, int64_t nterms, int64_t nlin);
 int pmt_quad_stages_f64(const pmt_quad_stage *stages, int64_t T, const int64_t *varmap, pmt_quadratic_term *out_quad,
                         pmt_linear_term *out_lin, double *stage_consts, double *out_const, void *stream);
+/* The same horizon with a weight, a linear term and scalar constants beside the stages — 0.5*(sum_t ..), a discount g_t*(..), a tunable
+ * rho*transpose(u_t)*R*u_t, an economic term dot(c_t, u_t), an offset — still one launch plus the short constant launch.  `terms` is a
+ * DEVICE array of T entries, entry t belonging to stage t of `stages`; `consts` a DEVICE array of nconsts (0 .. PMT_QUAD_STAGES_MAX_CONSTS)
+ * entries.  Weights are read on the device at run time: W_t = scale * (*weight), or scale when weight is NULL; W_c likewise from
+ * lin_scale / lin_weight (ignored when lin_vec is NULL); W_i likewise for constant i.  Each product scale * (*weight) is one rounded double.
+ * Stage t's slice equals, word for word, what two calls leave for that stage alone: pmt_quad_form_f64 / pmt_quad_form_shift_f64 (moi = 1,
+ * alpha = 1.0), then pmt_quad_gram_sum_f64 over [first block with (scale, weight), PMT_LSQ_LINEAR with (lin_scale, lin_weight, lin_vec)].
+ * With c(j,k), lin_j and cc_t = 0.5*T_t as pmt_quad_stages_f64 defines them, plain multiplies and adds, no fma:
+ *   quadratic terms  coeff(j,k) = W_t * c(j,k) (c = S[j,k], and 2*Q[j,j] on the diagonal: W_t * (2*Q[j,j])); the index words are unchanged.
+ *   linear terms     lin[j] = W_t * lin_j, then + W_c * c_t[j] when lin_vec is given.  A plain stage multiplies its +0.0: a negative W_t
+ *                    leaves -0.0 where no linear term follows, as pmt_quad_gram_sum_f64 does; the sign of that zero is part of the contract.
+ *   constant         stage_consts[t] = W_t * cc_t (a plain stage: W_t * +0.0).  *out_const = the chain-then-tree sum of stage_consts exactly
+ *                    as pmt_quad_stages_f64 adds it; then, in table order, s = s + W_i * (value_i ? *value_i : 1.0) for the nconsts
+ *                    constants, by one thread of the same second launch.  T == 0 writes only *out_const: the constants added onto 0.0.
+ * A stage with scale == 1.0, weight == NULL and lin_vec == NULL writes the words of pmt_quad_stages_f64: multiplying by 1.0 is exact.  A
+ * NaN weight puts NaN into its own stage's coefficients and into *out_const, and into no other stage's words.
+ * Everything else of pmt_quad_stages_f64's contract holds unchanged: every output word is written exactly once per call, nothing outside
+ * the slices, results independent of T, of a stage's position, of launch geometry and of timing; no workgroup waits for another, no
+ * atomics, no workspace; stage_consts needs no zeroing.  The chains behind lin_j and cc_t stay unweighted, so they keep their order.
+ * pmt_quad_stages_terms_check is host arithmetic over HOST copies of the three tables (no device call): everything
+ * pmt_quad_stages_check refuses, with its code; a null host_terms with T > 0 or a null host_consts with nconsts > 0: PMT_INVALID_ARGUMENT;
+ * nconsts outside 0 .. PMT_QUAD_STAGES_MAX_CONSTS: PMT_DIMENSION_MISMATCH.  pmt_quad_stages_terms_f64 itself rejects null pointers
+ * (PMT_INVALID_ARGUMENT) and negative counts (PMT_DIMENSION_MISMATCH) before any device call and does not check the tables again.
+ * Algorithmic bytes: those of pmt_quad_stages_f64, plus 40 per stage, n per linear vector and 24 per constant read. */
+typedef struct {
+    double scale; const double *weight;          /* W_t = weight ? scale * *weight : scale  (device scalar, read at run time) */
+    double lin_scale; const double *lin_weight;  /* W_c likewise; ignored when lin_vec is NULL */
+    const double *lin_vec;                       /* c_t (n doubles) of dot(c_t, x_t), or NULL */
+} pmt_quad_stage_terms;                          /* 40 bytes, no padding; entry t belongs to stage t */
+typedef struct {
+    double scale; const double *weight; const double *value;   /* W_s * (value ? *value : 1.0) */
+} pmt_quad_stage_const;                          /* 24 bytes */
+#define PMT_QUAD_STAGES_MAX_CONSTS 32
+int pmt_quad_stages_terms_check(const pmt_quad_stage *host_stages, const pmt_quad_stage_terms *host_terms, int64_t T,
+                                const pmt_quad_stage_const *host_consts, int64_t nconsts, int64_t nterms, int64_t nlin);
+int pmt_quad_stages_terms_f64(const pmt_quad_stage *stages, const pmt_quad_stage_terms *terms, int64_t T,
+                              const pmt_quad_stage_const *consts, int64_t nconsts, const int64_t *varmap,
+                              pmt_quadratic_term *out_quad, pmt_linear_term *out_lin, double *stage_consts, double *out_const, void *stream);
 
 /* Horizon dynamics constraints: the MOI.VectorAffineFunction buffers of T affine records from one launch — x_{t+1} == A*x_t + B*u_t (+ w_t)
  * for every stage of a horizon, the other half of the model whose objective pmt_quad_stages_f64 writes.  A record is a sum

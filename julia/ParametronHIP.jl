@@ -224,6 +224,36 @@ quad_stages!(out_quad, out_lin, stage_consts, out_const, stages::DevPtr, T, varm
     check(ccall((:pmt_quad_stages_f64, lib), Cint, (DevPtr, Int64, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
                 stages, T, varmap, out_quad, out_lin, stage_consts, out_const, stream))
 
+"pmt_quad_stage_terms (include/parametron_hip.h): what stands beside stage t of pmt_quad_stages_terms_f64 — the weight scale * (*weight)
+ (weight C_NULL: scale alone) and the linear term dot(c_t, x_t) with its own weight (lin_vec C_NULL: none); 40 bytes, no padding"
+struct QuadStageTerms
+    scale::Float64
+    weight::DevPtr
+    lin_scale::Float64
+    lin_weight::DevPtr
+    lin_vec::DevPtr
+end
+
+"pmt_quad_stage_const (include/parametron_hip.h): one scalar constant scale * (*weight) * (*value) beside the stages (value C_NULL: 1.0);
+ 24 bytes"
+struct QuadStageConst
+    scale::Float64
+    weight::DevPtr
+    value::DevPtr
+end
+
+"quad_stages_check over the stages, and the two further host tables: one QuadStageTerms per stage, at most 32 constants"
+quad_stages_terms_check(stages::Vector{QuadStage}, terms::Vector{QuadStageTerms}, consts::Vector{QuadStageConst}, nterms, nlin) =
+    check(ccall((:pmt_quad_stages_terms_check, lib), Cint, (Ptr{QuadStage}, Ptr{QuadStageTerms}, Int64, Ptr{QuadStageConst}, Int64, Int64, Int64),
+                stages, terms, length(stages), consts, length(consts), nterms, nlin))
+
+"quad_stages! with a weight and a linear term per stage and scalar constants beside the stages: `stages`, `terms` (T entries) and `consts`
+ (nconsts entries) are the DEVICE copies of tables quad_stages_terms_check accepted; the weights are read on the device at run time"
+quad_stages_terms!(out_quad, out_lin, stage_consts, out_const, stages::DevPtr, terms::DevPtr, T, consts::DevPtr, nconsts, varmap, stream) =
+    check(ccall((:pmt_quad_stages_terms_f64, lib), Cint,
+                (DevPtr, DevPtr, Int64, DevPtr, Int64, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
+                stages, terms, T, consts, nconsts, varmap, out_quad, out_lin, stage_consts, out_const, stream))
+
 "pmt_affine_part (include/parametron_hip.h): one leaf with terms of a record of pmt_affine_stages_f64 — a matrix (column-major, leading
  dimension ld) over `cols` model variables, or mat C_NULL for a Variable vector (cols 1); sign +1 | -1; 32 bytes, no padding"
 struct AffinePart

@@ -77,6 +77,42 @@ def quad_stages(stages):
     return arr
 
 
+PMT_QUAD_STAGES_MAX_CONSTS = 32
+
+
+class QuadStageTerms(C.Structure):
+    """pmt_quad_stage_terms: the weight and the linear term of one stage of pmt_quad_stages_terms_f64 (device addresses, or None)."""
+    _fields_ = [("scale", C.c_double), ("weight", C.c_void_p), ("lin_scale", C.c_double), ("lin_weight", C.c_void_p), ("lin_vec", C.c_void_p)]
+
+
+class QuadStageConst(C.Structure):
+    """pmt_quad_stage_const: one scalar constant beside the stages of pmt_quad_stages_terms_f64 (device addresses, or None)."""
+    _fields_ = [("scale", C.c_double), ("weight", C.c_void_p), ("value", C.c_void_p)]
+
+
+assert C.sizeof(QuadStageTerms) == 40 and C.sizeof(QuadStageConst) == 24
+
+
+def _scaled_struct_array(cls, rows, scales):
+    arr = (cls * max(len(rows), 1))()
+    for i, t in enumerate(rows):
+        for k in scales:
+            setattr(arr[i], k, 1.0)
+        for k, v in t.items():
+            setattr(arr[i], k, v)
+    return arr
+
+
+def quad_stage_terms(terms):
+    """host array of pmt_quad_stage_terms from dicts of its fields (missing fields: scale / lin_scale 1.0, pointers None)"""
+    return _scaled_struct_array(QuadStageTerms, terms, ("scale", "lin_scale"))
+
+
+def quad_stage_consts(consts):
+    """host array of pmt_quad_stage_const from dicts of its fields (missing fields: scale 1.0, pointers None)"""
+    return _scaled_struct_array(QuadStageConst, consts, ("scale",))
+
+
 PMT_AFFINE_STAGES_MAX_PARTS = 8
 
 
@@ -278,6 +314,8 @@ SIGNATURES = {
     "pmt_batch_horizon_expand_f64": (_ci, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pmt_quad_stages_check": (_ci, [_vp, _i64, _i64, _i64]),
     "pmt_quad_stages_f64": (_ci, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pmt_quad_stages_terms_check": (_ci, [_vp, _vp, _i64, _vp, _i64, _i64, _i64]),
+    "pmt_quad_stages_terms_f64": (_ci, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pmt_affine_stages_check": (_ci, [_vp, _i64, _vp, _i64, _i64, _i64]),
     "pmt_affine_stages_f64": (_ci, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "pmt_comm_unique_id": (_ci, [_vp]),

@@ -19,8 +19,12 @@
 //   - the epilogue writes 24-byte term structs row by row and 16-byte linear terms through wave_write_words (common.h), as quad_form_tile
 //     (form.hip) and sparse_form_kernel do: a slice starts at any 8-byte address.
 // The stages' constants go to stage_consts[t]; a second launch of one workgroup, ordered by the stream alone, adds them in S_d's order.
+// pmt_quad_stages_terms_f64 is the same pair of launches with a weight and a linear term dot(c_t, x_t) per stage and scalar constants
+// beside the stages, from two more device tables: both kernels are templates on TERMS, and the instantiations without it are the device
+// code of pmt_quad_stages_f64 unchanged.
 // LDS: 33280 (tile) + 8192 (P) + 2048 (c) + 2048 (tree) + 2048 (index words) + 2048 (lin) = 49664 bytes: three workgroups per CU.
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -37,6 +41,7 @@ constexpr int QS_WG_PER_CU = 3;
 static_assert(QS_MAX_N == PMT_QUAD_STAGES_MAX_N, "the header's bound is the kernel's");
 static_assert(QS_MAX_N <= QS_THREADS, "one thread per j adds the blocks; the tree takes one product per thread");
 static_assert(sizeof(pmt_quad_stage) == 56, "pmt_quad_stage: 56 bytes, no padding (the ctypes and Julia mirrors)");
+static_assert(sizeof(pmt_quad_stage_terms) == 40 && sizeof(pmt_quad_stage_const) == 24, "pmt_quad_stage_terms / _const: 40 / 24 bytes, no padding");
 
 struct QuadStagesArgs {
     const pmt_quad_stage *stages; int64_t T;
@@ -44,6 +49,13 @@ struct QuadStagesArgs {
     QT *quad; LT *lin;
     double *consts, *cst;
 };
+
+// pmt_quad_stages_terms_f64: the stages' weights and linear terms, and the table of scalar constants added behind the tree
+struct QuadStagesTermsArgs : QuadStagesArgs {
+    const pmt_quad_stage_terms *terms;
+    const pmt_quad_stage_const *cterms; int64_t nconsts;
+};
+template <bool TERMS> using QsArgs = std::conditional_t<TERMS, QuadStagesTermsArgs, QuadStagesArgs>;
 
 __device__ __forceinline__ int64_t qs_tri_pos(int64_t n, int64_t j, int64_t k) { return j * n - (j * (j - 1)) / 2 + (k - j); }
 
@@ -72,7 +84,12 @@ __device__ __forceinline__ void qs_landed(double (&v)[16]) {
 
 }  // namespace
 
-__global__ __launch_bounds__(QS_THREADS) void quad_stages_kernel(QuadStagesArgs g) {
+// TERMS (pmt_quad_stages_terms_f64): stage t is weighted and may carry a linear term (g.terms[t], pmt_quad_stage_terms): W_t multiplies
+// every value word, the linear coefficients and the constant as they are written, W_c * c_t[j] is added to the weighted linear
+// coefficient; the chains (part, cvec, the tree) stay unweighted, so lin_j and cc_t keep the order of the unweighted stage.  No LDS of
+// its own.  The instantiation without TERMS is the kernel of pmt_quad_stages_f64 as it was (tools/isa_diff.py).
+template <bool TERMS>
+__global__ __launch_bounds__(QS_THREADS) void quad_stages_kernel(QsArgs<TERMS> g) {
     typedef unsigned long long u64w;
     __shared__ double tile[QS_TILE][QS_TILE + 1];
     __shared__ double part[QS_MAX_NB][QS_MAX_N];          // P[B][j]
@@ -85,6 +102,8 @@ __global__ __launch_bounds__(QS_THREADS) void quad_stages_kernel(QuadStagesArgs 
 
     for (int64_t t = blockIdx.x; t < g.T; t += gridDim.x) {
         const pmt_quad_stage d = g.stages[t];
+        [[maybe_unused]] pmt_quad_stage_terms e;          // (asked for with the descriptor: one round trip for both)
+        if constexpr (TERMS) e = g.terms[t];
         const int n = d.n, nt = (n + QS_TILE - 1) / QS_TILE;
         const int64_t ldq = d.ldq;
         const double *__restrict__ Q = d.Q;
@@ -97,6 +116,15 @@ __global__ __launch_bounds__(QS_THREADS) void quad_stages_kernel(QuadStagesArgs 
         if (shift) pv = d.vec[ct];
         int64_t xv = d.xvar[ct];
         bool pending = true;
+        // the two weight Parameters and the thread's c_t[j] are asked for here too and looked at behind the first tile's loads.  No load is
+        // conditional: a pointer the entry does not give is replaced by the address of the entry's own scale, and the value dropped
+        double wt = 1.0, wc = 0.0, cl = 0.0, wv = 0.0, wcv = 0.0;
+        if constexpr (TERMS) {
+            const double *own = &g.terms[t].scale;
+            wv = *(e.weight ? e.weight : own);
+            wcv = *(e.lin_weight ? e.lin_weight : own);
+            cl = *(e.lin_vec ? e.lin_vec + ct : own);
+        }
 
         for (int bj = 0; bj < nt; ++bj) {
             for (int bk = bj; bk < nt; ++bk) {
@@ -139,6 +167,11 @@ __global__ __launch_bounds__(QS_THREADS) void quad_stages_kernel(QuadStagesArgs 
                     if (tid < n) {
                         var[tid] = varmap[xv - 1];
                         if (shift) cvec[tid] = signed_const(pv, d.sign);
+                    }
+                    if constexpr (TERMS) {              // W_t = scale * (*weight) or scale, W_c likewise: one rounded product each
+                        asm volatile("" : "+v"(wv), "+v"(wcv), "+v"(cl));
+                        wt = e.weight ? e.scale * wv : e.scale;
+                        wc = e.lin_weight ? e.lin_scale * wcv : e.lin_scale;
                     }
                     pending = false;
                 }
@@ -183,7 +216,8 @@ __global__ __launch_bounds__(QS_THREADS) void quad_stages_kernel(QuadStagesArgs 
                         if (f == 1) return rowvar;
                         if (f == 2) return (u64w)var[k0 + off + e];
                         const double v = tile[jj][off + e];
-                        return (u64w)__double_as_longlong((diagonal && e == 0) ? 2 * v : v);      // the row's first term is its diagonal term
+                        const double c = (diagonal && e == 0) ? 2 * v : v;                        // the row's first term is its diagonal term
+                        return (u64w)__double_as_longlong(TERMS ? wt * c : c);
                     });
                 }
                 __syncthreads();
@@ -198,6 +232,10 @@ __global__ __launch_bounds__(QS_THREADS) void quad_stages_kernel(QuadStagesArgs 
                 lin = part[0][tid];
                 for (int b = 1; b < nt; ++b) lin = lin + part[b][tid];
                 prod = cvec[tid] * lin;
+            }
+            if constexpr (TERMS) {                        // W_t * lin_j (a plain stage: W_t * +0.0), then + W_c * c_t[j]
+                lin = wt * lin;
+                if (e.lin_vec) lin = lin + wc * cl;
             }
             linv[tid] = lin;
         }
@@ -220,14 +258,19 @@ __global__ __launch_bounds__(QS_THREADS) void quad_stages_kernel(QuadStagesArgs 
             if (tid < h) red[tid] = red[tid] + red[tid + h];
             __syncthreads();
         }
-        if (tid == 0) g.consts[t] = shift ? 0.5 * red[0] : 0.0;
+        if (tid == 0) {
+            const double cc = shift ? 0.5 * red[0] : 0.0;
+            g.consts[t] = TERMS ? wt * cc : cc;
+        }
         __syncthreads();                                  // the next stage reuses cvec, part, red, var and linv
     }
 }
 
 // Behind quad_stages_kernel on the stream: one workgroup adds the T stage constants in S_d's order (gram_sum.hip: 256 chains onto 0.0,
-// chain c taking the stages c, c + 256, .. in order, then the halving tree).  T == 0 gives 0.0.
-__global__ __launch_bounds__(QS_THREADS) void quad_stages_const_kernel(QuadStagesArgs g) {
+// chain c taking the stages c, c + 256, .. in order, then the halving tree).  T == 0 gives 0.0.  TERMS: one thread then adds the scalar
+// constants in table order, s = s + W_i * (value_i or 1.0).
+template <bool TERMS>
+__global__ __launch_bounds__(QS_THREADS) void quad_stages_const_kernel(QsArgs<TERMS> g) {
     __shared__ double red[QS_THREADS];
     const int tid = threadIdx.x;
     const double *__restrict__ c = g.consts;
@@ -239,7 +282,19 @@ __global__ __launch_bounds__(QS_THREADS) void quad_stages_const_kernel(QuadStage
         if (tid < h) red[tid] = red[tid] + red[tid + h];
         __syncthreads();
     }
-    if (tid == 0) *g.cst = red[0];
+    if constexpr (TERMS) {
+        if (tid == 0) {
+            s = red[0];
+            for (int64_t i = 0; i < g.nconsts; ++i) {
+                const pmt_quad_stage_const k = g.cterms[i];
+                const double w = k.weight ? k.scale * *k.weight : k.scale;
+                s = s + w * (k.value ? *k.value : 1.0);
+            }
+            *g.cst = s;
+        }
+    } else {
+        if (tid == 0) *g.cst = red[0];
+    }
 }
 
 static int qs_cu_count() {
@@ -263,6 +318,22 @@ static bool qs_slices_ok(std::vector<std::pair<int64_t, int64_t>> &s, int64_t to
         end = p.first + p.second;
     }
     return true;
+}
+
+// the stage launch (none for T == 0) and the constant's, behind each other on the stream
+template <bool TERMS>
+static int qs_launch(void *stream, const QsArgs<TERMS> &g) {
+    return dispatch(stream, [=](hipStream_t s) {
+        if (g.T > 0) {
+            // three workgroups per CU stay resident (LDS); each walks the stages blockIdx.x, blockIdx.x + G, ..
+            const dim3 grid((unsigned)std::min<int64_t>(g.T, (int64_t)QS_WG_PER_CU * qs_cu_count()));
+            PMT_LAUNCH(quad_stages_kernel<TERMS>, grid, dim3(QS_THREADS), 0, s, g);
+            const int rc = check_launch("quad_stages_kernel");
+            if (rc != PMT_OK) return rc;
+        }
+        PMT_LAUNCH(quad_stages_const_kernel<TERMS>, dim3(1), dim3(QS_THREADS), 0, s, g);
+        return check_launch("quad_stages_const_kernel");
+    });
 }
 
 }  // namespace pmt
@@ -305,15 +376,35 @@ extern "C" int pmt_quad_stages_f64(const pmt_quad_stage *stages, int64_t T, cons
     g.varmap = varmap;
     g.quad = out_quad; g.lin = out_lin;
     g.consts = stage_consts; g.cst = out_const;
-    return dispatch(stream, [=](hipStream_t s) {
-        if (T > 0) {
-            // three workgroups per CU stay resident (LDS); each walks the stages blockIdx.x, blockIdx.x + G, ..
-            const dim3 grid((unsigned)std::min<int64_t>(T, (int64_t)QS_WG_PER_CU * qs_cu_count()));
-            PMT_LAUNCH(quad_stages_kernel, grid, dim3(QS_THREADS), 0, s, g);
-            const int rc = check_launch("quad_stages_kernel");
-            if (rc != PMT_OK) return rc;
-        }
-        PMT_LAUNCH(quad_stages_const_kernel, dim3(1), dim3(QS_THREADS), 0, s, g);
-        return check_launch("quad_stages_const_kernel");
-    });
+    return qs_launch<false>(stream, g);
+}
+
+extern "C" int pmt_quad_stages_terms_check(const pmt_quad_stage *host_stages, const pmt_quad_stage_terms *host_terms, int64_t T,
+                                           const pmt_quad_stage_const *host_consts, int64_t nconsts, int64_t nterms, int64_t nlin) {
+    const int rc = pmt_quad_stages_check(host_stages, T, nterms, nlin);
+    if (rc != PMT_OK) return rc;
+    PMT_REQUIRE(T == 0 || host_terms, PMT_INVALID_ARGUMENT, "quad_stages_terms: null table of stage terms");
+    PMT_REQUIRE(nconsts >= 0 && nconsts <= PMT_QUAD_STAGES_MAX_CONSTS, PMT_DIMENSION_MISMATCH, "quad_stages_terms: nconsts outside 0 .. 32");
+    PMT_REQUIRE(nconsts == 0 || host_consts, PMT_INVALID_ARGUMENT, "quad_stages_terms: null table of constants");
+    return PMT_OK;
+}
+
+extern "C" int pmt_quad_stages_terms_f64(const pmt_quad_stage *stages, const pmt_quad_stage_terms *terms, int64_t T,
+                                         const pmt_quad_stage_const *consts, int64_t nconsts, const int64_t *varmap,
+                                         pmt_quadratic_term *out_quad, pmt_linear_term *out_lin, double *stage_consts, double *out_const,
+                                         void *stream) {
+    PMT_REQUIRE(T >= 0, PMT_DIMENSION_MISMATCH, "quad_stages_terms: negative stage count");
+    PMT_REQUIRE(nconsts >= 0 && nconsts <= PMT_QUAD_STAGES_MAX_CONSTS, PMT_DIMENSION_MISMATCH, "quad_stages_terms: nconsts outside 0 .. 32");
+    PMT_REQUIRE(out_const, PMT_INVALID_ARGUMENT, "quad_stages_terms: null constant");
+    PMT_REQUIRE(nconsts == 0 || consts, PMT_INVALID_ARGUMENT, "quad_stages_terms: null table of constants");
+    PMT_REQUIRE(T == 0 || (stages && terms && varmap && out_quad && out_lin && stage_consts), PMT_INVALID_ARGUMENT,
+                "quad_stages_terms: null pointer");
+    QuadStagesTermsArgs g;
+    g.stages = stages; g.T = T;
+    g.varmap = varmap;
+    g.quad = out_quad; g.lin = out_lin;
+    g.consts = stage_consts; g.cst = out_const;
+    g.terms = terms;
+    g.cterms = consts; g.nconsts = nconsts;
+    return qs_launch<true>(stream, g);
 }

@@ -453,12 +453,14 @@ class _Record:
         return emit
 
     def _compile_stages(self, ctx, varmap_buf, handoff_varmap):
-        """The objective as a sum of horizon stages — dense forms, plain or shifted, of weight 1 over pairwise disjoint Variable vectors, more
+        """The objective as a sum of horizon stages — dense forms, plain or shifted, over pairwise disjoint Variable vectors, more
         of them than "canonical-groups" holds (plan.stages): ONE pmt_quad_stages_f64 writes every stage's canonical function from a device
         table of descriptors built, checked (pmt_quad_stages_check) and uploaded here once — straight into the stages' slices of the MOI
         buffers when their variables are consecutive in the sorted union z, into an arena otherwise, from where the unchanged
         pmt_quad_groups_gather_f64 places the rows, as _compile_groups does.  The stages' constants are added by the call's own second
-        launch.  update! allocates nothing and makes one call, or two with the gather."""
+        launch.  With weights, linear terms or constants beside the stages (plan.stage_terms, plan.stage_consts) the one call is
+        pmt_quad_stages_terms_f64 over two more tables, checked by pmt_quad_stages_terms_check.  update! allocates nothing and makes one
+        call, or two with the gather."""
         from . import _lib
         stages = self.plan.stages
         lay = _lib.GroupsLayout([q.xvars.vars for q in stages])
@@ -477,12 +479,34 @@ class _Record:
         arr = _lib.quad_stages([{"Q": q.mat.buf, "ldq": q.mat.lda, "xvar": q.xvars.buf, "vec": q.vec.buf if q.vec is not None else None,
                                  "n": q.mat.cols, "sign": q.sign if q.vec is not None else 0, "quad_at": int(oq[k]), "lin_at": int(ol[k])}
                                 for k, q in enumerate(stages)])
-        _lib.call("pmt_quad_stages_check", C.addressof(arr), T, nq, n)
-        table = ctx.alloc(C.sizeof(arr))
-        ctx.upload(table, np.frombuffer(arr, dtype=np.uint8).copy())
+        def weight(t):
+            return t.param.buf if t.param is not None else None
+
+        def uploaded(a):
+            buf = ctx.alloc(C.sizeof(a))
+            ctx.upload(buf, np.frombuffer(a, dtype=np.uint8).copy())
+            return buf
+        sterms, sconsts = self.plan.stage_terms, self.plan.stage_consts
+        if sterms is None and not sconsts:
+            # no weight, no linear term, no constant: the unweighted entry point, as before
+            _lib.call("pmt_quad_stages_check", C.addressof(arr), T, nq, n)
+            table = uploaded(arr)
+            launch = lambda c: c.call("pmt_quad_stages_f64", P(table), T, P(varmap_buf), P(bq), P(bl), P(consts), P(dc))
+        else:
+            # the weights, the linear terms' vectors and the constants are device mirrors of Parameters, read by the launch at run time
+            tarr = _lib.quad_stage_terms([{"scale": s.scale, "weight": weight(s)} if s.lin is None else
+                                          {"scale": s.scale, "weight": weight(s), "lin_scale": s.lin.scale, "lin_weight": weight(s.lin),
+                                           "lin_vec": s.lin.vec.buf} for s in sterms or [StageTerms()] * T])
+            carr = _lib.quad_stage_consts([{"scale": k.scale, "weight": weight(k), "value": k.value.buf if k.value is not None else None}
+                                           for k in sconsts])
+            nc = len(sconsts)
+            _lib.call("pmt_quad_stages_terms_check", C.addressof(arr), C.addressof(tarr), T, C.addressof(carr), nc, nq, n)
+            table, ttable, ctable = uploaded(arr), uploaded(tarr), uploaded(carr)
+            launch = lambda c: c.call("pmt_quad_stages_terms_f64", P(table), P(ttable), T, P(ctable), nc, P(varmap_buf), P(bq), P(bl), P(consts),
+                                      P(dc))
 
         def emit(c):
-            c.call("pmt_quad_stages_f64", P(table), T, P(varmap_buf), P(bq), P(bl), P(consts), P(dc))
+            launch(c)
             if not lay.ordered:
                 c.call("pmt_quad_groups_gather_f64", P(bq), P(tables[0]), P(tables[1]), n, nq, P(bl), P(tables[2]), n, P(dq), P(dl))
         return emit
@@ -833,34 +857,67 @@ def _lsq_groups(terms):
     return groups if all(_lsq_sum_combines(g.terms) for g in groups) else None
 
 
+class StageTerms:
+    """What stands beside stage t of a "canonical-stages" plan (pmt_quad_stage_terms): the stage's weight scale * param (param: the DNum of
+    a scalar Parameter, or None) and its linear term dot(c_t, x_t) (`lin`: the 'linear' LsqTerm with its own scale / param / vec, or None)"""
+    __slots__ = ("scale", "param", "lin")
+
+    def __init__(self, scale=1.0, param=None, lin=None):
+        self.scale, self.param, self.lin = scale, param, lin
+
+    def plain(self):
+        return self.scale == 1.0 and self.param is None and self.lin is None
+
+
 def _lsq_stages(terms):
-    """The QuadForms of an LsqTerm list that is a horizon of stage costs, or None: more than PMT_QUAD_MAX_GROUPS terms, every one a dense
-    form transpose(x_t)*Q*x_t or transpose(x_t (+|-) v_t)*Q*(x_t (+|-) v_t) of weight exactly 1 (no scale, no Parameter factor) over a
+    """(QuadForms, StageTerms per stage or None, 'constant' LsqTerms) of an LsqTerm list that is a horizon of stage costs, or None: more
+    than PMT_QUAD_MAX_GROUPS 'form' terms, every one a dense form transpose(x_t)*Q*x_t or transpose(x_t (+|-) v_t)*Q*(x_t (+|-) v_t) over a
     strictly increasing vector of 1 .. PMT_QUAD_STAGES_MAX_N variables, the vectors pairwise disjoint, and at least two stages reading the
-    same weight matrix (the device mirror of one matrix Parameter) — the horizon's shape; nine unrelated forms keep the literal path."""
+    same weight matrix (the device mirror of one matrix Parameter) — the horizon's shape; nine unrelated forms keep the literal path.
+    Every form may carry a weight (a number times at most one scalar Parameter: 0.5*(..), a discount, rho*transpose(u)*R*u); beside the
+    forms stand 'linear' terms dot(c_t, x_t), each over exactly the vector of one stage and at most one per stage, and at most
+    PMT_QUAD_STAGES_MAX_CONSTS 'constant' terms.  Anything else in the list — a block, a diagonal term, a sparse form, a linear term over
+    part of a stage or over other variables, a second one on a stage — leaves the sum to the literal path.  The StageTerms are None when
+    no stage has a weight or a linear term: with no constant either, the record is the unweighted one (pmt_quad_stages_f64)."""
     from . import _lib
     terms = terms or ()
-    if len(terms) <= _lib.PMT_QUAD_MAX_GROUPS:
+    forms = [t for t in terms if t.kind == "form"]
+    consts = [t for t in terms if t.kind == "constant"]
+    if len(forms) <= _lib.PMT_QUAD_MAX_GROUPS or len(consts) > _lib.PMT_QUAD_STAGES_MAX_CONSTS:
         return None
-    for t in terms:
-        if not (t.kind == "form" and isinstance(t.r, QuadForm) and t.scale == 1.0 and t.param is None and not t.host_scaled):
+    if any(t.kind not in ("form", "linear", "constant") or t.host_scaled for t in terms):
+        return None
+    for t in forms:
+        if not isinstance(t.r, QuadForm):
             return None
         v = t.r.xvars.vars
         if not 1 <= len(v) <= _lib.PMT_QUAD_STAGES_MAX_N or t.r.mat.cols != len(v) or np.any(np.diff(v) <= 0):
             return None
-    z = np.concatenate([t.r.xvars.vars for t in terms])
-    if len(np.unique(z)) != len(z) or len({id(t.r.mat) for t in terms}) == len(terms):
+    z = np.concatenate([t.r.xvars.vars for t in forms])
+    if len(np.unique(z)) != len(z) or len({id(t.r.mat) for t in forms}) == len(forms):
         return None
-    return [t.r for t in terms]
+    stage_terms = [StageTerms(t.scale, t.param) for t in forms]
+    first = {int(t.r.xvars.vars[0]): k for k, t in enumerate(forms)}             # (disjoint vectors: a stage is named by its first variable)
+    for t in terms:
+        if t.kind != "linear":
+            continue
+        v = t.xvars.vars if t.xvars is not None else ()
+        k = first.get(int(v[0])) if len(v) else None
+        if k is None or t.vec is None or stage_terms[k].lin is not None or not np.array_equal(v, forms[k].r.xvars.vars):
+            return None
+        stage_terms[k].lin = t
+    return [t.r for t in forms], None if all(s.plain() for s in stage_terms) else stage_terms, consts
 
 
 class QuadPlan:
     """How a quadratic record reaches its MOI function (quad_plan decides; Model.initialize and _Record.compile execute): the mode and what it
     reads — the operand r of dot(r, r) (`gram`), the QuadForm (`form`), the LsqTerm list (`terms`), the QuadGroups of a sum over disjoint
-    Variable vectors (`groups`) or the QuadForms of a horizon of stage costs (`stages`); `canonicalize`: through canonicalize! first."""
-    def __init__(self, mode, gram=None, form=None, terms=None, canonicalize=False, groups=None, stages=None):
+    Variable vectors (`groups`) or the QuadForms of a horizon of stage costs (`stages`, with the StageTerms beside them in `stage_terms` —
+    None: every stage has weight 1 and no linear term — and the 'constant' LsqTerms in `stage_consts`); `canonicalize`: through
+    canonicalize! first."""
+    def __init__(self, mode, gram=None, form=None, terms=None, canonicalize=False, groups=None, stages=None, stage_terms=None, stage_consts=()):
         self.mode, self.gram, self.form, self.terms, self.canonicalize, self.groups = mode, gram, form, terms, canonicalize, groups
-        self.stages = stages
+        self.stages, self.stage_terms, self.stage_consts = stages, stage_terms, list(stage_consts)
         # the MOI copy is the canonical least-squares node, bare or the weighted sum of such nodes (model.lane_order: side lane, small-plan order)
         self.gram_record = mode in ("canonical", "canonical-csc", "canonical-sum") or \
             (mode == "canonical-groups" and any(t.kind == "block" for g in groups for t in g.terms))
@@ -871,11 +928,12 @@ class QuadPlan:
         return [r for r in [self.gram] + [t.r for ts in lists for t in ts] + list(self.stages or ()) if r is not None]
 
 
-def quad_plan(terms, bare, kind, nq, is_objective, quadratic_mode, small, handoff, varmap=None, sparse_sums=False):
+def quad_plan(terms, bare, kind, nq, is_objective, quadratic_mode, small, handoff, varmap=None, sparse_sums=False, stage_terms=False):
     """The QuadPlan of a record over a node described by (terms, bare) = DeviceNode.(lsq_sum, lsq_bare); no mode unless kind == "quad".  `nq`:
     the terms of its literal expansion; `small`: Model._small; `varmap`: the optimizer's index map when it is fixed before the plan is recorded
-    (handoff "device" / "host_csc"); `sparse_sums`: weighted sums over sparse blocks take the sparse combine (Model passes True).  Host data
-    only: nothing is allocated, no stacked matrix is asked for.  First match wins."""
+    (handoff "device" / "host_csc"); `sparse_sums`: weighted sums over sparse blocks take the sparse combine (Model passes True);
+    `stage_terms`: a horizon with weights, linear terms or constants beside its stages takes "canonical-stages" (Model passes True; a caller
+    that does not ask gets the row as it was: such a horizon stays literal).  Host data only: nothing is allocated, no stacked matrix is asked for.  First match wins."""
     one = terms[0] if bare and kind == "quad" else None
     block = one.r if one is not None and one.kind == "block" else None
     if isinstance(block, DSparseAff) and (quadratic_mode == "literal" or handoff == "host_csc"):
@@ -930,11 +988,12 @@ def quad_plan(terms, bare, kind, nq, is_objective, quadratic_mode, small, handof
             groups = _lsq_groups(terms)
             if groups:
                 return QuadPlan("canonical-groups", groups=groups)
-            # a horizon of stage costs — more disjoint vectors than the groups hold, every term a dense form of weight 1, plain or
-            # shifted, two or more of them reading one weight matrix: all stages from one launch (pmt_quad_stages_f64)
+            # a horizon of stage costs — more disjoint vectors than the groups hold, every form dense, plain or shifted, two or more of
+            # them reading one weight matrix: all stages from one launch (pmt_quad_stages_f64; with weights, linear terms dot(c_t, x_t)
+            # or constants beside the stages pmt_quad_stages_terms_f64)
             stages = _lsq_stages(terms)
-            if stages:
-                return QuadPlan("canonical-stages", stages=stages)
+            if stages and (stage_terms or (stages[1] is None and not stages[2])):
+                return QuadPlan("canonical-stages", stages=stages[0], stage_terms=stages[1], stage_consts=stages[2])
     # anything else: the literal function through the generic device canonicalize! (sorted, duplicates combined) before the MOI copy
     return QuadPlan("literal", canonicalize=True)
 
