@@ -946,6 +946,55 @@ int pmt_batch_horizon_expand_f64(const double *slab, int64_t T, int64_t nx, int6
                                  pmt_quadratic_term *out_quad, pmt_linear_term *out_lin, double *out_const,
                                  pmt_vector_affine_term *out_vat, double *out_vconsts, void *stream);
 
+/* The batch of horizons' own dynamics: instance i's constraints x_{t+1} == A_i*x_t + B_i*u_t + w_{i,t} as a COMPACT section instead of rows of
+ * the dense C_i above — of those rows every word outside T-1 copies of [A_i | B_i] and one +-1.0 per row is a structural zero.  An instance's
+ * constraints are T vector-affine records over z = [x_0; u_0; x_1; u_1; ..], the records of pmt_affine_stages_f64 on the instance's own
+ * tables — in the reference matvecmul! (src/functions.jl:775-798) per product, vecadd! / vecsubtract! (:751-764: copyto! :419-427, add! /
+ * subtract! :452-485) per + / - and update!(::MOI.VectorAffineFunction, fs, varmap) (src/moi_interop.jl:64-81):
+ *   record 0              x_0 (+|-) h_{i,0}: the initial condition, one Variable-vector part
+ *   record t = 1 .. T-1   (+|-)x_t (+|-) A_i*x_{t-1} (+|-) B_i*u_{t-1} (+|-) h_{i,t}, the parts in this order (the spelling x+ - A*x - B*u - w);
+ *                         with nu == 0 there is no B part
+ * nx in 1 .. PMT_BATCH_HORIZON_MAX_DIM, nu in 0 .. PMT_BATCH_HORIZON_MAX_DIM, T in 1 .. PMT_BATCH_HORIZON_MAX_T.
+ * pmt_batch_horizon_dynamics_doubles (host arithmetic) is the section's length Ld = nx*(nx + nu) + T*nx.  pmt_batch_horizon_dynamics_f64
+ * writes, at out + i * out_stride (out_stride >= Ld; the words between two sections are never written), the section
+ *     [ AB: nx*(nx + nu) | h-consts: T*nx ]
+ * from the instance-major inputs A[B][nx*nx] and Bm[B][nx*nu], column-major with leading dimension nx, and h[B][T*nx], stage-major:
+ *   AB        row-major with row length nx + nu: AB[r*(nx + nu) + j] = A_i[r + j*nx] for j < nx, its sign bit flipped when sign_a == -1, and
+ *             B_i[r + (j - nx)*nx] for j >= nx, flipped when sign_b == -1 — a row is the coefficient words of one row of a record, part A
+ *             then part B.
+ *   h-consts  h-consts[t*nx + r] = 0.0 (+|-) h_i[t*nx + r] by sign_h, so a -0.0 does not survive; +0.0 with sign_h == 0 (h may be NULL).
+ * No arithmetic beyond that: copies, sign-bit flips and 0.0 (+|-) h.  Every word is written exactly once per call; no atomics, no workgroup
+ * waits for another; the words do not depend on B, on the instance's position, on launch geometry or on timing.  Each of T == 1, nu == 0 (Bm
+ * may be NULL) and sign_h == 0 is a complete section; B == 0 is PMT_OK without a launch, whatever the pointers.  Dimensions outside the
+ * limits, a negative B or out_stride < Ld: PMT_DIMENSION_MISMATCH; sign_a or sign_b not +-1, sign_h outside {-1, 0, 1} or a null pointer
+ * where data is needed: PMT_INVALID_ARGUMENT — all before any device call.  `out` and `out_stride` are free, so a caller places the section
+ * behind the instance's objective slab in one row: out = slabs + L, out_stride = L + Ld with pmt_batch_horizon_coeffs_f64 at the same stride.
+ * One launch, no workspace (csrc/batch_horizon_dyn.hip): persistent workgroups of 256 threads take the instances g, g + G, ..; [A_i | B_i]
+ * is read along its columns in tiles of 4096 words (64 rows x 64 columns; 32 x 128 up to 32 rows, 16 x 256 up to 16), every load of a tile
+ * unconditional on a clamped index and issued before the first value is looked at, transposed through LDS (pitch: the tile's columns + 1)
+ * and stored as 8-byte words with the column on the lanes — a section starts at any 8-byte address; h streams through registers.
+ * Instances of at most 512 AB words take a wave each, four to a workgroup, without LDS.  Algorithmic bytes per instance: 8 Ld read, 8 Ld
+ * written.
+ * pmt_batch_horizon_dynamics_expand_f64 rebuilds ONE instance's T MOI.VectorAffineFunction buffers from its section, with xvar the
+ * n = T*(nx + nu) model variables of z and indices through the varmap (NULL: the identity): nx + (T-1)*nx*(1 + nx + nu) terms and T*nx
+ * constants that are, word for word, what pmt_affine_stages_f64 writes for the instance's own tables —
+ *   stage 0       rows = nx, one Variable-vector part over xvar[0 .. nx) with sign sign_xp, term_offset = 0, row_len = 1
+ *   stage t >= 1  row_len = 1 + nx + nu, term_offset = nx + (t-1)*nx*(1 + nx + nu), the parts: the Variable vector over
+ *                 xvar[t*(nx + nu) .. + nx) with sign sign_xp; A_i over xvar[(t-1)*(nx + nu) .. + nx) with sign sign_a; B_i over the next nu
+ *                 entries with sign sign_b
+ *   all stages    const_offset = t*nx, vec = h_{i,t}, vec_sign = sign_h
+ * that is: row index r + 1 within each record, a Variable-part coefficient of +1.0 | -1.0, the AB words copied (they carry their signs),
+ * the constants copied; the columns of a row are the contiguous slice xvar[(t-1)*(nx + nu) .. t*(nx + nu)).  Every output needs 8-byte
+ * alignment only.  The dimension errors above (PMT_DIMENSION_MISMATCH), a sign_xp other than +-1 and a null section, xvar or output
+ * (PMT_INVALID_ARGUMENT) come before any device call.  A streaming launch: a workgroup per four rows of a stage, the stage's nx + nu index
+ * words vm[xvar[..]] fetched once into LDS, a wave per row through 16-byte stores; the section is read T-1 times, from cache; 24 bytes per
+ * term and 8 per constant written. */
+int64_t pmt_batch_horizon_dynamics_doubles(int64_t T, int64_t nx, int64_t nu);
+int pmt_batch_horizon_dynamics_f64(const double *A, const double *Bm, const double *h, int64_t B, int64_t T, int64_t nx, int64_t nu,
+                                   int sign_a, int sign_b, int sign_h, double *out, int64_t out_stride, void *stream);
+int pmt_batch_horizon_dynamics_expand_f64(const double *section, int64_t T, int64_t nx, int64_t nu, int sign_xp, const int64_t *xvar,
+                                          const int64_t *varmap, pmt_vector_affine_term *out_terms, double *out_consts, void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * Device-side Parameter update callbacks for synthetic inputs (counter-based):
  * dst[i] = scale * U[0,1)(seed, i)   — the analogue of `Parameter(rand!, zeros(n, n), model)` README.md:36-43

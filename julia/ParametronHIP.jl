@@ -706,6 +706,25 @@ batch_horizon_expand!(slab::DevPtr, T, nx, nu, m, xvar::DevPtr, varmap::DevPtr, 
                 (DevPtr, Int64, Int64, Int64, Int64, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
                 slab, T, nx, nu, m, xvar, varmap, out_quad, out_lin, out_const, out_vat, out_vconsts, stream))
 
+"doubles of one instance's dynamics section [AB: nx*(nx + nu) | h-consts: T*nx] of the batch of horizons"
+batch_horizon_dynamics_doubles(T, nx, nu) = ccall((:pmt_batch_horizon_dynamics_doubles, lib), Int64, (Int64, Int64, Int64), T, nx, nu)
+
+"one compact dynamics section per instance for the batch of horizons: x_0 ± h_0 and ±x_t ± A_i*x_{t-1} ± B_i*u_{t-1} ± h_t, t = 1 .. T-1
+ (nx, nu <= 128, T <= 512): instance-major A, B (column-major, leading dimension nx), stage-major h; AB row-major with the parts' signs on
+ its words, the constants 0.0 ± h; sign_h = 0: h may be C_NULL; nu = 0: B may be C_NULL.  out = slabs + L, out_stride = L + Ld puts the
+ section behind the instance's objective slab"
+batch_horizon_dynamics!(out::DevPtr, out_stride, A::DevPtr, B::DevPtr, h::DevPtr, nbatch, T, nx, nu, sign_a, sign_b, sign_h, stream) =
+    check(ccall((:pmt_batch_horizon_dynamics_f64, lib), Cint,
+                (DevPtr, DevPtr, DevPtr, Int64, Int64, Int64, Int64, Cint, Cint, Cint, DevPtr, Int64, Ptr{Cvoid}),
+                A, B, h, nbatch, T, nx, nu, sign_a, sign_b, sign_h, out, out_stride, stream))
+
+"one instance's T MOI.VectorAffineFunction buffers from its dynamics section, word for word what affine_stages! writes for the instance's
+ own tables; xvar: the n model variables of z, varmap may be C_NULL (the identity)"
+batch_horizon_dynamics_expand!(section::DevPtr, T, nx, nu, sign_xp, xvar::DevPtr, varmap::DevPtr, out_terms::DevPtr, out_consts::DevPtr, stream) =
+    check(ccall((:pmt_batch_horizon_dynamics_expand_f64, lib), Cint,
+                (DevPtr, Int64, Int64, Int64, Cint, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
+                section, T, nx, nu, sign_xp, xvar, varmap, out_terms, out_consts, stream))
+
 "the same callback RECORDED with its seed in a host word (`Ref{UInt64}`, kept alive by the caller): every replay draws the stream of the
 seed the word holds then — `seed[] += 1000` before `update!(plan)` is the whole callback"
 device_uniform_dyn!(dst::DevPtr, rows, cols, lda, seed::Ref{UInt64}, scale, stream) =

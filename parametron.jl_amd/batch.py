@@ -242,12 +242,17 @@ class BatchHorizon:
         self.Q, self.R, self.r, self.v, self.Cm, self.d = (torch.empty(self.B * self.per[k], dtype=f64, device=dev) for k in "QRrvCd")
         self.offsets, self.L = horizon_slab_layout(T, nx, nu, m)
         assert self.L == _lib.load().pmt_batch_horizon_slab_doubles(T, nx, nu, m)
-        self.local = torch.empty((self.B, self.L), dtype=f64, device=dev)
-        self.gathered = torch.empty((total, self.L), dtype=f64, device=dev) if world > 1 else self.local
+        self.stride = self.L + self._extra(dev)                  # doubles of one instance's row: the slab, and what a subclass appends
+        self.local = torch.empty((self.B, self.stride), dtype=f64, device=dev)
+        self.gathered = torch.empty((total, self.stride), dtype=f64, device=dev) if world > 1 else self.local
         self.stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         self.regenerate(0)
 
     _p = staticmethod(BatchLSQ._p)
+
+    def _extra(self, dev):
+        """doubles a subclass appends to every instance's row behind the slab, after allocating its own inputs (BatchMPC)"""
+        return 0
 
     def regenerate(self, epoch):
         """device-side Parameter callbacks (↔ rand! in README.md:36-43), one stream per Parameter and epoch"""
@@ -259,7 +264,7 @@ class BatchHorizon:
     def compute(self):
         """x_t - r_t, u_t as it is, C*z - d"""
         _lib.call("pmt_batch_horizon_coeffs_f64", self._p(self.Q), self._p(self.R), self._p(self.r), self._p(self.v), self._p(self.Cm),
-                  self._p(self.d), self.B, self.T, self.nx, self.nu, self.m, -1, 0, -1, self._p(self.local), self.L, self.stream)
+                  self._p(self.d), self.B, self.T, self.nx, self.nu, self.m, -1, 0, -1, self._p(self.local), self.stride, self.stream)
 
     def gather(self, dist):
         if self.world > 1:
@@ -281,9 +286,61 @@ class BatchHorizon:
         const = torch.empty(1, dtype=torch.float64, device=dev)
         vat = torch.empty(max(3 * m * n, 1), dtype=torch.int64, device=dev)
         vconsts = torch.empty(max(m, 1), dtype=torch.float64, device=dev)
-        _lib.call("pmt_batch_horizon_expand_f64", C.c_void_p(self.local.data_ptr() + 8 * i * self.L), T, self.nx, self.nu, m, self._p(xvar),
+        _lib.call("pmt_batch_horizon_expand_f64", C.c_void_p(self.local.data_ptr() + 8 * i * self.stride), T, self.nx, self.nu, m, self._p(xvar),
                   self._p(varmap), self._p(quad), self._p(lin), self._p(const), self._p(vat), self._p(vconsts), self.stream)
         return quad, lin, const, vat[:3 * m * n], vconsts[:m]
+
+
+def horizon_dynamics_layout(T, nx, nu):
+    """Offsets (in doubles) of the sections of one horizon instance's dynamics section [AB | h-consts] — AB the nx rows of [A_i | B_i],
+    row-major with row length nx + nu, then the T*nx record constants — and its length Ld (pmt_batch_horizon_dynamics_doubles)."""
+    nab = nx * (nx + nu)
+    return {"AB": 0, "hconst": nab}, nab + T * nx
+
+
+class BatchMPC(BatchHorizon):
+    """BatchHorizon with the instances' own dynamics x_0 == h_{i,0}, x_t == A_i*x_{t-1} + B_i*u_{t-1} + h_{i,t}: A[B][nx x nx], B[B][nx x nu]
+    and h[B][T x nx] beside the sibling's inputs, generated by the counter-based stream with GLOBAL element offsets like them.  One row per
+    instance, [horizon slab (L) | dynamics section (Ld)]: compute() is the sibling's launch at the row's stride and one launch of
+    pmt_batch_horizon_dynamics_f64 on the same stream; gather_slabs moves the rows as they are; expand() adds the T records' terms and
+    constants (pmt_batch_horizon_dynamics_expand_f64) to the sibling's five buffers.  m counts further dense rows C_i*z == d_i (default: none)."""
+
+    SEEDS = dict(BatchHorizon.SEEDS, A=307, B=308, h=309)
+
+    def __init__(self, torch, total, T, nx, nu, m=0, rank=0, world=1, device=None):
+        super().__init__(torch, total, T, nx, nu, m, rank, world, device)
+
+    def _extra(self, dev):
+        torch, T, nx, nu = self.torch, self.T, self.nx, self.nu
+        self.per.update({"A": nx * nx, "B": nx * nu, "h": T * nx})
+        self.A, self.Bm, self.h = (torch.empty(self.B * self.per[k], dtype=torch.float64, device=dev) for k in "ABh")
+        self.dyn_offsets, self.Ld = horizon_dynamics_layout(T, nx, nu)
+        assert self.Ld == _lib.load().pmt_batch_horizon_dynamics_doubles(T, nx, nu)
+        return self.Ld
+
+    def regenerate(self, epoch):
+        super().regenerate(epoch)
+        for name, buf in (("A", self.A), ("B", self.Bm), ("h", self.h)):
+            per = self.per[name]
+            _lib.call("pmt_fill_uniform_offset_f64", self._p(buf), self.B * per, C.c_uint64(self.SEEDS[name] + 1000 * epoch),
+                      C.c_uint64(self.lo * per), 1.0, self.stream)
+
+    def compute(self):
+        """the sibling's slab, and behind it x_t - A*x_{t-1} - B*u_{t-1} - h_t"""
+        super().compute()
+        _lib.call("pmt_batch_horizon_dynamics_f64", self._p(self.A), self._p(self.Bm), self._p(self.h), self.B, self.T, self.nx, self.nu, -1, -1, -1,
+                  C.c_void_p(self.local.data_ptr() + 8 * self.L), self.stride, self.stream)
+
+    def expand(self, i, xvar, varmap):
+        """the sibling's five buffers of local instance i, then the dynamics records' vector-affine terms (3 words each) and constants"""
+        torch, T, nx, w = self.torch, self.T, self.nx, self.nx + self.nu
+        dev = self.local.device
+        terms = torch.empty(3 * (nx + (T - 1) * nx * (1 + w)), dtype=torch.int64, device=dev)
+        consts = torch.empty(T * nx, dtype=torch.float64, device=dev)
+        five = super().expand(i, xvar, varmap)
+        _lib.call("pmt_batch_horizon_dynamics_expand_f64", C.c_void_p(self.local.data_ptr() + 8 * (i * self.stride + self.L)), T, nx, self.nu, 1,
+                  self._p(xvar), self._p(varmap), self._p(terms), self._p(consts), self.stream)
+        return five + (terms, consts)
 
 
 TOTAL, N, R, M = 8192, 128, 128, 16        # BASELINE config 4 (m is not stated there: 16, SURVEY.md section 8d)

@@ -1,0 +1,286 @@
+// The batch of horizons' dynamics rows as a compact section per instance (pmt_batch_horizon_dynamics_f64): instance i's constraints
+//     x_0 (+|-) h_{i,0},    (+|-)x_t (+|-) A_i*x_{t-1} (+|-) B_i*u_{t-1} (+|-) h_{i,t},  t = 1 .. T-1
+// over z = [x_0; u_0; x_1; u_1; ..] are T vector-affine records whose coefficient words are T-1 copies of [A_i | B_i] and a +-1.0 per row;
+// the section
+//     [ AB: nx*(nx + nu) row-major | h-consts: T*nx ]
+// holds what differs between instances once.  In the reference a batch is many independent Models (src/model.jl:1-22); per instance and
+// record this replaces matvecmul! (src/functions.jl:775-798), vecadd! / vecsubtract! (:751-764) and the MOI copy
+// (src/moi_interop.jl:64-81) — the records of affine_stages.hip on the instance's own tables.  Nothing is computed: copies, sign-bit flips
+// and 0.0 (+|-) h, so the launch is bound by its loads and stores.
+//
+// Persistent workgroups of 256 threads, workgroup g taking the instances g, g + G, ..  No workgroup waits for another, no atomics, no
+// workspace.  [A_i | B_i] (nx rows, nx + nu columns, both halves column-major with leading dimension nx) is walked in tiles of 4096 words:
+// 64 rows x 64 columns, or 32 x 128 with nx <= 32, or 16 x 256 with nx <= 16 (the kernel is instantiated by the tile's rows), so that a
+// column of a narrow instance does not leave three quarters of a wave's lanes idle.  A tile is read along its columns as batch_form_kernel
+// reads its tiles — no load is conditional (an index past the edge goes to the last row / column and is dropped), all 16 loads of a thread
+// are issued before the first value is looked at (bd_landed), the lane's coordinates are made opaque per tile — and transposed through an
+// LDS tile of pitch columns + 1 doubles: 16 consecutive lanes hold 16 rows of one column, a stride of 2 mod 32 dwords, which covers the 32
+// banks of a b64 write once; rows leave with the column on the lanes as 8-byte stores, so a section starts at any 8-byte address.  The
+// h-consts stream through registers, four clamped loads per thread in flight.  LDS: 33280 bytes, four workgroups per CU.
+// Small instances: with nx*(nx + nu) <= 512 words — (nx, nu) = (12, 4): 192 words — a tile, its two barriers and 16 loads per thread would be
+// spent on a fraction of one wave's worth of words.  Such instances take a WAVE each, four to a workgroup (batch_horizon_dyn_small_kernel):
+// the lanes walk the AB words in output order and read the entry each needs (the whole matrix is at most 4 KB, the reads of a wave fall
+// into its few cache lines), eight clamped loads per lane in flight; no LDS, no barrier.  The words are copies either way.
+//
+// pmt_batch_horizon_dynamics_expand_f64 rebuilds one instance's MOI buffers from its section: a streaming writer.  A workgroup per four
+// rows of a stage t >= 1: the stage's nx + nu index words vm[xvar[..]] are fetched once into LDS, then a wave per row writes its
+// 1 + nx + nu terms through wave_write_words (common.h), each AB word read by the one lane that stores it.  One more item writes stage 0,
+// the rest copy the constants, 256 each.
+#include <algorithm>
+
+#include "common.h"
+
+namespace pmt {
+
+namespace {
+
+typedef unsigned long long u64;
+
+constexpr int BD_THREADS = 256;
+constexpr int BD_WAVES = BD_THREADS / 64;
+constexpr int BD_TILE_WORDS = 4096;          // rows x columns of a tile: 16 loads per thread
+constexpr int BD_WG_PER_CU = 4;              // resident workgroups per CU of the tile kernel (LDS: 33280 bytes each)
+constexpr int BD_SMALL_WORDS = 512;          // AB words up to which an instance takes a wave: eight loads per lane
+constexpr int BD_SMALL_WG_PER_CU = 8;
+constexpr int BD_EXPAND_ROWS = BD_WAVES;     // rows of a stage per work item of the expansion: one per wave
+constexpr int BD_MAX_DIM = PMT_BATCH_HORIZON_MAX_DIM, BD_MAX_T = PMT_BATCH_HORIZON_MAX_T;
+constexpr u64 BD_SIGN_BIT = 0x8000000000000000ull;
+static_assert(2 * BD_MAX_DIM <= BD_THREADS, "one thread per index word of a stage; a 16-row tile holds a whole row of [A | B]");
+
+struct BatchDynArgs {
+    const u64 *A, *Bm;                       // instance-major: A[B][nx*nx], Bm[B][nx*nu] column-major, leading dimension nx
+    const double *h;                         // h[B][T*nx] stage-major
+    int64_t B;
+    int T, nx, nu, sign_h;
+    u64 flip_a, flip_b;                      // the sign bit where the sign is -1
+    double *out; int64_t out_stride;
+};
+
+// Every element of v is in its register here: loads issued above this point are not moved below it or into a branch.
+template <int N>
+__device__ __forceinline__ void bd_landed(u64 (&v)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) asm volatile("" : "+v"(v[i]));
+}
+
+// h-consts[i] = 0.0 (+|-) h[i], i < cnt, the `width` threads of the caller striding together; four clamped loads per thread in flight
+__device__ __forceinline__ void bd_consts(const double *__restrict__ h, int sign, int cnt, double *__restrict__ o, int first, int width) {
+    if (sign == 0) {
+        for (int i = first; i < cnt; i += width) o[i] = 0.0;
+        return;
+    }
+    for (int i0 = first; i0 < cnt; i0 += 4 * width) {
+        double hv[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int i = i0 + k * width;
+            hv[k] = h[i < cnt ? i : cnt - 1];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int i = i0 + k * width;
+            if (i < cnt) o[i] = signed_const(hv[k], sign);
+        }
+    }
+}
+
+}  // namespace
+
+// RL rows x CW = 4096 / RL columns a tile; thread (lr = tid % RL, lc = tid / RL) loads the columns lc, lc + 256 / RL, ..
+template <int RL>
+__global__ __launch_bounds__(BD_THREADS) void batch_horizon_dyn_kernel(BatchDynArgs g) {
+    constexpr int CW = BD_TILE_WORDS / RL, PITCH = CW + 1, CSTEP = BD_THREADS / RL;
+    __shared__ u64 tile[RL * PITCH];
+    const int T = g.T, nx = g.nx, nu = g.nu, w = nx + nu;
+    const int tid = threadIdx.x;
+    const u64 flip_a = g.flip_a, flip_b = g.flip_b;
+
+    for (int64_t inst = blockIdx.x; inst < g.B; inst += gridDim.x) {
+        const u64 *__restrict__ Ai = g.A + inst * nx * nx;
+        const u64 *__restrict__ Bi = nu ? g.Bm + inst * nx * nu : Ai;            // (nu == 0: no column selects it)
+        u64 *__restrict__ out = reinterpret_cast<u64 *>(g.out + inst * g.out_stride);
+        bd_consts(g.sign_h ? g.h + inst * T * nx : nullptr, g.sign_h, T * nx, g.out + inst * g.out_stride + (int64_t)nx * w, tid, BD_THREADS);
+
+        for (int r0 = 0; r0 < nx; r0 += RL) {
+            for (int c0 = 0; c0 < w; c0 += CW) {
+                // (the thread's coordinates are made opaque per tile: derived from loop invariants, the compiler otherwise keeps every
+                // address of the unrolled body alive across the whole instance loop)
+                int lr = tid % RL, lc = tid / RL;
+                asm volatile("" : "+v"(lr), "+v"(lc));
+                const int r = r0 + lr;
+                const unsigned rc = (unsigned)(r < nx ? r : nx - 1);
+                u64 v[16];
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int c = c0 + lc + CSTEP * i, cc = c < w ? c : w - 1;
+                    const u64 *__restrict__ col = cc < nx ? Ai + (unsigned)cc * (unsigned)nx : Bi + (unsigned)(cc - nx) * (unsigned)nx;
+                    v[i] = col[rc];
+                }
+                bd_landed(v);
+                // tile[row][column], each word with its part's sign
+#pragma unroll
+                for (int i = 0; i < 16; ++i) tile[lr * PITCH + lc + CSTEP * i] = v[i] ^ (c0 + lc + CSTEP * i < nx ? flip_a : flip_b);
+                __syncthreads();
+                // a wave per row, the column on the lanes
+                const int lane = tid & 63, wave = tid >> 6;
+                const int nr = nx - r0 < RL ? nx - r0 : RL, nc = w - c0 < CW ? w - c0 : CW;
+                for (int rr = wave; rr < nr; rr += BD_WAVES) {
+                    u64 *__restrict__ orow = out + (int64_t)(r0 + rr) * w + c0;
+                    for (int c = lane; c < nc; c += 64) orow[c] = tile[rr * PITCH + c];
+                }
+                __syncthreads();                          // the next tile reuses the LDS
+            }
+        }
+    }
+}
+
+// A wave per instance of at most BD_SMALL_WORDS AB words: lane l writes the words l, l + 64, .. of AB in output order
+__global__ __launch_bounds__(BD_THREADS) void batch_horizon_dyn_small_kernel(BatchDynArgs g) {
+    const int T = g.T, nx = g.nx, nu = g.nu, w = nx + nu, nab = nx * w;
+    const int lane = threadIdx.x & 63;
+    const int64_t wv = (int64_t)blockIdx.x * BD_WAVES + (threadIdx.x >> 6), nwv = (int64_t)gridDim.x * BD_WAVES;
+    const u64 flip_a = g.flip_a, flip_b = g.flip_b;
+    // the word's source: row r = e / w, column j = e - r*w of [A | B]  (the same for every instance)
+    unsigned src[BD_SMALL_WORDS / 64];
+    bool from_a[BD_SMALL_WORDS / 64];
+#pragma unroll
+    for (int k = 0; k < BD_SMALL_WORDS / 64; ++k) {
+        const int e = lane + 64 * k, ec = e < nab ? e : nab - 1;
+        const int r = ec / w, j = ec - r * w;
+        from_a[k] = j < nx;
+        src[k] = (unsigned)(r + (j < nx ? j : j - nx) * nx);
+    }
+    for (int64_t inst = wv; inst < g.B; inst += nwv) {
+        const u64 *__restrict__ Ai = g.A + inst * nx * nx;
+        const u64 *__restrict__ Bi = nu ? g.Bm + inst * nx * nu : Ai;            // (nu == 0: no word selects it)
+        u64 *__restrict__ out = reinterpret_cast<u64 *>(g.out + inst * g.out_stride);
+        u64 v[BD_SMALL_WORDS / 64];
+#pragma unroll
+        for (int k = 0; k < BD_SMALL_WORDS / 64; ++k) v[k] = (from_a[k] ? Ai : Bi)[src[k]];
+        bd_landed(v);
+#pragma unroll
+        for (int k = 0; k < BD_SMALL_WORDS / 64; ++k) {
+            const int e = lane + 64 * k;
+            if (e < nab) out[e] = v[k] ^ (from_a[k] ? flip_a : flip_b);
+        }
+        bd_consts(g.sign_h ? g.h + inst * T * nx : nullptr, g.sign_h, T * nx, g.out + inst * g.out_stride + nab, lane, 64);
+    }
+}
+
+// One instance's records from its section.  Items, dealt out over the workgroups: (stage t >= 1, four rows), then stage 0, then the
+// constants 256 at a time.
+__global__ __launch_bounds__(BD_THREADS) void batch_horizon_dyn_expand_kernel(const double *__restrict__ section, int T, int nx, int nu, int sign_xp,
+                                                                               const int64_t *__restrict__ xvar, const int64_t *__restrict__ varmap,
+                                                                               u64 *__restrict__ terms, double *__restrict__ consts) {
+    __shared__ u64 vmx[BD_THREADS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int w = nx + nu, row_len = 1 + w, bands = (nx + BD_EXPAND_ROWS - 1) / BD_EXPAND_ROWS, nconst = T * nx;
+    const int64_t ndyn = (int64_t)(T - 1) * bands, nitems = ndyn + 1 + (nconst + BD_THREADS - 1) / BD_THREADS;
+    const u64 *__restrict__ ab = reinterpret_cast<const u64 *>(section);
+    const u64 one = (u64)__double_as_longlong(1.0) ^ (sign_xp < 0 ? BD_SIGN_BIT : 0);
+    for (int64_t it = blockIdx.x; it < nitems; it += gridDim.x) {
+        if (it < ndyn) {
+            const int t = 1 + (int)(it / bands), r = (int)(it % bands) * BD_EXPAND_ROWS + wave;
+            // the columns of the stage's rows: the contiguous slice xvar[(t-1)*w .. t*w)
+            if (tid < w) vmx[tid] = (u64)map_var(varmap, xvar[(int64_t)(t - 1) * w + tid]);
+            __syncthreads();
+            if (r < nx) {
+                const u64 rowidx = (u64)(r + 1), xp = (u64)map_var(varmap, xvar[(int64_t)t * w + r]);
+                const u64 *__restrict__ row = ab + r * w;
+                wave_write_words<3>(terms + 3 * (nx + ((int64_t)(t - 1) * nx + r) * row_len), row_len, lane, [&](int q) -> u64 {
+                    const int e = q / 3, f = q - 3 * e;
+                    if (f == 0) return rowidx;
+                    if (e == 0) return f == 1 ? one : xp;
+                    return f == 1 ? row[e - 1] : vmx[e - 1];
+                });
+            }
+            __syncthreads();                              // the next item reuses vmx
+        } else if (it == ndyn) {
+            // stage 0: row i holds (i + 1, +-1.0, vm[xvar[i]])
+            for (int i0 = wave * 64; i0 < nx; i0 += BD_THREADS) {
+                wave_write_words<3>(terms + 3 * i0, nx - i0 < 64 ? nx - i0 : 64, lane, [&](int q) -> u64 {
+                    const int e = q / 3, f = q - 3 * e;
+                    if (f == 0) return (u64)(i0 + e + 1);
+                    return f == 1 ? one : (u64)map_var(varmap, xvar[i0 + e]);
+                });
+            }
+        } else {
+            const int i = (int)(it - ndyn - 1) * BD_THREADS + tid;
+            if (i < nconst) consts[i] = section[nx * w + i];
+        }
+    }
+}
+
+static int bd_cu_count() {
+    static int cus[16] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) { (void)hipGetLastError(); return 256; }
+    if (!cus[dev]) {
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) { (void)hipGetLastError(); v = 256; }
+        cus[dev] = v;
+    }
+    return cus[dev];
+}
+
+// the dimension checks both entry points share; `who` words the message
+static int bd_check_dims(const char *who, int64_t T, int64_t nx, int64_t nu) {
+    const std::string w(who);
+    PMT_REQUIRE(nx >= 1 && nx <= BD_MAX_DIM, PMT_DIMENSION_MISMATCH, w + ": nx outside 1 .. 128");
+    PMT_REQUIRE(nu >= 0 && nu <= BD_MAX_DIM, PMT_DIMENSION_MISMATCH, w + ": nu outside 0 .. 128");
+    PMT_REQUIRE(T >= 1 && T <= BD_MAX_T, PMT_DIMENSION_MISMATCH, w + ": T outside 1 .. 512");
+    return PMT_OK;
+}
+
+}  // namespace pmt
+
+using namespace pmt;
+
+extern "C" int64_t pmt_batch_horizon_dynamics_doubles(int64_t T, int64_t nx, int64_t nu) { return nx * (nx + nu) + T * nx; }
+
+extern "C" int pmt_batch_horizon_dynamics_f64(const double *A, const double *Bm, const double *h, int64_t B, int64_t T, int64_t nx, int64_t nu,
+                                              int sign_a, int sign_b, int sign_h, double *out, int64_t out_stride, void *stream) {
+    PMT_REQUIRE(B >= 0, PMT_DIMENSION_MISMATCH, "batch_horizon_dynamics: negative instance count");
+    const int rc = bd_check_dims("batch_horizon_dynamics", T, nx, nu);
+    if (rc != PMT_OK) return rc;
+    PMT_REQUIRE(out_stride >= pmt_batch_horizon_dynamics_doubles(T, nx, nu), PMT_DIMENSION_MISMATCH,
+                "batch_horizon_dynamics: out_stride smaller than the section");
+    PMT_REQUIRE((sign_a == 1 || sign_a == -1) && (sign_b == 1 || sign_b == -1), PMT_INVALID_ARGUMENT,
+                "batch_horizon_dynamics: sign_a and sign_b must be +1 or -1");
+    PMT_REQUIRE(sign_h >= -1 && sign_h <= 1, PMT_INVALID_ARGUMENT, "batch_horizon_dynamics: sign_h must be -1, 0 or +1");
+    if (B == 0) return PMT_OK;
+    PMT_REQUIRE(out && A && (nu == 0 || Bm) && (sign_h == 0 || h), PMT_INVALID_ARGUMENT, "batch_horizon_dynamics: null pointer");
+    BatchDynArgs g;
+    g.A = reinterpret_cast<const u64 *>(A); g.Bm = reinterpret_cast<const u64 *>(Bm); g.h = h;
+    g.B = B;
+    g.T = (int)T; g.nx = (int)nx; g.nu = (int)nu; g.sign_h = sign_h;
+    g.flip_a = sign_a < 0 ? BD_SIGN_BIT : 0; g.flip_b = sign_b < 0 ? BD_SIGN_BIT : 0;
+    g.out = out; g.out_stride = out_stride;
+    return dispatch(stream, [=](hipStream_t s) {
+        if (g.nx * (g.nx + g.nu) <= BD_SMALL_WORDS) {
+            const dim3 grid((unsigned)std::min<int64_t>(cdiv(B, BD_WAVES), (int64_t)BD_SMALL_WG_PER_CU * bd_cu_count()));
+            PMT_LAUNCH(batch_horizon_dyn_small_kernel, grid, dim3(BD_THREADS), 0, s, g);
+            return check_launch("batch_horizon_dyn_small_kernel");
+        }
+        const dim3 grid((unsigned)std::min<int64_t>(B, (int64_t)BD_WG_PER_CU * bd_cu_count()));
+        if (g.nx <= 16) PMT_LAUNCH(batch_horizon_dyn_kernel<16>, grid, dim3(BD_THREADS), 0, s, g);
+        else if (g.nx <= 32) PMT_LAUNCH(batch_horizon_dyn_kernel<32>, grid, dim3(BD_THREADS), 0, s, g);
+        else PMT_LAUNCH(batch_horizon_dyn_kernel<64>, grid, dim3(BD_THREADS), 0, s, g);
+        return check_launch("batch_horizon_dyn_kernel");
+    });
+}
+
+extern "C" int pmt_batch_horizon_dynamics_expand_f64(const double *section, int64_t T, int64_t nx, int64_t nu, int sign_xp, const int64_t *xvar,
+                                                     const int64_t *varmap, pmt_vector_affine_term *out_terms, double *out_consts, void *stream) {
+    const int rc = bd_check_dims("batch_horizon_dynamics_expand", T, nx, nu);
+    if (rc != PMT_OK) return rc;
+    PMT_REQUIRE(sign_xp == 1 || sign_xp == -1, PMT_INVALID_ARGUMENT, "batch_horizon_dynamics_expand: sign_xp must be +1 or -1");
+    PMT_REQUIRE(section && xvar && out_terms && out_consts, PMT_INVALID_ARGUMENT, "batch_horizon_dynamics_expand: null pointer");
+    const int iT = (int)T, inx = (int)nx, inu = (int)nu;
+    return dispatch(stream, [=](hipStream_t s) {
+        const int64_t items = (int64_t)(iT - 1) * cdiv(inx, BD_EXPAND_ROWS) + 1 + cdiv((int64_t)iT * inx, BD_THREADS);
+        PMT_LAUNCH(batch_horizon_dyn_expand_kernel, dim3((unsigned)std::min<int64_t>(items, (int64_t)8 * bd_cu_count())), dim3(BD_THREADS), 0, s, section, iT,
+                   inx, inu, sign_xp, xvar, varmap, reinterpret_cast<u64 *>(out_terms), out_consts);
+        return check_launch("batch_horizon_dyn_expand_kernel");
+    });
+}
