@@ -995,6 +995,64 @@ int pmt_batch_horizon_dynamics_f64(const double *A, const double *Bm, const doub
 int pmt_batch_horizon_dynamics_expand_f64(const double *section, int64_t T, int64_t nx, int64_t nu, int sign_xp, const int64_t *xvar,
                                           const int64_t *varmap, pmt_vector_affine_term *out_terms, double *out_consts, void *stream);
 
+/* The batch of horizons with a terminal cost, a weight per stage and linear stage terms — what pmt_quad_stages_terms_f64 added to the single
+ * horizon, for the fleet, still one launch without a workspace:
+ *   J_i = sum_{t<T} wx_{i,t} * transpose(x_t (+|-) r_{i,t})*Q_i*(x_t (+|-) r_{i,t}) + dot(gx_{i,t}, x_t)
+ *                 + wu_{i,t} * transpose(u_t (+|-) v_{i,t})*R_i*(u_t (+|-) v_{i,t}) + dot(gu_{i,t}, u_t)
+ *         + wN_i * transpose(x_T (+|-) rN_i)*P_i*(x_T (+|-) rN_i) + dot(gN_i, x_T)
+ * over z = [x_0; u_0; ..; x_{T-1}; u_{T-1}; x_T] subject to C_i*z (+|-) d_i: a discount or a scenario probability per stage (a weight of 0
+ * switches a stage off), the economic term or the gradient of a sequential linearisation, a terminal matrix of its own.  The terminal stage
+ * x_T exists only when P is given; with term = (P != NULL) in {0, 1}
+ *     n = T*(nx + nu) + term*nx variables,   ns = T*(1 + (nu > 0)) + term stages in z order: x_0, u_0, x_1, .., x_T (x_0, x_1, .. with nu == 0).
+ * pmt_batch_horizon_terms describes the inputs: a HOST struct of DEVICE pointers, all instance-major as in pmt_batch_horizon_coeffs_f64, read
+ * by the call and not kept.  A NULL weight array means every weight 1.0, a NULL linear array no linear term on those stages; each optional
+ * array is all or nothing for its kind of stage.  The slab of pmt_batch_horizon_terms_slab_doubles(T, nx, nu, term, m) doubles (host arithmetic)
+ * at out + i * out_stride (out_stride >= that length L; the words between two slabs are never written) is
+ *     [ SQ: nx(nx+1)/2 | SR: nu(nu+1)/2 | SP: term*nx(nx+1)/2 | W: ns | q: n | const: 1 | C: m*n row-major | d-consts: m ]
+ * fixed bit for bit — plain multiplies and adds, no fma, no floating-point atomics, no workgroup waits for another; independent of B, of the
+ * instance's position, of launch geometry and timing:
+ *   SQ, SR, SP  the moi = 1 coefficients of pmt_quad_form_f64 for Q_i / R_i / P_i, exactly as in pmt_batch_horizon_coeffs_f64: unweighted, once.
+ *   W           W[s] the weight of stage s in z order as read; 1.0 where the weight array is NULL.
+ *   q           in z order, stage s, row j: W_s * lin_j, then + g_s[j] when the stage has a linear vector; lin_j the chain of
+ *               pmt_quad_form_shift_f64 (64-column blocks, the first product starting the chain, the blocks in order).  A plain stage (sign 0)
+ *               multiplies its +0.0: a negative weight leaves -0.0 where no linear term follows, a NaN weight NaN.  These are the words
+ *               pmt_quad_stages_terms_f64 leaves with scale = 1.0, weight = &W_s, lin_scale = 1.0, lin_weight = NULL, lin_vec = g_s.
+ *   const       each stage constant W_s * (0.5 * T_s), the ns of them added in S_d's order — 256 chains over the stages in z order onto 0.0,
+ *               then the halving tree: what pmt_quad_stages_terms_f64 leaves in *out_const for the instance's own table with nconsts = 0.
+ *   C, d-consts as in pmt_batch_horizon_coeffs_f64, over the n columns of this z.
+ * With every optional pointer NULL the slab without its W section equals the slab of pmt_batch_horizon_coeffs_f64 word for word (multiplying
+ * by 1.0 is exact; a plain stage still yields +0.0).  A NaN weight reaches its own stage's q words and its own instance's const, no other word.
+ * Each of nu == 0 (R, v, wu, gu are not read), m == 0, term == 0 (rN, wN, gN are not read) and T == 1 is a complete slab; B == 0 is PMT_OK
+ * without a launch, whatever the device pointers.  A null `in`: PMT_INVALID_ARGUMENT.  A negative dimension, nx outside 1 ..
+ * PMT_BATCH_HORIZON_MAX_DIM, nu above it, T outside 1 .. PMT_BATCH_HORIZON_MAX_T, a term other than 0 or 1 (the expansion) or out_stride < L:
+ * PMT_DIMENSION_MISMATCH; a sign outside {-1, 0, 1} (sign_rN is checked without a P too) or a null pointer where data is needed (out, Q, R
+ * with nu > 0, a reference whose sign is not 0, C and d with m > 0): PMT_INVALID_ARGUMENT — all before any device call.  The walk is
+ * pmt_batch_horizon_coeffs_f64's (csrc/batch_horizon_terms.hip) with a third phase for P_i through the same resident tiles: three workgroups per CU
+ * with one tile (dims <= 64), one with three; a stage's weight and linear words are fetched with its reference, a round ahead.  Algorithmic
+ * bytes per instance: the sibling's, plus 8 (term*(nx^2 + nx) + ns + n) read where the optional arrays are given, 8 L written.
+ * pmt_batch_horizon_terms_expand_f64 rebuilds ONE instance's MOI buffers from its slab, xvar the n model variables of this z: out_quad (T (nx(nx+1)/2
+ * + nu(nu+1)/2) + term nx(nx+1)/2 terms) holds W_s * S[j,k] for stage s (the diagonal W_s * (2*M[j,j]); the section already holds 2*M[j,j]),
+ * out_lin (n terms) and *out_const are copied from the slab, the index words go through varmap: word for word what
+ * pmt_quad_stages_terms_check + pmt_quad_stages_terms_f64 write for the instance's own table [x_0, u_0, .., x_T] with the stages laid out one
+ * behind the other; out_vat (m*n terms) and out_vconsts (m) as pmt_batch_expand_f64 writes them.  Errors as the sibling's expansion.
+ * The dynamics of a horizon with a terminal stage have T + 1 records, up to x_T == A*x_{T-1} + B*u_{T-1} + h_T: call the unchanged
+ * pmt_batch_horizon_dynamics_f64 and pmt_batch_horizon_dynamics_expand_f64 with T + 1.  Their expansion reads only xvar[t*w .. t*w + nx) and
+ * xvar[(t-1)*w .. t*w), w = nx + nu, for the records t <= T: it never touches a u_T, so the n = T*w + nx variables of this z suffice. */
+typedef struct {
+    const double *Q, *R, *P;      /* [B][nx*nx], [B][nu*nu], [B][nx*nx] column-major; P NULL: no terminal stage */
+    const double *r, *v, *rN;     /* [B][T*nx], [B][T*nu], [B][nx]; may be NULL where the sign is 0 */
+    const double *wx, *wu, *wN;   /* [B][T], [B][T], [B]; NULL: every weight 1.0 */
+    const double *gx, *gu, *gN;   /* [B][T*nx], [B][T*nu], [B][nx]; NULL: no linear term on those stages */
+    const double *C, *d;          /* [B][m*n] column-major, [B][m] */
+    int32_t sign_r, sign_v, sign_rN, sign_d;
+} pmt_batch_horizon_terms;        /* 128 bytes, no padding */
+int64_t pmt_batch_horizon_terms_slab_doubles(int64_t T, int64_t nx, int64_t nu, int64_t term, int64_t m);
+int pmt_batch_horizon_terms_coeffs_f64(const pmt_batch_horizon_terms *in, int64_t B, int64_t T, int64_t nx, int64_t nu, int64_t m, double *out,
+                                       int64_t out_stride, void *stream);
+int pmt_batch_horizon_terms_expand_f64(const double *slab, int64_t T, int64_t nx, int64_t nu, int64_t term, int64_t m, const int64_t *xvar,
+                                       const int64_t *varmap, pmt_quadratic_term *out_quad, pmt_linear_term *out_lin, double *out_const,
+                                       pmt_vector_affine_term *out_vat, double *out_vconsts, void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * Device-side Parameter update callbacks for synthetic inputs (counter-based):
  * dst[i] = scale * U[0,1)(seed, i)   — the analogue of `Parameter(rand!, zeros(n, n), model)` README.md:36-43

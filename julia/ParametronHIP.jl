@@ -725,6 +725,49 @@ batch_horizon_dynamics_expand!(section::DevPtr, T, nx, nu, sign_xp, xvar::DevPtr
                 (DevPtr, Int64, Int64, Int64, Cint, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
                 section, T, nx, nu, sign_xp, xvar, varmap, out_terms, out_consts, stream))
 
+"pmt_batch_horizon_terms (include/parametron_hip.h): the inputs of batch_horizon_terms_coeffs!, device pointers, instance-major.  C_NULL: P no
+ terminal stage, a weight array every weight 1.0, a linear array no linear term, a reference only where its sign is 0; 128 bytes, no padding"
+struct BatchHorizonTerms
+    Q::DevPtr
+    R::DevPtr
+    P::DevPtr
+    r::DevPtr
+    v::DevPtr
+    rN::DevPtr
+    wx::DevPtr
+    wu::DevPtr
+    wN::DevPtr
+    gx::DevPtr
+    gu::DevPtr
+    gN::DevPtr
+    C::DevPtr
+    d::DevPtr
+    sign_r::Int32
+    sign_v::Int32
+    sign_rN::Int32
+    sign_d::Int32
+end
+
+"doubles of one instance's slab [SQ | SR | SP | W | q | const | C | d-consts] of the batch of horizons with terms; term = 1 with a terminal stage"
+batch_horizon_terms_slab_doubles(T, nx, nu, term, m) =
+    ccall((:pmt_batch_horizon_terms_slab_doubles, lib), Int64, (Int64, Int64, Int64, Int64, Int64), T, nx, nu, term, m)
+
+"one slab per instance for the batch of horizons with a terminal cost wN * transpose(x_T ± rN) * P_i * (x_T ± rN), a weight per stage and linear
+ stage terms dot(g, ·): W / q / const bit for bit what quad_stages_terms! writes for the instance's own table with scale = 1.0 and
+ weight = &W_s; with every optional pointer C_NULL the slab without its W section is batch_horizon_coeffs!'s"
+batch_horizon_terms_coeffs!(out::DevPtr, out_stride, desc::BatchHorizonTerms, B, T, nx, nu, m, stream) =
+    check(ccall((:pmt_batch_horizon_terms_coeffs_f64, lib), Cint,
+                (Ref{BatchHorizonTerms}, Int64, Int64, Int64, Int64, Int64, DevPtr, Int64, Ptr{Cvoid}),
+                desc, B, T, nx, nu, m, out, out_stride, stream))
+
+"one instance's MOI buffers from its slab with terms: the quadratic terms W_s * S[j,k], the linear terms and the constant copied — what
+ quad_stages_terms! writes for its table [x_0, u_0, .., x_T]; xvar: the n = T*(nx + nu) + term*nx model variables of z"
+batch_horizon_terms_expand!(slab::DevPtr, T, nx, nu, term, m, xvar::DevPtr, varmap::DevPtr, out_quad::DevPtr, out_lin::DevPtr, out_const::DevPtr,
+                            out_vat::DevPtr, out_vconsts::DevPtr, stream) =
+    check(ccall((:pmt_batch_horizon_terms_expand_f64, lib), Cint,
+                (DevPtr, Int64, Int64, Int64, Int64, Int64, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
+                slab, T, nx, nu, term, m, xvar, varmap, out_quad, out_lin, out_const, out_vat, out_vconsts, stream))
+
 "the same callback RECORDED with its seed in a host word (`Ref{UInt64}`, kept alive by the caller): every replay draws the stream of the
 seed the word holds then — `seed[] += 1000` before `update!(plan)` is the whole callback"
 device_uniform_dyn!(dst::DevPtr, rows, cols, lda, seed::Ref{UInt64}, scale, stream) =

@@ -145,6 +145,21 @@ def affine_stages(stages):
     return _struct_array(AffineStage, stages)
 
 
+class BatchHorizonTerms(C.Structure):
+    """pmt_batch_horizon_terms: the inputs of pmt_batch_horizon_terms_coeffs_f64 (device addresses, instance-major; None: P no terminal stage,
+    a weight array every weight 1.0, a linear array no linear term, a reference only where its sign is 0)."""
+    _fields_ = [(k, C.c_void_p) for k in ("Q", "R", "P", "r", "v", "rN", "wx", "wu", "wN", "gx", "gu", "gN", "C", "d")] + \
+               [(k, C.c_int32) for k in ("sign_r", "sign_v", "sign_rN", "sign_d")]
+
+
+assert C.sizeof(BatchHorizonTerms) == 128
+
+
+def batch_horizon_terms(**fields):
+    """one pmt_batch_horizon_terms from its fields (missing fields: None / 0)"""
+    return _struct_array(BatchHorizonTerms, [fields])[0]
+
+
 def stack_table(srcs, signs):
     """host image of the pmt_stack_column table of pmt_affine_stack_columns_f64: column c is signs[c] * (the column at device address
     srcs[c]).  The entry point reads the table on the device only, so the signs are checked here."""
@@ -312,6 +327,9 @@ SIGNATURES = {
     "pmt_batch_horizon_slab_doubles": (_i64, [_i64, _i64, _i64, _i64]),
     "pmt_batch_horizon_coeffs_f64": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _ci, _ci, _ci, _vp, _i64, _vp]),
     "pmt_batch_horizon_expand_f64": (_ci, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pmt_batch_horizon_terms_slab_doubles": (_i64, [_i64, _i64, _i64, _i64, _i64]),
+    "pmt_batch_horizon_terms_coeffs_f64": (_ci, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp]),
+    "pmt_batch_horizon_terms_expand_f64": (_ci, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pmt_batch_horizon_dynamics_doubles": (_i64, [_i64, _i64, _i64]),
     "pmt_batch_horizon_dynamics_f64": (_ci, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _ci, _ci, _vp, _i64, _vp]),
     "pmt_batch_horizon_dynamics_expand_f64": (_ci, [_vp, _i64, _i64, _i64, _ci, _vp, _vp, _vp, _vp, _vp]),
