@@ -109,26 +109,29 @@ class Communicator:
             self.handle = C.c_void_p()
 
 
-class BatchLSQ:
-    """Device-resident batch: A[B][r x n], b[B][r], C[B][m x n], d[B][m] generated by the counter-based stream so that
-    instance k holds the same data whatever the sharding (seed streams are indexed by GLOBAL element index)."""
+class _Batch:
+    """What the batched workloads share: rank `rank` owns the instances shard_range(total, rank, world); every input is a flat device tensor
+    of `per[name]` doubles per instance, generated by the counter-based stream — one stream per input and epoch, SEEDS[name] + 1000 * epoch,
+    drawn at GLOBAL element offsets, so instance k holds the same data whatever the sharding; one row of `stride` doubles per instance in
+    `local` (the slab of L doubles, and what a subclass appends behind it), all rows of all ranks in `gathered`.  A subclass names its
+    inputs and their sizes, its layout, and its launch (compute)."""
 
-    SEEDS = {"A": 101, "b": 102, "C": 103, "d": 104}
+    SEEDS = {}
+    SCALES = {"d": 2.0}                          # the range of an input's stream where it is not 1.0
+    ATTRS = {"C": "Cm", "B": "Bm"}               # an input is also an attribute of its name; C and B under these
 
-    def __init__(self, torch, total, n, r, m, rank=0, world=1, device=None):
+    def __init__(self, torch, total, rank, world, device, per, layout):
         _lib.require_gpu()
-        self.torch, self.total, self.n, self.r, self.m, self.rank, self.world = torch, total, n, r, m, rank, world
+        self.torch, self.total, self.rank, self.world = torch, total, rank, world
         self.lo, self.hi = shard_range(total, rank, world)
         self.B = self.hi - self.lo
         dev = device or torch.device("cuda", torch.cuda.current_device())
-        f64 = torch.float64
-        self.A = torch.empty(self.B * r * n, dtype=f64, device=dev)
-        self.b = torch.empty(self.B * r, dtype=f64, device=dev)
-        self.Cm = torch.empty(self.B * m * n, dtype=f64, device=dev)
-        self.d = torch.empty(self.B * m, dtype=f64, device=dev)
-        self.offsets, self.L = slab_layout(n, m)
-        self.local = torch.empty((self.B, self.L), dtype=f64, device=dev)
-        self.gathered = torch.empty((total, self.L), dtype=f64, device=dev) if world > 1 else self.local
+        self.per = per
+        self.inputs = self._alloc(per, dev)
+        self.offsets, self.L = layout
+        self.stride = self.L + self._extra(dev)                  # doubles of one instance's row: the slab, and what a subclass appends
+        self.local = torch.empty((self.B, self.stride), dtype=torch.float64, device=dev)
+        self.gathered = torch.empty((total, self.stride), dtype=torch.float64, device=dev) if world > 1 else self.local
         self.stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         self.regenerate(0)
 
@@ -136,16 +139,25 @@ class BatchLSQ:
     def _p(t):
         return C.c_void_p(t.data_ptr())
 
+    def _alloc(self, per, dev):
+        """name -> tensor of B * per[name] doubles, each also set as the attribute of its name"""
+        bufs = {k: self.torch.empty(self.B * cnt, dtype=self.torch.float64, device=dev) for k, cnt in per.items()}
+        for k, t in bufs.items():
+            setattr(self, self.ATTRS.get(k, k), t)
+        return bufs
+
+    def _extra(self, dev):
+        """doubles a subclass appends to every instance's row behind the slab, after allocating its own inputs (_Dynamics)"""
+        return 0
+
+    def _fill(self, bufs, per, epoch):
+        for name, buf in bufs.items():
+            _lib.call("pmt_fill_uniform_offset_f64", self._p(buf), self.B * per[name], C.c_uint64(self.SEEDS[name] + 1000 * epoch),
+                      C.c_uint64(self.lo * per[name]), self.SCALES.get(name, 1.0), self.stream)
+
     def regenerate(self, epoch):
         """device-side Parameter callbacks (↔ rand! in README.md:36-43), one stream per Parameter and epoch"""
-        n, r, m = self.n, self.r, self.m
-        for name, buf, per, scale in (("A", self.A, r * n, 1.0), ("b", self.b, r, 1.0), ("C", self.Cm, m * n, 1.0), ("d", self.d, m, 2.0)):
-            _lib.call("pmt_fill_uniform_offset_f64", self._p(buf), self.B * per, C.c_uint64(self.SEEDS[name] + 1000 * epoch),
-                      C.c_uint64(self.lo * per), scale, self.stream)
-
-    def compute(self):
-        _lib.call("pmt_batch_lsq_coeffs_f64", self._p(self.A), self._p(self.b), self._p(self.Cm), self._p(self.d), self.B, self.n, self.r,
-                  self.m, -1, -1, self._p(self.local), self.L, self.stream)
+        self._fill(self.inputs, self.per, epoch)
 
     def gather(self, dist):
         if self.world > 1:
@@ -154,6 +166,21 @@ class BatchLSQ:
     def step(self, dist):
         self.compute()
         self.gather(dist)
+
+
+class BatchLSQ(_Batch):
+    """Device-resident batch: A[B][r x n], b[B][r], C[B][m x n], d[B][m] generated by the counter-based stream so that
+    instance k holds the same data whatever the sharding (seed streams are indexed by GLOBAL element index)."""
+
+    SEEDS = {"A": 101, "b": 102, "C": 103, "d": 104}
+
+    def __init__(self, torch, total, n, r, m, rank=0, world=1, device=None):
+        self.n, self.r, self.m = n, r, m
+        super().__init__(torch, total, rank, world, device, {"A": r * n, "b": r, "C": m * n, "d": m}, slab_layout(n, m))
+
+    def compute(self):
+        _lib.call("pmt_batch_lsq_coeffs_f64", self._p(self.A), self._p(self.b), self._p(self.Cm), self._p(self.d), self.B, self.n, self.r,
+                  self.m, -1, -1, self._p(self.local), self.L, self.stream)
 
     def step_pipelined(self, comm, chunk):
         """pmt_batch_step_f64: compute chunk by chunk, chunk c on the wire (the library's RCCL communicator, its own stream) while
@@ -162,52 +189,21 @@ class BatchLSQ:
                   self.m, -1, -1, self._p(self.local), self._p(self.gathered), self.L, int(chunk), self.stream)
 
 
-class BatchTracking:
+class BatchTracking(_Batch):
     """Device-resident batch of tracking costs transpose(x - p_i) * Q_i * (x - p_i) over C_i*x == d_i (many small MPC instances, each with a
-    weight matrix and a reference of its own): Q[B][n x n], p[B][n], C[B][m x n], d[B][m] generated by the counter-based stream with GLOBAL
-    element offsets, so instance k holds the same data whatever the sharding.  One launch of pmt_batch_form_coeffs_f64 writes the slabs, in
-    the layout of BatchLSQ's — slab_layout, gather_slabs and pmt_batch_expand_f64 apply as they are.  There is no pipelined exchange for
-    this objective (pmt_batch_step_f64 computes the least-squares slabs): step() is compute() and one all-gather."""
+    weight matrix and a reference of its own): Q[B][n x n], p[B][n], C[B][m x n], d[B][m].  One launch of pmt_batch_form_coeffs_f64 writes
+    the slabs, in the layout of BatchLSQ's — slab_layout, gather_slabs and pmt_batch_expand_f64 apply as they are.  There is no pipelined
+    exchange for this objective (pmt_batch_step_f64 computes the least-squares slabs): step() is compute() and one all-gather."""
 
     SEEDS = {"Q": 201, "p": 202, "C": 203, "d": 204}
 
     def __init__(self, torch, total, n, m, rank=0, world=1, device=None):
-        _lib.require_gpu()
-        self.torch, self.total, self.n, self.m, self.rank, self.world = torch, total, n, m, rank, world
-        self.lo, self.hi = shard_range(total, rank, world)
-        self.B = self.hi - self.lo
-        dev = device or torch.device("cuda", torch.cuda.current_device())
-        f64 = torch.float64
-        self.Q = torch.empty(self.B * n * n, dtype=f64, device=dev)
-        self.p = torch.empty(self.B * n, dtype=f64, device=dev)
-        self.Cm = torch.empty(self.B * m * n, dtype=f64, device=dev)
-        self.d = torch.empty(self.B * m, dtype=f64, device=dev)
-        self.offsets, self.L = slab_layout(n, m)
-        self.local = torch.empty((self.B, self.L), dtype=f64, device=dev)
-        self.gathered = torch.empty((total, self.L), dtype=f64, device=dev) if world > 1 else self.local
-        self.stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        self.regenerate(0)
-
-    _p = staticmethod(BatchLSQ._p)
-
-    def regenerate(self, epoch):
-        """device-side Parameter callbacks (↔ rand! in README.md:36-43), one stream per Parameter and epoch"""
-        n, m = self.n, self.m
-        for name, buf, per, scale in (("Q", self.Q, n * n, 1.0), ("p", self.p, n, 1.0), ("C", self.Cm, m * n, 1.0), ("d", self.d, m, 2.0)):
-            _lib.call("pmt_fill_uniform_offset_f64", self._p(buf), self.B * per, C.c_uint64(self.SEEDS[name] + 1000 * epoch),
-                      C.c_uint64(self.lo * per), scale, self.stream)
+        self.n, self.m = n, m
+        super().__init__(torch, total, rank, world, device, {"Q": n * n, "p": n, "C": m * n, "d": m}, slab_layout(n, m))
 
     def compute(self):
         _lib.call("pmt_batch_form_coeffs_f64", self._p(self.Q), self._p(self.p), self._p(self.Cm), self._p(self.d), self.B, self.n, self.m,
                   -1, -1, self._p(self.local), self.L, self.stream)
-
-    def gather(self, dist):
-        if self.world > 1:
-            gather_slabs(dist, self.local, self.gathered)
-
-    def step(self, dist):
-        self.compute()
-        self.gather(dist)
 
 
 def horizon_slab_layout(T, nx, nu, m):
@@ -220,75 +216,58 @@ def horizon_slab_layout(T, nx, nu, m):
     return off, q + n + 1 + m * n + m
 
 
-class BatchHorizon:
-    """Device-resident batch of MPC horizons sum_t transpose(x_t - r_{i,t}) * Q_i * (x_t - r_{i,t}) + transpose(u_t) * R_i * u_t over
-    C_i*z == d_i, z = [x_0; u_0; x_1; ..] (a fleet of controllers, or of sampled scenarios: every instance with weights and stage references
-    of its own): Q[B][nx x nx], R[B][nu x nu], r[B][T x nx], v[B][T x nu], C[B][m x n], d[B][m] generated by the counter-based stream with
-    GLOBAL element offsets, so instance k holds the same data whatever the sharding.  One launch of pmt_batch_horizon_coeffs_f64 writes the
-    slabs (horizon_slab_layout); gather_slabs takes them as they are; expand() rebuilds one instance's MOI buffers.  There is no pipelined
-    exchange for this objective: step() is compute() and one all-gather."""
+class _HorizonBatch(_Batch):
+    """The horizon workloads: T stages of nx states and nu inputs, `term` terminal stages x_T behind them, n variables in z.  A subclass
+    names the entry point that expands a slab (EXPAND) and the dimensions it takes (_expand_dims)."""
 
-    SEEDS = {"Q": 301, "R": 302, "r": 303, "v": 304, "C": 305, "d": 306}
+    term = 0
 
-    def __init__(self, torch, total, T, nx, nu, m, rank=0, world=1, device=None):
-        _lib.require_gpu()
-        self.torch, self.total, self.T, self.nx, self.nu, self.m, self.rank, self.world = torch, total, T, nx, nu, m, rank, world
-        self.n = T * (nx + nu)
-        self.lo, self.hi = shard_range(total, rank, world)
-        self.B = self.hi - self.lo
-        dev = device or torch.device("cuda", torch.cuda.current_device())
-        f64 = torch.float64
-        self.per = {"Q": nx * nx, "R": nu * nu, "r": T * nx, "v": T * nu, "C": m * self.n, "d": m}
-        self.Q, self.R, self.r, self.v, self.Cm, self.d = (torch.empty(self.B * self.per[k], dtype=f64, device=dev) for k in "QRrvCd")
-        self.offsets, self.L = horizon_slab_layout(T, nx, nu, m)
-        assert self.L == _lib.load().pmt_batch_horizon_slab_doubles(T, nx, nu, m)
-        self.stride = self.L + self._extra(dev)                  # doubles of one instance's row: the slab, and what a subclass appends
-        self.local = torch.empty((self.B, self.stride), dtype=f64, device=dev)
-        self.gathered = torch.empty((total, self.stride), dtype=f64, device=dev) if world > 1 else self.local
-        self.stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        self.regenerate(0)
-
-    _p = staticmethod(BatchLSQ._p)
-
-    def _extra(self, dev):
-        """doubles a subclass appends to every instance's row behind the slab, after allocating its own inputs (BatchMPC)"""
-        return 0
-
-    def regenerate(self, epoch):
-        """device-side Parameter callbacks (↔ rand! in README.md:36-43), one stream per Parameter and epoch"""
-        for name, buf, scale in (("Q", self.Q, 1.0), ("R", self.R, 1.0), ("r", self.r, 1.0), ("v", self.v, 1.0), ("C", self.Cm, 1.0), ("d", self.d, 2.0)):
-            per = self.per[name]
-            _lib.call("pmt_fill_uniform_offset_f64", self._p(buf), self.B * per, C.c_uint64(self.SEEDS[name] + 1000 * epoch),
-                      C.c_uint64(self.lo * per), scale, self.stream)
-
-    def compute(self):
-        """x_t - r_t, u_t as it is, C*z - d"""
-        _lib.call("pmt_batch_horizon_coeffs_f64", self._p(self.Q), self._p(self.R), self._p(self.r), self._p(self.v), self._p(self.Cm),
-                  self._p(self.d), self.B, self.T, self.nx, self.nu, self.m, -1, 0, -1, self._p(self.local), self.stride, self.stream)
-
-    def gather(self, dist):
-        if self.world > 1:
-            gather_slabs(dist, self.local, self.gathered)
-
-    def step(self, dist):
-        self.compute()
-        self.gather(dist)
+    def __init__(self, torch, total, T, nx, nu, m, rank, world, device, per, layout):
+        self.T, self.nx, self.nu, self.m = T, nx, nu, m
+        super().__init__(torch, total, rank, world, device, per, layout)
 
     def expand(self, i, xvar, varmap):
-        """the MOI buffers of local instance i from its slab (pmt_batch_horizon_expand_f64): xvar the n model variables of z, varmap the
-        model-to-optimizer index map, both int64 device tensors -> (quadratic terms as 3 words each, linear terms as 2 words each, the
-        constant, vector-affine terms as 3 words each, their m constants), device tensors"""
-        torch, T, n, m = self.torch, self.T, self.n, self.m
-        nq = T * (self.nx * (self.nx + 1) // 2 + self.nu * (self.nu + 1) // 2)
+        """the MOI buffers of local instance i from its slab (EXPAND): xvar the n model variables of z, varmap the model-to-optimizer index
+        map, both int64 device tensors -> (quadratic terms as 3 words each, linear terms as 2 words each, the constant, vector-affine terms
+        as 3 words each, their m constants), device tensors"""
+        torch, n, m = self.torch, self.n, self.m
+        nqx = self.nx * (self.nx + 1) // 2
+        nq = self.T * (nqx + self.nu * (self.nu + 1) // 2) + self.term * nqx
         dev = self.local.device
         quad = torch.empty(3 * nq, dtype=torch.int64, device=dev)
         lin = torch.empty(2 * n, dtype=torch.int64, device=dev)
         const = torch.empty(1, dtype=torch.float64, device=dev)
         vat = torch.empty(max(3 * m * n, 1), dtype=torch.int64, device=dev)
         vconsts = torch.empty(max(m, 1), dtype=torch.float64, device=dev)
-        _lib.call("pmt_batch_horizon_expand_f64", C.c_void_p(self.local.data_ptr() + 8 * i * self.stride), T, self.nx, self.nu, m, self._p(xvar),
-                  self._p(varmap), self._p(quad), self._p(lin), self._p(const), self._p(vat), self._p(vconsts), self.stream)
+        _lib.call(self.EXPAND, C.c_void_p(self.local.data_ptr() + 8 * i * self.stride), *self._expand_dims(), self._p(xvar), self._p(varmap),
+                  self._p(quad), self._p(lin), self._p(const), self._p(vat), self._p(vconsts), self.stream)
         return quad, lin, const, vat[:3 * m * n], vconsts[:m]
+
+
+class BatchHorizon(_HorizonBatch):
+    """Device-resident batch of MPC horizons sum_t transpose(x_t - r_{i,t}) * Q_i * (x_t - r_{i,t}) + transpose(u_t) * R_i * u_t over
+    C_i*z == d_i, z = [x_0; u_0; x_1; ..] (a fleet of controllers, or of sampled scenarios: every instance with weights and stage references
+    of its own): Q[B][nx x nx], R[B][nu x nu], r[B][T x nx], v[B][T x nu], C[B][m x n], d[B][m].  One launch of
+    pmt_batch_horizon_coeffs_f64 writes the slabs (horizon_slab_layout); gather_slabs takes them as they are; expand() rebuilds one
+    instance's MOI buffers.  There is no pipelined exchange for this objective: step() is compute() and one all-gather."""
+
+    SEEDS = {"Q": 301, "R": 302, "r": 303, "v": 304, "C": 305, "d": 306}
+    EXPAND = "pmt_batch_horizon_expand_f64"
+
+    def __init__(self, torch, total, T, nx, nu, m, rank=0, world=1, device=None):
+        self.n = T * (nx + nu)
+        layout = horizon_slab_layout(T, nx, nu, m)
+        assert layout[1] == _lib.load().pmt_batch_horizon_slab_doubles(T, nx, nu, m)
+        super().__init__(torch, total, T, nx, nu, m, rank, world, device,
+                         {"Q": nx * nx, "R": nu * nu, "r": T * nx, "v": T * nu, "C": m * self.n, "d": m}, layout)
+
+    def compute(self):
+        """x_t - r_t, u_t as it is, C*z - d"""
+        _lib.call("pmt_batch_horizon_coeffs_f64", self._p(self.Q), self._p(self.R), self._p(self.r), self._p(self.v), self._p(self.Cm),
+                  self._p(self.d), self.B, self.T, self.nx, self.nu, self.m, -1, 0, -1, self._p(self.local), self.stride, self.stream)
+
+    def _expand_dims(self):
+        return self.T, self.nx, self.nu, self.m
 
 
 def horizon_dynamics_layout(T, nx, nu):
@@ -298,190 +277,25 @@ def horizon_dynamics_layout(T, nx, nu):
     return {"AB": 0, "hconst": nab}, nab + T * nx
 
 
-class BatchMPC(BatchHorizon):
-    """BatchHorizon with the instances' own dynamics x_0 == h_{i,0}, x_t == A_i*x_{t-1} + B_i*u_{t-1} + h_{i,t}: A[B][nx x nx], B[B][nx x nu]
-    and h[B][T x nx] beside the sibling's inputs, generated by the counter-based stream with GLOBAL element offsets like them.  One row per
-    instance, [horizon slab (L) | dynamics section (Ld)]: compute() is the sibling's launch at the row's stride and one launch of
-    pmt_batch_horizon_dynamics_f64 on the same stream; gather_slabs moves the rows as they are; expand() adds the T records' terms and
-    constants (pmt_batch_horizon_dynamics_expand_f64) to the sibling's five buffers.  m counts further dense rows C_i*z == d_i (default: none)."""
-
-    SEEDS = dict(BatchHorizon.SEEDS, A=307, B=308, h=309)
-
-    def __init__(self, torch, total, T, nx, nu, m=0, rank=0, world=1, device=None):
-        super().__init__(torch, total, T, nx, nu, m, rank, world, device)
+class _Dynamics:
+    """A horizon workload with the instances' own dynamics x_0 == h_{i,0}, x_t == A_i*x_{t-1} + B_i*u_{t-1} + h_{i,t} in Td = T + term
+    records: A[B][nx x nx], B[B][nx x nu] and h[B][Td x nx] beside the sibling's inputs (not among `inputs`: those are the sibling's).  One
+    row per instance, [slab (L) | dynamics section (Ld)]: compute() is the sibling's launch at the row's stride and one launch of
+    pmt_batch_horizon_dynamics_f64 on the same stream; gather_slabs moves the rows as they are; expand() adds the Td records' terms and
+    constants (pmt_batch_horizon_dynamics_expand_f64: it reads no variable past x_{Td-1}) to the sibling's five buffers."""
 
     def _extra(self, dev):
-        torch, T, nx, nu = self.torch, self.T, self.nx, self.nu
-        self.per.update({"A": nx * nx, "B": nx * nu, "h": T * nx})
-        self.A, self.Bm, self.h = (torch.empty(self.B * self.per[k], dtype=torch.float64, device=dev) for k in "ABh")
-        self.dyn_offsets, self.Ld = horizon_dynamics_layout(T, nx, nu)
-        assert self.Ld == _lib.load().pmt_batch_horizon_dynamics_doubles(T, nx, nu)
-        return self.Ld
-
-    def regenerate(self, epoch):
-        super().regenerate(epoch)
-        for name, buf in (("A", self.A), ("B", self.Bm), ("h", self.h)):
-            per = self.per[name]
-            _lib.call("pmt_fill_uniform_offset_f64", self._p(buf), self.B * per, C.c_uint64(self.SEEDS[name] + 1000 * epoch),
-                      C.c_uint64(self.lo * per), 1.0, self.stream)
-
-    def compute(self):
-        """the sibling's slab, and behind it x_t - A*x_{t-1} - B*u_{t-1} - h_t"""
-        super().compute()
-        _lib.call("pmt_batch_horizon_dynamics_f64", self._p(self.A), self._p(self.Bm), self._p(self.h), self.B, self.T, self.nx, self.nu, -1, -1, -1,
-                  C.c_void_p(self.local.data_ptr() + 8 * self.L), self.stride, self.stream)
-
-    def expand(self, i, xvar, varmap):
-        """the sibling's five buffers of local instance i, then the dynamics records' vector-affine terms (3 words each) and constants"""
-        torch, T, nx, w = self.torch, self.T, self.nx, self.nx + self.nu
-        dev = self.local.device
-        terms = torch.empty(3 * (nx + (T - 1) * nx * (1 + w)), dtype=torch.int64, device=dev)
-        consts = torch.empty(T * nx, dtype=torch.float64, device=dev)
-        five = super().expand(i, xvar, varmap)
-        _lib.call("pmt_batch_horizon_dynamics_expand_f64", C.c_void_p(self.local.data_ptr() + 8 * (i * self.stride + self.L)), T, nx, self.nu, 1,
-                  self._p(xvar), self._p(varmap), self._p(terms), self._p(consts), self.stream)
-        return five + (terms, consts)
-
-
-def horizon_terms_slab_layout(T, nx, nu, m, terminal):
-    """Offsets (in doubles) of the sections of one weighted horizon instance's slab [SQ | SR | SP | W | q | const | C | d-consts] over
-    n = T*(nx + nu) + term*nx variables — SP only with a terminal stage, W the ns = T*(1 + (nu > 0)) + term stage weights in z order — and
-    the slab length (pmt_batch_horizon_terms_slab_doubles)."""
-    term = 1 if terminal else 0
-    n, ns = T * (nx + nu) + term * nx, T * (2 if nu else 1) + term
-    nqx, nqu = nx * (nx + 1) // 2, nu * (nu + 1) // 2
-    w0 = nqx + nqu + term * nqx
-    q = w0 + ns
-    off = {"SQ": 0, "SR": nqx, "SP": nqx + nqu, "W": w0, "q": q, "const": q + n, "C": q + n + 1, "dconst": q + n + 1 + m * n}
-    L = q + n + 1 + m * n + m
-    assert L == _lib.load().pmt_batch_horizon_terms_slab_doubles(T, nx, nu, term, m)
-    return off, L
-
-
-class BatchWeightedHorizon:
-    """Device-resident batch of MPC horizons with a terminal cost, stage weights and linear stage terms,
-        sum_t wx_{i,t} * transpose(x_t - r_{i,t}) * Q_i * (x_t - r_{i,t}) + dot(gx_{i,t}, x_t) + wu_{i,t} * transpose(u_t) * R_i * u_t + dot(gu_{i,t}, u_t)
-        + wN_i * transpose(x_T - rN_i) * P_i * (x_T - rN_i) + dot(gN_i, x_T)
-    over C_i*z == d_i, z = [x_0; u_0; ..; u_{T-1}; x_T]: the sibling of BatchHorizon for fleets whose objectives carry a discount or a scenario
-    probability per stage, an economic term, a terminal matrix.  `terminal` adds P, rN (and x_T to z), `weights` the arrays wx, wu, wN,
-    `linear` the arrays gx, gu, gN; `signs` = (sign_r, sign_v, sign_rN, sign_d), a reference with sign 0 is not allocated.  All inputs are
-    generated by the counter-based stream with GLOBAL element offsets and seeds of their own, so instance k holds the same data whatever the
-    sharding.  One launch of pmt_batch_horizon_terms_coeffs_f64 writes the slabs (horizon_terms_slab_layout); gather_slabs takes them as they
-    are; expand() rebuilds one instance's MOI buffers.  There is no pipelined exchange for this objective: step() is compute() and one
-    all-gather."""
-
-    SEEDS = {"Q": 401, "R": 402, "P": 403, "r": 404, "v": 405, "rN": 406, "wx": 407, "wu": 408, "wN": 409, "gx": 410, "gu": 411, "gN": 412,
-             "C": 413, "d": 414}
-    SCALES = {"d": 2.0}
-
-    def __init__(self, torch, total, T, nx, nu, m, terminal=True, weights=True, linear=True, signs=(-1, 0, -1, -1), rank=0, world=1, device=None):
-        _lib.require_gpu()
-        self.torch, self.total, self.T, self.nx, self.nu, self.m, self.rank, self.world = torch, total, T, nx, nu, m, rank, world
-        self.term = 1 if terminal else 0
-        self.n = T * (nx + nu) + self.term * nx
-        self.signs = dict(zip(("r", "v", "rN", "d"), signs))
-        self.lo, self.hi = shard_range(total, rank, world)
-        self.B = self.hi - self.lo
-        dev = device or torch.device("cuda", torch.cuda.current_device())
-        f64 = torch.float64
-        self.per = {"Q": nx * nx, "R": nu * nu, "C": m * self.n, "d": m}
-        if self.signs["r"]:
-            self.per["r"] = T * nx
-        if self.signs["v"] and nu:
-            self.per["v"] = T * nu
-        if terminal:
-            self.per["P"] = nx * nx
-            if self.signs["rN"]:
-                self.per["rN"] = nx
-        if weights:
-            self.per.update({"wx": T, "wu": T if nu else 0}, **({"wN": 1} if terminal else {}))
-        if linear:
-            self.per.update({"gx": T * nx, "gu": T * nu}, **({"gN": nx} if terminal else {}))
-        self.inputs = {k: torch.empty(self.B * per, dtype=f64, device=dev) for k, per in self.per.items()}
-        self.offsets, self.L = horizon_terms_slab_layout(T, nx, nu, m, terminal)
-        self.stride = self.L + self._extra(dev)                  # doubles of one instance's row: the slab, and what a subclass appends
-        self.local = torch.empty((self.B, self.stride), dtype=f64, device=dev)
-        self.gathered = torch.empty((total, self.stride), dtype=f64, device=dev) if world > 1 else self.local
-        self.stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        self.regenerate(0)
-
-    _p = staticmethod(BatchLSQ._p)
-
-    def _extra(self, dev):
-        """doubles a subclass appends to every instance's row behind the slab, after allocating its own inputs (BatchWeightedMPC)"""
-        return 0
-
-    def regenerate(self, epoch):
-        """device-side Parameter callbacks (↔ rand! in README.md:36-43), one stream per Parameter and epoch"""
-        for name, buf in self.inputs.items():
-            per = self.per[name]
-            _lib.call("pmt_fill_uniform_offset_f64", self._p(buf), self.B * per, C.c_uint64(self.SEEDS[name] + 1000 * epoch),
-                      C.c_uint64(self.lo * per), self.SCALES.get(name, 1.0), self.stream)
-
-    def descriptor(self):
-        """the pmt_batch_horizon_terms of this shard's inputs"""
-        ptrs = {k: (buf.data_ptr() if self.per[k] else None) for k, buf in self.inputs.items()}
-        return _lib.batch_horizon_terms(sign_r=self.signs["r"], sign_v=self.signs["v"], sign_rN=self.signs["rN"], sign_d=self.signs["d"], **ptrs)
-
-    def compute(self):
-        desc = self.descriptor()
-        _lib.call("pmt_batch_horizon_terms_coeffs_f64", C.byref(desc), self.B, self.T, self.nx, self.nu, self.m, self._p(self.local), self.stride,
-                  self.stream)
-
-    def gather(self, dist):
-        if self.world > 1:
-            gather_slabs(dist, self.local, self.gathered)
-
-    def step(self, dist):
-        self.compute()
-        self.gather(dist)
-
-    def expand(self, i, xvar, varmap):
-        """the MOI buffers of local instance i from its slab (pmt_batch_horizon_terms_expand_f64): xvar the n model variables of z, varmap the
-        model-to-optimizer index map, both int64 device tensors -> (quadratic terms as 3 words each, linear terms as 2 words each, the
-        constant, vector-affine terms as 3 words each, their m constants), device tensors"""
-        torch, T, n, m = self.torch, self.T, self.n, self.m
-        nqx = self.nx * (self.nx + 1) // 2
-        nq = T * (nqx + self.nu * (self.nu + 1) // 2) + self.term * nqx
-        dev = self.local.device
-        quad = torch.empty(3 * nq, dtype=torch.int64, device=dev)
-        lin = torch.empty(2 * n, dtype=torch.int64, device=dev)
-        const = torch.empty(1, dtype=torch.float64, device=dev)
-        vat = torch.empty(max(3 * m * n, 1), dtype=torch.int64, device=dev)
-        vconsts = torch.empty(max(m, 1), dtype=torch.float64, device=dev)
-        _lib.call("pmt_batch_horizon_terms_expand_f64", C.c_void_p(self.local.data_ptr() + 8 * i * self.stride), T, self.nx, self.nu, self.term, m,
-                  self._p(xvar), self._p(varmap), self._p(quad), self._p(lin), self._p(const), self._p(vat), self._p(vconsts), self.stream)
-        return quad, lin, const, vat[:3 * m * n], vconsts[:m]
-
-
-class BatchWeightedMPC(BatchWeightedHorizon):
-    """BatchWeightedHorizon with the instances' own dynamics, as BatchMPC is BatchHorizon with them: A[B][nx x nx], B[B][nx x nu] and
-    h[B][Td x nx] beside the sibling's inputs.  With a terminal stage the dynamics have Td = T + 1 records, up to
-    x_T == A_i*x_{T-1} + B_i*u_{T-1} + h_{i,T} (so T <= 511 then); without one Td = T.  One row per instance, [slab (L) | dynamics section (Ld)]:
-    compute() is the sibling's launch at the row's stride and one launch of the unchanged pmt_batch_horizon_dynamics_f64 with Td; expand()
-    adds the Td records' terms and constants (pmt_batch_horizon_dynamics_expand_f64 with Td: it reads no variable past x_T, so the n
-    variables of this z suffice).  m counts further dense rows C_i*z == d_i (default: none)."""
-
-    SEEDS = dict(BatchWeightedHorizon.SEEDS, A=415, B=416, h=417)
-
-    def __init__(self, torch, total, T, nx, nu, m=0, terminal=True, weights=True, linear=True, signs=(-1, 0, -1, -1), rank=0, world=1, device=None):
-        super().__init__(torch, total, T, nx, nu, m, terminal, weights, linear, signs, rank, world, device)
-
-    def _extra(self, dev):
-        torch, nx, nu = self.torch, self.nx, self.nu
+        nx, nu = self.nx, self.nu
         self.Td = self.T + self.term
         self.dyn_per = {"A": nx * nx, "B": nx * nu, "h": self.Td * nx}
-        self.A, self.Bm, self.h = (torch.empty(self.B * self.dyn_per[k], dtype=torch.float64, device=dev) for k in "ABh")
+        self.dyn_inputs = self._alloc(self.dyn_per, dev)
         self.dyn_offsets, self.Ld = horizon_dynamics_layout(self.Td, nx, nu)
         assert self.Ld == _lib.load().pmt_batch_horizon_dynamics_doubles(self.Td, nx, nu)
         return self.Ld
 
     def regenerate(self, epoch):
         super().regenerate(epoch)
-        for name, buf in (("A", self.A), ("B", self.Bm), ("h", self.h)):
-            per = self.dyn_per[name]
-            _lib.call("pmt_fill_uniform_offset_f64", self._p(buf), self.B * per, C.c_uint64(self.SEEDS[name] + 1000 * epoch),
-                      C.c_uint64(self.lo * per), 1.0, self.stream)
+        self._fill(self.dyn_inputs, self.dyn_per, epoch)
 
     def compute(self):
         """the sibling's slab, and behind it x_t - A*x_{t-1} - B*u_{t-1} - h_t for t = 1 .. Td-1"""
@@ -499,6 +313,89 @@ class BatchWeightedMPC(BatchWeightedHorizon):
         _lib.call("pmt_batch_horizon_dynamics_expand_f64", C.c_void_p(self.local.data_ptr() + 8 * (i * self.stride + self.L)), Td, nx, self.nu, 1,
                   self._p(xvar), self._p(varmap), self._p(terms), self._p(consts), self.stream)
         return five + (terms, consts)
+
+
+class BatchMPC(_Dynamics, BatchHorizon):
+    """BatchHorizon with the instances' own dynamics (_Dynamics, Td = T records).  m counts further dense rows C_i*z == d_i (default: none)."""
+
+    SEEDS = dict(BatchHorizon.SEEDS, A=307, B=308, h=309)
+
+    def __init__(self, torch, total, T, nx, nu, m=0, rank=0, world=1, device=None):
+        super().__init__(torch, total, T, nx, nu, m, rank, world, device)
+
+
+def horizon_terms_slab_layout(T, nx, nu, m, terminal):
+    """Offsets (in doubles) of the sections of one weighted horizon instance's slab [SQ | SR | SP | W | q | const | C | d-consts] over
+    n = T*(nx + nu) + term*nx variables — SP only with a terminal stage, W the ns = T*(1 + (nu > 0)) + term stage weights in z order — and
+    the slab length (pmt_batch_horizon_terms_slab_doubles)."""
+    term = 1 if terminal else 0
+    n, ns = T * (nx + nu) + term * nx, T * (2 if nu else 1) + term
+    nqx, nqu = nx * (nx + 1) // 2, nu * (nu + 1) // 2
+    w0 = nqx + nqu + term * nqx
+    q = w0 + ns
+    off = {"SQ": 0, "SR": nqx, "SP": nqx + nqu, "W": w0, "q": q, "const": q + n, "C": q + n + 1, "dconst": q + n + 1 + m * n}
+    L = q + n + 1 + m * n + m
+    assert L == _lib.load().pmt_batch_horizon_terms_slab_doubles(T, nx, nu, term, m)
+    return off, L
+
+
+class BatchWeightedHorizon(_HorizonBatch):
+    """Device-resident batch of MPC horizons with a terminal cost, stage weights and linear stage terms,
+        sum_t wx_{i,t} * transpose(x_t - r_{i,t}) * Q_i * (x_t - r_{i,t}) + dot(gx_{i,t}, x_t) + wu_{i,t} * transpose(u_t) * R_i * u_t + dot(gu_{i,t}, u_t)
+        + wN_i * transpose(x_T - rN_i) * P_i * (x_T - rN_i) + dot(gN_i, x_T)
+    over C_i*z == d_i, z = [x_0; u_0; ..; u_{T-1}; x_T]: the sibling of BatchHorizon for fleets whose objectives carry a discount or a scenario
+    probability per stage, an economic term, a terminal matrix.  `terminal` adds P, rN (and x_T to z), `weights` the arrays wx, wu, wN,
+    `linear` the arrays gx, gu, gN; `signs` = (sign_r, sign_v, sign_rN, sign_d), a reference with sign 0 is not allocated.  All inputs have
+    seeds of their own.  One launch of pmt_batch_horizon_terms_coeffs_f64 writes the slabs (horizon_terms_slab_layout); gather_slabs takes
+    them as they are; expand() rebuilds one instance's MOI buffers.  There is no pipelined exchange for this objective: step() is compute()
+    and one all-gather."""
+
+    SEEDS = {"Q": 401, "R": 402, "P": 403, "r": 404, "v": 405, "rN": 406, "wx": 407, "wu": 408, "wN": 409, "gx": 410, "gu": 411, "gN": 412,
+             "C": 413, "d": 414}
+    EXPAND = "pmt_batch_horizon_terms_expand_f64"
+
+    def __init__(self, torch, total, T, nx, nu, m, terminal=True, weights=True, linear=True, signs=(-1, 0, -1, -1), rank=0, world=1, device=None):
+        self.term = 1 if terminal else 0
+        self.n = T * (nx + nu) + self.term * nx
+        self.signs = dict(zip(("r", "v", "rN", "d"), signs))
+        per = {"Q": nx * nx, "R": nu * nu, "C": m * self.n, "d": m}
+        if self.signs["r"]:
+            per["r"] = T * nx
+        if self.signs["v"] and nu:
+            per["v"] = T * nu
+        if terminal:
+            per["P"] = nx * nx
+            if self.signs["rN"]:
+                per["rN"] = nx
+        if weights:
+            per.update({"wx": T, "wu": T if nu else 0}, **({"wN": 1} if terminal else {}))
+        if linear:
+            per.update({"gx": T * nx, "gu": T * nu}, **({"gN": nx} if terminal else {}))
+        super().__init__(torch, total, T, nx, nu, m, rank, world, device, per, horizon_terms_slab_layout(T, nx, nu, m, terminal))
+
+    def descriptor(self):
+        """the pmt_batch_horizon_terms of this shard's inputs"""
+        ptrs = {k: (buf.data_ptr() if self.per[k] else None) for k, buf in self.inputs.items()}
+        return _lib.batch_horizon_terms(sign_r=self.signs["r"], sign_v=self.signs["v"], sign_rN=self.signs["rN"], sign_d=self.signs["d"], **ptrs)
+
+    def compute(self):
+        desc = self.descriptor()
+        _lib.call("pmt_batch_horizon_terms_coeffs_f64", C.byref(desc), self.B, self.T, self.nx, self.nu, self.m, self._p(self.local), self.stride,
+                  self.stream)
+
+    def _expand_dims(self):
+        return self.T, self.nx, self.nu, self.term, self.m
+
+
+class BatchWeightedMPC(_Dynamics, BatchWeightedHorizon):
+    """BatchWeightedHorizon with the instances' own dynamics (_Dynamics), as BatchMPC is BatchHorizon with them.  With a terminal stage the
+    dynamics have Td = T + 1 records, up to x_T == A_i*x_{T-1} + B_i*u_{T-1} + h_{i,T} (so T <= 511 then); without one Td = T.  m counts
+    further dense rows C_i*z == d_i (default: none)."""
+
+    SEEDS = dict(BatchWeightedHorizon.SEEDS, A=415, B=416, h=417)
+
+    def __init__(self, torch, total, T, nx, nu, m=0, terminal=True, weights=True, linear=True, signs=(-1, 0, -1, -1), rank=0, world=1, device=None):
+        super().__init__(torch, total, T, nx, nu, m, terminal, weights, linear, signs, rank, world, device)
 
 
 TOTAL, N, R, M = 8192, 128, 128, 16        # BASELINE config 4 (m is not stated there: 16, SURVEY.md section 8d)

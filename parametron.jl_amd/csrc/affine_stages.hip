@@ -118,18 +118,6 @@ __global__ __launch_bounds__(AS_THREADS) void affine_stages_kernel(AffineStagesA
     }
 }
 
-static int as_cu_count() {
-    static int cus[16] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) { (void)hipGetLastError(); return 256; }
-    if (!cus[dev]) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) { (void)hipGetLastError(); v = 256; }
-        cus[dev] = v;
-    }
-    return cus[dev];
-}
-
 // slices [at, at + len) sorted by their start tile [0, total): the first starts at 0, each starts where the one before ends, the last ends at total
 static bool as_slices_tile(std::vector<std::pair<int64_t, int64_t>> &s, int64_t total) {
     std::sort(s.begin(), s.end());
@@ -199,7 +187,7 @@ extern "C" int pmt_affine_stages_f64(const pmt_affine_stage *stages, int64_t T, 
     g.terms = reinterpret_cast<u64 *>(out_terms); g.consts = out_consts;
     return dispatch(stream, [=](hipStream_t s) {
         // persistent in x over the records; fewer records than resident workgroups: up to AS_SPLIT workgroups share each record's items
-        const int64_t resident = (int64_t)AS_WG_PER_CU * as_cu_count();
+        const int64_t resident = (int64_t)AS_WG_PER_CU * cu_count();
         const unsigned gy = (unsigned)std::max<int64_t>(1, std::min<int64_t>(AS_SPLIT, resident / T));
         const dim3 grid((unsigned)std::min<int64_t>(T, resident / gy), gy);
         PMT_LAUNCH(affine_stages_kernel, grid, dim3(AS_THREADS), 0, s, g);

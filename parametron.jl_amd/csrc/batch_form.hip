@@ -15,7 +15,7 @@
 // alone, bit for bit.  The Q section leaves as 8-byte stores with k on the lanes: a slab starts at any 8-byte address.
 // LDS: 33280 (tile) + 8192 (P) + 2048 (c) + 2048 (tree) = 45568 bytes: three workgroups per CU.
 // What the time is made of (profiles/r18_batch_form.txt): round trips to HBM.  No load is conditional and all loads of a tile are issued
-// before the first value is looked at (bf_landed); p and d are asked for at the top of an instance.  8192 x (128, 16): 462 us, 0.51 of 8 TB/s
+// before the first value is looked at (landed); p and d are asked for at the top of an instance.  8192 x (128, 16): 462 us, 0.51 of 8 TB/s
 // on the algorithmic bytes, against 871 us with every load waited for in turn.
 #include <algorithm>
 
@@ -39,31 +39,6 @@ struct BatchFormArgs {
     int n, sign_p, sign_d;
     double *out; int64_t out_stride;
 };
-
-__device__ __forceinline__ int64_t bf_tri_pos(int64_t n, int64_t j, int64_t k) { return j * n - (j * (j - 1)) / 2 + (k - j); }
-
-// ((s(0)*c(0) + s(1)*c(1)) + ..) + s(len-1)*c(len-1): the first product starts the chain.  The operands of eight steps are read from LDS
-// together — one LDS round trip per eight dependent additions instead of one per addition; the order of the additions is the chain's.
-template <typename FS, typename FC>
-__device__ __forceinline__ double bf_chain(int len, FS s, FC c) {
-    double acc = s(0) * c(0);
-    int k = 1;
-    for (; k + 8 <= len; k += 8) {
-        double a[8], b[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { a[i] = s(k + i); b[i] = c(k + i); }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { const double pr = a[i] * b[i]; acc = acc + pr; }
-    }
-    for (; k < len; ++k) acc = acc + s(k) * c(k);
-    return acc;
-}
-
-// Every element of v is in its register here: loads issued above this point are not moved below it or into a branch.
-__device__ __forceinline__ void bf_landed(double (&v)[16]) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) asm volatile("" : "+v"(v[i]));
-}
 
 }  // namespace
 
@@ -98,7 +73,7 @@ __global__ __launch_bounds__(BF_THREADS) void batch_form_kernel(BatchFormArgs g)
                 // lower[i] = Q[k0 + lane, j0 + wave + 4 i] (k on the lanes); upper[i] = Q[j0 + lane, k0 + wave + 4 i] (j on the lanes)
                 // Out-of-range entries are 0.0: the load goes to the instance's last row / column instead and is dropped, so no load is
                 // conditional and an address is the uniform base plus one 32-bit offset.  All loads of a tile are issued before the first
-                // value is looked at (bf_landed: left to itself the compiler sinks every load into its own branch and waits for each in turn).
+                // value is looked at (landed: left to itself the compiler sinks every load into its own branch and waits for each in turn).
                 double lower[16], upper[16];
                 const int rk = k0 + lane, rj = j0 + lane;
                 const unsigned ork = (unsigned)(rk < n ? rk : n - 1), orj = (unsigned)(rj < n ? rj : n - 1);
@@ -113,11 +88,11 @@ __global__ __launch_bounds__(BF_THREADS) void batch_form_kernel(BatchFormArgs g)
                         const int c = k0 + wave + 4 * i;
                         upper[i] = Q[orj + (unsigned)(c < n ? c : n - 1) * (unsigned)n];
                     }
-                    bf_landed(upper);
+                    landed(upper);
 #pragma unroll
                     for (int i = 0; i < 16; ++i) upper[i] = (rj < n && k0 + wave + 4 * i < n) ? upper[i] : 0.0;
                 }
-                bf_landed(lower);
+                landed(lower);
 #pragma unroll
                 for (int i = 0; i < 16; ++i) lower[i] = (rk < n && j0 + wave + 4 * i < n) ? lower[i] : 0.0;
                 if (diagonal) {
@@ -150,10 +125,10 @@ __global__ __launch_bounds__(BF_THREADS) void batch_form_kernel(BatchFormArgs g)
                 if (shift) {
                     // plain multiplies and adds, ascending, the first product starting the chain
                     if (wave == 0 && lane < jw) {
-                        part[bk][j0 + lane] = bf_chain(kw, [&](int kk) { const double a = tile[lane][kk]; return (diagonal && kk == lane) ? 2 * a : a; },
+                        part[bk][j0 + lane] = chain(kw, [&](int kk) { const double a = tile[lane][kk]; return (diagonal && kk == lane) ? 2 * a : a; },
                                                        [&](int kk) { return cvec[k0 + kk]; });
                     } else if (wave == 1 && !diagonal && lane < kw) {
-                        part[bj][k0 + lane] = bf_chain(jw, [&](int jj) { return tile[jj][lane]; }, [&](int jj) { return cvec[j0 + jj]; });
+                        part[bj][k0 + lane] = chain(jw, [&](int jj) { return tile[jj][lane]; }, [&](int jj) { return cvec[j0 + jj]; });
                     }
                 }
                 // the Q section: row j holds its columns k >= j; this tile's piece of it, k on the lanes
@@ -163,7 +138,7 @@ __global__ __launch_bounds__(BF_THREADS) void batch_form_kernel(BatchFormArgs g)
                     const int k = k0 + lane;
                     if (j < n && k < n && k >= j) {
                         const double v = tile[jj][lane];
-                        out[bf_tri_pos(n, j, k)] = (k == j) ? 2 * v : v;
+                        out[tri_pos(n, j, k)] = (k == j) ? 2 * v : v;
                     }
                 }
                 __syncthreads();
@@ -206,7 +181,7 @@ __global__ __launch_bounds__(BF_THREADS) void batch_form_kernel(BatchFormArgs g)
                         const int c = c0 + wave + 4 * i;
                         cin[i] = Ci[(c < n ? c : n - 1) * m + rc];
                     }
-                    bf_landed(cin);
+                    landed(cin);
 #pragma unroll
                     for (int i = 0; i < 16; ++i) tile[wave + 4 * i][lane] = cin[i];
                     __syncthreads();
@@ -227,18 +202,6 @@ __global__ __launch_bounds__(BF_THREADS) void batch_form_kernel(BatchFormArgs g)
         }
         __syncthreads();                                  // the next instance reuses cvec, part and red
     }
-}
-
-static int bf_cu_count() {
-    static int cus[16] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) { (void)hipGetLastError(); return 256; }
-    if (!cus[dev]) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) { (void)hipGetLastError(); v = 256; }
-        cus[dev] = v;
-    }
-    return cus[dev];
 }
 
 }  // namespace pmt
@@ -262,7 +225,7 @@ extern "C" int pmt_batch_form_coeffs_f64(const double *Q, const double *p, const
     g.out = out; g.out_stride = out_stride;
     return dispatch(stream, [=](hipStream_t s) {
         // three workgroups per CU stay resident (LDS); each walks the instances blockIdx.x, blockIdx.x + G, ..
-        const dim3 grid((unsigned)std::min<int64_t>(B, (int64_t)BF_WG_PER_CU * bf_cu_count()));
+        const dim3 grid((unsigned)std::min<int64_t>(B, (int64_t)BF_WG_PER_CU * cu_count()));
         PMT_LAUNCH(batch_form_kernel, grid, dim3(BF_THREADS), 0, s, g);
         return check_launch("batch_form_kernel");
     });

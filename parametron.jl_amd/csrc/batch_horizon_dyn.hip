@@ -13,7 +13,7 @@
 // 64 rows x 64 columns, or 32 x 128 with nx <= 32, or 16 x 256 with nx <= 16 (the kernel is instantiated by the tile's rows), so that a
 // column of a narrow instance does not leave three quarters of a wave's lanes idle.  A tile is read along its columns as batch_form_kernel
 // reads its tiles — no load is conditional (an index past the edge goes to the last row / column and is dropped), all 16 loads of a thread
-// are issued before the first value is looked at (bd_landed), the lane's coordinates are made opaque per tile — and transposed through an
+// are issued before the first value is looked at (landed), the lane's coordinates are made opaque per tile — and transposed through an
 // LDS tile of pitch columns + 1 doubles: 16 consecutive lanes hold 16 rows of one column, a stride of 2 mod 32 dwords, which covers the 32
 // banks of a b64 write once; rows leave with the column on the lanes as 8-byte stores, so a section starts at any 8-byte address.  The
 // h-consts stream through registers, four clamped loads per thread in flight.  LDS: 33280 bytes, four workgroups per CU.
@@ -55,13 +55,6 @@ struct BatchDynArgs {
     u64 flip_a, flip_b;                      // the sign bit where the sign is -1
     double *out; int64_t out_stride;
 };
-
-// Every element of v is in its register here: loads issued above this point are not moved below it or into a branch.
-template <int N>
-__device__ __forceinline__ void bd_landed(u64 (&v)[N]) {
-#pragma unroll
-    for (int i = 0; i < N; ++i) asm volatile("" : "+v"(v[i]));
-}
 
 // h-consts[i] = 0.0 (+|-) h[i], i < cnt, the `width` threads of the caller striding together; four clamped loads per thread in flight
 __device__ __forceinline__ void bd_consts(const double *__restrict__ h, int sign, int cnt, double *__restrict__ o, int first, int width) {
@@ -116,7 +109,7 @@ __global__ __launch_bounds__(BD_THREADS) void batch_horizon_dyn_kernel(BatchDynA
                     const u64 *__restrict__ col = cc < nx ? Ai + (unsigned)cc * (unsigned)nx : Bi + (unsigned)(cc - nx) * (unsigned)nx;
                     v[i] = col[rc];
                 }
-                bd_landed(v);
+                landed(v);
                 // tile[row][column], each word with its part's sign
 #pragma unroll
                 for (int i = 0; i < 16; ++i) tile[lr * PITCH + lc + CSTEP * i] = v[i] ^ (c0 + lc + CSTEP * i < nx ? flip_a : flip_b);
@@ -157,7 +150,7 @@ __global__ __launch_bounds__(BD_THREADS) void batch_horizon_dyn_small_kernel(Bat
         u64 v[BD_SMALL_WORDS / 64];
 #pragma unroll
         for (int k = 0; k < BD_SMALL_WORDS / 64; ++k) v[k] = (from_a[k] ? Ai : Bi)[src[k]];
-        bd_landed(v);
+        landed(v);
 #pragma unroll
         for (int k = 0; k < BD_SMALL_WORDS / 64; ++k) {
             const int e = lane + 64 * k;
@@ -211,18 +204,6 @@ __global__ __launch_bounds__(BD_THREADS) void batch_horizon_dyn_expand_kernel(co
     }
 }
 
-static int bd_cu_count() {
-    static int cus[16] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) { (void)hipGetLastError(); return 256; }
-    if (!cus[dev]) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) { (void)hipGetLastError(); v = 256; }
-        cus[dev] = v;
-    }
-    return cus[dev];
-}
-
 // the dimension checks both entry points share; `who` words the message
 static int bd_check_dims(const char *who, int64_t T, int64_t nx, int64_t nu) {
     const std::string w(who);
@@ -258,11 +239,11 @@ extern "C" int pmt_batch_horizon_dynamics_f64(const double *A, const double *Bm,
     g.out = out; g.out_stride = out_stride;
     return dispatch(stream, [=](hipStream_t s) {
         if (g.nx * (g.nx + g.nu) <= BD_SMALL_WORDS) {
-            const dim3 grid((unsigned)std::min<int64_t>(cdiv(B, BD_WAVES), (int64_t)BD_SMALL_WG_PER_CU * bd_cu_count()));
+            const dim3 grid((unsigned)std::min<int64_t>(cdiv(B, BD_WAVES), (int64_t)BD_SMALL_WG_PER_CU * cu_count()));
             PMT_LAUNCH(batch_horizon_dyn_small_kernel, grid, dim3(BD_THREADS), 0, s, g);
             return check_launch("batch_horizon_dyn_small_kernel");
         }
-        const dim3 grid((unsigned)std::min<int64_t>(B, (int64_t)BD_WG_PER_CU * bd_cu_count()));
+        const dim3 grid((unsigned)std::min<int64_t>(B, (int64_t)BD_WG_PER_CU * cu_count()));
         if (g.nx <= 16) PMT_LAUNCH(batch_horizon_dyn_kernel<16>, grid, dim3(BD_THREADS), 0, s, g);
         else if (g.nx <= 32) PMT_LAUNCH(batch_horizon_dyn_kernel<32>, grid, dim3(BD_THREADS), 0, s, g);
         else PMT_LAUNCH(batch_horizon_dyn_kernel<64>, grid, dim3(BD_THREADS), 0, s, g);
@@ -279,7 +260,7 @@ extern "C" int pmt_batch_horizon_dynamics_expand_f64(const double *section, int6
     const int iT = (int)T, inx = (int)nx, inu = (int)nu;
     return dispatch(stream, [=](hipStream_t s) {
         const int64_t items = (int64_t)(iT - 1) * cdiv(inx, BD_EXPAND_ROWS) + 1 + cdiv((int64_t)iT * inx, BD_THREADS);
-        PMT_LAUNCH(batch_horizon_dyn_expand_kernel, dim3((unsigned)std::min<int64_t>(items, (int64_t)8 * bd_cu_count())), dim3(BD_THREADS), 0, s, section, iT,
+        PMT_LAUNCH(batch_horizon_dyn_expand_kernel, dim3((unsigned)std::min<int64_t>(items, (int64_t)8 * cu_count())), dim3(BD_THREADS), 0, s, section, iT,
                    inx, inu, sign_xp, xvar, varmap, reinterpret_cast<u64 *>(out_terms), out_consts);
         return check_launch("batch_horizon_dyn_expand_kernel");
     });

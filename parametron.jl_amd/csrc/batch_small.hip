@@ -507,18 +507,6 @@ __global__ __launch_bounds__(NT, 2) void batch_small_kernel(SmallArgs p) {
     else storer_waves(p, sh, tid - NH - NL, n, nchunk);
 }
 
-static int cu_count() {
-    static int cus[16] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) { (void)hipGetLastError(); return 256; }
-    if (!cus[dev]) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) { (void)hipGetLastError(); v = 256; }
-        cus[dev] = v;
-    }
-    return cus[dev];
-}
-
 // out: slab base; the sections of an instance's slab are contiguous ([Q | q | const | C | d], batch.hip)
 int launch_batch_small(const double *A, int64_t lda, int64_t rows, int64_t cols, int64_t strideA, const double *b, int64_t strideb, int sign,
                        int64_t B, double *out, int64_t out_stride, const double *Cm, int64_t m, const double *d, int sign_d, hipStream_t s) {

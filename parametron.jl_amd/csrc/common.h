@@ -1,4 +1,4 @@
-// Shared host-side plumbing for libparametron_hip.so (gfx950 only).
+// Shared host-side plumbing for libparametron_hip.so (gfx950 only), and the small device helpers several kernel files use.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -85,6 +85,19 @@ inline int check_launch(const char *name) {
 
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// The current device's number of CUs (what the persistent kernels size their grids by), asked for once per device; 256 where it cannot be.
+inline int cu_count() {
+    static int cus[16] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) { (void)hipGetLastError(); return 256; }
+    if (!cus[dev]) {
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) { (void)hipGetLastError(); v = 256; }
+        cus[dev] = v;
+    }
+    return cus[dev];
+}
+
 // 0.0 (+|-) v : the constant a zero!'d AffineFunction ends up with after add!/subtract! of a Number
 // (src/functions.jl:244,452,474).  sign == 0 -> 0.0.
 __device__ __forceinline__ double signed_const(double v, int sign) {
@@ -92,6 +105,33 @@ __device__ __forceinline__ double signed_const(double v, int sign) {
 }
 __device__ __forceinline__ int64_t map_var(const int64_t *__restrict__ varmap, int64_t var) {
     return varmap ? varmap[var - 1] : var;
+}
+
+// Position of (j, k), j <= k, in the row-major upper triangle of an n x n matrix (the order of a canonical form's quadratic terms).
+__device__ __forceinline__ int64_t tri_pos(int64_t n, int64_t j, int64_t k) { return j * n - (j * (j - 1)) / 2 + (k - j); }
+
+// ((s(0)*c(0) + s(1)*c(1)) + ..) + s(len-1)*c(len-1): the first product starts the chain.  The operands of eight steps are read from LDS
+// together — one LDS round trip per eight dependent additions instead of one per addition; the order of the additions is the chain's.
+template <typename FS, typename FC>
+__device__ __forceinline__ double chain(int len, FS s, FC c) {
+    double acc = s(0) * c(0);
+    int k = 1;
+    for (; k + 8 <= len; k += 8) {
+        double a[8], b[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { a[i] = s(k + i); b[i] = c(k + i); }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { const double pr = a[i] * b[i]; acc = acc + pr; }
+    }
+    for (; k < len; ++k) acc = acc + s(k) * c(k);
+    return acc;
+}
+
+// Every element of v is in its register here: loads issued above this point are not moved below it or into a branch.
+template <typename V, int N>
+__device__ __forceinline__ void landed(V (&v)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) asm volatile("" : "+v"(v[i]));
 }
 
 // One wave writes `nterms` consecutive terms of W 8-byte words each, starting at `seg`, as 16-byte chunks (global_store_dwordx4)

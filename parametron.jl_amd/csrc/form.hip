@@ -31,8 +31,6 @@ struct FormArgs {
     const double *v; int sign; double *part;              // the shifted form (pmt_quad_form_shift_f64): x (+|-) v, the workspace P[nb + 1][n]
 };
 
-__device__ __forceinline__ int64_t form_tri_pos(int64_t n, int64_t j, int64_t k) { return j * n - (j * (j - 1)) / 2 + (k - j); }
-
 // SHIFT: the tile of the shifted form transpose(x (+|-) v) * Q * (x (+|-) v).  The quadratic part is the plain form's; the tile's S, in LDS
 // after the transpose-add, also gives this tile's share of lin = S*c: one chain per row over the tile's columns (P[K][j], j in block J) and,
 // off the diagonal, one per column over its rows (P[J][k], k in block K; S is bitwise symmetric).  Every (B, j) of the workspace is written
@@ -130,7 +128,7 @@ __device__ __forceinline__ void quad_form_tile(const FormArgs &g) {
             const int off = (int)(ks - k0);
             const u64w rowvar = (u64w)map_var(g.varmap, g.xvar[j]);
             const bool dbl = g.moi && diagonal;                         // the row's first term is its diagonal term
-            wave_write_words<3>(reinterpret_cast<u64w *>(g.quad + form_tri_pos(n, j, ks)), (int)(ke - ks), lane, [&](int q) -> u64w {
+            wave_write_words<3>(reinterpret_cast<u64w *>(g.quad + tri_pos(n, j, ks)), (int)(ke - ks), lane, [&](int q) -> u64w {
                 const int t = q / 3, f = q - 3 * t;
                 if (f == 1) return rowvar;
                 if (f == 2) return (u64w)colvar[off + t];

@@ -58,8 +58,6 @@ __device__ __forceinline__ double sum_diag_shift_at(const SumArgs &g, const Cols
     return d;
 }
 
-__device__ __forceinline__ int64_t tri_pos(int64_t n, int64_t j, int64_t k) { return j * n - (j * (j - 1)) / 2 + (k - j); }
-
 // One 64 x 64 tile of the upper triangle per workgroup (row-major order of the tile pairs).  Block 1's coefficients are read from the
 // term array (row-major), the CSC columns of blocks 2..K coalesced (a tile column is 64 consecutive doubles) and transposed through LDS;
 // the combined coefficients go back through LDS so that each wave rewrites whole row segments of 24-byte terms with 16-byte stores.

@@ -57,31 +57,6 @@ struct QuadStagesTermsArgs : QuadStagesArgs {
 };
 template <bool TERMS> using QsArgs = std::conditional_t<TERMS, QuadStagesTermsArgs, QuadStagesArgs>;
 
-__device__ __forceinline__ int64_t qs_tri_pos(int64_t n, int64_t j, int64_t k) { return j * n - (j * (j - 1)) / 2 + (k - j); }
-
-// ((s(0)*c(0) + s(1)*c(1)) + ..) + s(len-1)*c(len-1): the first product starts the chain.  The operands of eight steps are read from LDS
-// together; the order of the additions is the chain's.
-template <typename FS, typename FC>
-__device__ __forceinline__ double qs_chain(int len, FS s, FC c) {
-    double acc = s(0) * c(0);
-    int k = 1;
-    for (; k + 8 <= len; k += 8) {
-        double a[8], b[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { a[i] = s(k + i); b[i] = c(k + i); }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { const double pr = a[i] * b[i]; acc = acc + pr; }
-    }
-    for (; k < len; ++k) acc = acc + s(k) * c(k);
-    return acc;
-}
-
-// Every element of v is in its register here: loads issued above this point are not moved below it or into a branch.
-__device__ __forceinline__ void qs_landed(double (&v)[16]) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) asm volatile("" : "+v"(v[i]));
-}
-
 }  // namespace
 
 // TERMS (pmt_quad_stages_terms_f64): stage t is weighted and may carry a linear term (g.terms[t], pmt_quad_stage_terms): W_t multiplies
@@ -136,7 +111,7 @@ __global__ __launch_bounds__(QS_THREADS) void quad_stages_kernel(QsArgs<TERMS> g
                 const int j0 = bj * QS_TILE, k0 = bk * QS_TILE;
                 // lower[i] = Q[k0 + lane, j0 + wave + 4 i] (k on the lanes); upper[i] = Q[j0 + lane, k0 + wave + 4 i] (j on the lanes)
                 // Out-of-range entries are 0.0: the load goes to the stage's last row / column instead and is dropped, so no load is
-                // conditional.  All loads of a tile are issued before the first value is looked at (qs_landed).
+                // conditional.  All loads of a tile are issued before the first value is looked at (landed).
                 double lower[16], upper[16];
                 const int rk = k0 + lane, rj = j0 + lane;
                 const int ork = rk < n ? rk : n - 1, orj = rj < n ? rj : n - 1;
@@ -151,11 +126,11 @@ __global__ __launch_bounds__(QS_THREADS) void quad_stages_kernel(QsArgs<TERMS> g
                         const int c = k0 + wave + 4 * i;
                         upper[i] = Q[orj + (int64_t)(c < n ? c : n - 1) * ldq];
                     }
-                    qs_landed(upper);
+                    landed(upper);
 #pragma unroll
                     for (int i = 0; i < 16; ++i) upper[i] = (rj < n && k0 + wave + 4 * i < n) ? upper[i] : 0.0;
                 }
-                qs_landed(lower);
+                landed(lower);
 #pragma unroll
                 for (int i = 0; i < 16; ++i) lower[i] = (rk < n && j0 + wave + 4 * i < n) ? lower[i] : 0.0;
                 if (diagonal) {
@@ -196,10 +171,10 @@ __global__ __launch_bounds__(QS_THREADS) void quad_stages_kernel(QsArgs<TERMS> g
                 if (shift) {
                     // plain multiplies and adds, ascending, the first product starting the chain
                     if (wave == 0 && lane < jw) {
-                        part[bk][j0 + lane] = qs_chain(kw, [&](int kk) { const double a = tile[lane][kk]; return (diagonal && kk == lane) ? 2 * a : a; },
+                        part[bk][j0 + lane] = chain(kw, [&](int kk) { const double a = tile[lane][kk]; return (diagonal && kk == lane) ? 2 * a : a; },
                                                        [&](int kk) { return cvec[k0 + kk]; });
                     } else if (wave == 1 && !diagonal && lane < kw) {
-                        part[bj][k0 + lane] = qs_chain(jw, [&](int jj) { return tile[jj][lane]; }, [&](int jj) { return cvec[j0 + jj]; });
+                        part[bj][k0 + lane] = chain(jw, [&](int jj) { return tile[jj][lane]; }, [&](int jj) { return cvec[j0 + jj]; });
                     }
                 }
                 // the quadratic terms: row j holds its columns k >= j; this tile's piece of it, a wave per row segment, 16-byte stores
@@ -211,7 +186,7 @@ __global__ __launch_bounds__(QS_THREADS) void quad_stages_kernel(QsArgs<TERMS> g
                     if (ke <= ks) continue;
                     const int off = ks - k0;
                     const u64w rowvar = (u64w)var[j];
-                    wave_write_words<3>(reinterpret_cast<u64w *>(oq + qs_tri_pos(n, j, ks)), ke - ks, lane, [&](int q) -> u64w {
+                    wave_write_words<3>(reinterpret_cast<u64w *>(oq + tri_pos(n, j, ks)), ke - ks, lane, [&](int q) -> u64w {
                         const int e = q / 3, f = q - 3 * e;
                         if (f == 1) return rowvar;
                         if (f == 2) return (u64w)var[k0 + off + e];
@@ -297,18 +272,6 @@ __global__ __launch_bounds__(QS_THREADS) void quad_stages_const_kernel(QsArgs<TE
     }
 }
 
-static int qs_cu_count() {
-    static int cus[16] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) { (void)hipGetLastError(); return 256; }
-    if (!cus[dev]) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) { (void)hipGetLastError(); v = 256; }
-        cus[dev] = v;
-    }
-    return cus[dev];
-}
-
 // slices [at, at + len) of the stages, sorted by their start, stay inside [0, total) and do not overlap
 static bool qs_slices_ok(std::vector<std::pair<int64_t, int64_t>> &s, int64_t total) {
     std::sort(s.begin(), s.end());
@@ -326,7 +289,7 @@ static int qs_launch(void *stream, const QsArgs<TERMS> &g) {
     return dispatch(stream, [=](hipStream_t s) {
         if (g.T > 0) {
             // three workgroups per CU stay resident (LDS); each walks the stages blockIdx.x, blockIdx.x + G, ..
-            const dim3 grid((unsigned)std::min<int64_t>(g.T, (int64_t)QS_WG_PER_CU * qs_cu_count()));
+            const dim3 grid((unsigned)std::min<int64_t>(g.T, (int64_t)QS_WG_PER_CU * cu_count()));
             PMT_LAUNCH(quad_stages_kernel<TERMS>, grid, dim3(QS_THREADS), 0, s, g);
             const int rc = check_launch("quad_stages_kernel");
             if (rc != PMT_OK) return rc;
