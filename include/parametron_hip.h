@@ -61,7 +61,9 @@ int pmt_device_count(void);
 /* y = A*x (+|-) b as Vector{AffineFunction}: out_terms[row*cols + col] = (A[row,col], xvar[col]),
  * out_consts[row] = 0.0 (+|-) b[row].   sign: +1 vecadd!, -1 vecsubtract!, 0 no vector (b ignored).
  * Replaces matvecmul!(y, A, x::Vector{Variable}) src/functions.jl:775-798 fused with
- * vecadd!/vecsubtract!(dest, y, b) :751-764 (copyto! :422-427, add!/subtract! Number :452,:474). */
+ * vecadd!/vecsubtract!(dest, y, b) :751-764 (copyto! :422-427, add!/subtract! Number :452,:474).
+ * A block of more than 65535 * 64 = 4194240 rows (with columns) is refused with PMT_DIMENSION_MISMATCH, here and in
+ * pmt_affine_pack_vector_f64: the kernel's grid has one block row per 64 rows and does not wrap. */
 int pmt_affine_assemble_f64(const double *A, int64_t lda, int64_t rows, int64_t cols,
                             const int64_t *xvar, const double *b, int sign,
                             pmt_linear_term *out_terms, double *out_consts, void *stream);

@@ -177,6 +177,15 @@ static int validate_affine(const double *A, int64_t lda, int64_t rows, int64_t c
     PMT_REQUIRE(sign == 0 || b || rows == 0, PMT_INVALID_ARGUMENT, "affine: sign != 0 needs b");
     return PMT_OK;
 }
+// The tile kernel's grid has one block row per tile row and does not wrap: 65535 block rows is what the literal term builders launch at
+// most (quad.hip), and nothing larger has been run.  Beyond it (64-row tiles: such a block has 1024 tiles or more) the shape is refused
+// before anything is launched or recorded, instead of leaving it to the launch.
+constexpr int64_t AFFINE_MAX_TILE_ROWS = 65535;
+static int validate_affine_tiles(int64_t rows, int64_t cols) {
+    PMT_REQUIRE(cols == 0 || cdiv(rows, TILE) <= AFFINE_MAX_TILE_ROWS, PMT_DIMENSION_MISMATCH,
+                "affine: more than 65535 * 64 rows in one dense block");
+    return PMT_OK;
+}
 
 // term buffers are write-once streams: non-temporal stores (tuning builds can switch them off with PMT_NONTEMPORAL=0)
 static bool env_nt() {
@@ -268,6 +277,7 @@ extern "C" int pmt_affine_assemble_f64(const double *A, int64_t lda, int64_t row
                                        int sign, pmt_linear_term *out_terms, double *out_consts, void *stream) {
     int rc = validate_affine(A, lda, rows, cols, xvar, b, sign, out_terms);
     if (rc) return rc;
+    if ((rc = validate_affine_tiles(rows, cols))) return rc;
     if (cols == 0 && rows > 0 && out_consts)
         return b && sign ? pmt_consts_f64(b, rows, sign, out_consts, stream)
                          : dispatch(stream, [=](hipStream_t s) { PMT_HIP_CHECK(hipMemsetAsync(out_consts, 0, rows * sizeof(double), s)); return PMT_OK; });
@@ -284,6 +294,7 @@ extern "C" int pmt_affine_pack_vector_f64(const double *A, int64_t lda, int64_t 
                                           double *out_consts, void *stream) {
     int rc = validate_affine(A, lda, rows, cols, xvar, b, sign, out_terms);
     if (rc) return rc;
+    if ((rc = validate_affine_tiles(rows, cols))) return rc;
     if (cols == 0 && rows > 0 && out_consts)
         return b && sign ? pmt_consts_f64(b, rows, sign, out_consts, stream)
                          : dispatch(stream, [=](hipStream_t s) { PMT_HIP_CHECK(hipMemsetAsync(out_consts, 0, rows * sizeof(double), s)); return PMT_OK; });

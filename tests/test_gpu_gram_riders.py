@@ -84,6 +84,8 @@ class Pack:
         self.d_h = d if has_b else None
         self.dd = g.to_dev(d) if has_b else None
         xv = rng.permutation(node.n)[:cols].astype(np.int64) + 1
+        if cols > node.n:                                            # more columns than the node has variables: some of them share one
+            xv = np.concatenate([xv, rng.integers(1, node.n + 1, size=cols - node.n, dtype=np.int64)])
         self.xvar, self.vm = g.to_dev(xv), node.vm
         self.terms = np.zeros(rows * cols, dtype=g.VAT)
         self.terms["out"] = np.repeat(np.arange(rows, dtype=np.int64) + ROW_OFFSET + 1, cols)
@@ -145,6 +147,8 @@ CASES = [
     ("64x128-no-consts", 64, 128, {"has_consts": False}),
     ("1x64-one-tile", 1, 64, {}),                             # fewer tiles than workgroups that run dry
     ("512x1024", 512, 1024, {}),                              # hundreds of tiles: every dry workgroup loops
+    ("66x32726-64-row-tiles-cold", 66, 32726, {}),            # 1024 tiles: 64-row tiles, nontemporal loads, the three-store row pairs
+    ("66x32726-64-row-tiles-cold-odd-lda", 66, 32726, {"pad": 1}),   # ... over the scalar load path
 ]
 
 
