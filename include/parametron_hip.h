@@ -284,7 +284,15 @@ int pmt_quad_gram_deliver_f64(const double *A, int64_t lda, int64_t rows, int64_
  *                       S_d = sum_j v_j^2: 256 chains (chain t adds j = t, t + 256, .. in order), then a halving tree (t += t + 128, t + 64, ..)
  * Block 1 alone with the constant weight +1 (no weight pointer, scale 1.0) touches only the n diagonal terms, lin and the constant;
  * otherwise one 64 x 64 tile of the upper triangle per workgroup rewrites every term (csrc/gram_sum.hip).  Recorded into a plan behind
- * stream-K Gram nodes (whose constant is written at the end of the replay), the constant step is queued behind those constants. */
+ * stream-K Gram nodes (whose constant is written at the end of the replay), the constant step is queued behind those constants.
+ * For a binding author, said plainly:
+ *   - Block 1 is the first PMT_LSQ_BLOCK of the list, at ANY index (lam*dot(x, x) + dot(r, r) puts it second): W_1 is that term's weight, the
+ *     later blocks are the PMT_LSQ_BLOCK terms behind it, and the diagonal / linear / constant terms count wherever they stand, in front of
+ *     it too.  Its `values`, `lin` and `constant` fields are never read.
+ *   - A term that is absent contributes NOTHING: there is no `+ 0.0` for it.  Without a diagonal term no D is added, so a coefficient
+ *     W_1*Q_1[j,j] = -0.0 stays -0.0; lin[j] and the constant likewise take only the terms that exist.
+ *   - Block 1 alone at the constant weight +1 leaves every word it does not name as it is, bit for bit: the off-diagonal coefficients are not
+ *     rewritten (not even multiplied by 1.0) and, without a diagonal term, neither are the diagonal ones. */
 #define PMT_LSQ_BLOCK 1
 #define PMT_LSQ_DIAG 2
 #define PMT_LSQ_LINEAR 3
@@ -307,7 +315,9 @@ int pmt_quad_gram_sum_f64(int64_t cols, const pmt_lsq_term *terms, int nterms, p
  * z = [x; u], pmt_affine_stack_columns_f64).  term_cols[t] (a HOST array of nterms pointers, or NULL for all terms) lists the device
  * positions term t covers: term_ncols[t] strictly increasing positions in 0 .. cols-1, read on the host at call time; NULL (the pointer
  * array or its entry t) means every column.  Blocks and constants cover every column (a list for them is an error).  The vec of a subset
- * term has one entry per listed position (term_ncols[t] entries).  A position a term does not list gets nothing from it (no + 0.0);
+ * term has one entry per listed position (term_ncols[t] entries; a list of 0 positions is allowed: such a term adds nothing to any coefficient,
+ * a diagonal one with v still adds W_d*S_d = W_d*0.0 to the constant).  A position a term does not list gets nothing from it (no + 0.0: a -0.0 there stays -0.0, and in the diagonal-only form of
+ * block 1 alone at weight +1 the diagonal coefficient of a position no diagonal term lists is not rewritten at all);
  * otherwise the order is the one fixed above for pmt_quad_gram_sum_f64, restricted to the listed positions:
  *   D_j = ((2*W_d1) + (2*W_d2)) + .. over the diagonal terms listing j (added only when one does); lin[j] takes the terms listing j in
  *   the order above; S_d is the chain-then-tree sum over the term's own vector.

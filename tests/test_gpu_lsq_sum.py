@@ -16,6 +16,7 @@ from parametron_jl_amd import _lib  # noqa: E402
 from parametron_jl_amd.device import fetch_f64  # noqa: E402
 from parametron_jl_amd.moi import _gram_rows  # noqa: E402
 from oracle import oracle as O  # noqa: E402
+from lsq_sum_util import tree_sumsq  # noqa: E402
 
 DEV = "cuda:0"
 
@@ -30,21 +31,6 @@ def stream():
 
 def bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
-
-
-def tree_sumsq(v):
-    """S = sum_j v_j^2 in the kernel's order: 256 chains (chain t: j = t, t + 256, .. in order), then the halving tree"""
-    red = np.zeros(256)
-    for t in range(256):
-        s = 0.0
-        for x in v[t::256]:
-            s = s + x * x
-        red[t] = s
-    h = 128
-    while h:
-        red[:h] = red[:h] + red[h:2 * h]
-        h >>= 1
-    return red[0]
 
 
 def restate(n, terms):

@@ -16,20 +16,27 @@ import parametron_jl_amd as P  # noqa: E402
 from parametron_jl_amd import _lib  # noqa: E402
 from parametron_jl_amd.device import fetch_f64, fetch_terms  # noqa: E402
 from oracle import oracle as O  # noqa: E402
-from test_gpu_lsq_sum import bits, dptr, stream, tree_sumsq  # noqa: E402
+from lsq_sum_util import tree_sumsq  # noqa: E402
+from sparse_assemble_util import values as special_values  # noqa: E402
+from test_gpu_lsq_sum import bits, dptr, stream  # noqa: E402
 
 DEV = "cuda:0"
 
 
 # ------------------------------------------------------------------ 1. the stacking entry, bit for bit
-@pytest.mark.parametrize("rows", [0, 1, 37, 64, 65, 2049, 4097])
+@pytest.mark.parametrize("rows", [0, 1, 37, 64, 65, 2047, 2048, 2049, 2050, 4097])
 def test_stack_entry_matches_numpy(rows):
+    """(2047, 2048, 2050: the 2048-row chunk edge in both phases.)  The last source column holds the special-value family — both zeros,
+    denormals, the infinities, a NaN with a payload — and is stacked once with each sign: -v flips the sign bit, of a NaN and of a zero too"""
     rng = np.random.default_rng(rows)
-    ldas = (rows + 3, rows + 1 if rows % 2 == 0 else rows, rows + 64)          # odd and even source pitches
-    srcs = [torch.from_numpy(rng.standard_normal(max(lda * 7, 1))).to(DEV) for lda in ldas]
-    cols = [(k, j) for k in range(3) for j in range(7)]
+    ldas = (rows + 3, rows + 1 if rows % 2 == 0 else rows, rows + 64, rows + 2)  # odd and even source pitches
+    hosts = [rng.standard_normal(max(lda * 7, 1)) for lda in ldas[:3]] + [np.full(rows + 2, 7.5)]
+    hosts[3][:rows] = special_values(rows, rows)
+    srcs = [torch.from_numpy(h).to(DEV) for h in hosts]
+    cols = [(k, j) for k in range(3) for j in range(7)] + [(3, 0), (3, 0)]
     perm = rng.permutation(len(cols))
     signs = rng.choice([1, -1], len(cols))
+    signs[perm == 21], signs[perm == 22] = -1, 1
     ncols = len(cols)
     for ldo in (rows + 5, max(rows, 1) + 2):                                    # odd / even destination pitch
         out = torch.full((ldo * ncols + 3,), 7.25, dtype=torch.float64, device=DEV)
@@ -40,9 +47,12 @@ def test_stack_entry_matches_numpy(rows):
         got = out.cpu().numpy()
         assert got[0] == 7.25 and np.all(got[1 + ldo * ncols:] == 7.25)
         hs = [s.cpu().numpy() for s in srcs]
+        for h, was in zip(hs, hosts):
+            assert np.array_equal(bits(h), bits(was)), "a source changed"
         for c, p in enumerate(perm):
             k, j = cols[p]
-            want = signs[c] * hs[k][j * ldas[k]:j * ldas[k] + rows]
+            v = hs[k][j * ldas[k]:j * ldas[k] + rows]
+            want = np.negative(v) if signs[c] < 0 else v
             col = got[1 + c * ldo:1 + (c + 1) * ldo]
             assert np.array_equal(bits(col[:rows]), bits(want)), "column %d" % c
             assert np.all(col[rows:] == 7.25), "padding rows written"
