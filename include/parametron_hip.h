@@ -225,6 +225,17 @@ int pmt_quad_gram_constant_order(int64_t rows, int64_t cols, int *order, int *gr
  * tile of two whole 64-column panels but a workgroup's last IS deferred.  Both 0 for shapes of the other forms.
  * The results do not depend on it (the sums add the same operands level by level); tests use it to know which path they exercise. */
 int pmt_quad_gram_mid_defers(int64_t rows, int64_t cols, int *plan, int *whole_rounds);
+/* Pure host query beside it: does the one-launch form of an undelivered plain call run its first body tiles as STRIPS (gram_mid.hip:
+ * mid_strips)?  *strips: how many — a strip is four consecutive strictly upper tiles of the walk, one WHOLE tile per wave of a workgroup,
+ * so a coefficient of such a tile is ONE chain: the 8-row groups 0, 1, 2, .. of the matrix in MFMA k order (rows 2 k, 2 k + 1 of a group
+ * in contraction slot k), with no wave level and no chunk level; *tiles_in_strips (may be null): 4 * *strips, the first ranks of the walk.
+ * Every other tile, q and c'c are summed as they always were.  Non-zero only where the shape defers with whole rounds
+ * (pmt_quad_gram_mid_defers), cols is a multiple of 64, there are at least 1.5 strips per workgroup AND the plan's cost estimate says
+ * that strips in rounds of one per CU end sooner than single tiles (it says no where the strips would fill the last round badly: 4096 x
+ * 3584 has 384 whole strips and takes none) — a shape that meets the first three conditions may still report 0; the call then runs the strip
+ * build with 16-byte aligned operands and an even pitch (terms only), otherwise the kernels it ran before.  A function of (rows, cols)
+ * alone, as the order is: repeated launches and concurrent streams give the same bits.  Both 0 for shapes of the other forms. */
+int pmt_quad_gram_mid_strips(int64_t rows, int64_t cols, int *strips, int *tiles_in_strips);
 int pmt_quad_gram_f64(const double *A, int64_t lda, int64_t rows, int64_t cols,
                       const int64_t *xvar, const double *b, int sign,
                       int moi, const int64_t *varmap,

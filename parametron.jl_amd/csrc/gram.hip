@@ -519,6 +519,14 @@ extern "C" int pmt_quad_gram_mid_defers(int64_t rows, int64_t cols, int *plan, i
     return PMT_OK;
 }
 
+extern "C" int pmt_quad_gram_mid_strips(int64_t rows, int64_t cols, int *strips, int *tiles_in_strips) {
+    PMT_REQUIRE(rows >= 0 && cols >= 0 && strips, PMT_INVALID_ARGUMENT, "quad_gram_mid_strips: bad argument");
+    int ns = 0, nt = 0;
+    if (gram_form(rows, cols, true, false) == GramForm::Mid) gram_mid_strips(rows, cols, &ns, &nt);
+    *strips = ns; if (tiles_in_strips) *tiles_in_strips = nt;
+    return PMT_OK;
+}
+
 extern "C" size_t pmt_quad_gram_workspace_bytes(int64_t rows, int64_t cols) {
     // The most that a form the shape takes across call kinds (plain or CSC, delivered; a tiny node none) needs, and never less than the
     // stream-K node's need — its partial tiles (which the fused form's strict launch shares), the chunk sums of q, the chains of c'c.

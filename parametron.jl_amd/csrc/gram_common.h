@@ -201,6 +201,7 @@ int launch_gram_tall(const double *A, int64_t lda, int64_t rows, int64_t cols, c
 size_t gram_mid_workspace_bytes(int64_t rows, int64_t cols);
 int gram_mid_counters(int64_t cols);
 bool gram_mid_defers(int64_t rows, int64_t cols, bool *whole_rounds);          // the shape's plan defers tiles (gram_mid.hip: MidWalk)
+bool gram_mid_strips(int64_t rows, int64_t cols, int *strips, int *tiles_in_strips);          // the shape's plan runs its first body tiles as strips, a whole tile per wave (gram_mid.hip: mid_strips)
 int launch_gram_mid(const double *A, int64_t lda, int64_t rows, int64_t cols, const int64_t *xvar, const double *b, int sign, int moi,
                     const int64_t *varmap, pmt_quadratic_term *out_quad, double *out_csc, double alpha, pmt_linear_term *out_lin,
                     double *out_const, void *workspace, unsigned *counters, const void *riders, int nriders, int rider_tiles, hipStream_t s);

@@ -24,6 +24,9 @@
 // added in one of two places — by halving behind the item's loop (mid_tail), or, for a DEFERRED tile of the persistent walk, row by row
 // inside the next item's loop from the four raw partials in LDS (mid_wo_op: (p0 + p2) + (p1 + p3)) — each level the same two operands,
 // so the same bits; pmt_quad_gram_mid_defers tells which shapes defer (profiles/r20_deferred_tile.txt).
+// A tile inside a STRIP (mid_strips; pmt_quad_gram_mid_strips tells which shapes have them and how many of their first body tiles they
+// take — again (rows, cols) alone) is ONE wave's for the whole contraction: a coefficient is ONE chain, the 8-row groups 0, 1, 2, .. of
+// the matrix in MFMA k order, with no wave level and no chunk level.  Every other tile of such a launch, q and c'c are summed as above.
 #include "affine_tile.h"
 #include "gram_common.h"
 
@@ -88,15 +91,36 @@ __device__ __forceinline__ void mid_walk_note(unsigned long long *w, int k, unsi
 }
 #define MID_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x < 1024) { const unsigned long long t_ = wall_clock64(); g_mid_trace[blockIdx.x * 8 + (k)] = t_; \
                           mid_walk_note(reinterpret_cast<unsigned long long *>(sh + MSH_AT), (k), t_); } } while (0)
-extern "C" int pmt_mid_trace_read(unsigned long long *host) {
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_mid_trace), sizeof(unsigned long long) * 1024 * 8) == hipSuccess ? 0 : 1;
-}
-extern "C" int pmt_mid_walk_read(unsigned long long *host) {
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_mid_walk), sizeof(unsigned long long) * 1024 * 8) == hipSuccess ? 0 : 1;
-}
-extern "C" int pmt_mid_riders_read(unsigned long long *host) {
+// (the stamps are per translation unit: the strip build, gram_mid_strips.hip, has its own; the readers overlay the workgroups that
+// build stamped — a traced process launches one shape)
+#ifdef PMT_MID_STRIPS_TU
+extern "C" int pmt_mid_strips_trace_read(int which, unsigned long long *host) {
+    if (which == 0) return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_mid_trace), sizeof(unsigned long long) * 1024 * 8) == hipSuccess ? 0 : 1;
+    if (which == 1) return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_mid_walk), sizeof(unsigned long long) * 1024 * 8) == hipSuccess ? 0 : 1;
     return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_mid_riders), sizeof(unsigned long long) * 1024 * 2) == hipSuccess ? 0 : 1;
 }
+#else
+extern "C" int pmt_mid_strips_trace_read(int which, unsigned long long *host);
+static int mid_trace_overlay(int which, unsigned long long *host, int words, int key) {
+    static unsigned long long other[1024 * 8];
+    if (pmt_mid_strips_trace_read(which, other)) return 1;
+    for (int b = 0; b < 1024; ++b)
+        if (other[b * words + key]) for (int i = 0; i < words; ++i) host[b * words + i] = other[b * words + i];
+    return 0;
+}
+extern "C" int pmt_mid_trace_read(unsigned long long *host) {
+    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_mid_trace), sizeof(unsigned long long) * 1024 * 8) != hipSuccess) return 1;
+    return mid_trace_overlay(0, host, 8, 0);
+}
+extern "C" int pmt_mid_walk_read(unsigned long long *host) {
+    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_mid_walk), sizeof(unsigned long long) * 1024 * 8) != hipSuccess) return 1;
+    return mid_trace_overlay(1, host, 8, 0);
+}
+extern "C" int pmt_mid_riders_read(unsigned long long *host) {
+    if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_mid_riders), sizeof(unsigned long long) * 1024 * 2) != hipSuccess) return 1;
+    return mid_trace_overlay(2, host, 2, 1);
+}
+#endif
 #else
 #define MID_STAMP(k) do { } while (0)
 #define MID_TRACE_WORDS 0
@@ -146,6 +170,7 @@ struct MidArgs {
     int n_off, s_off, s_diag;                // strictly upper tiles, row chunks of one, row chunks of a diagonal tile
     int gpc_off, gpc_diag;                   // 8-row groups per chunk
     int n_tail, s_tail, gpc_tail;            // the LAST n_tail strictly upper tiles (in the order they are walked) in s_tail chunks instead (mid_plan)
+    int n_strips;                            // the FIRST 4 n_strips body tiles of the walk as strips, a whole tile per wave (mid_strips; in the padding the nine ints left: the layout of the others is what it was)
     double *ws;                              // one MSTRIDE slot per workgroup
     unsigned *counters;                      // one per tile, zero between launches (the last arriver re-arms its tile's)
     int xcd;                                 // workgroup ids in the XCD-aware order (gram_mid_kernel)
@@ -404,6 +429,51 @@ __device__ __forceinline__ void mid_wo_run(double *sh, int &q, int wave, int pmo
     }
 }
 
+// The write-out of a pending tile of a STRIP (mid_strips): the tile is ONE wave's — its 64 finished sums per lane lie in the wave's own
+// [a][lane] region, its column variables and row descriptors in the wave's own map area — and the wave writes all 64 rows, MWO_RPS per
+// step, in the order i = (step's rows) >> 4, b, tm: the rows 16 tm + 4 b + i of one step share i and b and with them the lanes' offsets.
+// Per row: the descriptor, ONE partial, doubled, the column's variable, three 8-byte global stores — no sum: nothing was split.
+constexpr int MSO_STEPS = MT / MWO_RPS;            // steps per tile and wave
+constexpr int MSO_ROW_OPS = 8;
+constexpr int MSO_OPS = 2 + MSO_ROW_OPS * MWO_RPS;
+constexpr int MSA = 3 * MT;                        // a wave's map area (u64): the tile's column variables, then its 64 row descriptors (address of the row's first term, row variable)
+static_assert(MSO_OPS <= 16 + 92, "a step's free places: 16 MFMAs of phase 0, 92 of phase 1");
+__device__ __forceinline__ void mid_so_op(int n, MidWo &r, const MidWoAt &at) {          // (at.pmo: the wave's map area)
+    const int i0 = at.q * MWO_RPS, i = i0 >> 4, b = (i0 >> 2) & 3, tm0 = i0 & 3;
+    if (n == 0) {
+        // entry (row, lane) of the tile is accumulator a = 16 tm + 4 (lane >> 4) + (((lane >> 2) - b) & 3) of lane 16 i + 4 b + (lane & 3) (mid_pos)
+        const int lane = mid_fresh_lane();
+        r.rb = at.sh + MDEF + at.wave * MDPART + ((lane >> 4) * 4 + (((lane >> 2) - b) & 3)) * MDP + (lane & 3) + tm0 * 16 * MDP + i * 16 + b * 4;
+        return;
+    }
+    if (n == 1) { r.so = 24u * (unsigned)mid_fresh_lane(); return; }
+    const int e = (n - 2) / MSO_ROW_OPS, o = (n - 2) % MSO_ROW_OPS;
+    const int row = 16 * (tm0 + e) + 4 * b + i;
+    const u64 *area = reinterpret_cast<const u64 *>(at.sh + at.pmo);
+    if (o == 0) { r.dsc[0] = area[MT + 2 * row]; r.dsc[1] = area[MT + 2 * row + 1]; }
+    else if (o == 1) r.p[0] = r.rb[e * 16 * MDP];
+    else if (o == 2) r.m = area[mid_fresh_lane()];
+    else if (o == 3) {
+        const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)r.dsc[0]), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(r.dsc[0] >> 32));
+        r.dst = (u64)hi << 32 | lo;
+    } else if (o == 4) r.p[0] = 2 * r.p[0];
+    else {
+        typedef __attribute__((address_space(1))) u64 gu64;          // (global stores, not flat ones: mid_wo_op)
+        gu64 *d = reinterpret_cast<gu64 *>(r.dst + r.so);
+        if (o == 5) d[0] = (u64)__double_as_longlong(r.p[0]);
+        else if (o == 6) d[1] = r.dsc[1];
+        else d[2] = r.m;
+    }
+}
+__device__ __forceinline__ void mid_so_run(double *sh, int &q, int wave, int pmo) {
+    for (; q < MSO_STEPS; ++q) {
+        MidWo r;
+        const MidWoAt at = {sh, q, wave, pmo};
+#pragma unroll
+        for (int n = 0; n < MSO_OPS; ++n) mid_so_op(n, r, at);
+    }
+}
+
 // One 8-row group AND the loads of the group D further on, as ONE pinned instruction stream (the FAST load path).  The
 // workgroup has one wave per SIMD: whatever is not an MFMA stands in the wave's only issue stream.  mid_compute + mid_load put the 16 LDS
 // operations of a group in one run in front of the MFMAs and its 8 loads (with a 64-bit vector add each: the compiler hoists the zero
@@ -419,8 +489,8 @@ __device__ __forceinline__ void mid_wo_run(double *sh, int &q, int wave, int pmo
 // item; in the round that ends an item of the persistent walk, the bases of the NEXT item's tile (mid_body) — the lane offsets of two
 // whole panels differ by a multiple of the pitch, so the redirect is a scalar select and the stream keeps its instructions.
 // WO: the step also carries one step of a deferred tile's write-out (mid_wo_op), one operation behind each MFMA that has nothing behind it
-// yet — the same 128 MFMAs, 16 LDS operations and 8 loads in the same places.
-template <bool DIAG, bool WO = false>
+// yet — the same 128 MFMAs, 16 LDS operations and 8 loads in the same places.  ST: the pending tile is a strip's (mid_so_op).
+template <bool DIAG, bool WO = false, bool ST = false>
 __device__ __forceinline__ void mid_step(const MidArgs &g, double *__restrict__ rot, int64_t next_row0, const char *base_a, const char *base_b,
                                          unsigned (&voff)[DIAG ? 4 : 8], f64x2 (&buf)[DIAG ? 4 : 8], f64x2 &cb, int sign, int lane,
                                          double (&acc)[MACC], double (&qacc)[4], const MidWoAt &wo = MidWoAt()) {
@@ -455,7 +525,7 @@ __device__ __forceinline__ void mid_step(const MidArgs &g, double *__restrict__ 
                 const int a = (tm * 4 + c) * 4;
                 acc[a] = __builtin_amdgcn_mfma_f64_4x4x4f64(pass ? buf[tm].y : buf[tm].x, pass ? bv[c][0].y : bv[c][0].x, acc[a], 0, 0, 0);
                 if (k < 16) { MID_SB(); lds_op(k); MID_SB(); }
-                else if constexpr (WO) { if (wn < MWO_OPS) { MID_SB(); mid_wo_op(wn, wr, wo); MID_SB(); ++wn; } }
+                else if constexpr (WO) { if (wn < (ST ? MSO_OPS : MWO_OPS)) { MID_SB(); if constexpr (ST) mid_so_op(wn, wr, wo); else mid_wo_op(wn, wr, wo); MID_SB(); ++wn; } }
                 ++k;
             }
     if (DIAG) {
@@ -483,7 +553,7 @@ __device__ __forceinline__ void mid_step(const MidArgs &g, double *__restrict__ 
                     const int a = (tm * 4 + c) * 4 + r;
                     acc[a] = __builtin_amdgcn_mfma_f64_4x4x4f64(pass ? buf[tm].y : buf[tm].x, pass ? bv[c][r].y : bv[c][r].x, acc[a], 0, 0, 0);
                     if (!DIAG && nb < 4) { MID_SB(); reload(4 + nb); MID_SB(); ++nb; }
-                    else if constexpr (WO) { if (wn < MWO_OPS) { MID_SB(); mid_wo_op(wn, wr, wo); MID_SB(); ++wn; } }
+                    else if constexpr (WO) { if (wn < (ST ? MSO_OPS : MWO_OPS)) { MID_SB(); if constexpr (ST) mid_so_op(wn, wr, wo); else mid_wo_op(wn, wr, wo); MID_SB(); ++wn; } }
                 }
         MID_SB();
         reload(tm);
@@ -1042,7 +1112,10 @@ __device__ __forceinline__ void mid_tile_of(int t, int nb, int &jb, int &kb) {
 
 // one work item of the launch: (tile, chunk) number `id`, or the constant's (the last one)
 struct MidItem { int kind, jb, kb, chunk, nch, gpc, first, rank; };          // kind: 0 a strictly upper tile, 1 a diagonal one, 2 the constant
-template <bool COLS>
+// ST (the strip build, behind its strips): the ids 0 .. n_strips - 1 are the strips (mid_strips) and the first 4 n_strips ranks of the walk
+// theirs; the body tiles behind them, the tails, the diagonal chunks and the constant follow in the order they always had, with the
+// workspace slots and counters they always had.
+template <bool COLS, bool ST = false>
 __device__ __forceinline__ MidItem mid_decode(const MidArgs &g, int id) {
     // XCD-aware order: workgroup ids go round-robin over the 8 XCDs (id % 8), each with its own 4 MB L2.  The (chunk, tile) list is walked
     // CHUNK-major and cut into 8 contiguous pieces, one per XCD: the 32 workgroups an XCD runs at a time work on the same rows of A and
@@ -1050,30 +1123,31 @@ __device__ __forceinline__ MidItem mid_decode(const MidArgs &g, int id) {
     // (id = tile * S + chunk) every XCD touched every row chunk of every panel and 4096 x 1024 ran out of the Infinity Cache at 1.76 us per
     // 8-row group instead of 1.15 (profiles/r06_gram_mid.txt).
     MidItem it = {2, 0, 0, 0, 1, 0, 0, 0};
-    const int nbody = g.n_off - g.n_tail, wbody = nbody * g.s_off, noff = wbody + g.n_tail * g.s_tail;
+    const int sb = ST ? g.n_strips : 0;          // (ST: s_off = 1)
+    const int nbody = g.n_off - g.n_tail - 4 * sb, wbody = sb + nbody * g.s_off, noff = wbody + g.n_tail * g.s_tail;
     if (id < noff) {
         // body tiles (ranks 0 .. nbody - 1 of the walk) in s_off chunks, then the tail tiles in s_tail chunks: chunk-major inside each part
         const bool tail = id >= wbody;
-        const int base = tail ? wbody : 0, ntile = tail ? g.n_tail : nbody, nch = tail ? g.s_tail : g.s_off;
+        const int base = tail ? wbody : sb, ntile = tail ? g.n_tail : nbody, nch = tail ? g.s_tail : g.s_off;
         const int k = g.xcd ? mid_xcd_rank(id, base, ntile * nch) : ((id - base) % nch) * ntile + (id - base) / nch;
         const int chunk = k / ntile;
-        const int rank = (tail ? nbody : 0) + (k - chunk * ntile);          // the tile's place in the walk: its workspace slots and its counters
+        const int rank = 4 * sb + (tail ? nbody : 0) + (k - chunk * ntile);          // the tile's place in the walk: its workspace slots and its counters
         int t = rank, jb, kb;
-        if (g.xcd) mid_tile_of<COLS>(t, g.nb, jb, kb);
+        if (g.xcd || ST) mid_tile_of<COLS>(t, g.nb, jb, kb);          // (ST: ONE walk for the strips and the tiles behind them, whatever the order of the ids — mid_strips takes its ranks from mid_tile_of)
         else {
             kb = 1;
             while (t >= kb) { t -= kb; ++kb; }                     // strictly upper tiles, column by column: (0,1), (0,2), (1,2), (0,3), ..
             jb = t;
         }
         it.kind = 0; it.jb = jb; it.kb = kb; it.chunk = chunk; it.nch = nch; it.gpc = tail ? g.gpc_tail : g.gpc_off;
-        it.first = tail ? wbody + (rank - nbody) * g.s_tail : rank * g.s_off;
+        it.first = tail ? wbody + 3 * sb + (rank - 4 * sb - nbody) * g.s_tail : rank * g.s_off;
         it.rank = rank;
         return it;
     }
     if (id < noff + g.nb * g.s_diag) {
         const int k = g.xcd ? mid_xcd_rank(id, noff, g.nb * g.s_diag) : ((id - noff) % g.s_diag) * g.nb + (id - noff) / g.s_diag;
         const int chunk = k / g.nb, jb = k - chunk * g.nb;
-        it.kind = 1; it.jb = jb; it.kb = jb; it.chunk = chunk; it.nch = g.s_diag; it.gpc = g.gpc_diag; it.first = noff + jb * g.s_diag; it.rank = g.n_off + jb;
+        it.kind = 1; it.jb = jb; it.kb = jb; it.chunk = chunk; it.nch = g.s_diag; it.gpc = g.gpc_diag; it.first = noff + 3 * sb + jb * g.s_diag; it.rank = g.n_off + jb;
     }
     return it;
 }
@@ -1089,6 +1163,130 @@ __device__ __forceinline__ void mid_item(const MidArgs &g, double *sh, int tid, 
     if (it.kind == 1) mid_body<true, FAST, DF>(g, sh, tid, it.jb, it.kb, it.chunk, it.nch, it.gpc, it.first, g.counters + it.rank * MCNT, wk, pbuf);
     else mid_constant(g, sh, tid);          // (nothing is pending: the item behind a deferring one is a body tile, MidWalk)
     mid_forget(pbuf);
+}
+
+// The STRIPS of the strip build (gram_mid_kernel<true, true, true>; launch_gram_mid: a shape of many body tiles, profiles/r25_gram_strips.txt).
+// Strip i is the four consecutive ranks 4 i .. 4 i + 3 of the body walk; wave w of the workgroup that draws it owns rank 4 i + w for the
+// WHOLE contraction: all 8-row groups 0, 1, 2, .. through mid_step with its own two scalar bases, its 64 accumulators the finished sums of
+// its tile.  Between two strips of a workgroup no wave reads what another wrote but the ticket:
+//   * the look-ahead of the walk, per wave: the workgroup holds one strip in hand; the last round of a wave's loop loads the first D groups
+//     of ITS tile of that strip (the same lane offsets, both bases shifted); lane 0 of the workgroup draws the ticket behind it in front of
+//     its last round and hands it over through one of two alternating words of LDS at the ONE barrier a strip ends with;
+//   * the deferred write-out, per wave: behind its loop the wave leaves its accumulators in its own [a][lane] region (pitch MDP) and the
+//     tile's column variables and row descriptors in its own map area, and writes the tile inside the first MSO_STEPS / D rounds of its
+//     next loop (mid_so_op), the rest behind that loop where it is shorter — producer and consumer are the same wave, whose LDS operations
+//     execute in order.  The area is written behind the loop, when nothing is pending any more: one area per wave is enough.
+// A workgroup's last strip (the id in hand is no strip) writes its tiles at once: nothing is pending when the function returns, behind a
+// barrier the LDS is the walk's (MidWalk).  Returns the id in hand, the workgroup's first item that is no strip.
+__device__ __forceinline__ int mid_strips(const MidArgs &g, double *sh, int tid, int *slot, unsigned *ticket, int id0, f64x2 (&pbuf)[PMT_MID_D][8]) {
+    constexpr int D = PMT_MID_D;
+    constexpr int MSH_AT = MidLds<true>::SH;
+    (void)MSH_AT;                                                  // (read by the trace build only)
+    asm volatile("" : "+v"(tid));
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lm = lane & 15, lk = lane >> 4;
+    // (stated uniform, as mid_body states its loop bounds: the loops and the rows' addresses stay scalar in every build, the traced one included)
+    const int ns = __builtin_amdgcn_readfirstlane(g.n_strips), ngroups = __builtin_amdgcn_readfirstlane((int)(g.rows >> 3));      // (rows a multiple of 32 D: whole rounds, none ragged)
+    double *rot = sh + wave * 512;
+    const int pmo = MidLds<true>::QW + wave * MSA;
+    static_assert(MidLds<true>::QW + 4 * MSA <= MidLds<true>::SH, "the four waves' map areas lie behind the partials");
+    int id = blockIdx.x;                                           // (the launch has more strips than workgroups)
+    if (tid == 0) slot[0] = id0 + 8 * (int)__hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    int hand = __builtin_amdgcn_readfirstlane(slot[0]), par = 1;
+    int woq = MSO_STEPS;                                           // the pending tile's next write-out step; MSO_STEPS: none pending
+    bool pre = false;                                              // the first D groups are in pbuf already
+    int jb, kb;
+    mid_tile_of<true>(4 * mid_xcd_rank(id, 0, ns) + wave, g.nb, jb, kb);
+    for (;;) {
+        MID_STAMP(0);
+        const bool more = __builtin_amdgcn_readfirstlane((int)(hand < ns)) != 0;          // (the workgroup's: every wave sees the same ticket)
+        woq = __builtin_amdgcn_readfirstlane(woq);
+        int njb = jb, nkb = kb;
+        if (more) mid_tile_of<true>(4 * mid_xcd_rank(hand, 0, ns) + wave, g.nb, njb, nkb);
+        const int64_t cj0 = (int64_t)jb * MT, ck0 = (int64_t)kb * MT;
+        double acc[MACC], qacc[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int a = 0; a < MACC; ++a) acc[a] = 0.0;
+        unsigned voff[8];
+#pragma unroll
+        for (int t = 0; t < 8; ++t) voff[t] = (unsigned)((((t < 4 ? cj0 : ck0) + 16 * (t & 3) + lm) * g.lda + 2 * lk) * 8);          // (whole panels)
+        f64x2 cb[D];
+        if (!pre) {
+#pragma unroll
+            for (int d = 0; d < D; ++d) {
+                __builtin_amdgcn_sched_barrier(0);
+                mid_load<false, true>(g, (int64_t)d * 8, lane, cj0, ck0, voff, pbuf[d], cb[d]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        const int ahead_at = more ? ngroups - D : -1;
+        const int64_t shift_a = more ? ((int64_t)njb * MT - cj0) * g.lda * 8 : 0, shift_b = more ? ((int64_t)nkb * MT - ck0) * g.lda * 8 : 0;
+        int s0 = 0;
+        // the first rounds behind a strip: the same rounds with the wave's pending tile in them, a step per group
+        static_assert(MSO_STEPS % D == 0, "whole rounds of write-out steps");
+        for (; s0 + D <= ngroups && woq < MSO_STEPS; s0 += D, woq += D) {
+            const bool ahead = s0 == ahead_at;
+#pragma unroll
+            for (int d = 0; d < D; ++d) {
+                const int64_t row = ahead ? (int64_t)d * 8 : (int64_t)min(s0 + d + D, ngroups - 1) * 8;
+                const char *base = reinterpret_cast<const char *>(g.A + row);
+                const MidWoAt at = {sh, woq + d, wave, pmo};
+                mid_step<false, true, true>(g, rot, row, base + (ahead ? shift_a : 0), base + (ahead ? shift_b : 0), voff, pbuf[d], cb[d], g.sign, lane, acc, qacc, at);
+            }
+        }
+        // the steady rounds; the last one of a strip with another in hand stands behind the loop, the ticket's draw in front of it (mid_body)
+        const bool late = more && s0 + D <= ngroups;
+        for (; s0 + D <= ngroups - (late ? D : 0); s0 += D) {
+#pragma unroll
+            for (int d = 0; d < D; ++d) {
+                const int64_t row = (int64_t)min(s0 + d + D, ngroups - 1) * 8;
+                const char *base = reinterpret_cast<const char *>(g.A + row);
+                mid_step<false>(g, rot, row, base, base, voff, pbuf[d], cb[d], g.sign, lane, acc, qacc);
+            }
+        }
+        unsigned drawn = 0;
+        if (late) {
+            if (tid == 0) drawn = __builtin_amdgcn_atomic_inc32(ticket, ~0u, __ATOMIC_RELAXED, "agent");
+#pragma unroll
+            for (int d = 0; d < D; ++d) {
+                const char *base = reinterpret_cast<const char *>(g.A + (int64_t)d * 8);
+                mid_step<false>(g, rot, (int64_t)d * 8, base + shift_a, base + shift_b, voff, pbuf[d], cb[d], g.sign, lane, acc, qacc);
+            }
+        } else if (more && tid == 0) drawn = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        MID_STAMP(1);
+        // what the rounds did not take of the tile before this one goes out first; then this tile takes the region and the area
+        mid_so_run(sh, woq, wave, pmo);
+        double *mine = sh + MDEF + wave * MDPART + lane;
+#pragma unroll
+        for (int a = 0; a < MACC; ++a) mine[a * MDP] = acc[a];
+        {
+            u64 *area = reinterpret_cast<u64 *>(sh + pmo);
+            const int64_t n = g.cols, j = cj0 + lane;
+            const int64_t vc = g.xvar[ck0 + lane], vr = g.xvar[j];
+            area[lane] = (u64)(g.moi ? map_var(g.varmap, vc) : vc);
+            area[MT + 2 * lane] = (u64)(reinterpret_cast<u64 *>(g.out_quad) + (u64)(j * n - (j * (j - 1)) / 2 + (ck0 - j)) * 3);
+            area[MT + 2 * lane + 1] = (u64)(g.moi ? map_var(g.varmap, vr) : vr);
+        }
+        // (the wave reads back what its other lanes wrote: its LDS operations execute in order; nothing moves across this point)
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        woq = 0;
+        if (!more) {
+            mid_so_run(sh, woq, wave, pmo);
+#ifdef PMT_MID_TRACE
+            __builtin_amdgcn_s_waitcnt(0);
+            MID_STAMP(6);
+#endif
+            return hand;
+        }
+        if (tid == 0) slot[par] = id0 + 8 * (int)drawn;
+        __syncthreads();                                           // the strip's one barrier: the ticket
+        id = hand; hand = __builtin_amdgcn_readfirstlane(slot[par]); par ^= 1;
+        jb = njb; kb = nkb; pre = true;
+        MID_STAMP(5);
+    }
 }
 
 // One tile of a RIDER: a dense MOI constraint pack recorded beside the node (plan.hip) whose tiles the persistent workgroups draw from
@@ -1129,8 +1327,10 @@ static_assert(TILE * PITCH + TILE <= MQBUF, "a rider's tile and its variable-map
 // tile run inside the first rounds of the next item's loop instead of behind its own.
 // A workgroup whose ticket has run dry then draws RIDER tiles (mid_rider_tile) until those are exhausted too, and leaves: Gram items
 // always come first; the launch of one workgroup per item takes no riders.
-template <bool FAST, bool DF>
+// ST (with FAST and DF): the launch's first g.n_strips items are STRIPS (mid_strips); behind them the walk above, as the deferring build runs it.
+template <bool FAST, bool DF, bool ST = false>
 __global__ __launch_bounds__(256, PMT_MID_WPS) void gram_mid_kernel(MidArgs g) {
+    static_assert(!ST || (FAST && DF), "strips: the fast load path, in the LDS of the deferring build");
     constexpr int MSH_AT = MidLds<DF>::SH;
     __shared__ double sh[MSH_AT + MID_TRACE_WORDS];
     __shared__ int next_id, ahead_id;
@@ -1143,20 +1343,29 @@ __global__ __launch_bounds__(256, PMT_MID_WPS) void gram_mid_kernel(MidArgs g) {
     MidWalk wk = {};
     wk.ticket = g.tickets + x; wk.id0 = x + 8 * per; wk.slot = &ahead_id;
     if constexpr (DF) wk.woq = MWO_STEPS;
-    const int wbody = (g.n_off - g.n_tail) * g.s_off;
-    const bool look = FAST && g.persist && g.s_off == 1;
+    const int wbody = ST ? g.n_off - g.n_tail - 3 * g.n_strips : (g.n_off - g.n_tail) * g.s_off;
+    bool look = FAST && g.persist && g.s_off == 1;
     int id = blockIdx.x, hand = -1;                                // `hand`: the id behind `id`, once drawn
+    if constexpr (ST) {
+        // the strips first; behind them the workgroup draws on demand (few body tiles are left, if any: nothing to look ahead for)
+        __shared__ int strip_slot[2];
+        id = mid_strips(g, sh, tid, strip_slot, wk.ticket, wk.id0, pbuf);
+        mid_forget(pbuf);
+        look = false;
+        __syncthreads();                                           // every wave has written its last tile: the LDS is the walk's
+    }
     if (look) {
         if (tid == 0) next_id = wk.id0 + 8 * (int)__hip_atomic_fetch_add(wk.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __syncthreads();
         hand = next_id;
     }
-    MidItem cur = mid_decode<DF>(g, id);
+    MidItem cur = mid_decode<DF, ST>(g, id);
     for (;;) {
+        if constexpr (ST) { if (id >= g.total) break; }            // (a workgroup whose XCD has nothing behind its strips)
         wk.early = hand >= 0 && hand < wbody;                      // (ids ascend: id is a body item as well; s_off = 1: both are unsplit)
         wk.next_full = false;
         if (wk.early) {
-            const MidItem nx = mid_decode<DF>(g, hand);
+            const MidItem nx = mid_decode<DF, ST>(g, hand);
             wk.next_full = (int64_t)(nx.kb + 1) * MT <= g.cols;
             wk.njb = nx.jb; wk.nkb = nx.kb; wk.nrank = nx.rank;
         }
@@ -1175,7 +1384,7 @@ __global__ __launch_bounds__(256, PMT_MID_WPS) void gram_mid_kernel(MidArgs g) {
             id = next_id;
         }
         if (id >= g.total) break;
-        cur = mid_decode<DF>(g, id);
+        cur = mid_decode<DF, ST>(g, id);
     }
     // (nothing is pending here, MidWalk: a workgroup's last body item does not defer — the riders and the end of the walk need no write-out)
     if (g.rider_tiles > 0) {
@@ -1212,6 +1421,16 @@ __global__ __launch_bounds__(256, PMT_MID_WPS) void gram_mid_kernel(MidArgs g) {
     }
 }
 
+// The STRIP build is instantiated in a translation unit of its own, gram_mid_strips.hip, which is this file without its host part: with
+// the third build beside it the compiler re-associates address arithmetic in <true, true, false> (21 instructions more), and the builds
+// without strips are to stay the kernels they were, instruction for instruction (tools/isa_diff.py; profiles/r25_gram_strips.txt).
+int launch_gram_mid_strips(const MidArgs &g, unsigned grid, hipStream_t s);
+#ifdef PMT_MID_STRIPS_TU
+int launch_gram_mid_strips(const MidArgs &g, unsigned grid, hipStream_t s) {
+    PMT_LAUNCH_NAMED("gram_mid_kernel", (gram_mid_kernel<true, true, true>), dim3(grid), dim3(256), 0, s, g);
+    return check_launch("gram_mid_kernel");
+}
+#else
 // c'c alone, in the same order 5 (the staged host delivery of a shape the one-launch form otherwise takes: gram.hip)
 __global__ __launch_bounds__(256) void gram_mid_constant_kernel(MidArgs g) {
     __shared__ double sh[8];
@@ -1245,6 +1464,33 @@ bool gram_mid_defers(int64_t rows, int64_t cols, bool *whole_rounds) {
     if (whole_rounds) *whole_rounds = can && mid_rows_defer(rows);
     return can;
 }
+// How many of the body tiles go in STRIPS (mid_strips), from (rows, cols) alone: 0, or all whole strips from the front of the walk — the
+// tiles left over (at most three), the tails, the diagonal chunks and the constant stay the items they were, behind the strips in the
+// ticket order, so the end of the launch keeps its fine-grained work.  A shape takes them where tiles would be deferred with whole rounds
+// on every wave, every panel is whole, there are at least 1.5 strips per workgroup (with one nothing is ever pending; up to 4096 columns
+// that leaves no room for a smaller count of whole rounds of strips: 2016 body tiles are 1.97 rounds) — and where the estimate says so,
+// in the style of mid_plan: a strip is four tile times and ~2 us, a tile of its own a tile time and ~5 us (3.5 beside its loop, 1.5 in
+// the write-out rounds: profiles/r20_deferred_tile.txt); strips run in rounds of PMT_MID_G, the rest fills the CUs evenly.  Config 2:
+// 504 strips, 994 us against 1029 for single tiles by this estimate (measured: -22 us per step, profiles/r25_gram_strips.txt); 4096 x 3584
+// (384 strips: half of the CUs idle for a whole strip) stays as it is.
+static int mid_plan_strips(const MidPlan &p, int64_t rows, int64_t cols) {
+    if (!mid_plan_defers(p) || !mid_rows_defer(rows) || cols % MT) return 0;
+    const int nbody = p.n_off - p.n_tail, ns = nbody / 4;
+    if (2 * ns < 3 * PMT_MID_G) return 0;
+    const double tile_us = PMT_MID_TAIL_US * (double)cdiv(cdiv(rows, 8), 4);
+    const double chunk_us = PMT_MID_TAIL_US * 0.69 * (double)cdiv(p.gpc_diag, 4) + 5.0 + (p.s_diag > 1 ? 1.0 : 0.0);
+    const double rest_us = (double)p.n_tail * p.s_tail * (PMT_MID_TAIL_US * (double)cdiv(p.gpc_tail, 4) + 6.0) + (double)p.nb * p.s_diag * chunk_us;
+    const double strip_us = 4.0 * tile_us + 2.0, item_us = tile_us + 5.0;
+    const double t_strips = std::max((double)cdiv(ns, PMT_MID_G) * strip_us, ((double)ns * strip_us + (double)(nbody - 4 * ns) * item_us + rest_us) / PMT_MID_G);
+    const double t_items = ((double)nbody * item_us + rest_us) / PMT_MID_G;
+    return t_strips < t_items ? ns : 0;
+}
+bool gram_mid_strips(int64_t rows, int64_t cols, int *strips, int *tiles_in_strips) {
+    const int ns = cols > 0 && rows > 0 ? mid_plan_strips(mid_plan(rows, cols), rows, cols) : 0;
+    if (strips) *strips = ns;
+    if (tiles_in_strips) *tiles_in_strips = 4 * ns;
+    return ns > 0;
+}
 int gram_mid_counters(int64_t cols) { const int nb = (int)cdiv(cols, MT); return MCNT * (nb * (nb + 1) / 2) + 16; }      // (+ the tickets)
 
 // the whole node in one launch; `counters`: gram_mid_counters(cols) zeroed words owned by the calling stream (streams.h: SideStream)
@@ -1272,11 +1518,16 @@ int launch_gram_mid(const double *A, int64_t lda, int64_t rows, int64_t cols, co
     const unsigned grid = g.persist ? (unsigned)PMT_MID_G : (unsigned)p.wgs;
     // the deferring form where tiles will be deferred (gram_mid_defers + what the call adds: the fast load path, terms and nothing else)
     const bool df = fast && mid_plan_defers(p) && mid_rows_defer(rows) && out_quad && !out_csc;
+    // ... and the strip build where the shape's plan has strips (gram_mid_strips): its ids are the strips, then the items that are left
+    g.n_strips = df ? mid_plan_strips(p, rows, cols) : 0;
+    g.total = p.wgs - 3 * g.n_strips;
     // (instantiated in this order, the builds without deferred tiles are kernels 1 and 2 of the file as in the parent: tools/isa_diff.py)
     if (fast && !df) PMT_LAUNCH_NAMED("gram_mid_kernel", (gram_mid_kernel<true, false>), dim3(grid), dim3(256), 0, s, g);
     else if (!fast) PMT_LAUNCH_NAMED("gram_mid_kernel", (gram_mid_kernel<false, false>), dim3(grid), dim3(256), 0, s, g);
-    else PMT_LAUNCH_NAMED("gram_mid_kernel", (gram_mid_kernel<true, true>), dim3(grid), dim3(256), 0, s, g);
+    else if (!g.n_strips) PMT_LAUNCH_NAMED("gram_mid_kernel", (gram_mid_kernel<true, true>), dim3(grid), dim3(256), 0, s, g);
+    else return launch_gram_mid_strips(g, grid, s);
     return check_launch("gram_mid_kernel");
 }
+#endif          // PMT_MID_STRIPS_TU
 
 }  // namespace pmt
