@@ -10,6 +10,7 @@ import ctypes as C
 
 import numpy as np
 
+from . import _lib
 from ._lib import LT, QT, VAT, ArgumentError, DimensionMismatch, ErrorException
 from .device import DAff, DAffVec, DDenseAff, DQuad, DSparseAff, DStackedAff, DVarsAff, P
 from .functions import AffineFunction, LinearTerm, QuadraticFunction, QuadraticTerm, Variable, _isnum
@@ -161,10 +162,24 @@ def _gram_rows(gram):
     return padded
 
 
+def _buf(x):                                                              # the address of a device value, None for none
+    return x.buf if x is not None else None
+
+
+def _vec_sign(vec, sign):                                                 # (address, sign) of the vector in (+|-) vec; none: (None, 0)
+    b = _buf(vec)
+    return b, sign if b else 0
+
+
+def _table(ctx, arr):                                                     # a ctypes table in a device buffer of its own; the context keeps a
+    # view of `arr` (no copy) for the upload: it is not to be written afterwards
+    return ctx.upload_new(np.frombuffer(arr, dtype=np.uint8))
+
+
 def _gram_args(g):
     """the leading arguments of the Gram family: r = mat*x (+|-) vec"""
-    vec = g.vec.buf if g.vec is not None else None
-    return (P(g.mat.buf), g.mat.lda, _gram_rows(g), g.mat.cols, P(g.xvars.buf), P(vec), g.sign if vec else 0)
+    vec, sign = _vec_sign(g.vec, g.sign)
+    return (P(g.mat.buf), g.mat.lda, _gram_rows(g), g.mat.cols, P(g.xvars.buf), P(vec), sign)
 
 
 def _gram_workspace(ctx, g):
@@ -188,6 +203,56 @@ def _form_call(c, q, varmap_buf, alpha, outs, ws):
 def _form_workspace(ctx, q):
     """the partial sums of a shifted form's linear part (allocated at compile: update! allocates nothing); a plain form has none"""
     return ctx.alloc(max(16, int(ctx.lib.pmt_quad_form_shift_workspace_bytes(q.mat.cols)))) if q.vec is not None else None
+
+
+def _sparse_gram_call(c, r, T, varmap_buf, dq, dl, dc):                    # the sparse Gram node's call (moi = 1); T: r.gram_tables()
+    vec, sign = _vec_sign(r.vec, r.sign)
+    c.call("pmt_sparse_gram_f64", P(r.spmat.buf), *T.call_args(r.rows), P(r.xvars.buf), P(vec), sign, 1, P(varmap_buf), P(dq), P(dl), P(dc))
+
+
+def _sparse_form_call(c, q, T, varmap_buf, dq, dc):                        # the sparse form node's call (moi = 1); T: q.form_tables()
+    c.call("pmt_sparse_form_f64", P(q.spmat.buf), *T.call_args(), P(q.xvars.buf), 1, P(varmap_buf), P(dq), P(dc))
+
+
+def _static_indices(f, T, xvars, handoff_varmap):
+    """The index fields of a sparse record's terms (T.pair_j, pair_k, lin_col: their columns of x) are static: written into f's host arrays
+    at compile, through the hand-off's map, where its generic route finds them before the first update; the kernels rewrite them."""
+    x = xvars.vars if handoff_varmap is None else np.asarray(handoff_varmap, dtype=np.int64)[xvars.vars - 1]
+    f.quadratic_terms["row"], f.quadratic_terms["col"], f.quadratic_terms["coeff"] = x[T.pair_j], x[T.pair_k], 0.0
+    f.affine_terms["var"], f.affine_terms["coeff"] = x[T.lin_col], 0.0
+
+
+def _part_of(v, x):
+    """The subset rule of the weighted sums, for the variables `v` of a diagonal / linear term and the record's strictly increasing `x`,
+    read by the decision (_lsq_sum_combines, _sparse_sum_combines) and the execution (_term_positions) alike: None when v is x itself,
+    the int64 positions of v in x when v is a non-empty strictly increasing part of x, False when it is neither (the sum is refused)."""
+    if np.array_equal(v, x):
+        return None
+    pos = np.searchsorted(x, v).astype(np.int64)
+    if len(v) and np.all(np.diff(v) > 0) and np.all(pos < len(x)) and np.array_equal(x[np.minimum(pos, len(x) - 1)], v):
+        return pos
+    return False
+
+
+def _term_positions(terms, x):                                            # _part_of per term; None also for a term without variables
+    lists = [_part_of(t.xvars.vars, x) if t.kind in ("diag", "linear") else None for t in terms]
+    if any(p is False for p in lists):                                    # (the plan's predicate refuses such a list: quad_plan)
+        raise ArgumentError("a term of the sum lies over variables that are no strictly increasing part of x")
+    return lists
+
+
+def _lsq_desc(t):
+    """What the descriptors of the dense and the sparse combine (pmt_lsq_term, pmt_sparse_lsq_term) share for the LsqTerm t: kind (a form
+    stands where a block stands), scale, weight, a diagonal term's vector and sign, a linear term's vector, a constant's value."""
+    kind = {"block": _lib.PMT_LSQ_BLOCK, "form": _lib.PMT_LSQ_BLOCK, "diag": _lib.PMT_LSQ_DIAG, "linear": _lib.PMT_LSQ_LINEAR,
+            "constant": _lib.PMT_LSQ_CONSTANT}
+    d = {"kind": kind[t.kind], "scale": t.scale, "weight": _buf(t.param)}
+    if t.kind in ("diag", "linear"):
+        d["vec"], sign = _vec_sign(t.vec, t.sign)
+        d["sign"] = sign if t.kind == "diag" else 0
+    elif t.kind == "constant":
+        d["vec"] = _buf(t.value)
+    return d
 
 
 class _Record:
@@ -227,7 +292,7 @@ class _Record:
         self.side_lane_ok = False                                         # _implicit_twins, _compile_static: reads Parameter values only, writes its own buffers
         self.on_side_lane = False                                         # Model._record_tape, before the emitter runs
         self.terms_static = False                                         # _compile_static: the terms are host data, only the constants are rebuilt
-        self.groups_ordered = None                                        # _compile_groups: every group is one slice of the destination
+        self.groups_ordered = None                                        # _compile_layout: every group / stage is one slice of the destination
         self._sub_args = []                                               # _lsq_sum_emitter: host arrays a recorded combine reads
         self._fetch_recorded = False                                      # record_fetch: the copies are entries of the tape
 
@@ -267,6 +332,32 @@ class _Record:
         the tape — a node of the one launch — instead of a D2H copy behind every replay (a hipMemcpyAsync of 8 bytes is ~5 us of host time)"""
         return self._cbuf.ctypes.data if self.model._small else out.const
 
+    def _quad_buffers(self, ctx, nl, nq, twin, lin=True, floor=0):
+        """self.f: the ScalarQuadraticFunction of nl linear and nq quadratic terms; self.dev: its device buffers {"quad", "lin", "const"},
+        returned as (dq, dl, dc).  `twin`: they are _twin's — the record's kernels can write a small model's page-locked host arrays —,
+        otherwise plain device buffers (the forms and combines of models beyond the small plan).  `lin` False: no linear terms, neither
+        buffer nor key.  `floor` 1: room for one term at least, as canonical-sum has always asked (quad_plan does not keep its x from being
+        empty); forms, groups and stages ask for exactly their terms, as before — pmt_plan_alloc hands out no empty buffer either way."""
+        self.f = f = ScalarQuadraticFunction(nl, nq, alloc=ctx.pinned_array)
+        if twin:
+            dq, dl, dc = self._twin(ctx, f.quadratic_terms, 24 * nq), self._twin(ctx, f.affine_terms, 16 * nl), self._twin(ctx, self._cbuf, 8)
+        else:
+            dq = ctx.alloc(24 * max(nq, floor))
+            dl = ctx.alloc(16 * max(nl, floor)) if lin else None
+            dc = ctx.alloc(8)
+        self.dev = {"quad": dq, "lin": dl, "const": dc} if lin else {"quad": dq, "const": dc}
+        return dq, dl, dc
+
+    def _csc_buffers(self, ctx, xvars, handoff_varmap, floor=0):
+        """A record over x = `xvars` whose hand-off takes the CSC values of P (x keeps its order under its index map): self.f without
+        quadratic terms, self.dev with "P_values" / "P_vars" / "lin" / "const"; returns (dp, dl, dc, alpha), alpha -1.0 for Maximize;
+        `floor`: as in _quad_buffers (1: the Gram node's)."""
+        n = len(xvars.vars)
+        self.f = ScalarQuadraticFunction(n, 0, alloc=ctx.pinned_array)
+        dp, dl, dc = ctx.alloc(8 * max(n * (n + 1) // 2, floor)), ctx.alloc(16 * max(n, floor)), ctx.alloc(8)
+        self.dev = {"P_values": dp, "P_vars": handoff_varmap[xvars.vars - 1], "lin": dl, "const": dc}
+        return dp, dl, dc, -1.0 if self.model.sense == "Maximize" else 1.0
+
     def _compile_affine(self, ctx, varmap_buf, handoff_varmap):
         out, zero_copy = self.expr.out, self.model._small
         n = out.nterms
@@ -285,7 +376,7 @@ class _Record:
         out.materialize()
         self.f = ScalarQuadraticFunction(out.nl, out.nq, alloc=ctx.pinned_array)
         dq, dl = self._twin(ctx, self.f.quadratic_terms, 24 * out.nq), self._twin(ctx, self.f.affine_terms, 16 * out.nl)
-        dconst = self._const_twin(out)
+        dconst = self._const_twin(out)                                    # (the word the expression's node writes: no buffer of the record's)
         self.dev = {"quad": dq, "lin": dl, "const": dconst}
 
         def emit(c):
@@ -301,13 +392,9 @@ class _Record:
         gram = self.plan.gram
         n = gram.mat.cols
         nq = n * (n + 1) // 2
-        csc = self.plan.mode == "canonical-csc"
-        self.f = f = ScalarQuadraticFunction(n, 0 if csc else nq, alloc=ctx.pinned_array)
         ws = _gram_workspace(ctx, gram)
-        if csc:
-            dp, dl, dc = ctx.alloc(8 * max(nq, 1)), ctx.alloc(16 * max(n, 1)), ctx.alloc(8)
-            self.dev = {"P_values": dp, "P_vars": handoff_varmap[gram.xvars.vars - 1], "lin": dl, "const": dc}
-            alpha = -1.0 if self.model.sense == "Maximize" else 1.0
+        if self.plan.mode == "canonical-csc":
+            dp, dl, dc, alpha = self._csc_buffers(ctx, gram.xvars, handoff_varmap, floor=1)
             if not (self.model.handoff == "host_csc" and self.model._overlap_fetch):
                 return lambda c: c.call("pmt_quad_gram_csc_f64", *_gram_args(gram), P(varmap_buf), alpha, P(dp), None, P(dl), P(dc), P(ws))
             # host solver hand-off: the contraction finishes P column band by column band and every finished group of bands leaves
@@ -315,8 +402,7 @@ class _Record:
             host_P = self.dev["P_host"] = ctx.pinned_array(max(nq, 1), np.float64)
             return lambda c: c.call("pmt_quad_gram_csc_deliver_f64", *_gram_args(gram), P(varmap_buf), alpha, P(dp),
                                     host_P.ctypes.data_as(C.c_void_p), 0, P(dl), P(dc), P(ws))
-        dq, dl, dc = self._twin(ctx, f.quadratic_terms, 24 * nq), self._twin(ctx, f.affine_terms, 16 * n), self._twin(ctx, self._cbuf, 8)
-        self.dev = {"quad": dq, "lin": dl, "const": dc}
+        (dq, dl, dc), f = self._quad_buffers(ctx, n, nq, twin=True), self.f
         if not (self.model._overlap_moi and nq > 0):
             return lambda c: c.call("pmt_quad_gram_f64", *_gram_args(gram), 1, P(varmap_buf), P(dq), P(dl), P(dc), P(ws))
         # the quadratic terms leave for f.quadratic_terms (page-locked) row band by row band while the contraction runs
@@ -333,19 +419,12 @@ class _Record:
         n = form.mat.cols
         nq = n * (n + 1) // 2
         if form.vec is not None:
-            self.f = ScalarQuadraticFunction(n, nq, alloc=ctx.pinned_array)
-            dq, dl, dc, ws = ctx.alloc(24 * nq), ctx.alloc(16 * n), ctx.alloc(8), _form_workspace(ctx, form)
-            self.dev = {"quad": dq, "lin": dl, "const": dc}
+            (dq, dl, dc), ws = self._quad_buffers(ctx, n, nq, twin=False), _form_workspace(ctx, form)
             return lambda c: _form_call(c, form, varmap_buf, 1.0, (P(dq), None, P(dl), P(dc)), ws)
         if handoff_varmap is not None:
-            self.f = ScalarQuadraticFunction(n, 0, alloc=ctx.pinned_array)
-            dp, dl, dc = ctx.alloc(8 * nq), ctx.alloc(16 * n), ctx.alloc(8)
-            self.dev = {"P_values": dp, "P_vars": handoff_varmap[form.xvars.vars - 1], "lin": dl, "const": dc}
-            alpha = -1.0 if self.model.sense == "Maximize" else 1.0
+            dp, dl, dc, alpha = self._csc_buffers(ctx, form.xvars, handoff_varmap)
             return lambda c: c.call("pmt_quad_form_f64", *_form_args(form, varmap_buf, alpha), None, P(dp), P(dl), P(dc))
-        self.f = ScalarQuadraticFunction(0, nq, alloc=ctx.pinned_array)
-        dq, dc = ctx.alloc(24 * nq), ctx.alloc(8)
-        self.dev = {"quad": dq, "const": dc}                              # (no "lin": a bare form has no linear terms)
+        dq, _, dc = self._quad_buffers(ctx, 0, nq, twin=False, lin=False)     # (no "lin": a bare form has no linear terms)
         return lambda c: c.call("pmt_quad_form_f64", *_form_args(form, varmap_buf, 1.0), P(dq), None, None, P(dc))
 
     def _compile_lsq_sum(self, ctx, varmap_buf, handoff_varmap):
@@ -355,16 +434,11 @@ class _Record:
         (its linear terms and constant are zero).  The terms are final only after the combine: no overlapped delivery of the quadratic terms."""
         terms = self.plan.terms
         n = [t for t in terms if t.kind in ("block", "form")][0].r.mat.cols
-        nq = n * (n + 1) // 2
-        self.f = ScalarQuadraticFunction(n, nq, alloc=ctx.pinned_array)
-        dq, dl, dc = ctx.alloc(24 * max(nq, 1)), ctx.alloc(16 * max(n, 1)), ctx.alloc(8)
-        self.dev = {"quad": dq, "lin": dl, "const": dc}
-        return self._lsq_sum_emitter(ctx, varmap_buf, terms, dq, dl, dc)
+        return self._lsq_sum_emitter(ctx, varmap_buf, terms, *self._quad_buffers(ctx, n, n * (n + 1) // 2, twin=False, floor=1))
 
     def _lsq_sum_emitter(self, ctx, varmap_buf, terms, dq, dl, dc):
         """The steps of _compile_lsq_sum for the term list `terms`, writing the function into the device buffers dq / dl / dc (addresses;
         n(n+1)/2 quadratic terms, n linear terms, the constant) — the whole objective's, or one group's part of it (_compile_groups)."""
-        from . import _lib
         blocks = [t for t in terms if t.kind in ("block", "form")]
         g1 = blocks[0].r
         n = g1.mat.cols
@@ -372,28 +446,12 @@ class _Record:
         ws = [_gram_workspace(ctx, t.r) if t.kind == "block" else _form_workspace(ctx, t.r) for t in blocks]
         # per block 2..K: its CSC values, linear terms and constant
         parts = [(ctx.alloc(8 * max(nq, 1)), ctx.alloc(16 * max(n, 1)), ctx.alloc(8)) for _ in blocks[1:]]
-        desc, k = [], 0
-        for t in terms:
-            d = {"kind": {"block": _lib.PMT_LSQ_BLOCK, "form": _lib.PMT_LSQ_BLOCK, "diag": _lib.PMT_LSQ_DIAG, "linear": _lib.PMT_LSQ_LINEAR,
-                          "constant": _lib.PMT_LSQ_CONSTANT}[t.kind],
-                 "scale": t.scale, "weight": t.param.buf if t.param is not None else None}
-            if t.kind in ("block", "form"):
-                if k > 0:
-                    d["values"], d["lin"], d["constant"] = parts[k - 1]
-                k += 1
-            elif t.kind == "diag":
-                d["vec"] = t.vec.buf if t.vec is not None else None
-                d["sign"] = t.sign if t.vec is not None else 0
-            elif t.kind == "linear":
-                d["vec"] = t.vec.buf
-            elif t.value is not None:
-                d["vec"] = t.value.buf
-            desc.append(d)
+        desc = [_lsq_desc(t) for t in terms]
+        for d, part in zip([d for t, d in zip(terms, desc) if t.kind in ("block", "form")][1:], parts):
+            d["values"], d["lin"], d["constant"] = part
         arr = _lib.lsq_terms(desc)
         # diagonal / linear terms over part of x: their positions in x (pmt_quad_gram_sum_sub_f64); over all of x: the plain combine
-        x = g1.xvars.vars
-        lists = [np.searchsorted(x, t.xvars.vars).astype(np.int64) if t.kind in ("diag", "linear") and not np.array_equal(t.xvars.vars, x) else None
-                 for t in terms]
+        lists = _term_positions(terms, g1.xvars.vars)
         sub = any(p is not None for p in lists)
         if sub:
             ptrs = (C.c_void_p * len(lists))(*[p.ctypes.data if p is not None else None for p in lists])
@@ -420,191 +478,142 @@ class _Record:
                 c.call("pmt_quad_gram_sum_f64", n, C.addressof(arr), len(desc), P(dq), P(dl), P(dc))
         return emit
 
-    def _compile_groups(self, ctx, varmap_buf, handoff_varmap):
-        """The objective as a sum over groups of blocks / forms with pairwise disjoint Variable vectors (plan.groups): every group is written
-        by the steps of its own canonical-sum list (_lsq_sum_emitter) — straight into its slice of the MOI buffers when the groups' variables
-        are consecutive in the sorted union z (pointer + offset: no copy, no extra pass), into an arena otherwise, from where
-        pmt_quad_groups_gather_f64 places the rows through tables built here.  pmt_quad_groups_constant_f64 adds the groups' constants.
-        As in canonical-sum the terms are final only after the last step: no overlapped delivery of the quadratic terms."""
-        from . import _lib
-        groups = self.plan.groups
-        lay = _lib.GroupsLayout([g.vars for g in groups])
-        G, n, nq = len(groups), lay.nlin, lay.nterms
-        self.f = ScalarQuadraticFunction(n, nq, alloc=ctx.pinned_array)
-        dq, dl, dc, consts = ctx.alloc(24 * nq), ctx.alloc(16 * n), ctx.alloc(8), ctx.alloc(8 * G)
-        self.dev = {"quad": dq, "lin": dl, "const": dc}
+    def _compile_layout(self, ctx, lay, nconsts):
+        """What _compile_groups and _compile_stages share (`lay`: the GroupsLayout of their pairwise disjoint Variable vectors): the function
+        over the sorted union z, `nconsts` words for the parts' constants, and where the parts are written — their slices of the MOI buffers
+        when every part's variables are consecutive in z (pointer + offset: no copy, no extra pass), an arena otherwise, from where
+        pmt_quad_groups_gather_f64 places the rows through the tables uploaded here.  Returns (bq, bl, oq, ol, consts, dc, gather): part k
+        starts oq[k] quadratic / ol[k] linear terms behind bq / bl; gather(c) emits the gather, or nothing without an arena."""
+        n, nq = lay.nlin, lay.nterms
+        (dq, dl, dc), consts = self._quad_buffers(ctx, n, nq, twin=False), ctx.alloc(8 * nconsts)
         self.groups_ordered = lay.ordered
         if lay.ordered:
-            bq, bl, oq, ol = dq, dl, lay.dst_quad, lay.dst_lin
-        else:
-            bq, bl, oq, ol = ctx.alloc(24 * nq), ctx.alloc(16 * n), lay.src_quad, lay.src_lin
-            tables = [ctx.alloc(8 * len(t)) for t in (lay.row_src, lay.row_dst, lay.lin_src)]
-            for buf, t in zip(tables, (lay.row_src, lay.row_dst, lay.lin_src)):
-                ctx.upload(buf, t)
+            return dq, dl, lay.dst_quad, lay.dst_lin, consts, dc, lambda c: None
+        bq, bl = ctx.alloc(24 * nq), ctx.alloc(16 * n)
+        row_src, row_dst, lin_src = [ctx.upload_new(t) for t in (lay.row_src, lay.row_dst, lay.lin_src)]
+        return bq, bl, lay.src_quad, lay.src_lin, consts, dc, \
+            lambda c: c.call("pmt_quad_groups_gather_f64", P(bq), P(row_src), P(row_dst), n, nq, P(bl), P(lin_src), n, P(dq), P(dl))
+
+    def _compile_groups(self, ctx, varmap_buf, handoff_varmap):
+        """The objective as a sum over groups of blocks / forms with pairwise disjoint Variable vectors (plan.groups): every group is written
+        by the steps of its own canonical-sum list (_lsq_sum_emitter) into its part of the layout (_compile_layout: its slice of the MOI
+        buffers, or the arena and the gather).  pmt_quad_groups_constant_f64 adds the groups' constants.
+        As in canonical-sum the terms are final only after the last step: no overlapped delivery of the quadratic terms."""
+        groups, G = self.plan.groups, len(self.plan.groups)
+        bq, bl, oq, ol, consts, dc, gather = self._compile_layout(ctx, _lib.GroupsLayout([g.vars for g in groups]), G)
         emits = [self._lsq_sum_emitter(ctx, varmap_buf, g.terms, bq + 24 * int(oq[k]), bl + 16 * int(ol[k]), consts + 8 * k)
                  for k, g in enumerate(groups)]
 
         def emit(c):
             for e in emits:
                 e(c)
-            if not lay.ordered:
-                c.call("pmt_quad_groups_gather_f64", P(bq), P(tables[0]), P(tables[1]), n, nq, P(bl), P(tables[2]), n, P(dq), P(dl))
+            gather(c)
             c.call("pmt_quad_groups_constant_f64", P(consts), G, P(dc))
         return emit
 
     def _compile_stages(self, ctx, varmap_buf, handoff_varmap):
         """The objective as a sum of horizon stages — dense forms, plain or shifted, over pairwise disjoint Variable vectors, more
         of them than "canonical-groups" holds (plan.stages): ONE pmt_quad_stages_f64 writes every stage's canonical function from a device
-        table of descriptors built, checked (pmt_quad_stages_check) and uploaded here once — straight into the stages' slices of the MOI
-        buffers when their variables are consecutive in the sorted union z, into an arena otherwise, from where the unchanged
-        pmt_quad_groups_gather_f64 places the rows, as _compile_groups does.  The stages' constants are added by the call's own second
-        launch.  With weights, linear terms or constants beside the stages (plan.stage_terms, plan.stage_consts) the one call is
-        pmt_quad_stages_terms_f64 over two more tables, checked by pmt_quad_stages_terms_check.  update! allocates nothing and makes one
-        call, or two with the gather."""
-        from . import _lib
+        table of descriptors built, checked (pmt_quad_stages_check) and uploaded here once, into the stages' parts of the layout
+        (_compile_layout: their slices of the MOI buffers, or the arena and the unchanged gather).  The stages' constants are added by
+        the call's own second launch.  With weights, linear terms or constants beside the stages (plan.stage_terms, plan.stage_consts)
+        the one call is pmt_quad_stages_terms_f64 over two more tables, checked by pmt_quad_stages_terms_check.  update! allocates
+        nothing and makes one call, or two with the gather."""
         stages = self.plan.stages
         lay = _lib.GroupsLayout([q.xvars.vars for q in stages])
         T, n, nq = len(stages), lay.nlin, lay.nterms
-        self.f = ScalarQuadraticFunction(n, nq, alloc=ctx.pinned_array)
-        dq, dl, dc, consts = ctx.alloc(24 * nq), ctx.alloc(16 * n), ctx.alloc(8), ctx.alloc(8 * T)
-        self.dev = {"quad": dq, "lin": dl, "const": dc}
-        self.groups_ordered = lay.ordered
-        if lay.ordered:
-            bq, bl, oq, ol = dq, dl, lay.dst_quad, lay.dst_lin
-        else:
-            bq, bl, oq, ol = ctx.alloc(24 * nq), ctx.alloc(16 * n), lay.src_quad, lay.src_lin
-            tables = [ctx.alloc(8 * len(t)) for t in (lay.row_src, lay.row_dst, lay.lin_src)]
-            for buf, t in zip(tables, (lay.row_src, lay.row_dst, lay.lin_src)):
-                ctx.upload(buf, t)
-        arr = _lib.quad_stages([{"Q": q.mat.buf, "ldq": q.mat.lda, "xvar": q.xvars.buf, "vec": q.vec.buf if q.vec is not None else None,
-                                 "n": q.mat.cols, "sign": q.sign if q.vec is not None else 0, "quad_at": int(oq[k]), "lin_at": int(ol[k])}
-                                for k, q in enumerate(stages)])
-        def weight(t):
-            return t.param.buf if t.param is not None else None
-
-        def uploaded(a):
-            buf = ctx.alloc(C.sizeof(a))
-            ctx.upload(buf, np.frombuffer(a, dtype=np.uint8).copy())
-            return buf
+        bq, bl, oq, ol, consts, dc, gather = self._compile_layout(ctx, lay, T)
+        vs = [_vec_sign(q.vec, q.sign) for q in stages]
+        arr = _lib.quad_stages([{"Q": q.mat.buf, "ldq": q.mat.lda, "xvar": q.xvars.buf, "vec": vec, "n": q.mat.cols, "sign": sign,
+                                 "quad_at": int(oq[k]), "lin_at": int(ol[k])} for k, (q, (vec, sign)) in enumerate(zip(stages, vs))])
         sterms, sconsts = self.plan.stage_terms, self.plan.stage_consts
         if sterms is None and not sconsts:
             # no weight, no linear term, no constant: the unweighted entry point, as before
             _lib.call("pmt_quad_stages_check", C.addressof(arr), T, nq, n)
-            table = uploaded(arr)
+            table = _table(ctx, arr)
             launch = lambda c: c.call("pmt_quad_stages_f64", P(table), T, P(varmap_buf), P(bq), P(bl), P(consts), P(dc))
         else:
             # the weights, the linear terms' vectors and the constants are device mirrors of Parameters, read by the launch at run time
-            tarr = _lib.quad_stage_terms([{"scale": s.scale, "weight": weight(s)} if s.lin is None else
-                                          {"scale": s.scale, "weight": weight(s), "lin_scale": s.lin.scale, "lin_weight": weight(s.lin),
+            tarr = _lib.quad_stage_terms([{"scale": s.scale, "weight": _buf(s.param)} if s.lin is None else
+                                          {"scale": s.scale, "weight": _buf(s.param), "lin_scale": s.lin.scale, "lin_weight": _buf(s.lin.param),
                                            "lin_vec": s.lin.vec.buf} for s in sterms or [StageTerms()] * T])
-            carr = _lib.quad_stage_consts([{"scale": k.scale, "weight": weight(k), "value": k.value.buf if k.value is not None else None}
-                                           for k in sconsts])
+            carr = _lib.quad_stage_consts([{"scale": k.scale, "weight": _buf(k.param), "value": _buf(k.value)} for k in sconsts])
             nc = len(sconsts)
             _lib.call("pmt_quad_stages_terms_check", C.addressof(arr), C.addressof(tarr), T, C.addressof(carr), nc, nq, n)
-            table, ttable, ctable = uploaded(arr), uploaded(tarr), uploaded(carr)
+            table, ttable, ctable = _table(ctx, arr), _table(ctx, tarr), _table(ctx, carr)
             launch = lambda c: c.call("pmt_quad_stages_terms_f64", P(table), P(ttable), T, P(ctable), nc, P(varmap_buf), P(bq), P(bl), P(consts),
                                       P(dc))
 
         def emit(c):
             launch(c)
-            if not lay.ordered:
-                c.call("pmt_quad_groups_gather_f64", P(bq), P(tables[0]), P(tables[1]), n, nq, P(bl), P(tables[2]), n, P(dq), P(dl))
+            gather(c)
         return emit
 
-    # the quadratic forms by plan.mode (quad_plan)
     def _compile_sparse_gram(self, ctx, varmap_buf, handoff_varmap):
         """dot(r, r), r = C*x (+|-) d with a sparse C (plan.gram, a DSparseAff): pmt_sparse_gram_f64 streams the pattern's product list
         (DSpMat.gram_tables, built here once) and writes the canonical MOI function — one quadratic term per pair of columns sharing a row,
-        one linear term per non-empty column.  The index fields are static: they are written into the host arrays here, where the
-        hand-off's generic route finds them before the first update; the kernel rewrites them through varmap_buf at every call, so the
-        record follows the optimizer's index map like the dense forms."""
+        one linear term per non-empty column.  The index fields are static (_static_indices); the kernel rewrites them through varmap_buf
+        at every call, so the record follows the optimizer's index map like the dense forms."""
         r = self.plan.gram
         T = r.gram_tables()
-        self.f = f = ScalarQuadraticFunction(T.nlin, T.nq, alloc=ctx.pinned_array)
-        x = r.xvars.vars if handoff_varmap is None else np.asarray(handoff_varmap, dtype=np.int64)[r.xvars.vars - 1]
-        f.quadratic_terms["row"], f.quadratic_terms["col"], f.quadratic_terms["coeff"] = x[T.pair_j], x[T.pair_k], 0.0
-        f.affine_terms["var"], f.affine_terms["coeff"] = x[T.lin_col], 0.0
-        dq, dl, dc = self._twin(ctx, f.quadratic_terms, 24 * T.nq), self._twin(ctx, f.affine_terms, 16 * T.nlin), self._twin(ctx, self._cbuf, 8)
-        self.dev = {"quad": dq, "lin": dl, "const": dc}
-        vec = r.vec.buf if r.vec is not None else None
-        return lambda c: c.call("pmt_sparse_gram_f64", P(r.spmat.buf), *T.call_args(r.rows), P(r.xvars.buf), P(vec), r.sign if vec else 0, 1,
-                                P(varmap_buf), P(dq), P(dl), P(dc))
+        dq, dl, dc = self._quad_buffers(ctx, T.nlin, T.nq, twin=True)
+        _static_indices(self.f, T, r.xvars, handoff_varmap)
+        return lambda c: _sparse_gram_call(c, r, T, varmap_buf, dq, dl, dc)
 
     def _compile_sparse_form(self, ctx, varmap_buf, handoff_varmap):
         """transpose(x) * Q * x with a sparse Q (plan.form, a SparseQuadForm), the counterpart of _compile_sparse_gram: pmt_sparse_form_f64
         streams the pattern's pair and source tables (DSpMat.form_tables, built here once) and writes the canonical MOI function — one
-        quadratic term per unordered pair with a stored entry, no linear terms, constant 0.0.  The index fields are static: written into the
-        host arrays here through the hand-off's map, where the generic route finds them; the kernel rewrites them through varmap_buf."""
+        quadratic term per unordered pair with a stored entry, no linear terms, constant 0.0.  The index fields are static (_static_indices)."""
         form = self.plan.form
         T = form.form_tables()
-        self.f = f = ScalarQuadraticFunction(0, T.nq, alloc=ctx.pinned_array)
-        x = form.xvars.vars if handoff_varmap is None else np.asarray(handoff_varmap, dtype=np.int64)[form.xvars.vars - 1]
-        f.quadratic_terms["row"], f.quadratic_terms["col"], f.quadratic_terms["coeff"] = x[T.pair_j], x[T.pair_k], 0.0
-        dq, dl, dc = self._twin(ctx, f.quadratic_terms, 24 * T.nq), self._twin(ctx, f.affine_terms, 0), self._twin(ctx, self._cbuf, 8)
-        self.dev = {"quad": dq, "lin": dl, "const": dc}                   # ("lin": no terms; the hand-off's generic route asks for the key)
-        return lambda c: c.call("pmt_sparse_form_f64", P(form.spmat.buf), *T.call_args(), P(form.xvars.buf), 1, P(varmap_buf), P(dq), P(dc))
+        dq, _, dc = self._quad_buffers(ctx, 0, T.nq, twin=True)            # ("lin": no terms; the hand-off's generic route asks for the key)
+        _static_indices(self.f, T, form.xvars, handoff_varmap)
+        return lambda c: _sparse_form_call(c, form, T, varmap_buf, dq, dc)
 
     def _compile_sparse_sum(self, ctx, varmap_buf, handoff_varmap):
         """A weighted sum over sparse least-squares blocks, diagonal, linear and constant terms over one x (plan.terms; quad_plan:
         _sparse_sum_combines): every block by the unchanged pmt_sparse_gram_f64 (moi = 1) into its own scratch term lists, then ONE
         pmt_sparse_gram_sum_f64 weights and adds them through the gather tables of the symbolic merge (device.SparseSumTables, built here
         once) and writes every term of the MOI buffers once — also straight into the page-locked host arrays of a small model.  The index
-        fields are static: written into the host arrays here through the hand-off's map, as _compile_sparse_gram does; the kernel rewrites
-        them through varmap_buf at every call.  A sparse form transpose(x)*Q*x among the blocks (LsqTerm 'form', a SparseQuadForm) is written
+        fields are static (_static_indices).  A sparse form transpose(x)*Q*x among the blocks (LsqTerm 'form', a SparseQuadForm) is written
         by pmt_sparse_form_f64 (moi = 1) into a scratch quad list and constant word of its own and described to the unchanged combine as a
         block without linear terms: a 16-byte dummy `lin`, the all-0xFFFFFFFF `lin_at` the merge writes for nlin_b = 0."""
-        from . import _lib
         from .device import SparseSumTables
         terms = self.plan.terms
         blocks = [t for t in terms if t.kind in ("block", "form")]
         xv = blocks[0].r.xvars
         n = len(xv.vars)
+        desc = [_lsq_desc(t) for t in terms]
+        lists = _term_positions(terms, xv.vars)
         # a sparse form stands where a block stands: its own scratch quad list and constant word (pmt_sparse_form_f64, moi = 1), no linear terms
-        kind = {"block": _lib.PMT_LSQ_BLOCK, "form": _lib.PMT_LSQ_BLOCK, "diag": _lib.PMT_LSQ_DIAG, "linear": _lib.PMT_LSQ_LINEAR,
-                "constant": _lib.PMT_LSQ_CONSTANT}
-        lists = [np.searchsorted(xv.vars, t.xvars.vars).astype(np.int64) if t.kind in ("diag", "linear") and not np.array_equal(t.xvars.vars, xv.vars)
-                 else None for t in terms]
         Ts = [t.r.form_tables() if t.kind == "form" else t.r.gram_tables() for t in blocks]
-        S = SparseSumTables(ctx, n, Ts, [(kind[t.kind], t.kind == "diag" and t.vec is not None, p) for t, p in zip(terms, lists)])
-        self.f = f = ScalarQuadraticFunction(S.nlin, S.nq, alloc=ctx.pinned_array)
-        x = xv.vars if handoff_varmap is None else np.asarray(handoff_varmap, dtype=np.int64)[xv.vars - 1]
-        f.quadratic_terms["row"], f.quadratic_terms["col"], f.quadratic_terms["coeff"] = x[S.pair_j], x[S.pair_k], 0.0
-        f.affine_terms["var"], f.affine_terms["coeff"] = x[S.lin_col], 0.0
-        dq, dl, dc = self._twin(ctx, f.quadratic_terms, 24 * S.nq), self._twin(ctx, f.affine_terms, 16 * S.nlin), self._twin(ctx, self._cbuf, 8)
-        self.dev = {"quad": dq, "lin": dl, "const": dc}
+        S = SparseSumTables(ctx, n, Ts, [(d["kind"], t.kind == "diag" and t.vec is not None, p) for t, d, p in zip(terms, desc, lists)])
+        dq, dl, dc = self._quad_buffers(ctx, S.nlin, S.nq, twin=True)
+        _static_indices(self.f, S, xv, handoff_varmap)
         # per block: the scratch lists pmt_sparse_gram_f64 writes (its own nq / nlin terms, its constant)
         parts = [(ctx.alloc(24 * max(T.nq, 1)), ctx.alloc(16 * max(T.nlin, 1)), ctx.alloc(8)) for T in Ts]
-        desc, k = [], 0
-        for i, t in enumerate(terms):
-            d = {"kind": kind[t.kind], "scale": t.scale, "weight": t.param.buf if t.param is not None else None}
+        k = 0
+        for i, (t, d) in enumerate(zip(terms, desc)):
             if t.kind in ("block", "form"):
                 d["quad"], d["lin"], d["constant"] = parts[k]             # (a form's lin: a dummy allocation; its lin_at is all 0xFFFFFFFF)
                 d["quad_at"], d["lin_at"] = S.dev["quad_at"][k], S.dev["lin_at"][k]
                 k += 1
             elif t.kind in ("diag", "linear"):
-                d["vec"] = t.vec.buf if t.vec is not None else None
-                d["sign"] = t.sign if t.kind == "diag" and t.vec is not None else 0
-                d["pos"] = S.dev["term_pos"].get(i)
-                d["nvec"] = len(t.xvars.vars)
-            elif t.value is not None:
-                d["vec"] = t.value.buf
-            desc.append(d)
+                d["pos"], d["nvec"] = S.dev["term_pos"].get(i), len(t.xvars.vars)
         arr = _lib.sparse_lsq_terms(desc)
         self._sub_args.append((S, arr))                                     # (the entry reads the descriptors when the call is recorded)
 
         def emit(c):
             for t, T, part in zip(blocks, Ts, parts):
-                r = t.r
                 if t.kind == "form":
-                    c.call("pmt_sparse_form_f64", P(r.spmat.buf), *T.call_args(), P(r.xvars.buf), 1, P(varmap_buf), P(part[0]), P(part[2]))
-                    continue
-                vec = r.vec.buf if r.vec is not None else None
-                c.call("pmt_sparse_gram_f64", P(r.spmat.buf), *T.call_args(r.rows), P(r.xvars.buf), P(vec), r.sign if vec else 0, 1,
-                       P(varmap_buf), P(part[0]), P(part[1]), P(part[2]))
+                    _sparse_form_call(c, t.r, T, varmap_buf, part[0], part[2])
+                else:
+                    _sparse_gram_call(c, t.r, T, varmap_buf, *part)
             c.call("pmt_sparse_gram_sum_f64", n, C.addressof(arr), len(desc), P(S.dev["pair_j"]), P(S.dev["pair_k"]), S.nq, P(S.dev["lin_col"]),
                    S.nlin, P(xv.buf), P(varmap_buf), P(dq), P(dl), P(dc))
         return emit
 
+    # the quadratic forms by plan.mode (quad_plan)
     _QUAD_FORMS = {"canonical-sparse": _compile_sparse_gram, "canonical-sparse-form": _compile_sparse_form, "canonical-sparse-sum": _compile_sparse_sum, "literal": _compile_literal, "canonical": _compile_gram, "canonical-csc": _compile_gram, "canonical-form": _compile_form,
                    "canonical-sum": _compile_lsq_sum, "canonical-groups": _compile_groups, "canonical-stages": _compile_stages}
 
@@ -670,13 +679,13 @@ class _Record:
     def _compile_dense(self, ctx, varmap_buf):
         out = self.expr.out
         dt, dc = self._implicit_twins(ctx)
-        vec = out.vec.buf if out.vec is not None else None
+        vec, sign = _vec_sign(out.vec, out.sign)
 
         def emit(c):
             # on the side lane (Model._record_tape sets on_side_lane before the emitter runs): the low-footprint kernel that is co-resident
             # with the contraction it runs beside
             c.call("pmt_affine_pack_vector_background_f64" if self.on_side_lane else "pmt_affine_pack_vector_f64", P(out.mat.buf), out.mat.lda,
-                   out.mat.rows, out.mat.cols, P(out.xvars.buf), P(vec), out.sign if vec else 0, P(varmap_buf), 0, P(dt), P(dc))
+                   out.mat.rows, out.mat.cols, P(out.xvars.buf), P(vec), sign, P(varmap_buf), 0, P(dt), P(dc))
         return emit
 
     def _compile_vars(self, ctx, varmap_buf):
@@ -761,7 +770,6 @@ def _lsq_sum_combines(terms):
     transpose(x) * Q * x count among them —, at most PMT_LSQ_MAX_TERMS terms, every block over the same strictly increasing x (a stacked block
     over its sorted union z), every diagonal / linear term over x or a strictly increasing part of it (pmt_quad_gram_sum_sub_f64, whose launch
     holds at most PMT_LSQ_MAX_RUNS runs of positions)."""
-    from . import _lib
     blocks = [t for t in terms or () if t.kind in ("block", "form")]
     if any(isinstance(t.r, (DSparseAff, SparseQuadForm)) for t in blocks):   # a sparse block or form: the dense combine cannot take it (_sparse_sum_combines)
         return False
@@ -775,12 +783,11 @@ def _lsq_sum_combines(terms):
         if t.kind in ("block", "form"):
             if not np.array_equal(t.r.xvars.vars, x.vars):
                 return False
-        elif t.xvars is not None and not np.array_equal(t.xvars.vars, x.vars):
-            v = t.xvars.vars
-            pos = np.searchsorted(x.vars, v)
-            if not (len(v) and np.all(np.diff(v) > 0) and np.all(pos < len(x.vars)) and np.array_equal(x.vars[np.minimum(pos, len(x.vars) - 1)], v)):
+        elif t.xvars is not None:
+            pos = _part_of(t.xvars.vars, x.vars)
+            if pos is False:
                 return False
-            runs += _lib.column_runs(pos)
+            runs += _lib.column_runs(pos) if pos is not None else 0
     return runs <= _lib.PMT_LSQ_MAX_RUNS
 
 
@@ -795,7 +802,6 @@ def _sparse_sum_combines(terms):
     dense block, no dense form beside them —, at most PMT_LSQ_MAX_TERMS terms, every block over the same strictly
     increasing x, every diagonal / linear term over x or a strictly increasing part of it (_lsq_sum_combines' subset rule; the positions
     are held in tables, so there is no limit on their runs)."""
-    from . import _lib
     terms = terms or ()
     blocks = [t for t in terms if t.kind in ("block", "form")]
     if not 1 <= len(blocks) <= _lib.PMT_LSQ_MAX_BLOCKS or len(terms) > _lib.PMT_LSQ_MAX_TERMS:
@@ -803,16 +809,8 @@ def _sparse_sum_combines(terms):
     if not all(_sparse_form_term(t) or (t.kind == "block" and isinstance(t.r, DSparseAff) and t.r.gram_operand()) for t in blocks):
         return False
     x = blocks[0].r.xvars.vars
-    for t in terms:
-        if t.kind in ("block", "form"):
-            if not np.array_equal(t.r.xvars.vars, x):
-                return False
-        elif t.xvars is not None and not np.array_equal(t.xvars.vars, x):
-            v = t.xvars.vars
-            pos = np.searchsorted(x, v)
-            if not (len(v) and np.all(np.diff(v) > 0) and np.all(pos < len(x)) and np.array_equal(x[np.minimum(pos, len(x) - 1)], v)):
-                return False
-    return True
+    return all(np.array_equal(t.r.xvars.vars, x) if t.kind in ("block", "form") else t.xvars is None or _part_of(t.xvars.vars, x) is not False
+               for t in terms)
 
 
 # A sum over disjoint Variable vectors whose literal function is smaller than this keeps the literal expansion + canonicalize: such models
@@ -834,7 +832,6 @@ def _lsq_groups(terms):
     that holds its variables (a strictly increasing part of ONE group's set: _lsq_sum_combines' subset rule), constants join the first group;
     every group's list, expression order kept, is one the combine takes on its own (_lsq_sum_combines).  A term over variables of no group,
     or of two, leaves the whole sum to the literal path."""
-    from . import _lib
     groups = []
     for t in terms or ():
         if t.kind in ("block", "form") and not any(np.array_equal(t.r.xvars.vars, g.vars) for g in groups):
@@ -879,7 +876,6 @@ def _lsq_stages(terms):
     PMT_QUAD_STAGES_MAX_CONSTS 'constant' terms.  Anything else in the list — a block, a diagonal term, a sparse form, a linear term over
     part of a stage or over other variables, a second one on a stage — leaves the sum to the literal path.  The StageTerms are None when
     no stage has a weight or a linear term: with no constant either, the record is the unweighted one (pmt_quad_stages_f64)."""
-    from . import _lib
     terms = terms or ()
     forms = [t for t in terms if t.kind == "form"]
     consts = [t for t in terms if t.kind == "constant"]
@@ -1041,7 +1037,6 @@ class AffineStageGroup:
         return parts, stages, slices, ta, ca
 
     def _build(self, ctx, varmap_buf):
-        from . import _lib
         parts, stages, self.slices, nterms, nconsts = self._layout()
         parr, sarr = _lib.affine_parts(parts), _lib.affine_stages(stages)
         T = len(stages)
@@ -1049,9 +1044,7 @@ class AffineStageGroup:
         self.terms_host, self.consts_host = ctx.pinned_array(nterms, VAT), ctx.pinned_array(nconsts, np.float64)
         dterms, dconsts = ctx.alloc(24 * nterms), ctx.alloc(8 * nconsts)
         self.dev = {"terms": dterms, "consts": dconsts}
-        stable, ptable = ctx.alloc(C.sizeof(sarr)), ctx.alloc(C.sizeof(parr))
-        ctx.upload(stable, np.frombuffer(sarr, dtype=np.uint8).copy())
-        ctx.upload(ptable, np.frombuffer(parr, dtype=np.uint8).copy())
+        stable, ptable = _table(ctx, sarr), _table(ctx, parr)
         return lambda c: c.call("pmt_affine_stages_f64", P(stable), T, P(ptable), P(varmap_buf), P(dterms), P(dconsts))
 
     def compile_member(self, r, ctx, varmap_buf):

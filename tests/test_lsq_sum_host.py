@@ -377,3 +377,36 @@ def test_refusals_leave_the_argument_arrays_alone(lib):
     _refused(lib, A, 200, [b1, diag, lin], lists=[None, list(range(0, 80, 2)), list(range(100, 150, 2))])      # 40 + 25 runs: the 65th is refused mid-walk
     _refused(lib, D, 2 ** 31, [b1, diag], lists=[None, [1]])
     _refused(lib, D, 2 ** 31, [b1])
+
+
+# ---- the subset rule of the weighted sums: the decisions and the compile sites read one function (moi._part_of)
+X = [2, 4, 5, 9]
+
+
+@pytest.mark.parametrize("v, want", [(X, None), ([4, 9], [1, 3]), ([9], [3]), ([], False), ([4, 4], False), ([9, 4], False), ([3], False),
+                                     ([4, 10], False)])
+def test_the_subset_rule_as_a_table(lib, v, want):
+    """None: the whole vector; a list: the positions of a non-empty strictly increasing part of x; False: refused — and both
+    predicates refuse a term list exactly where the function refuses the variables of its diagonal or linear term, and the compile
+    sites' lists are the function's answers and raise where it refuses"""
+    import sparse_gram_util as SG
+    from parametron_jl_amd.lazyexpression import LsqTerm
+    from parametron_jl_amd.moi import _lsq_sum_combines, _part_of, _sparse_sum_combines, _term_positions
+    from test_record_tape_host import _b, _block, _xvars
+    from test_sparse_gram_host import _sparse_block
+    pos = _part_of(np.array(v, dtype=np.int64), np.array(X, dtype=np.int64))
+    if want is None or want is False:
+        assert pos is want
+    else:
+        assert pos.dtype == np.int64 and pos.tolist() == want
+    pattern = SG.from_mask(np.ones((6, len(X)), dtype=bool), np.random.default_rng(1))
+    dense, sparse = LsqTerm("block", r=_block(6, X)), LsqTerm("block", r=_sparse_block(pattern, X))
+    for term in (LsqTerm("diag", xvars=_xvars(v)), LsqTerm("linear", xvars=_xvars(v), vec=_b(len(v)))):
+        assert _lsq_sum_combines([dense, term]) == (pos is not False), term.kind
+        assert _sparse_sum_combines([sparse, term]) == (pos is not False), term.kind
+        if pos is False:
+            with pytest.raises(lib.ArgumentError):
+                _term_positions([dense, term], np.array(X, dtype=np.int64))
+        else:
+            first, got = _term_positions([dense, term], np.array(X, dtype=np.int64))
+            assert first is None and (got is None if pos is None else got.tolist() == want)

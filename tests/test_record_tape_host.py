@@ -27,6 +27,7 @@ class StubContext:
     def __init__(self, lib):
         self.lib = lib.load()
         self.calls, self.allocs, self.fetched, self.recorded = [], [], [], []
+        self.raw = []                                                       # (name, args) of every call, the arguments as they were passed
         self._next = 1 << 44
 
     def alloc(self, nbytes):
@@ -47,6 +48,7 @@ class StubContext:
         pass
 
     def call(self, name, *args):
+        self.raw.append((name, args))
         self.calls.append((name, tuple(a for a in args if isinstance(a, (int, float)) and not isinstance(a, bool) and abs(a) < 2 ** 32)))
 
     # a copy "lands" at once: every byte 0x40 (the double 32.5019...), so that the test sees where a constant was fetched to

@@ -328,18 +328,12 @@ def test_rule_bilinear_takes_a_sparse_parameter_and_says_why_not(lib):
 
 
 # ---- the record
-class _Ctx(StubContext):
-    def call(self, name, *args):
-        self.raw = getattr(self, "raw", []) + [(name, args)]
-        super().call(name, *args)
-
-
 @pytest.mark.parametrize("small", [False, True])
 @pytest.mark.parametrize("mapped", [False, True])
 def test_canonical_sparse_form_record_tape(lib, small, mapped):
     from parametron_jl_amd.moi import QuadPlan
     Q = _q9()
-    ctx = _Ctx(lib)
+    ctx = StubContext(lib)
     idx = np.arange(2, 11)
     form = _sparse_form(Q, idx, ctx=ctx)
     model = _model(small=small)
@@ -370,7 +364,7 @@ def test_canonical_sparse_sum_record_tape_with_a_form(lib):
     Q = _q9()
     rng = np.random.default_rng(5)
     Cs = SG.from_mask(rng.random((40, 9)) < 0.3, rng)
-    ctx = _Ctx(lib)
+    ctx = StubContext(lib)
     idx = np.arange(2, 11)
     form, r1 = _sparse_form(Q, idx, ctx=ctx), _sparse_block(Cs, idx, ctx=ctx)
     terms = [LsqTerm("block", r=r1), LsqTerm("form", r=form, scale=0.5), LsqTerm("constant", scale=2.0)]

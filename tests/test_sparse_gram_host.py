@@ -251,18 +251,12 @@ def test_quad_plan_dense_rows_are_unchanged(lib):
 
 
 # ---- the record
-class _Ctx(StubContext):
-    def call(self, name, *args):
-        self.raw = getattr(self, "raw", []) + [(name, args)]
-        super().call(name, *args)
-
-
 @pytest.mark.parametrize("small", [False, True])
 def test_canonical_sparse_record_tape(lib, small):
     from parametron_jl_amd.moi import QuadPlan
     from test_record_tape_host import _b
     Cs = _small_pattern()
-    ctx = _Ctx(lib)
+    ctx = StubContext(lib)
     idx = np.arange(2, 11)
     r = _sparse_block(Cs, idx, vec=_b(40), sign=-1, ctx=ctx)
     model = _model(small=small)

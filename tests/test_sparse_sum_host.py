@@ -272,19 +272,13 @@ def test_model_asks_for_sparse_sums(lib):
 
 
 # ---- the record
-class _Ctx(StubContext):
-    def call(self, name, *args):
-        self.raw = getattr(self, "raw", []) + [(name, args)]
-        super().call(name, *args)
-
-
 @pytest.mark.parametrize("small", [False, True])
 def test_canonical_sparse_sum_record_tape(lib, small):
     from parametron_jl_amd.device import DNum
     from parametron_jl_amd.lazyexpression import LsqTerm
     from parametron_jl_amd.moi import QuadPlan
     C1, C2 = _pattern(5), _pattern(6, m=17)
-    ctx = _Ctx(lib)
+    ctx = StubContext(lib)
     idx = np.arange(2, 11)
     r1, r2 = _sparse_block(C1, idx, vec=_b(40), sign=-1, ctx=ctx), _sparse_block(C2, idx, ctx=ctx)
     lam = DNum.__new__(DNum)
