@@ -1018,6 +1018,57 @@ int pmt_batch_horizon_dynamics_f64(const double *A, const double *Bm, const doub
 int pmt_batch_horizon_dynamics_expand_f64(const double *section, int64_t T, int64_t nx, int64_t nu, int sign_xp, const int64_t *xvar,
                                           const int64_t *varmap, pmt_vector_affine_term *out_terms, double *out_consts, void *stream);
 
+/* The batch of horizons' TIME-VARYING dynamics: instance i's constraints x_t == A_{i,t}*x_{t-1} + B_{i,t}*u_{t-1} + h_{i,t} with a matrix pair
+ * per stage — the fleet that re-linearises every stage at every solve (real-time iteration, gain scheduling, trajectory tracking, scenario
+ * trees over a nonlinear plant).  The siblings of pmt_batch_horizon_dynamics_*: the same argument order, limits and error codes, the same
+ * records over z = [x_0; u_0; x_1; u_1; ..] — those of pmt_affine_stages_f64 on the instance's own tables; in the reference matvecmul!
+ * (src/functions.jl:775-798) per product, vecadd! / vecsubtract! (:751-764: copyto! :419-427, add! / subtract! :452-485) per + / - and
+ * update!(::MOI.VectorAffineFunction, fs, varmap) (src/moi_interop.jl:64-81):
+ *   record 0              x_0 (+|-) h_{i,0}
+ *   record t = 1 .. T-1   (+|-)x_t (+|-) A_{i,t}*x_{t-1} (+|-) B_{i,t}*u_{t-1} (+|-) h_{i,t}, the parts in this order; with nu == 0 there is no B part
+ * nx in 1 .. PMT_BATCH_HORIZON_MAX_DIM, nu in 0 .. PMT_BATCH_HORIZON_MAX_DIM, T in 1 .. PMT_BATCH_HORIZON_MAX_T.
+ * pmt_batch_horizon_dynamics_tv_doubles (host arithmetic) is the section's length Ltv = (T-1)*nx*(nx + nu) + T*nx.
+ * pmt_batch_horizon_dynamics_tv_f64 writes, at out + i * out_stride (out_stride >= Ltv; the words between two sections are never written), the
+ * section
+ *     [ AB_1 | AB_2 | .. | AB_{T-1} | h-consts: T*nx ]
+ * from inputs that are instance-major, then stage-major: A[B][T-1][nx*nx] and Bm[B][T-1][nx*nu], each matrix column-major with leading
+ * dimension nx, matrix index s = t-1 belonging to record t; h[B][T*nx] as in the sibling:
+ *   AB_t      nx*(nx + nu) words at (t-1)*nx*(nx + nu), row-major with row length nx + nu: AB_t[r*(nx + nu) + j] = A_{i,t}[r + j*nx] for j < nx,
+ *             its sign bit flipped when sign_a == -1, and B_{i,t}[r + (j - nx)*nx] for j >= nx, flipped when sign_b == -1 — exactly the
+ *             words the sibling's AB holds for that matrix pair.
+ *   h-consts  h-consts[t*nx + r] = 0.0 (+|-) h_i[t*nx + r] by sign_h, so a -0.0 does not survive; +0.0 with sign_h == 0 (h may be NULL).
+ * No arithmetic beyond that, so there is no order question.  Every word is written exactly once per call; no atomics, no workgroup waits
+ * for another, no workspace; the words do not depend on B, on the instance's position, on launch geometry or on timing.  Each of T == 1
+ * (the constants only; A and Bm may be NULL), nu == 0 (Bm may be NULL) and sign_h == 0 is a complete section; B == 0 is PMT_OK without a
+ * launch, whatever the pointers.  Dimensions outside the limits, a negative B or out_stride < Ltv: PMT_DIMENSION_MISMATCH; sign_a or
+ * sign_b not +-1, sign_h outside {-1, 0, 1} or a null pointer where data is needed: PMT_INVALID_ARGUMENT — all before any device call.
+ * `out` and `out_stride` are free as in the sibling: out = slabs + L, out_stride = L + Ltv puts the section behind the objective slab.
+ * Two anchors, both exact:
+ *   - with A_{i,t} = A_i and B_{i,t} = B_i for every t, every block AB_t and the h-consts equal, word for word, the AB and the h-consts
+ *     of pmt_batch_horizon_dynamics_f64's section for (A_i, B_i, h_i);
+ *   - pmt_batch_horizon_dynamics_tv_expand_f64 rebuilds ONE instance's nx + (T-1)*nx*(1 + nx + nu) vector-affine terms and T*nx constants,
+ *     word for word what pmt_affine_stages_f64 writes for the instance's own tables: the table layout given above for
+ *     pmt_batch_horizon_dynamics_expand_f64 (stage 0: one Variable-vector part, row_len 1, term_offset 0; stage t >= 1: row_len 1 + nx + nu,
+ *     term_offset nx + (t-1)*nx*(1 + nx + nu), the Variable vector over xvar[t*(nx + nu) .. + nx) with sign_xp, then the matrix parts over
+ *     xvar[(t-1)*(nx + nu) ..); const_offset t*nx, vec = h_{i,t}, vec_sign = sign_h), except that stage t's matrix parts point at A_{i,t}
+ *     and B_{i,t}.  Row index r + 1 within each record, a Variable-part coefficient of +1.0 | -1.0, the AB_t words copied (they carry their
+ *     signs), the constants copied.  xvar: the n = T*(nx + nu) model variables of z (a horizon with a terminal stage: T + 1 records over
+ *     T*(nx + nu) + nx variables, as for the sibling); varmap NULL: the identity.  Errors as the sibling's expansion.
+ * Every output needs 8-byte alignment only.  One launch (csrc/batch_horizon_ltv.hip).  The work item is one matrix pair (i, t), item =
+ * i*(T-1) + t-1 — consecutive items are contiguous in A and Bm — dealt over persistent workgroups of 256 threads, so that few instances
+ * with many stages fill the device as many instances with few do; (i, t) follows the item without a division per item, all offsets are
+ * 64-bit.  Tiles as in the sibling (4096 words read along the columns, loads unconditional on clamped indices and issued together,
+ * transposed through LDS, 8-byte stores with the column on the lanes), the next tile's loads in flight under the current tile's stores,
+ * and a tile of 2048 words, eight workgroups per CU, where that holds a whole row (nx + nu <= 64 at 17 .. 32 rows, <= 128 up to 16);
+ * pairs of at most 512 AB words take a wave each without LDS.  Item (i, t) also writes the nx constants of stage t, the item of t = 1
+ * those of stage 0 with them; T == 1 is a launch of the constants alone.  The expansion is the sibling's streaming writer reading row r of
+ * AB_t: each section word is read once.  Algorithmic bytes per instance: 8 Ltv read, 8 Ltv written. */
+int64_t pmt_batch_horizon_dynamics_tv_doubles(int64_t T, int64_t nx, int64_t nu);
+int pmt_batch_horizon_dynamics_tv_f64(const double *A, const double *Bm, const double *h, int64_t B, int64_t T, int64_t nx, int64_t nu,
+                                      int sign_a, int sign_b, int sign_h, double *out, int64_t out_stride, void *stream);
+int pmt_batch_horizon_dynamics_tv_expand_f64(const double *section, int64_t T, int64_t nx, int64_t nu, int sign_xp, const int64_t *xvar,
+                                             const int64_t *varmap, pmt_vector_affine_term *out_terms, double *out_consts, void *stream);
+
 /* The batch of horizons with a terminal cost, a weight per stage and linear stage terms — what pmt_quad_stages_terms_f64 added to the single
  * horizon, for the fleet, still one launch without a workspace:
  *   J_i = sum_{t<T} wx_{i,t} * transpose(x_t (+|-) r_{i,t})*Q_i*(x_t (+|-) r_{i,t}) + dot(gx_{i,t}, x_t)

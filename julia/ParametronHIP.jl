@@ -725,6 +725,25 @@ batch_horizon_dynamics_expand!(section::DevPtr, T, nx, nu, sign_xp, xvar::DevPtr
                 (DevPtr, Int64, Int64, Int64, Cint, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
                 section, T, nx, nu, sign_xp, xvar, varmap, out_terms, out_consts, stream))
 
+"doubles of one instance's time-varying dynamics section [AB_1 | .. | AB_{T-1} | h-consts: T*nx], each AB_t nx*(nx + nu) words"
+batch_horizon_dynamics_tv_doubles(T, nx, nu) = ccall((:pmt_batch_horizon_dynamics_tv_doubles, lib), Int64, (Int64, Int64, Int64), T, nx, nu)
+
+"one compact section per instance for horizons whose dynamics change with the stage: x_0 ± h_0 and ±x_t ± A_{i,t}*x_{t-1} ± B_{i,t}*u_{t-1} ± h_t,
+ t = 1 .. T-1 (nx, nu <= 128, T <= 512): A[nbatch][T-1][nx*nx], B[nbatch][T-1][nx*nu] instance- then stage-major (column-major, leading
+ dimension nx; matrix index t-1 belongs to record t), stage-major h; every AB_t is the block batch_horizon_dynamics! writes for that pair, the
+ constants 0.0 ± h; sign_h = 0: h may be C_NULL; nu = 0: B may be C_NULL; T = 1: A and B may be C_NULL"
+batch_horizon_dynamics_tv!(out::DevPtr, out_stride, A::DevPtr, B::DevPtr, h::DevPtr, nbatch, T, nx, nu, sign_a, sign_b, sign_h, stream) =
+    check(ccall((:pmt_batch_horizon_dynamics_tv_f64, lib), Cint,
+                (DevPtr, DevPtr, DevPtr, Int64, Int64, Int64, Int64, Cint, Cint, Cint, DevPtr, Int64, Ptr{Cvoid}),
+                A, B, h, nbatch, T, nx, nu, sign_a, sign_b, sign_h, out, out_stride, stream))
+
+"one instance's T MOI.VectorAffineFunction buffers from its time-varying dynamics section, word for word what affine_stages! writes for the
+ instance's own tables with stage t's matrix parts at A_{i,t}, B_{i,t}; xvar: the n model variables of z, varmap may be C_NULL (the identity)"
+batch_horizon_dynamics_tv_expand!(section::DevPtr, T, nx, nu, sign_xp, xvar::DevPtr, varmap::DevPtr, out_terms::DevPtr, out_consts::DevPtr, stream) =
+    check(ccall((:pmt_batch_horizon_dynamics_tv_expand_f64, lib), Cint,
+                (DevPtr, Int64, Int64, Int64, Cint, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
+                section, T, nx, nu, sign_xp, xvar, varmap, out_terms, out_consts, stream))
+
 "pmt_batch_horizon_terms (include/parametron_hip.h): the inputs of batch_horizon_terms_coeffs!, device pointers, instance-major.  C_NULL: P no
  terminal stage, a weight array every weight 1.0, a linear array no linear term, a reference only where its sign is 0; 128 bytes, no padding"
 struct BatchHorizonTerms

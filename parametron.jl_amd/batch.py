@@ -324,6 +324,65 @@ class BatchMPC(_Dynamics, BatchHorizon):
         super().__init__(torch, total, T, nx, nu, m, rank, world, device)
 
 
+def horizon_dynamics_tv_layout(T, nx, nu):
+    """Offsets (in doubles) of the sections of one horizon instance's time-varying dynamics section [AB_1 | .. | AB_{T-1} | h-consts] —
+    "AB" the list of the T - 1 blocks' offsets (AB_t at index t - 1: the nx rows of [A_{i,t} | B_{i,t}], row-major with row length nx + nu),
+    then the T*nx record constants — and its length Ltv (pmt_batch_horizon_dynamics_tv_doubles)."""
+    nab = nx * (nx + nu)
+    Ltv = (T - 1) * nab + T * nx
+    assert Ltv == _lib.load().pmt_batch_horizon_dynamics_tv_doubles(T, nx, nu)
+    return {"AB": [s * nab for s in range(T - 1)], "hconst": (T - 1) * nab}, Ltv
+
+
+class _TimeVaryingDynamics:
+    """A horizon workload with dynamics that change with the stage, x_0 == h_{i,0}, x_t == A_{i,t}*x_{t-1} + B_{i,t}*u_{t-1} + h_{i,t}, in
+    Td = T + term records (the fleet that re-linearises every stage at every solve): A[B][Td-1][nx x nx], B[B][Td-1][nx x nu] and
+    h[B][Td x nx] beside the sibling's inputs (not among `inputs`: those are the sibling's), with seeds of their own and drawn at global
+    element offsets like every input.  One row per instance, [slab (L) | dynamics section (Ltv)]: compute() is the sibling's launch at the
+    row's stride and one launch of pmt_batch_horizon_dynamics_tv_f64 on the same stream; gather_slabs moves the rows as they are; expand()
+    adds the Td records' terms and constants (pmt_batch_horizon_dynamics_tv_expand_f64: it reads no variable past x_{Td-1}) to the sibling's
+    five buffers."""
+
+    def _extra(self, dev):
+        nx, nu = self.nx, self.nu
+        self.Td = self.T + self.term
+        self.dyn_per = {"A": (self.Td - 1) * nx * nx, "B": (self.Td - 1) * nx * nu, "h": self.Td * nx}
+        self.dyn_inputs = self._alloc(self.dyn_per, dev)
+        self.dyn_offsets, self.Ltv = horizon_dynamics_tv_layout(self.Td, nx, nu)
+        return self.Ltv
+
+    def regenerate(self, epoch):
+        super().regenerate(epoch)
+        self._fill(self.dyn_inputs, self.dyn_per, epoch)
+
+    def compute(self):
+        """the sibling's slab, and behind it x_t - A_t*x_{t-1} - B_t*u_{t-1} - h_t for t = 1 .. Td-1"""
+        super().compute()
+        _lib.call("pmt_batch_horizon_dynamics_tv_f64", self._p(self.A), self._p(self.Bm), self._p(self.h), self.B, self.Td, self.nx, self.nu, -1, -1, -1,
+                  C.c_void_p(self.local.data_ptr() + 8 * self.L), self.stride, self.stream)
+
+    def expand(self, i, xvar, varmap):
+        """the sibling's five buffers of local instance i, then the dynamics records' vector-affine terms (3 words each) and constants"""
+        torch, Td, nx, w = self.torch, self.Td, self.nx, self.nx + self.nu
+        dev = self.local.device
+        terms = torch.empty(3 * (nx + (Td - 1) * nx * (1 + w)), dtype=torch.int64, device=dev)
+        consts = torch.empty(Td * nx, dtype=torch.float64, device=dev)
+        five = super().expand(i, xvar, varmap)
+        _lib.call("pmt_batch_horizon_dynamics_tv_expand_f64", C.c_void_p(self.local.data_ptr() + 8 * (i * self.stride + self.L)), Td, nx, self.nu, 1,
+                  self._p(xvar), self._p(varmap), self._p(terms), self._p(consts), self.stream)
+        return five + (terms, consts)
+
+
+class BatchLTVMPC(_TimeVaryingDynamics, BatchHorizon):
+    """BatchHorizon with dynamics of its own per instance and stage (_TimeVaryingDynamics, Td = T records).  m counts further dense rows
+    C_i*z == d_i (default: none)."""
+
+    SEEDS = dict(BatchHorizon.SEEDS, A=310, B=311, h=312)
+
+    def __init__(self, torch, total, T, nx, nu, m=0, rank=0, world=1, device=None):
+        super().__init__(torch, total, T, nx, nu, m, rank, world, device)
+
+
 def horizon_terms_slab_layout(T, nx, nu, m, terminal):
     """Offsets (in doubles) of the sections of one weighted horizon instance's slab [SQ | SR | SP | W | q | const | C | d-consts] over
     n = T*(nx + nu) + term*nx variables — SP only with a terminal stage, W the ns = T*(1 + (nu > 0)) + term stage weights in z order — and
@@ -393,6 +452,17 @@ class BatchWeightedMPC(_Dynamics, BatchWeightedHorizon):
     further dense rows C_i*z == d_i (default: none)."""
 
     SEEDS = dict(BatchWeightedHorizon.SEEDS, A=415, B=416, h=417)
+
+    def __init__(self, torch, total, T, nx, nu, m=0, terminal=True, weights=True, linear=True, signs=(-1, 0, -1, -1), rank=0, world=1, device=None):
+        super().__init__(torch, total, T, nx, nu, m, terminal, weights, linear, signs, rank, world, device)
+
+
+class BatchWeightedLTVMPC(_TimeVaryingDynamics, BatchWeightedHorizon):
+    """BatchWeightedHorizon with dynamics of its own per instance and stage (_TimeVaryingDynamics), as BatchLTVMPC is BatchHorizon with them.
+    With a terminal stage the dynamics have Td = T + 1 records, up to x_T == A_{i,T}*x_{T-1} + B_{i,T}*u_{T-1} + h_{i,T} (so T <= 511 then);
+    without one Td = T.  m counts further dense rows C_i*z == d_i (default: none)."""
+
+    SEEDS = dict(BatchWeightedHorizon.SEEDS, A=418, B=419, h=420)
 
     def __init__(self, torch, total, T, nx, nu, m=0, terminal=True, weights=True, linear=True, signs=(-1, 0, -1, -1), rank=0, world=1, device=None):
         super().__init__(torch, total, T, nx, nu, m, terminal, weights, linear, signs, rank, world, device)
