@@ -1069,6 +1069,61 @@ int pmt_batch_horizon_dynamics_tv_f64(const double *A, const double *Bm, const d
 int pmt_batch_horizon_dynamics_tv_expand_f64(const double *section, int64_t T, int64_t nx, int64_t nu, int sign_xp, const int64_t *xvar,
                                              const int64_t *varmap, pmt_vector_affine_term *out_terms, double *out_consts, void *stream);
 
+/* The batch of horizons with TIME-VARYING stage weights: the fleet that re-linearises every stage at every solve re-linearises its cost as
+ * well — the Gauss-Newton or exact Hessian block of stage t changes with the stage — so instance i has a matrix per stage,
+ *   J_i = sum_{t<T} transpose(x_t (+|-) r_{i,t})*Q_{i,t}*(x_t (+|-) r_{i,t}) + transpose(u_t (+|-) v_{i,t})*R_{i,t}*(u_t (+|-) v_{i,t})
+ *         [+ transpose(x_T (+|-) r_{i,T})*Q_{i,T}*(x_T (+|-) r_{i,T})  when term == 1]
+ * over z = [x_0; u_0; ..; u_{T-1}; (x_T)] subject to the siblings' dense constraint block C_i*z (+|-) d_i: the objective sibling of
+ * pmt_batch_horizon_dynamics_tv_f64, with the limits and error codes of pmt_batch_horizon_coeffs_f64.  With term in {0, 1}
+ *     n = T*(nx + nu) + term*nx variables,   ns = T*(1 + (nu > 0)) + term stages in z order: x_0, u_0, x_1, .., (x_T)  (x_0, x_1, .. with nu == 0).
+ * Inputs are instance-major, then stage-major: Q[B][T+term][nx*nx] and R[B][T][nu*nu], each matrix column-major with leading dimension nx / nu
+ * (they need not be symmetric), r[B][T+term][nx], v[B][T][nu], C[B][m*n] column-major, d[B][m].  The slab of
+ * pmt_batch_horizon_tv_slab_doubles(T, nx, nu, term, m) doubles (host arithmetic) at out + i * out_stride (out_stride >= that length L; the
+ * words between two slabs are never written; every slab word is written exactly once per call) is
+ *     [ S: ns blocks in z order, block s = nd(nd+1)/2 words (nd = nx or nu) | q: n | sconst: ns | const: 1 | C: m*n row-major | d-consts: m ]
+ * fixed bit for bit — plain multiplies and adds, no fma, no floating-point atomics, no workgroup waits for another; independent of B, of the
+ * instance's position, of launch geometry and of timing:
+ *   S           block s is the SQ / SR section of pmt_batch_horizon_coeffs_f64 for that stage's matrix M: M[j,k] + M[k,j] at
+ *               tri(j,k) = j*nd - j*(j-1)/2 + k - j for j < k, 2*M[j,j] on the diagonal.
+ *   q           in z order: stage s's nd words are the lin_j of pmt_quad_form_shift_f64 for (the stage's matrix, its reference, its sign) in
+ *               that node's order (64-column chains, the first product starting the chain, the nb <= 2 blocks in order).  A sign of 0 is the
+ *               plain stage: +0.0, and the reference pointer may be NULL.
+ *   sconst      sconst[s] = the stage's constant 0.5 * T_s in that node's chain-then-tree order; a plain stage: +0.0.
+ *   const       the ns sconst words added in S_d's order — 256 chains onto 0.0, chain c taking the stages c, c + 256, .. in order, then the
+ *               halving tree: what pmt_quad_stages_f64 leaves in *out_const for the instance's own table.
+ *   C, d-consts as in pmt_batch_horizon_coeffs_f64, over the n columns of this z.
+ * Anchors, all exact: with Q_{i,t} = Q_i and R_{i,t} = R_i every S block, q and const equal the words of pmt_batch_horizon_coeffs_f64
+ * (term == 0); block s, the stage's q words and sconst[s] equal the [Q | q | const] slab pmt_batch_form_coeffs_f64 writes for that stage as an
+ * instance of its own (n = nd, m = 0).  Each of nu == 0 (R and v may be NULL), m == 0, term == 0 and T == 1 is a complete slab; B == 0 is
+ * PMT_OK without a launch, whatever the pointers.  A negative dimension, nx outside 1 .. PMT_BATCH_HORIZON_MAX_DIM, nu above it, T outside
+ * 1 .. PMT_BATCH_HORIZON_MAX_T, a term other than 0 or 1 or out_stride < L: PMT_DIMENSION_MISMATCH; a sign outside {-1, 0, 1} or a null pointer
+ * where data is needed (out, Q, R with nu > 0, a reference whose sign is not 0, C and d with m > 0): PMT_INVALID_ARGUMENT — all before any
+ * device call.  No workspace.
+ * A streaming problem — every matrix is read once, about half its bytes are written, nothing is shared between stages — so the work item is
+ * one STAGE, dealt over persistent workgroups of 256 threads; (i, t) follows the item without a division per item, all offsets are 64-bit:
+ * 64 instances of 100 stages fill the device as 800 of 8 do.  The x stages of the batch are contiguous in Q and the u stages in R, so the call
+ * is up to three launches ordered by the stream alone (csrc/batch_horizon_tv.hip): the x stages, the u stages (nu > 0), and a short launch
+ * with a workgroup per instance that adds the instance's sconst words into const and writes C and the d-consts (these ride in that third
+ * launch; with m == 0 it is a wave per instance and const alone).  Stages of nd <= 8 / 16 / 32 / 64 are packed 32 / 16 / 4 / 1 to a
+ * workgroup pass (8, 16, 64 or 256 threads a stage, 8 or 16 loads a thread): the matrix is one tile, symmetrised through LDS from one
+ * load, the next pass's loads issued before this pass's stores, the chain by one thread per row and the tree inside the stage's 8, 16, 32
+ * or 64 lanes.  Stages of 65 .. 128 rows take pmt_batch_form_coeffs_f64's walk of the three upper 64 x 64 tiles.  Four workgroups per CU,
+ * six at nd <= 8.  Algorithmic bytes per instance: 8 ((T+term)(nx^2 + nx) + T(nu^2 + nu) + m n + m) read, 8 L written.
+ * pmt_batch_horizon_tv_expand_f64 rebuilds ONE instance's MOI buffers from its slab, xvar the n model variables of this z and indices through
+ * the varmap (required): out_quad (T (nx(nx+1)/2 + nu(nu+1)/2) + term nx(nx+1)/2 terms), out_lin (n terms) and *out_const are, word for
+ * word, what pmt_quad_stages_check + pmt_quad_stages_f64 write for the instance's own table — the stages laid out one behind the other,
+ * quad_at / lin_at cumulative in z order, stage s's Q pointer at its own matrix; out_vat (m*n terms) and out_vconsts (m) as
+ * pmt_batch_horizon_expand_f64 writes them.  Every output needs 8-byte alignment only.  Errors as the sibling's expansion, and a term other than
+ * 0 or 1: PMT_DIMENSION_MISMATCH.  A streaming launch: 8 L bytes read, 24 / 16 / 24 bytes per term written.
+ * The dynamics beside it: pmt_batch_horizon_dynamics_tv_f64 with T + term records at out + L, both calls at out_stride >= L + Ltv. */
+int64_t pmt_batch_horizon_tv_slab_doubles(int64_t T, int64_t nx, int64_t nu, int64_t term, int64_t m);
+int pmt_batch_horizon_tv_coeffs_f64(const double *Q, const double *R, const double *r, const double *v, const double *C, const double *d,
+                                    int64_t B, int64_t T, int64_t nx, int64_t nu, int64_t term, int64_t m,
+                                    int sign_r, int sign_v, int sign_d, double *out, int64_t out_stride, void *stream);
+int pmt_batch_horizon_tv_expand_f64(const double *slab, int64_t T, int64_t nx, int64_t nu, int64_t term, int64_t m,
+                                    const int64_t *xvar, const int64_t *varmap, pmt_quadratic_term *out_quad, pmt_linear_term *out_lin,
+                                    double *out_const, pmt_vector_affine_term *out_vat, double *out_vconsts, void *stream);
+
 /* The batch of horizons with a terminal cost, a weight per stage and linear stage terms — what pmt_quad_stages_terms_f64 added to the single
  * horizon, for the fleet, still one launch without a workspace:
  *   J_i = sum_{t<T} wx_{i,t} * transpose(x_t (+|-) r_{i,t})*Q_i*(x_t (+|-) r_{i,t}) + dot(gx_{i,t}, x_t)

@@ -744,6 +744,29 @@ batch_horizon_dynamics_tv_expand!(section::DevPtr, T, nx, nu, sign_xp, xvar::Dev
                 (DevPtr, Int64, Int64, Int64, Cint, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
                 section, T, nx, nu, sign_xp, xvar, varmap, out_terms, out_consts, stream))
 
+"doubles of one instance's slab [S: ns blocks in z order | q: n | sconst: ns | const | C: m*n | d-consts: m] of a horizon with a weight matrix
+ per stage, n = T*(nx + nu) + term*nx, ns = T*(1 + (nu > 0)) + term"
+batch_horizon_tv_slab_doubles(T, nx, nu, term, m) =
+    ccall((:pmt_batch_horizon_tv_slab_doubles, lib), Int64, (Int64, Int64, Int64, Int64, Int64), T, nx, nu, term, m)
+
+"one slab per instance for horizons whose stage weights change with the stage: sum_t (x_t ± r_t)'Q_{i,t}(x_t ± r_t) + (u_t ± v_t)'R_{i,t}(u_t ± v_t),
+ with term = 1 a last stage x_T under Q_{i,T}, subject to C_i*z ± d_i (nx, nu <= 128, T <= 512): Q[nbatch][T+term][nx*nx], R[nbatch][T][nu*nu]
+ instance- then stage-major (column-major), r[nbatch][T+term][nx], v[nbatch][T][nu]; every block, q word and constant is what quad_stages!
+ writes for the instance's own table; a sign of 0: the reference may be C_NULL; nu = 0: R and v may be C_NULL"
+batch_horizon_tv_coeffs!(out::DevPtr, out_stride, Q::DevPtr, R::DevPtr, r::DevPtr, v::DevPtr, C::DevPtr, d::DevPtr, nbatch, T, nx, nu, term, m,
+                         sign_r, sign_v, sign_d, stream) =
+    check(ccall((:pmt_batch_horizon_tv_coeffs_f64, lib), Cint,
+                (DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, Int64, Int64, Int64, Int64, Int64, Int64, Cint, Cint, Cint, DevPtr, Int64, Ptr{Cvoid}),
+                Q, R, r, v, C, d, nbatch, T, nx, nu, term, m, sign_r, sign_v, sign_d, out, out_stride, stream))
+
+"one instance's MOI buffers from its slab of batch_horizon_tv_coeffs!, word for word what quad_stages! writes for the instance's own table with
+ stage s's Q at its own matrix; xvar: the n model variables of z, varmap required"
+batch_horizon_tv_expand!(slab::DevPtr, T, nx, nu, term, m, xvar::DevPtr, varmap::DevPtr, out_quad::DevPtr, out_lin::DevPtr, out_const::DevPtr,
+                         out_vat::DevPtr, out_vconsts::DevPtr, stream) =
+    check(ccall((:pmt_batch_horizon_tv_expand_f64, lib), Cint,
+                (DevPtr, Int64, Int64, Int64, Int64, Int64, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
+                slab, T, nx, nu, term, m, xvar, varmap, out_quad, out_lin, out_const, out_vat, out_vconsts, stream))
+
 "pmt_batch_horizon_terms (include/parametron_hip.h): the inputs of batch_horizon_terms_coeffs!, device pointers, instance-major.  C_NULL: P no
  terminal stage, a weight array every weight 1.0, a linear array no linear term, a reference only where its sign is 0; 128 bytes, no padding"
 struct BatchHorizonTerms

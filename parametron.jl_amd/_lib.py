@@ -337,6 +337,9 @@ SIGNATURES = {
     "pmt_batch_horizon_dynamics_tv_doubles": (_i64, [_i64, _i64, _i64]),
     "pmt_batch_horizon_dynamics_tv_f64": (_ci, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _ci, _ci, _ci, _vp, _i64, _vp]),
     "pmt_batch_horizon_dynamics_tv_expand_f64": (_ci, [_vp, _i64, _i64, _i64, _ci, _vp, _vp, _vp, _vp, _vp]),
+    "pmt_batch_horizon_tv_slab_doubles": (_i64, [_i64, _i64, _i64, _i64, _i64]),
+    "pmt_batch_horizon_tv_coeffs_f64": (_ci, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _ci, _ci, _ci, _vp, _i64, _vp]),
+    "pmt_batch_horizon_tv_expand_f64": (_ci, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pmt_quad_stages_check": (_ci, [_vp, _i64, _i64, _i64]),
     "pmt_quad_stages_f64": (_ci, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pmt_quad_stages_terms_check": (_ci, [_vp, _vp, _i64, _vp, _i64, _i64, _i64]),

@@ -468,7 +468,67 @@ class BatchWeightedLTVMPC(_TimeVaryingDynamics, BatchWeightedHorizon):
         super().__init__(torch, total, T, nx, nu, m, terminal, weights, linear, signs, rank, world, device)
 
 
-TOTAL, N, R, M = 8192, 128, 128, 16        # BASELINE config 4 (m is not stated there: 16)
+def horizon_tv_slab_layout(T, nx, nu, m, terminal):
+    """Offsets (in doubles) of the sections of one instance's slab [S | q | sconst | const | C | d-consts] of a horizon with a weight matrix
+    per stage, over n = T*(nx + nu) + term*nx variables — "S" the list of the ns = T*(1 + (nu > 0)) + term blocks' offsets in z order
+    (x_0, u_0, x_1, .., x_T; block s holds nd(nd+1)/2 words, nd = nx or nu), sconst the ns stage constants — and the slab length
+    (pmt_batch_horizon_tv_slab_doubles)."""
+    term = 1 if terminal else 0
+    n, ns = T * (nx + nu) + term * nx, T * (2 if nu else 1) + term
+    nqx, nqu = nx * (nx + 1) // 2, nu * (nu + 1) // 2
+    blocks = []
+    for t in range(T + term):
+        blocks.append(t * (nqx + nqu))
+        if nu and t < T:
+            blocks.append(t * (nqx + nqu) + nqx)
+    q = T * (nqx + nqu) + term * nqx
+    off = {"S": blocks, "q": q, "sconst": q + n, "const": q + n + ns, "C": q + n + ns + 1, "dconst": q + n + ns + 1 + m * n}
+    L = q + n + ns + 1 + m * n + m
+    assert L == _lib.load().pmt_batch_horizon_tv_slab_doubles(T, nx, nu, term, m)
+    return off, L
+
+
+class BatchTVHorizon(_HorizonBatch):
+    """Device-resident batch of MPC horizons whose stage weights change with the stage,
+        sum_t transpose(x_t - r_{i,t}) * Q_{i,t} * (x_t - r_{i,t}) + transpose(u_t) * R_{i,t} * u_t  [+ transpose(x_T - r_{i,T}) * Q_{i,T} * (x_T - r_{i,T})]
+    over C_i*z == d_i, z = [x_0; u_0; ..; u_{T-1}; (x_T)] — the fleet that re-linearises its cost at every stage and solve (a Gauss-Newton or
+    exact Hessian block per stage): Q[B][T+term][nx x nx], R[B][T][nu x nu], r[B][T+term][nx], v[B][T][nu], C[B][m x n], d[B][m].
+    `terminal` adds the stage x_T with a matrix and a reference of its own.  pmt_batch_horizon_tv_coeffs_f64 writes the slabs
+    (horizon_tv_slab_layout); gather_slabs takes them as they are; expand() rebuilds one instance's MOI buffers.  There is no pipelined
+    exchange for this objective: step() is compute() and one all-gather."""
+
+    SEEDS = {"Q": 501, "R": 502, "r": 503, "v": 504, "C": 505, "d": 506}
+    EXPAND = "pmt_batch_horizon_tv_expand_f64"
+
+    def __init__(self, torch, total, T, nx, nu, m, terminal=False, rank=0, world=1, device=None):
+        self.term = 1 if terminal else 0
+        self.n = T * (nx + nu) + self.term * nx
+        Tx = T + self.term
+        super().__init__(torch, total, T, nx, nu, m, rank, world, device,
+                         {"Q": Tx * nx * nx, "R": T * nu * nu, "r": Tx * nx, "v": T * nu, "C": m * self.n, "d": m},
+                         horizon_tv_slab_layout(T, nx, nu, m, terminal))
+
+    def compute(self):
+        """x_t - r_t, u_t as it is, C*z - d"""
+        _lib.call("pmt_batch_horizon_tv_coeffs_f64", self._p(self.Q), self._p(self.R), self._p(self.r), self._p(self.v), self._p(self.Cm),
+                  self._p(self.d), self.B, self.T, self.nx, self.nu, self.term, self.m, -1, 0, -1, self._p(self.local), self.stride, self.stream)
+
+    def _expand_dims(self):
+        return self.T, self.nx, self.nu, self.term, self.m
+
+
+class BatchTVMPC(_TimeVaryingDynamics, BatchTVHorizon):
+    """BatchTVHorizon with dynamics of its own per instance and stage (_TimeVaryingDynamics): time-varying weights and time-varying dynamics
+    in one row [slab | Ltv].  With a terminal stage the dynamics have Td = T + 1 records, up to x_T == A_{i,T}*x_{T-1} + B_{i,T}*u_{T-1} +
+    h_{i,T} (so T <= 511 then); without one Td = T.  m counts further dense rows C_i*z == d_i (default: none)."""
+
+    SEEDS = dict(BatchTVHorizon.SEEDS, A=507, B=508, h=509)
+
+    def __init__(self, torch, total, T, nx, nu, m=0, terminal=False, rank=0, world=1, device=None):
+        super().__init__(torch, total, T, nx, nu, m, terminal, rank, world, device)
+
+
+TOTAL, N, R, M = 8192, 128, 128, 16      # BASELINE config 4 (m is not stated there: 16, SURVEY.md section 8d)
 
 
 def sharded_report(world, ranks_seen, steps, warmup, t_pipe, t_mono, t_compute, nchunks, total=TOTAL, n=N, r=R, m=M):
