@@ -206,11 +206,16 @@ class BatchTracking(_Batch):
                   -1, -1, self._p(self.local), self.L, self.stream)
 
 
+def horizon_sizes(T, nx, nu, term=0):
+    """What every horizon layout counts: (nqx, nqu, n, ns) — the words of the upper triangle of an nx x nx and of an nu x nu matrix, the
+    n = T*(nx + nu) + term*nx variables of z, the ns = T*(1 + (nu > 0)) + term stages in z order."""
+    return nx * (nx + 1) // 2, nu * (nu + 1) // 2, T * (nx + nu) + term * nx, T * (2 if nu else 1) + term
+
+
 def horizon_slab_layout(T, nx, nu, m):
     """Offsets (in doubles) of the sections of one horizon instance's slab [SQ | SR | q | const | C | d-consts] over n = T*(nx + nu)
     variables, and the slab length (pmt_batch_horizon_slab_doubles)."""
-    n = T * (nx + nu)
-    nqx, nqu = nx * (nx + 1) // 2, nu * (nu + 1) // 2
+    nqx, nqu, n, _ = horizon_sizes(T, nx, nu)
     q = nqx + nqu
     off = {"SQ": 0, "SR": nqx, "q": q, "const": q + n, "C": q + n + 1, "dconst": q + n + 1 + m * n}
     return off, q + n + 1 + m * n + m
@@ -277,30 +282,36 @@ def horizon_dynamics_layout(T, nx, nu):
     return {"AB": 0, "hconst": nab}, nab + T * nx
 
 
-class _Dynamics:
-    """A horizon workload with the instances' own dynamics x_0 == h_{i,0}, x_t == A_i*x_{t-1} + B_i*u_{t-1} + h_{i,t} in Td = T + term
-    records: A[B][nx x nx], B[B][nx x nu] and h[B][Td x nx] beside the sibling's inputs (not among `inputs`: those are the sibling's).  One
-    row per instance, [slab (L) | dynamics section (Ld)]: compute() is the sibling's launch at the row's stride and one launch of
-    pmt_batch_horizon_dynamics_f64 on the same stream; gather_slabs moves the rows as they are; expand() adds the Td records' terms and
-    constants (pmt_batch_horizon_dynamics_expand_f64: it reads no variable past x_{Td-1}) to the sibling's five buffers."""
+class _DynamicsRows:
+    """A horizon workload with dynamics rows of the instances' own in Td = T + term records: A, B and h[B][Td x nx] beside the sibling's
+    inputs (not among `inputs`: those are the sibling's), with seeds of their own and drawn at global element offsets like every input.
+    One row per instance, [slab (L) | dynamics section]: compute() is the sibling's launch at the row's stride and one launch of DYN_COEFFS
+    on the same stream; gather_slabs moves the rows as they are; expand() adds the Td records' terms and constants (DYN_EXPAND: it reads no
+    variable past x_{Td-1}) to the sibling's five buffers.  A subclass names the two entry points, the section's layout function with the
+    attribute that holds its length, and how many [A | B] pairs an instance has."""
+
+    DYN_COEFFS = DYN_EXPAND = DYN_LAYOUT = None
 
     def _extra(self, dev):
         nx, nu = self.nx, self.nu
         self.Td = self.T + self.term
-        self.dyn_per = {"A": nx * nx, "B": nx * nu, "h": self.Td * nx}
+        pairs = self._pairs()
+        self.dyn_per = {"A": pairs * nx * nx, "B": pairs * nx * nu, "h": self.Td * nx}
         self.dyn_inputs = self._alloc(self.dyn_per, dev)
-        self.dyn_offsets, self.Ld = horizon_dynamics_layout(self.Td, nx, nu)
-        assert self.Ld == _lib.load().pmt_batch_horizon_dynamics_doubles(self.Td, nx, nu)
-        return self.Ld
+        layout, length = self.DYN_LAYOUT
+        self.dyn_offsets, Ld = layout(self.Td, nx, nu)
+        assert Ld == getattr(_lib.load(), self.DYN_COEFFS.replace("_f64", "_doubles"))(self.Td, nx, nu)
+        setattr(self, length, Ld)
+        return Ld
 
     def regenerate(self, epoch):
         super().regenerate(epoch)
         self._fill(self.dyn_inputs, self.dyn_per, epoch)
 
     def compute(self):
-        """the sibling's slab, and behind it x_t - A*x_{t-1} - B*u_{t-1} - h_t for t = 1 .. Td-1"""
+        """the sibling's slab, and behind it x_t - A*x_{t-1} - B*u_{t-1} - h_t for t = 1 .. Td-1 (A, B the stage's own where they vary)"""
         super().compute()
-        _lib.call("pmt_batch_horizon_dynamics_f64", self._p(self.A), self._p(self.Bm), self._p(self.h), self.B, self.Td, self.nx, self.nu, -1, -1, -1,
+        _lib.call(self.DYN_COEFFS, self._p(self.A), self._p(self.Bm), self._p(self.h), self.B, self.Td, self.nx, self.nu, -1, -1, -1,
                   C.c_void_p(self.local.data_ptr() + 8 * self.L), self.stride, self.stream)
 
     def expand(self, i, xvar, varmap):
@@ -310,9 +321,20 @@ class _Dynamics:
         terms = torch.empty(3 * (nx + (Td - 1) * nx * (1 + w)), dtype=torch.int64, device=dev)
         consts = torch.empty(Td * nx, dtype=torch.float64, device=dev)
         five = super().expand(i, xvar, varmap)
-        _lib.call("pmt_batch_horizon_dynamics_expand_f64", C.c_void_p(self.local.data_ptr() + 8 * (i * self.stride + self.L)), Td, nx, self.nu, 1,
-                  self._p(xvar), self._p(varmap), self._p(terms), self._p(consts), self.stream)
+        _lib.call(self.DYN_EXPAND, C.c_void_p(self.local.data_ptr() + 8 * (i * self.stride + self.L)), Td, nx, self.nu, 1, self._p(xvar),
+                  self._p(varmap), self._p(terms), self._p(consts), self.stream)
         return five + (terms, consts)
+
+
+class _Dynamics(_DynamicsRows):
+    """_DynamicsRows with one pair per instance, x_0 == h_{i,0}, x_t == A_i*x_{t-1} + B_i*u_{t-1} + h_{i,t}: A[B][nx x nx], B[B][nx x nu]; the
+    section [AB | h-consts] of Ld doubles."""
+
+    DYN_COEFFS, DYN_EXPAND = "pmt_batch_horizon_dynamics_f64", "pmt_batch_horizon_dynamics_expand_f64"
+    DYN_LAYOUT = (horizon_dynamics_layout, "Ld")
+
+    def _pairs(self):
+        return 1
 
 
 class BatchMPC(_Dynamics, BatchHorizon):
@@ -334,43 +356,15 @@ def horizon_dynamics_tv_layout(T, nx, nu):
     return {"AB": [s * nab for s in range(T - 1)], "hconst": (T - 1) * nab}, Ltv
 
 
-class _TimeVaryingDynamics:
-    """A horizon workload with dynamics that change with the stage, x_0 == h_{i,0}, x_t == A_{i,t}*x_{t-1} + B_{i,t}*u_{t-1} + h_{i,t}, in
-    Td = T + term records (the fleet that re-linearises every stage at every solve): A[B][Td-1][nx x nx], B[B][Td-1][nx x nu] and
-    h[B][Td x nx] beside the sibling's inputs (not among `inputs`: those are the sibling's), with seeds of their own and drawn at global
-    element offsets like every input.  One row per instance, [slab (L) | dynamics section (Ltv)]: compute() is the sibling's launch at the
-    row's stride and one launch of pmt_batch_horizon_dynamics_tv_f64 on the same stream; gather_slabs moves the rows as they are; expand()
-    adds the Td records' terms and constants (pmt_batch_horizon_dynamics_tv_expand_f64: it reads no variable past x_{Td-1}) to the sibling's
-    five buffers."""
+class _TimeVaryingDynamics(_DynamicsRows):
+    """_DynamicsRows with a pair per stage, x_0 == h_{i,0}, x_t == A_{i,t}*x_{t-1} + B_{i,t}*u_{t-1} + h_{i,t} (the fleet that re-linearises
+    every stage at every solve): A[B][Td-1][nx x nx], B[B][Td-1][nx x nu]; the section [AB_1 | .. | AB_{Td-1} | h-consts] of Ltv doubles."""
 
-    def _extra(self, dev):
-        nx, nu = self.nx, self.nu
-        self.Td = self.T + self.term
-        self.dyn_per = {"A": (self.Td - 1) * nx * nx, "B": (self.Td - 1) * nx * nu, "h": self.Td * nx}
-        self.dyn_inputs = self._alloc(self.dyn_per, dev)
-        self.dyn_offsets, self.Ltv = horizon_dynamics_tv_layout(self.Td, nx, nu)
-        return self.Ltv
+    DYN_COEFFS, DYN_EXPAND = "pmt_batch_horizon_dynamics_tv_f64", "pmt_batch_horizon_dynamics_tv_expand_f64"
+    DYN_LAYOUT = (horizon_dynamics_tv_layout, "Ltv")
 
-    def regenerate(self, epoch):
-        super().regenerate(epoch)
-        self._fill(self.dyn_inputs, self.dyn_per, epoch)
-
-    def compute(self):
-        """the sibling's slab, and behind it x_t - A_t*x_{t-1} - B_t*u_{t-1} - h_t for t = 1 .. Td-1"""
-        super().compute()
-        _lib.call("pmt_batch_horizon_dynamics_tv_f64", self._p(self.A), self._p(self.Bm), self._p(self.h), self.B, self.Td, self.nx, self.nu, -1, -1, -1,
-                  C.c_void_p(self.local.data_ptr() + 8 * self.L), self.stride, self.stream)
-
-    def expand(self, i, xvar, varmap):
-        """the sibling's five buffers of local instance i, then the dynamics records' vector-affine terms (3 words each) and constants"""
-        torch, Td, nx, w = self.torch, self.Td, self.nx, self.nx + self.nu
-        dev = self.local.device
-        terms = torch.empty(3 * (nx + (Td - 1) * nx * (1 + w)), dtype=torch.int64, device=dev)
-        consts = torch.empty(Td * nx, dtype=torch.float64, device=dev)
-        five = super().expand(i, xvar, varmap)
-        _lib.call("pmt_batch_horizon_dynamics_tv_expand_f64", C.c_void_p(self.local.data_ptr() + 8 * (i * self.stride + self.L)), Td, nx, self.nu, 1,
-                  self._p(xvar), self._p(varmap), self._p(terms), self._p(consts), self.stream)
-        return five + (terms, consts)
+    def _pairs(self):
+        return self.Td - 1
 
 
 class BatchLTVMPC(_TimeVaryingDynamics, BatchHorizon):
@@ -388,8 +382,7 @@ def horizon_terms_slab_layout(T, nx, nu, m, terminal):
     n = T*(nx + nu) + term*nx variables — SP only with a terminal stage, W the ns = T*(1 + (nu > 0)) + term stage weights in z order — and
     the slab length (pmt_batch_horizon_terms_slab_doubles)."""
     term = 1 if terminal else 0
-    n, ns = T * (nx + nu) + term * nx, T * (2 if nu else 1) + term
-    nqx, nqu = nx * (nx + 1) // 2, nu * (nu + 1) // 2
+    nqx, nqu, n, ns = horizon_sizes(T, nx, nu, term)
     w0 = nqx + nqu + term * nqx
     q = w0 + ns
     off = {"SQ": 0, "SR": nqx, "SP": nqx + nqu, "W": w0, "q": q, "const": q + n, "C": q + n + 1, "dconst": q + n + 1 + m * n}
@@ -474,8 +467,7 @@ def horizon_tv_slab_layout(T, nx, nu, m, terminal):
     (x_0, u_0, x_1, .., x_T; block s holds nd(nd+1)/2 words, nd = nx or nu), sconst the ns stage constants — and the slab length
     (pmt_batch_horizon_tv_slab_doubles)."""
     term = 1 if terminal else 0
-    n, ns = T * (nx + nu) + term * nx, T * (2 if nu else 1) + term
-    nqx, nqu = nx * (nx + 1) // 2, nu * (nu + 1) // 2
+    nqx, nqu, n, ns = horizon_sizes(T, nx, nu, term)
     blocks = []
     for t in range(T + term):
         blocks.append(t * (nqx + nqu))

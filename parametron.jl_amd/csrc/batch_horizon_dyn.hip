@@ -22,30 +22,17 @@
 // the lanes walk the AB words in output order and read the entry each needs (the whole matrix is at most 4 KB, the reads of a wave fall
 // into its few cache lines), eight clamped loads per lane in flight; no LDS, no barrier.  The words are copies either way.
 //
-// pmt_batch_horizon_dynamics_expand_f64 rebuilds one instance's MOI buffers from its section: a streaming writer.  A workgroup per four
-// rows of a stage t >= 1: the stage's nx + nu index words vm[xvar[..]] are fetched once into LDS, then a wave per row writes its
-// 1 + nx + nu terms through wave_write_words (common.h), each AB word read by the one lane that stores it.  One more item writes stage 0,
-// the rest copy the constants, 256 each.
-#include <algorithm>
-
-#include "common.h"
+// pmt_batch_horizon_dynamics_expand_f64 rebuilds one instance's MOI buffers from its section: the streaming writer both dynamics files
+// share (dynamics_expand<false>, dynamics_tile.h, where the tile's loads, the small path's word source, the constants of the launch
+// shape and the dimension check lie too).
+#include "dynamics_tile.h"
 
 namespace pmt {
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int BD_THREADS = 256;
-constexpr int BD_WAVES = BD_THREADS / 64;
-constexpr int BD_TILE_WORDS = 4096;          // rows x columns of a tile: 16 loads per thread
+constexpr int BD_LOADS = 16;                 // loads per thread of a tile: 4096 words
 constexpr int BD_WG_PER_CU = 4;              // resident workgroups per CU of the tile kernel (LDS: 33280 bytes each)
-constexpr int BD_SMALL_WORDS = 512;          // AB words up to which an instance takes a wave: eight loads per lane
-constexpr int BD_SMALL_WG_PER_CU = 8;
-constexpr int BD_EXPAND_ROWS = BD_WAVES;     // rows of a stage per work item of the expansion: one per wave
-constexpr int BD_MAX_DIM = PMT_BATCH_HORIZON_MAX_DIM, BD_MAX_T = PMT_BATCH_HORIZON_MAX_T;
-constexpr u64 BD_SIGN_BIT = 0x8000000000000000ull;
-static_assert(2 * BD_MAX_DIM <= BD_THREADS, "one thread per index word of a stage; a 16-row tile holds a whole row of [A | B]");
 
 struct BatchDynArgs {
     const u64 *A, *Bm;                       // instance-major: A[B][nx*nx], Bm[B][nx*nu] column-major, leading dimension nx
@@ -79,10 +66,10 @@ __device__ __forceinline__ void bd_consts(const double *__restrict__ h, int sign
 
 }  // namespace
 
-// RL rows x CW = 4096 / RL columns a tile; thread (lr = tid % RL, lc = tid / RL) loads the columns lc, lc + 256 / RL, ..
+// RL rows x CW = 4096 / RL columns a tile (dynamics_tile.h), one instance per pass of a workgroup
 template <int RL>
-__global__ __launch_bounds__(BD_THREADS) void batch_horizon_dyn_kernel(BatchDynArgs g) {
-    constexpr int CW = BD_TILE_WORDS / RL, PITCH = CW + 1, CSTEP = BD_THREADS / RL;
+__global__ __launch_bounds__(DY_THREADS) void batch_horizon_dyn_kernel(BatchDynArgs g) {
+    constexpr int CW = DY_THREADS * BD_LOADS / RL, PITCH = CW + 1, CSTEP = DY_THREADS / RL;
     __shared__ u64 tile[RL * PITCH];
     const int T = g.T, nx = g.nx, nu = g.nu, w = nx + nu;
     const int tid = threadIdx.x;
@@ -92,32 +79,24 @@ __global__ __launch_bounds__(BD_THREADS) void batch_horizon_dyn_kernel(BatchDynA
         const u64 *__restrict__ Ai = g.A + inst * nx * nx;
         const u64 *__restrict__ Bi = nu ? g.Bm + inst * nx * nu : Ai;            // (nu == 0: no column selects it)
         u64 *__restrict__ out = reinterpret_cast<u64 *>(g.out + inst * g.out_stride);
-        bd_consts(g.sign_h ? g.h + inst * T * nx : nullptr, g.sign_h, T * nx, g.out + inst * g.out_stride + (int64_t)nx * w, tid, BD_THREADS);
+        bd_consts(g.sign_h ? g.h + inst * T * nx : nullptr, g.sign_h, T * nx, g.out + inst * g.out_stride + (int64_t)nx * w, tid, DY_THREADS);
 
         for (int r0 = 0; r0 < nx; r0 += RL) {
             for (int c0 = 0; c0 < w; c0 += CW) {
-                // (the thread's coordinates are made opaque per tile: derived from loop invariants, the compiler otherwise keeps every
-                // address of the unrolled body alive across the whole instance loop)
-                int lr = tid % RL, lc = tid / RL;
-                asm volatile("" : "+v"(lr), "+v"(lc));
-                const int r = r0 + lr;
-                const unsigned rc = (unsigned)(r < nx ? r : nx - 1);
-                u64 v[16];
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int c = c0 + lc + CSTEP * i, cc = c < w ? c : w - 1;
-                    const u64 *__restrict__ col = cc < nx ? Ai + (unsigned)cc * (unsigned)nx : Bi + (unsigned)(cc - nx) * (unsigned)nx;
-                    v[i] = col[rc];
-                }
+                int lr, lc;
+                u64 v[BD_LOADS];
+                dynamics_tile_load<RL, BD_LOADS>(Ai, Bi, nx, w, r0, c0, tid, v, lr, lc);
                 landed(v);
                 // tile[row][column], each word with its part's sign
+                // (batch_horizon_ltv.hip holds this store too: moved into a shared function it compiles to other device code)
 #pragma unroll
-                for (int i = 0; i < 16; ++i) tile[lr * PITCH + lc + CSTEP * i] = v[i] ^ (c0 + lc + CSTEP * i < nx ? flip_a : flip_b);
+                for (int i = 0; i < BD_LOADS; ++i) tile[lr * PITCH + lc + CSTEP * i] = v[i] ^ (c0 + lc + CSTEP * i < nx ? flip_a : flip_b);
                 __syncthreads();
                 // a wave per row, the column on the lanes
+                // (batch_horizon_ltv.hip holds this write-out too: moved into a shared function it compiles to other device code)
                 const int lane = tid & 63, wave = tid >> 6;
                 const int nr = nx - r0 < RL ? nx - r0 : RL, nc = w - c0 < CW ? w - c0 : CW;
-                for (int rr = wave; rr < nr; rr += BD_WAVES) {
+                for (int rr = wave; rr < nr; rr += DY_WAVES) {
                     u64 *__restrict__ orow = out + (int64_t)(r0 + rr) * w + c0;
                     for (int c = lane; c < nc; c += 64) orow[c] = tile[rr * PITCH + c];
                 }
@@ -127,32 +106,27 @@ __global__ __launch_bounds__(BD_THREADS) void batch_horizon_dyn_kernel(BatchDynA
     }
 }
 
-// A wave per instance of at most BD_SMALL_WORDS AB words: lane l writes the words l, l + 64, .. of AB in output order
-__global__ __launch_bounds__(BD_THREADS) void batch_horizon_dyn_small_kernel(BatchDynArgs g) {
+// A wave per instance of at most DY_SMALL_WORDS AB words (dynamics_tile.h)
+__global__ __launch_bounds__(DY_THREADS) void batch_horizon_dyn_small_kernel(BatchDynArgs g) {
     const int T = g.T, nx = g.nx, nu = g.nu, w = nx + nu, nab = nx * w;
     const int lane = threadIdx.x & 63;
-    const int64_t wv = (int64_t)blockIdx.x * BD_WAVES + (threadIdx.x >> 6), nwv = (int64_t)gridDim.x * BD_WAVES;
+    const int64_t wv = (int64_t)blockIdx.x * DY_WAVES + (threadIdx.x >> 6), nwv = (int64_t)gridDim.x * DY_WAVES;
     const u64 flip_a = g.flip_a, flip_b = g.flip_b;
-    // the word's source: row r = e / w, column j = e - r*w of [A | B]  (the same for every instance)
-    unsigned src[BD_SMALL_WORDS / 64];
-    bool from_a[BD_SMALL_WORDS / 64];
+    unsigned src[DY_SMALL_LOADS];
+    bool from_a[DY_SMALL_LOADS];
 #pragma unroll
-    for (int k = 0; k < BD_SMALL_WORDS / 64; ++k) {
-        const int e = lane + 64 * k, ec = e < nab ? e : nab - 1;
-        const int r = ec / w, j = ec - r * w;
-        from_a[k] = j < nx;
-        src[k] = (unsigned)(r + (j < nx ? j : j - nx) * nx);
-    }
+    for (int k = 0; k < DY_SMALL_LOADS; ++k) src[k] = dynamics_small_source(lane + 64 * k, nx, w, nab, from_a[k]);
     for (int64_t inst = wv; inst < g.B; inst += nwv) {
         const u64 *__restrict__ Ai = g.A + inst * nx * nx;
         const u64 *__restrict__ Bi = nu ? g.Bm + inst * nx * nu : Ai;            // (nu == 0: no word selects it)
         u64 *__restrict__ out = reinterpret_cast<u64 *>(g.out + inst * g.out_stride);
-        u64 v[BD_SMALL_WORDS / 64];
+        // (batch_horizon_ltv.hip holds the load and the flip / store loop too: moved into shared functions they compile to other device code)
+        u64 v[DY_SMALL_LOADS];
 #pragma unroll
-        for (int k = 0; k < BD_SMALL_WORDS / 64; ++k) v[k] = (from_a[k] ? Ai : Bi)[src[k]];
+        for (int k = 0; k < DY_SMALL_LOADS; ++k) v[k] = (from_a[k] ? Ai : Bi)[src[k]];
         landed(v);
 #pragma unroll
-        for (int k = 0; k < BD_SMALL_WORDS / 64; ++k) {
+        for (int k = 0; k < DY_SMALL_LOADS; ++k) {
             const int e = lane + 64 * k;
             if (e < nab) out[e] = v[k] ^ (from_a[k] ? flip_a : flip_b);
         }
@@ -160,57 +134,10 @@ __global__ __launch_bounds__(BD_THREADS) void batch_horizon_dyn_small_kernel(Bat
     }
 }
 
-// One instance's records from its section.  Items, dealt out over the workgroups: (stage t >= 1, four rows), then stage 0, then the
-// constants 256 at a time.
-__global__ __launch_bounds__(BD_THREADS) void batch_horizon_dyn_expand_kernel(const double *__restrict__ section, int T, int nx, int nu, int sign_xp,
+__global__ __launch_bounds__(DY_THREADS) void batch_horizon_dyn_expand_kernel(const double *__restrict__ section, int T, int nx, int nu, int sign_xp,
                                                                                const int64_t *__restrict__ xvar, const int64_t *__restrict__ varmap,
                                                                                u64 *__restrict__ terms, double *__restrict__ consts) {
-    __shared__ u64 vmx[BD_THREADS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int w = nx + nu, row_len = 1 + w, bands = (nx + BD_EXPAND_ROWS - 1) / BD_EXPAND_ROWS, nconst = T * nx;
-    const int64_t ndyn = (int64_t)(T - 1) * bands, nitems = ndyn + 1 + (nconst + BD_THREADS - 1) / BD_THREADS;
-    const u64 *__restrict__ ab = reinterpret_cast<const u64 *>(section);
-    const u64 one = (u64)__double_as_longlong(1.0) ^ (sign_xp < 0 ? BD_SIGN_BIT : 0);
-    for (int64_t it = blockIdx.x; it < nitems; it += gridDim.x) {
-        if (it < ndyn) {
-            const int t = 1 + (int)(it / bands), r = (int)(it % bands) * BD_EXPAND_ROWS + wave;
-            // the columns of the stage's rows: the contiguous slice xvar[(t-1)*w .. t*w)
-            if (tid < w) vmx[tid] = (u64)map_var(varmap, xvar[(int64_t)(t - 1) * w + tid]);
-            __syncthreads();
-            if (r < nx) {
-                const u64 rowidx = (u64)(r + 1), xp = (u64)map_var(varmap, xvar[(int64_t)t * w + r]);
-                const u64 *__restrict__ row = ab + r * w;
-                wave_write_words<3>(terms + 3 * (nx + ((int64_t)(t - 1) * nx + r) * row_len), row_len, lane, [&](int q) -> u64 {
-                    const int e = q / 3, f = q - 3 * e;
-                    if (f == 0) return rowidx;
-                    if (e == 0) return f == 1 ? one : xp;
-                    return f == 1 ? row[e - 1] : vmx[e - 1];
-                });
-            }
-            __syncthreads();                              // the next item reuses vmx
-        } else if (it == ndyn) {
-            // stage 0: row i holds (i + 1, +-1.0, vm[xvar[i]])
-            for (int i0 = wave * 64; i0 < nx; i0 += BD_THREADS) {
-                wave_write_words<3>(terms + 3 * i0, nx - i0 < 64 ? nx - i0 : 64, lane, [&](int q) -> u64 {
-                    const int e = q / 3, f = q - 3 * e;
-                    if (f == 0) return (u64)(i0 + e + 1);
-                    return f == 1 ? one : (u64)map_var(varmap, xvar[i0 + e]);
-                });
-            }
-        } else {
-            const int i = (int)(it - ndyn - 1) * BD_THREADS + tid;
-            if (i < nconst) consts[i] = section[nx * w + i];
-        }
-    }
-}
-
-// the dimension checks both entry points share; `who` words the message
-static int bd_check_dims(const char *who, int64_t T, int64_t nx, int64_t nu) {
-    const std::string w(who);
-    PMT_REQUIRE(nx >= 1 && nx <= BD_MAX_DIM, PMT_DIMENSION_MISMATCH, w + ": nx outside 1 .. 128");
-    PMT_REQUIRE(nu >= 0 && nu <= BD_MAX_DIM, PMT_DIMENSION_MISMATCH, w + ": nu outside 0 .. 128");
-    PMT_REQUIRE(T >= 1 && T <= BD_MAX_T, PMT_DIMENSION_MISMATCH, w + ": T outside 1 .. 512");
-    return PMT_OK;
+    dynamics_expand<false>(section, T, nx, nu, sign_xp, xvar, varmap, terms, consts);
 }
 
 }  // namespace pmt
@@ -222,7 +149,7 @@ extern "C" int64_t pmt_batch_horizon_dynamics_doubles(int64_t T, int64_t nx, int
 extern "C" int pmt_batch_horizon_dynamics_f64(const double *A, const double *Bm, const double *h, int64_t B, int64_t T, int64_t nx, int64_t nu,
                                               int sign_a, int sign_b, int sign_h, double *out, int64_t out_stride, void *stream) {
     PMT_REQUIRE(B >= 0, PMT_DIMENSION_MISMATCH, "batch_horizon_dynamics: negative instance count");
-    const int rc = bd_check_dims("batch_horizon_dynamics", T, nx, nu);
+    const int rc = dynamics_check_dims("batch_horizon_dynamics", T, nx, nu);
     if (rc != PMT_OK) return rc;
     PMT_REQUIRE(out_stride >= pmt_batch_horizon_dynamics_doubles(T, nx, nu), PMT_DIMENSION_MISMATCH,
                 "batch_horizon_dynamics: out_stride smaller than the section");
@@ -235,33 +162,30 @@ extern "C" int pmt_batch_horizon_dynamics_f64(const double *A, const double *Bm,
     g.A = reinterpret_cast<const u64 *>(A); g.Bm = reinterpret_cast<const u64 *>(Bm); g.h = h;
     g.B = B;
     g.T = (int)T; g.nx = (int)nx; g.nu = (int)nu; g.sign_h = sign_h;
-    g.flip_a = sign_a < 0 ? BD_SIGN_BIT : 0; g.flip_b = sign_b < 0 ? BD_SIGN_BIT : 0;
+    g.flip_a = sign_a < 0 ? DY_SIGN_BIT : 0; g.flip_b = sign_b < 0 ? DY_SIGN_BIT : 0;
     g.out = out; g.out_stride = out_stride;
     return dispatch(stream, [=](hipStream_t s) {
-        if (g.nx * (g.nx + g.nu) <= BD_SMALL_WORDS) {
-            const dim3 grid((unsigned)std::min<int64_t>(cdiv(B, BD_WAVES), (int64_t)BD_SMALL_WG_PER_CU * cu_count()));
-            PMT_LAUNCH(batch_horizon_dyn_small_kernel, grid, dim3(BD_THREADS), 0, s, g);
+        if (g.nx * (g.nx + g.nu) <= DY_SMALL_WORDS) {
+            const dim3 grid((unsigned)std::min<int64_t>(cdiv(B, DY_WAVES), (int64_t)DY_SMALL_WG_PER_CU * cu_count()));
+            PMT_LAUNCH(batch_horizon_dyn_small_kernel, grid, dim3(DY_THREADS), 0, s, g);
             return check_launch("batch_horizon_dyn_small_kernel");
         }
         const dim3 grid((unsigned)std::min<int64_t>(B, (int64_t)BD_WG_PER_CU * cu_count()));
-        if (g.nx <= 16) PMT_LAUNCH(batch_horizon_dyn_kernel<16>, grid, dim3(BD_THREADS), 0, s, g);
-        else if (g.nx <= 32) PMT_LAUNCH(batch_horizon_dyn_kernel<32>, grid, dim3(BD_THREADS), 0, s, g);
-        else PMT_LAUNCH(batch_horizon_dyn_kernel<64>, grid, dim3(BD_THREADS), 0, s, g);
+        if (g.nx <= 16) PMT_LAUNCH(batch_horizon_dyn_kernel<16>, grid, dim3(DY_THREADS), 0, s, g);
+        else if (g.nx <= 32) PMT_LAUNCH(batch_horizon_dyn_kernel<32>, grid, dim3(DY_THREADS), 0, s, g);
+        else PMT_LAUNCH(batch_horizon_dyn_kernel<64>, grid, dim3(DY_THREADS), 0, s, g);
         return check_launch("batch_horizon_dyn_kernel");
     });
 }
 
 extern "C" int pmt_batch_horizon_dynamics_expand_f64(const double *section, int64_t T, int64_t nx, int64_t nu, int sign_xp, const int64_t *xvar,
                                                      const int64_t *varmap, pmt_vector_affine_term *out_terms, double *out_consts, void *stream) {
-    const int rc = bd_check_dims("batch_horizon_dynamics_expand", T, nx, nu);
+    const int rc = dynamics_check_dims("batch_horizon_dynamics_expand", T, nx, nu);
     if (rc != PMT_OK) return rc;
     PMT_REQUIRE(sign_xp == 1 || sign_xp == -1, PMT_INVALID_ARGUMENT, "batch_horizon_dynamics_expand: sign_xp must be +1 or -1");
     PMT_REQUIRE(section && xvar && out_terms && out_consts, PMT_INVALID_ARGUMENT, "batch_horizon_dynamics_expand: null pointer");
     const int iT = (int)T, inx = (int)nx, inu = (int)nu;
     return dispatch(stream, [=](hipStream_t s) {
-        const int64_t items = (int64_t)(iT - 1) * cdiv(inx, BD_EXPAND_ROWS) + 1 + cdiv((int64_t)iT * inx, BD_THREADS);
-        PMT_LAUNCH(batch_horizon_dyn_expand_kernel, dim3((unsigned)std::min<int64_t>(items, (int64_t)8 * cu_count())), dim3(BD_THREADS), 0, s, section, iT,
-                   inx, inu, sign_xp, xvar, varmap, reinterpret_cast<u64 *>(out_terms), out_consts);
-        return check_launch("batch_horizon_dyn_expand_kernel");
+        return dynamics_expand_launch("batch_horizon_dyn_expand_kernel", batch_horizon_dyn_expand_kernel, s, section, iT, inx, inu, sign_xp, xvar, varmap, out_terms, out_consts);
     });
 }

@@ -16,7 +16,7 @@
 // h-consts: item (i, t-1) writes the nx constants of stage t, and the item of t = 1 those of stage 0 with them (2*nx contiguous words, one
 // thread each) — every item carries the same few words, nothing serialises behind one item, and the load rides with the item's first
 // tile.  T == 1 has no item: its section is the constants alone (batch_horizon_ltv_consts_kernel, 256 / nx instances per workgroup pass).
-// Tiles are batch_horizon_dyn.hip's: 4096 words read along the columns (64 x 64, 32 x 128 up to 32 rows, 16 x 256 up to 16), every load
+// Tiles are batch_horizon_dyn.hip's (the loads: dynamics_tile.h): 4096 words read along the columns (64 x 64, 32 x 128 up to 32 rows, 16 x 256 up to 16), every load
 // unconditional on a clamped index and issued before the first value is looked at (landed), lane coordinates opaque per tile, transposed
 // through an LDS tile of pitch columns + 1, rows leaving with the column on the lanes as 8-byte stores.  New here: an item is a few tiles
 // at most (one at (32, 16)), so the walk over (item, row tile, column tile) is ONE loop and the next tile's loads are issued as soon as the
@@ -26,29 +26,18 @@
 // what a launch bound by the bytes it has in flight needs.
 // Pairs of at most 512 AB words take a wave each, four to a workgroup, without LDS (batch_horizon_ltv_small_kernel).
 //
-// pmt_batch_horizon_dynamics_tv_expand_f64 is batch_horizon_dyn.hip's streaming writer with the row source moved to AB_t: each section
-// word is read once.
-#include <algorithm>
-
-#include "common.h"
+// pmt_batch_horizon_dynamics_tv_expand_f64 is the streaming writer both dynamics files share (dynamics_expand<true>, dynamics_tile.h) with
+// the row source at AB_t: each section word is read once.
+#include "dynamics_tile.h"
+#include "horizon_tile.h"
 
 namespace pmt {
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int LT_THREADS = 256;
-constexpr int LT_WAVES = LT_THREADS / 64;
 constexpr int LT_LOADS = 16, LT_LOADS_HALF = 8;                // loads per thread of a tile: 4096 words, or 2048 where they hold a whole row
 constexpr int LT_WG_PER_CU = 4, LT_WG_PER_CU_HALF = 8;         // resident workgroups per CU of the tile kernel (LDS: at most 33280 / 16640 bytes each)
-constexpr int LT_SMALL_WORDS = 512;          // AB words up to which a matrix pair takes a wave: eight loads per lane
-constexpr int LT_SMALL_WG_PER_CU = 8;
-constexpr int LT_EXPAND_ROWS = LT_WAVES;     // rows of a stage per work item of the expansion: one per wave
-constexpr int LT_MAX_DIM = PMT_BATCH_HORIZON_MAX_DIM, LT_MAX_T = PMT_BATCH_HORIZON_MAX_T;
-constexpr u64 LT_SIGN_BIT = 0x8000000000000000ull;
-static_assert(2 * LT_MAX_DIM <= LT_THREADS, "one thread per constant of an item's two stages, per index word of a stage");
-static_assert(2 * 22 <= 64 && 23 * 23 > LT_SMALL_WORDS, "a wave's item has nx <= 22: one lane per constant of its two stages");
+static_assert(2 * 22 <= 64 && 23 * 23 > DY_SMALL_WORDS, "a wave's item has nx <= 22: one lane per constant of its two stages");
 
 struct BatchLtvArgs {
     const u64 *A, *Bm;                       // instance-, then stage-major: A[B][T-1][nx*nx], Bm[B][T-1][nx*nu] column-major, leading dimension nx
@@ -59,17 +48,6 @@ struct BatchLtvArgs {
     double *out; int64_t out_stride;
 };
 
-// An item's place (item = inst*(T-1) + s) and its walk in steps of `stride` items without a division per step
-struct LtvItem {
-    int64_t item, inst;
-    int s;
-    __device__ __forceinline__ LtvItem(unsigned first, int per) : item(first), inst(first / (unsigned)per), s((int)(first % (unsigned)per)) {}
-    __device__ __forceinline__ void step(unsigned stride, int step_inst, int step_s, int per) {
-        item += stride; inst += step_inst; s += step_s;
-        if (s >= per) { s -= per; ++inst; }
-    }
-};
-
 // the constants an item writes: the stage s + 1, and stage 0 with it where s == 0 — `cnt` contiguous words from `first`
 __device__ __forceinline__ void ltv_const_range(int s, int nx, int &first, int &cnt) {
     first = s ? (s + 1) * nx : 0;
@@ -77,38 +55,27 @@ __device__ __forceinline__ void ltv_const_range(int s, int nx, int &first, int &
 }
 
 // thread k's constant of the item, on a clamped index (the load is unconditional; sign_h == 0 reads word 0 of g.h and drops it)
-__device__ __forceinline__ double ltv_const_load(const BatchLtvArgs &g, const LtvItem &p, int k) {
+__device__ __forceinline__ double ltv_const_load(const BatchLtvArgs &g, const HorizonItem &p, int k) {
     int first, cnt;
     ltv_const_range(p.s, g.nx, first, cnt);
     const int64_t at = p.inst * g.T * g.nx + first + (k < cnt ? k : cnt - 1);
     return g.h[g.sign_h ? at : 0];
 }
 
-__device__ __forceinline__ void ltv_const_store(const BatchLtvArgs &g, const LtvItem &p, int k, double hv) {
+__device__ __forceinline__ void ltv_const_store(const BatchLtvArgs &g, const HorizonItem &p, int k, double hv) {
     int first, cnt;
     ltv_const_range(p.s, g.nx, first, cnt);
     if (k < cnt) g.out[p.inst * g.out_stride + (int64_t)(g.T - 1) * g.nx * (g.nx + g.nu) + first + k] = signed_const(hv, g.sign_h);
 }
 
-// the tile (r0, c0) of item p's [A | B] into v, thread (lr = tid % RL, lc = tid / RL) taking the columns lc, lc + 256 / RL, ..
+// the tile (r0, c0) of item p's [A | B] into v (dynamics_tile.h), and the thread's constant of the item with it
 template <int RL, int LPT>
-__device__ __forceinline__ void ltv_tile_load(const BatchLtvArgs &g, const LtvItem &p, int r0, int c0, int tid, u64 (&v)[LPT], double &hv) {
-    constexpr int CSTEP = LT_THREADS / RL;
-    const int nx = g.nx, nu = g.nu, w = nx + nu;
+__device__ __forceinline__ void ltv_tile_load(const BatchLtvArgs &g, const HorizonItem &p, int r0, int c0, int tid, u64 (&v)[LPT], double &hv) {
+    const int nx = g.nx, nu = g.nu;
     const u64 *__restrict__ Ai = g.A + p.item * nx * nx;
     const u64 *__restrict__ Bi = nu ? g.Bm + p.item * nx * nu : Ai;              // (nu == 0: no column selects it)
-    // (the thread's coordinates are made opaque per tile: derived from loop invariants, the compiler otherwise keeps every address of the
-    // unrolled body alive across the whole item loop)
-    int lr = tid % RL, lc = tid / RL;
-    asm volatile("" : "+v"(lr), "+v"(lc));
-    const int r = r0 + lr;
-    const unsigned rc = (unsigned)(r < nx ? r : nx - 1);
-#pragma unroll
-    for (int i = 0; i < LPT; ++i) {
-        const int c = c0 + lc + CSTEP * i, cc = c < w ? c : w - 1;
-        const u64 *__restrict__ col = cc < nx ? Ai + (unsigned)cc * (unsigned)nx : Bi + (unsigned)(cc - nx) * (unsigned)nx;
-        v[i] = col[rc];
-    }
+    int lr, lc;
+    dynamics_tile_load<RL, LPT>(Ai, Bi, nx, nx + nu, r0, c0, tid, v, lr, lc);
     hv = ltv_const_load(g, p, tid);
 }
 
@@ -116,8 +83,8 @@ __device__ __forceinline__ void ltv_tile_load(const BatchLtvArgs &g, const LtvIt
 
 // RL rows x CW = 256 * LPT / RL columns a tile.  One loop over the workgroup's tiles: (item, r0, c0), the column tile running fastest.
 template <int RL, int LPT>
-__global__ __launch_bounds__(LT_THREADS) void batch_horizon_ltv_kernel(BatchLtvArgs g) {
-    constexpr int CW = LT_THREADS * LPT / RL, PITCH = CW + 1, CSTEP = LT_THREADS / RL;
+__global__ __launch_bounds__(DY_THREADS) void batch_horizon_ltv_kernel(BatchLtvArgs g) {
+    constexpr int CW = DY_THREADS * LPT / RL, PITCH = CW + 1, CSTEP = DY_THREADS / RL;
     __shared__ u64 tile[RL * PITCH];
     const int nx = g.nx, w = nx + g.nu, per = g.T - 1;
     const int64_t nab = (int64_t)nx * w;
@@ -126,7 +93,7 @@ __global__ __launch_bounds__(LT_THREADS) void batch_horizon_ltv_kernel(BatchLtvA
     const int step_inst = (int)(G / (unsigned)per), step_s = (int)(G % (unsigned)per);
     const u64 flip_a = g.flip_a, flip_b = g.flip_b;
 
-    LtvItem p(blockIdx.x, per);
+    HorizonItem p(blockIdx.x, per);
     if (p.item >= g.items) return;
     int r0 = 0, c0 = 0;
     u64 v[LPT];
@@ -135,6 +102,7 @@ __global__ __launch_bounds__(LT_THREADS) void batch_horizon_ltv_kernel(BatchLtvA
     for (;;) {
         landed(v);
         // tile[row][column], each word with its part's sign; the item's constants leave with its first tile
+        // (batch_horizon_dyn.hip holds this store too: moved into a shared function it compiles to other device code)
         {
             int lr = tid % RL, lc = tid / RL;
             asm volatile("" : "+v"(lr), "+v"(lc));
@@ -144,7 +112,7 @@ __global__ __launch_bounds__(LT_THREADS) void batch_horizon_ltv_kernel(BatchLtvA
         if (r0 == 0 && c0 == 0) ltv_const_store(g, p, tid, hv);
         __syncthreads();
         // the next tile: its loads are in flight under this tile's stores (past the last tile: this tile again, dropped)
-        LtvItem q = p;
+        HorizonItem q = p;
         int qr = r0, qc = c0 + CW;
         if (qc >= w) {
             qc = 0; qr += RL;
@@ -154,10 +122,11 @@ __global__ __launch_bounds__(LT_THREADS) void batch_horizon_ltv_kernel(BatchLtvA
         if (!more) { q = p; qr = r0; qc = c0; }
         ltv_tile_load<RL, LPT>(g, q, qr, qc, tid, v, hv);
         // a wave per row, the column on the lanes
+        // (batch_horizon_dyn.hip holds this write-out too: moved into a shared function it compiles to other device code)
         {
             u64 *__restrict__ ob = reinterpret_cast<u64 *>(g.out) + p.inst * g.out_stride + p.s * nab;
             const int nr = nx - r0 < RL ? nx - r0 : RL, nc = w - c0 < CW ? w - c0 : CW;
-            for (int rr = wave; rr < nr; rr += LT_WAVES) {
+            for (int rr = wave; rr < nr; rr += DY_WAVES) {
                 u64 *__restrict__ orow = ob + (int64_t)(r0 + rr) * w + c0;
                 for (int c = lane; c < nc; c += 64) orow[c] = tile[rr * PITCH + c];
             }
@@ -168,34 +137,29 @@ __global__ __launch_bounds__(LT_THREADS) void batch_horizon_ltv_kernel(BatchLtvA
     }
 }
 
-// A wave per matrix pair of at most LT_SMALL_WORDS AB words: lane l writes the words l, l + 64, .. of AB_t in output order
-__global__ __launch_bounds__(LT_THREADS) void batch_horizon_ltv_small_kernel(BatchLtvArgs g) {
+// A wave per matrix pair of at most DY_SMALL_WORDS AB words: lane l writes the words l, l + 64, .. of AB_t in output order
+__global__ __launch_bounds__(DY_THREADS) void batch_horizon_ltv_small_kernel(BatchLtvArgs g) {
     const int nx = g.nx, nu = g.nu, w = nx + nu, nab = nx * w, per = g.T - 1;
     const int lane = threadIdx.x & 63;
-    const unsigned wv = blockIdx.x * LT_WAVES + (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), nwv = gridDim.x * LT_WAVES;
+    const unsigned wv = blockIdx.x * DY_WAVES + (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), nwv = gridDim.x * DY_WAVES;
     const int step_inst = (int)(nwv / (unsigned)per), step_s = (int)(nwv % (unsigned)per);
     const u64 flip_a = g.flip_a, flip_b = g.flip_b;
-    // the word's source: row r = e / w, column j = e - r*w of [A | B]  (the same for every item)
-    unsigned src[LT_SMALL_WORDS / 64];
-    bool from_a[LT_SMALL_WORDS / 64];
+    unsigned src[DY_SMALL_LOADS];
+    bool from_a[DY_SMALL_LOADS];
 #pragma unroll
-    for (int k = 0; k < LT_SMALL_WORDS / 64; ++k) {
-        const int e = lane + 64 * k, ec = e < nab ? e : nab - 1;
-        const int r = ec / w, j = ec - r * w;
-        from_a[k] = j < nx;
-        src[k] = (unsigned)(r + (j < nx ? j : j - nx) * nx);
-    }
-    for (LtvItem p(wv, per); p.item < g.items; p.step(nwv, step_inst, step_s, per)) {
+    for (int k = 0; k < DY_SMALL_LOADS; ++k) src[k] = dynamics_small_source(lane + 64 * k, nx, w, nab, from_a[k]);
+    for (HorizonItem p(wv, per); p.item < g.items; p.step(nwv, step_inst, step_s, per)) {
         const u64 *__restrict__ Ai = g.A + p.item * nx * nx;
         const u64 *__restrict__ Bi = nu ? g.Bm + p.item * nx * nu : Ai;          // (nu == 0: no word selects it)
         u64 *__restrict__ out = reinterpret_cast<u64 *>(g.out) + p.inst * g.out_stride + (int64_t)p.s * nab;
-        u64 v[LT_SMALL_WORDS / 64];
+        // (batch_horizon_dyn.hip holds the load and the flip / store loop too: moved into shared functions they compile to other device code)
+        u64 v[DY_SMALL_LOADS];
 #pragma unroll
-        for (int k = 0; k < LT_SMALL_WORDS / 64; ++k) v[k] = (from_a[k] ? Ai : Bi)[src[k]];
+        for (int k = 0; k < DY_SMALL_LOADS; ++k) v[k] = (from_a[k] ? Ai : Bi)[src[k]];
         const double hv = ltv_const_load(g, p, lane);
         landed(v);
 #pragma unroll
-        for (int k = 0; k < LT_SMALL_WORDS / 64; ++k) {
+        for (int k = 0; k < DY_SMALL_LOADS; ++k) {
             const int e = lane + 64 * k;
             if (e < nab) out[e] = v[k] ^ (from_a[k] ? flip_a : flip_b);
         }
@@ -204,66 +168,18 @@ __global__ __launch_bounds__(LT_THREADS) void batch_horizon_ltv_small_kernel(Bat
 }
 
 // T == 1: the section is the nx constants of stage 0.  256 / nx instances per pass of a workgroup, a thread per word.
-__global__ __launch_bounds__(LT_THREADS) void batch_horizon_ltv_consts_kernel(const double *__restrict__ h, int64_t B, int nx, int sign_h,
+__global__ __launch_bounds__(DY_THREADS) void batch_horizon_ltv_consts_kernel(const double *__restrict__ h, int64_t B, int nx, int sign_h,
                                                                                double *__restrict__ out, int64_t out_stride) {
-    const int each = LT_THREADS / nx, sub = (int)threadIdx.x / nx, r = (int)threadIdx.x - sub * nx;
+    const int each = DY_THREADS / nx, sub = (int)threadIdx.x / nx, r = (int)threadIdx.x - sub * nx;
     if (sub >= each) return;
     for (int64_t i = (int64_t)blockIdx.x * each + sub; i < B; i += (int64_t)gridDim.x * each)
         out[i * out_stride + r] = sign_h ? signed_const(h[i * nx + r], sign_h) : 0.0;
 }
 
-// One instance's records from its section.  Items, dealt out over the workgroups: (stage t >= 1, four rows), then stage 0, then the
-// constants 256 at a time.
-__global__ __launch_bounds__(LT_THREADS) void batch_horizon_ltv_expand_kernel(const double *__restrict__ section, int T, int nx, int nu, int sign_xp,
+__global__ __launch_bounds__(DY_THREADS) void batch_horizon_ltv_expand_kernel(const double *__restrict__ section, int T, int nx, int nu, int sign_xp,
                                                                                const int64_t *__restrict__ xvar, const int64_t *__restrict__ varmap,
                                                                                u64 *__restrict__ terms, double *__restrict__ consts) {
-    __shared__ u64 vmx[LT_THREADS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int w = nx + nu, row_len = 1 + w, bands = (nx + LT_EXPAND_ROWS - 1) / LT_EXPAND_ROWS, nconst = T * nx;
-    const int64_t nab = (int64_t)nx * w;
-    const int64_t ndyn = (int64_t)(T - 1) * bands, nitems = ndyn + 1 + (nconst + LT_THREADS - 1) / LT_THREADS;
-    const u64 *__restrict__ ab = reinterpret_cast<const u64 *>(section);
-    const u64 one = (u64)__double_as_longlong(1.0) ^ (sign_xp < 0 ? LT_SIGN_BIT : 0);
-    for (int64_t it = blockIdx.x; it < nitems; it += gridDim.x) {
-        if (it < ndyn) {
-            const int t = 1 + (int)(it / bands), r = (int)(it % bands) * LT_EXPAND_ROWS + wave;
-            // the columns of the stage's rows: the contiguous slice xvar[(t-1)*w .. t*w)
-            if (tid < w) vmx[tid] = (u64)map_var(varmap, xvar[(int64_t)(t - 1) * w + tid]);
-            __syncthreads();
-            if (r < nx) {
-                const u64 rowidx = (u64)(r + 1), xp = (u64)map_var(varmap, xvar[(int64_t)t * w + r]);
-                const u64 *__restrict__ row = ab + (t - 1) * nab + r * w;
-                wave_write_words<3>(terms + 3 * (nx + ((int64_t)(t - 1) * nx + r) * row_len), row_len, lane, [&](int q) -> u64 {
-                    const int e = q / 3, f = q - 3 * e;
-                    if (f == 0) return rowidx;
-                    if (e == 0) return f == 1 ? one : xp;
-                    return f == 1 ? row[e - 1] : vmx[e - 1];
-                });
-            }
-            __syncthreads();                              // the next item reuses vmx
-        } else if (it == ndyn) {
-            // stage 0: row i holds (i + 1, +-1.0, vm[xvar[i]])
-            for (int i0 = wave * 64; i0 < nx; i0 += LT_THREADS) {
-                wave_write_words<3>(terms + 3 * i0, nx - i0 < 64 ? nx - i0 : 64, lane, [&](int q) -> u64 {
-                    const int e = q / 3, f = q - 3 * e;
-                    if (f == 0) return (u64)(i0 + e + 1);
-                    return f == 1 ? one : (u64)map_var(varmap, xvar[i0 + e]);
-                });
-            }
-        } else {
-            const int i = (int)(it - ndyn - 1) * LT_THREADS + tid;
-            if (i < nconst) consts[i] = section[(T - 1) * nab + i];
-        }
-    }
-}
-
-// the dimension checks both entry points share; `who` words the message
-static int ltv_check_dims(const char *who, int64_t T, int64_t nx, int64_t nu) {
-    const std::string w(who);
-    PMT_REQUIRE(nx >= 1 && nx <= LT_MAX_DIM, PMT_DIMENSION_MISMATCH, w + ": nx outside 1 .. 128");
-    PMT_REQUIRE(nu >= 0 && nu <= LT_MAX_DIM, PMT_DIMENSION_MISMATCH, w + ": nu outside 0 .. 128");
-    PMT_REQUIRE(T >= 1 && T <= LT_MAX_T, PMT_DIMENSION_MISMATCH, w + ": T outside 1 .. 512");
-    return PMT_OK;
+    dynamics_expand<true>(section, T, nx, nu, sign_xp, xvar, varmap, terms, consts);
 }
 
 }  // namespace pmt
@@ -275,7 +191,7 @@ extern "C" int64_t pmt_batch_horizon_dynamics_tv_doubles(int64_t T, int64_t nx, 
 extern "C" int pmt_batch_horizon_dynamics_tv_f64(const double *A, const double *Bm, const double *h, int64_t B, int64_t T, int64_t nx, int64_t nu,
                                                  int sign_a, int sign_b, int sign_h, double *out, int64_t out_stride, void *stream) {
     PMT_REQUIRE(B >= 0, PMT_DIMENSION_MISMATCH, "batch_horizon_dynamics_tv: negative instance count");
-    const int rc = ltv_check_dims("batch_horizon_dynamics_tv", T, nx, nu);
+    const int rc = dynamics_check_dims("batch_horizon_dynamics_tv", T, nx, nu);
     if (rc != PMT_OK) return rc;
     PMT_REQUIRE(out_stride >= pmt_batch_horizon_dynamics_tv_doubles(T, nx, nu), PMT_DIMENSION_MISMATCH,
                 "batch_horizon_dynamics_tv: out_stride smaller than the section");
@@ -289,44 +205,42 @@ extern "C" int pmt_batch_horizon_dynamics_tv_f64(const double *A, const double *
     g.h = sign_h ? h : reinterpret_cast<const double *>(A);
     g.items = B * (T - 1);
     g.T = (int)T; g.nx = (int)nx; g.nu = (int)nu; g.sign_h = sign_h;
-    g.flip_a = sign_a < 0 ? LT_SIGN_BIT : 0; g.flip_b = sign_b < 0 ? LT_SIGN_BIT : 0;
+    g.flip_a = sign_a < 0 ? DY_SIGN_BIT : 0; g.flip_b = sign_b < 0 ? DY_SIGN_BIT : 0;
     g.out = out; g.out_stride = out_stride;
     return dispatch(stream, [=](hipStream_t s) {
         if (g.T == 1) {
-            const dim3 grid((unsigned)std::min<int64_t>(cdiv(B, LT_THREADS / g.nx), (int64_t)LT_SMALL_WG_PER_CU * cu_count()));
-            PMT_LAUNCH(batch_horizon_ltv_consts_kernel, grid, dim3(LT_THREADS), 0, s, h, B, g.nx, g.sign_h, g.out, g.out_stride);
+            const dim3 grid((unsigned)std::min<int64_t>(cdiv(B, DY_THREADS / g.nx), (int64_t)DY_SMALL_WG_PER_CU * cu_count()));
+            PMT_LAUNCH(batch_horizon_ltv_consts_kernel, grid, dim3(DY_THREADS), 0, s, h, B, g.nx, g.sign_h, g.out, g.out_stride);
             return check_launch("batch_horizon_ltv_consts_kernel");
         }
-        if (g.nx * (g.nx + g.nu) <= LT_SMALL_WORDS) {
-            const dim3 grid((unsigned)std::min<int64_t>(cdiv(g.items, LT_WAVES), (int64_t)LT_SMALL_WG_PER_CU * cu_count()));
-            PMT_LAUNCH(batch_horizon_ltv_small_kernel, grid, dim3(LT_THREADS), 0, s, g);
+        if (g.nx * (g.nx + g.nu) <= DY_SMALL_WORDS) {
+            const dim3 grid((unsigned)std::min<int64_t>(cdiv(g.items, DY_WAVES), (int64_t)DY_SMALL_WG_PER_CU * cu_count()));
+            PMT_LAUNCH(batch_horizon_ltv_small_kernel, grid, dim3(DY_THREADS), 0, s, g);
             return check_launch("batch_horizon_ltv_small_kernel");
         }
         // a tile of half the words where it still holds a whole row of [A | B]: half the loads of a narrow pair fall on clamped columns
         // otherwise, and twice the workgroups are resident
         const int w = g.nx + g.nu, rl = g.nx <= 16 ? 16 : (g.nx <= 32 ? 32 : 64);
-        const bool half = w <= LT_THREADS * LT_LOADS_HALF / rl;
+        const bool half = w <= DY_THREADS * LT_LOADS_HALF / rl;
         const dim3 grid((unsigned)std::min<int64_t>(g.items, (int64_t)(half ? LT_WG_PER_CU_HALF : LT_WG_PER_CU) * cu_count()));
-        if (rl == 16 && half) PMT_LAUNCH_NAMED("batch_horizon_ltv_kernel", (batch_horizon_ltv_kernel<16, LT_LOADS_HALF>), grid, dim3(LT_THREADS), 0, s, g);
-        else if (rl == 16) PMT_LAUNCH_NAMED("batch_horizon_ltv_kernel", (batch_horizon_ltv_kernel<16, LT_LOADS>), grid, dim3(LT_THREADS), 0, s, g);
-        else if (rl == 32 && half) PMT_LAUNCH_NAMED("batch_horizon_ltv_kernel", (batch_horizon_ltv_kernel<32, LT_LOADS_HALF>), grid, dim3(LT_THREADS), 0, s, g);
-        else if (rl == 32) PMT_LAUNCH_NAMED("batch_horizon_ltv_kernel", (batch_horizon_ltv_kernel<32, LT_LOADS>), grid, dim3(LT_THREADS), 0, s, g);
-        else PMT_LAUNCH_NAMED("batch_horizon_ltv_kernel", (batch_horizon_ltv_kernel<64, LT_LOADS>), grid, dim3(LT_THREADS), 0, s, g);
+        if (rl == 16 && half) PMT_LAUNCH_NAMED("batch_horizon_ltv_kernel", (batch_horizon_ltv_kernel<16, LT_LOADS_HALF>), grid, dim3(DY_THREADS), 0, s, g);
+        else if (rl == 16) PMT_LAUNCH_NAMED("batch_horizon_ltv_kernel", (batch_horizon_ltv_kernel<16, LT_LOADS>), grid, dim3(DY_THREADS), 0, s, g);
+        else if (rl == 32 && half) PMT_LAUNCH_NAMED("batch_horizon_ltv_kernel", (batch_horizon_ltv_kernel<32, LT_LOADS_HALF>), grid, dim3(DY_THREADS), 0, s, g);
+        else if (rl == 32) PMT_LAUNCH_NAMED("batch_horizon_ltv_kernel", (batch_horizon_ltv_kernel<32, LT_LOADS>), grid, dim3(DY_THREADS), 0, s, g);
+        else PMT_LAUNCH_NAMED("batch_horizon_ltv_kernel", (batch_horizon_ltv_kernel<64, LT_LOADS>), grid, dim3(DY_THREADS), 0, s, g);
         return check_launch("batch_horizon_ltv_kernel");
     });
 }
 
 extern "C" int pmt_batch_horizon_dynamics_tv_expand_f64(const double *section, int64_t T, int64_t nx, int64_t nu, int sign_xp, const int64_t *xvar,
                                                         const int64_t *varmap, pmt_vector_affine_term *out_terms, double *out_consts, void *stream) {
-    const int rc = ltv_check_dims("batch_horizon_dynamics_tv_expand", T, nx, nu);
+    const int rc = dynamics_check_dims("batch_horizon_dynamics_tv_expand", T, nx, nu);
     if (rc != PMT_OK) return rc;
     PMT_REQUIRE(sign_xp == 1 || sign_xp == -1, PMT_INVALID_ARGUMENT, "batch_horizon_dynamics_tv_expand: sign_xp must be +1 or -1");
     PMT_REQUIRE(section && xvar && out_terms && out_consts, PMT_INVALID_ARGUMENT, "batch_horizon_dynamics_tv_expand: null pointer");
     const int iT = (int)T, inx = (int)nx, inu = (int)nu;
     return dispatch(stream, [=](hipStream_t s) {
-        const int64_t items = (int64_t)(iT - 1) * cdiv(inx, LT_EXPAND_ROWS) + 1 + cdiv((int64_t)iT * inx, LT_THREADS);
-        PMT_LAUNCH(batch_horizon_ltv_expand_kernel, dim3((unsigned)std::min<int64_t>(items, (int64_t)8 * cu_count())), dim3(LT_THREADS), 0, s, section, iT,
-                   inx, inu, sign_xp, xvar, varmap, reinterpret_cast<u64 *>(out_terms), out_consts);
-        return check_launch("batch_horizon_ltv_expand_kernel");
+        return dynamics_expand_launch("batch_horizon_ltv_expand_kernel", batch_horizon_ltv_expand_kernel, s, section, iT, inx, inu, sign_xp, xvar, varmap, out_terms,
+                                      out_consts);
     });
 }

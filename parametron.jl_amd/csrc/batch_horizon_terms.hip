@@ -88,6 +88,7 @@ __global__ __launch_bounds__(HT_THREADS) void batch_horizon_terms_kernel(BatchHo
         }
 
         // the stage constants in z order, added in S_d's order: 256 chains onto 0.0, then the halving tree
+        // (batch_horizon.hip and batch_horizon_tv.hip's tail hold this sum too: moved into a shared function it compiles to other device code)
         {
             double s = 0.0;
             for (int t = tid; t < ns; t += HT_THREADS) s = s + sc[t];
@@ -101,7 +102,7 @@ __global__ __launch_bounds__(HT_THREADS) void batch_horizon_terms_kernel(BatchHo
         }
 
         // the constraint block: C_i column-major -> row-major through tile 0 (rows on the lanes in, columns on the lanes out)
-        // (batch_horizon.hip holds this block too: moved into a shared function it compiles to other device code)
+        // (batch_horizon.hip and batch_horizon_tv.hip's tail hold this block too: moved into a shared function it compiles to other device code)
         if (m > 0) {
             const double *__restrict__ Ci = g.in.C + inst * m * n;
             double *__restrict__ oc = oq + n + 1;
@@ -146,7 +147,6 @@ __global__ __launch_bounds__(HT_THREADS) void batch_horizon_terms_expand_kernel(
                                                                                  const int64_t *__restrict__ varmap, QT *__restrict__ oq,
                                                                                  LT *__restrict__ ol, double *__restrict__ oc, VAT *__restrict__ ov,
                                                                                  double *__restrict__ ovc) {
-    typedef unsigned long long u64w;
     const int lane = threadIdx.x & 63;
     const int64_t wv = (int64_t)blockIdx.x * HT_WAVES + (threadIdx.x >> 6), nwv = (int64_t)gridDim.x * HT_WAVES;
     const int w = nx + nu, xs = nu > 0 ? 2 : 1, ns = T * xs + term;
@@ -163,33 +163,14 @@ __global__ __launch_bounds__(HT_THREADS) void batch_horizon_terms_expand_kernel(
             const bool isu = !last && wi >= nx;
             const int nd = isu ? nu : nx, j = isu ? wi - nx : wi;
             const int64_t zb = u - j;                                            // the stage's first variable in z
-            const double wt = sw[last ? T * xs : t * xs + (isu ? 1 : 0)];
             const double *__restrict__ sec = (last ? slab + nqx + nqu : (isu ? slab + nqx : slab)) + tri_pos(nd, j, j);
             QT *__restrict__ dst = oq + (int64_t)t * (nqx + nqu) + (isu ? nqx : 0) + tri_pos(nd, j, j);
-            const u64w rowvar = (u64w)map_var(varmap, xvar[zb + j]);
-            wave_write_words<3>(reinterpret_cast<u64w *>(dst), nd - j, lane, [&](int q) -> u64w {
-                const int e = q / 3, f = q - 3 * e;
-                if (f == 1) return rowvar;
-                if (f == 2) return (u64w)map_var(varmap, xvar[zb + j + e]);
-                return (u64w)__double_as_longlong(wt * sec[e]);
-            });
+            expand_quad_row(sec, dst, sw + (last ? T * xs : t * xs + (isu ? 1 : 0)), nd - j, xvar + zb + j, varmap, lane);
         } else {
             expand_rest(u, u1, u2, u3, n, m, sq, scn, sd, xvar, varmap, ol, ov, ovc, lane);
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) *oc = sq[n];
-}
-
-// the dimension checks both entry points share; `who` words the message
-static int bt_check_dims(const char *who, int64_t T, int64_t nx, int64_t nu, int64_t term, int64_t m) {
-    const std::string w(who);
-    PMT_REQUIRE(T >= 0 && nx >= 0 && nu >= 0 && m >= 0, PMT_DIMENSION_MISMATCH, w + ": negative dimension");
-    PMT_REQUIRE(nx >= 1, PMT_DIMENSION_MISMATCH, w + ": nx < 1");
-    PMT_REQUIRE(nx <= HT_MAX_DIM && nu <= HT_MAX_DIM, PMT_DIMENSION_MISMATCH, w + ": nx or nu above 128");
-    PMT_REQUIRE(T >= 1 && T <= HT_MAX_T, PMT_DIMENSION_MISMATCH, w + ": T outside 1 .. 512");
-    PMT_REQUIRE(term == 0 || term == 1, PMT_DIMENSION_MISMATCH, w + ": term must be 0 or 1");
-    PMT_REQUIRE(m <= (INT64_C(1) << 40), PMT_DIMENSION_MISMATCH, w + ": m beyond 2^40");
-    return PMT_OK;
 }
 
 }  // namespace pmt
@@ -206,7 +187,7 @@ extern "C" int pmt_batch_horizon_terms_coeffs_f64(const pmt_batch_horizon_terms 
     PMT_REQUIRE(in, PMT_INVALID_ARGUMENT, "batch_horizon_terms: null descriptor");
     PMT_REQUIRE(B >= 0, PMT_DIMENSION_MISMATCH, "batch_horizon_terms: negative dimension");
     const int term = in->P ? 1 : 0;
-    const int rc = bt_check_dims("batch_horizon_terms", T, nx, nu, term, m);
+    const int rc = check_dims("batch_horizon_terms", T, nx, nu, term, m);
     if (rc != PMT_OK) return rc;
     const int64_t L = pmt_batch_horizon_terms_slab_doubles(T, nx, nu, term, m);
     PMT_REQUIRE(out_stride >= L, PMT_DIMENSION_MISMATCH, "batch_horizon_terms: out_stride smaller than the slab");
@@ -241,16 +222,14 @@ extern "C" int pmt_batch_horizon_terms_expand_f64(const double *slab, int64_t T,
                                                   const int64_t *xvar, const int64_t *varmap, pmt_quadratic_term *out_quad,
                                                   pmt_linear_term *out_lin, double *out_const, pmt_vector_affine_term *out_vat,
                                                   double *out_vconsts, void *stream) {
-    const int rc = bt_check_dims("batch_horizon_terms_expand", T, nx, nu, term, m);
+    const int rc = check_dims("batch_horizon_terms_expand", T, nx, nu, term, m);
     if (rc != PMT_OK) return rc;
     PMT_REQUIRE(slab && xvar && varmap && out_quad && out_lin && out_const && (m == 0 || (out_vat && out_vconsts)), PMT_INVALID_ARGUMENT,
                 "batch_horizon_terms_expand: null pointer");
     const int iT = (int)T, inx = (int)nx, inu = (int)nu, iterm = (int)term;
     return dispatch(stream, [=](hipStream_t s) {
-        const int64_t n = (int64_t)iT * (inx + inu) + (int64_t)iterm * inx;
-        const int64_t units = n + cdiv(n, 64) + cdiv(m * n, 64) + cdiv(m, 64);
-        PMT_LAUNCH(batch_horizon_terms_expand_kernel, dim3((unsigned)std::min<int64_t>(cdiv(units, HT_WAVES), 4096)), dim3(HT_THREADS), 0, s, slab,
-                   iT, inx, inu, iterm, m, xvar, varmap, out_quad, out_lin, out_const, out_vat, out_vconsts);
+        PMT_LAUNCH(batch_horizon_terms_expand_kernel, expand_grid((int64_t)iT * (inx + inu) + (int64_t)iterm * inx, m), dim3(HT_THREADS), 0, s, slab, iT, inx,
+                   inu, iterm, m, xvar, varmap, out_quad, out_lin, out_const, out_vat, out_vconsts);
         return check_launch("batch_horizon_terms_expand_kernel");
     });
 }

@@ -74,17 +74,6 @@ struct TvTailArgs {
     double *out; int64_t out_stride;
 };
 
-// An item's place (item = inst*per + t) and its walk in steps of `stride` items without a division per step
-struct TvItem {
-    int64_t item, inst;
-    int t;
-    __device__ __forceinline__ TvItem(unsigned first, int per) : item(first), inst(first / (unsigned)per), t((int)(first % (unsigned)per)) {}
-    __device__ __forceinline__ void step(unsigned stride, int step_inst, int step_t, int per) {
-        item += stride; inst += step_inst; t += step_t;
-        if (t >= per) { t -= per; ++inst; }
-    }
-};
-
 // The W x W tile of item `item` (clamped by the caller) into v, thread tl of the item's 256 / P taking (row tl % W, columns tl / W + CSTEP*i);
 // every load unconditional on a clamped index.  rv: the reference word of row tl (threads past the last row load the last again).
 template <int W, int CSTEP, int LPT>
@@ -121,7 +110,7 @@ __global__ __launch_bounds__(TV_THREADS) void batch_horizon_tv_packed_kernel(TvS
 
     // the workgroup's passes: the items pass*P .. pass*P + P - 1, this thread's the one of its sub; a sub past the last item loads the last
     // item again and writes nothing
-    TvItem p(blockIdx.x * P + sub, per);
+    HorizonItem p(blockIdx.x * P + sub, per);
     int64_t pass0 = (int64_t)blockIdx.x * P;              // the pass's first item: the same for the whole workgroup
     if (pass0 > last) return;
     double v[LPT], rv;
@@ -158,7 +147,7 @@ __global__ __launch_bounds__(TV_THREADS) void batch_horizon_tv_packed_kernel(TvS
             __syncthreads();
         }
         // the next pass: its loads are in flight under this pass's stores and chains (past the last pass: the last item again, dropped)
-        TvItem q = p;
+        HorizonItem q = p;
         q.step(stride, step_inst, step_t, per);
         const bool more = pass0 + stride <= last;
         tv_packed_load<W, CSTEP, LPT>(g, q.item < last ? q.item : last, tl, v, rv);
@@ -166,7 +155,7 @@ __global__ __launch_bounds__(TV_THREADS) void batch_horizon_tv_packed_kernel(TvS
         double *__restrict__ out = g.out + p.inst * g.out_stride;
         if (live) {
             // the block: row j holds its columns k >= j, k on the lanes, CSTEP rows at a time
-            double *__restrict__ osec = out + g.blk0 + p.t * g.blk_step;
+            double *__restrict__ osec = out + g.blk0 + p.s * g.blk_step;
             const int k = tl % W, jr = tl / W;
             for (int j0 = 0; j0 < nd; j0 += CSTEP) {
                 const int j = j0 + jr;
@@ -186,11 +175,11 @@ __global__ __launch_bounds__(TV_THREADS) void batch_horizon_tv_packed_kernel(TvS
                 lin = chain(nd, [&](int kk) { const double a = tl_[tl * PITCH + kk]; return kk == tl ? 2 * a : a; }, [&](int kk) { return cs[kk]; });
                 prod = cs[tl] * lin;
             }
-            out[g.q0 + (int64_t)p.t * g.q_step + tl] = lin;
+            out[g.q0 + (int64_t)p.s * g.q_step + tl] = lin;
         }
         double t = 0.0 + prod;
         for (int h = W >> 1; h > 0; h >>= 1) t = t + __shfl_down(t, h, W);
-        if (live && tl == 0) out[g.sc0 + (int64_t)p.t * g.sc_step] = 0.5 * t;
+        if (live && tl == 0) out[g.sc0 + (int64_t)p.s * g.sc_step] = 0.5 * t;
         __syncthreads();                                  // the next pass reuses the LDS
         if (!more) break;
         p = q; pass0 += stride;
@@ -235,7 +224,7 @@ __global__ __launch_bounds__(TV_THREADS) void batch_horizon_tv_wide_kernel(TvSta
     const unsigned G = gridDim.x;
     const int step_inst = (int)(G / (unsigned)per), step_t = (int)(G % (unsigned)per);
 
-    TvItem p(blockIdx.x, per);
+    HorizonItem p(blockIdx.x, per);
     if (p.item >= g.items) return;
     int ti = 0;
     double lower[16], upper[16];
@@ -285,7 +274,7 @@ __global__ __launch_bounds__(TV_THREADS) void batch_horizon_tv_wide_kernel(TvSta
             __syncthreads();
         }
         // the next tile: its loads are in flight under this tile's chains and stores (past the last tile: this tile again, dropped)
-        TvItem q = p;
+        HorizonItem q = p;
         int qi = ti + 1;
         if (qi == 3) { qi = 0; q.step(G, step_inst, step_t, per); }
         const bool more = q.item < g.items;
@@ -306,7 +295,7 @@ __global__ __launch_bounds__(TV_THREADS) void batch_horizon_tv_wide_kernel(TvSta
                 }
             }
             // the block: row j holds its columns k >= j; this tile's piece of it, k on the lanes
-            double *__restrict__ osec = out + g.blk0 + p.t * g.blk_step;
+            double *__restrict__ osec = out + g.blk0 + p.s * g.blk_step;
 #pragma unroll 4
             for (int r = 0; r < 16; ++r) {
                 const int jj = wave * 16 + r, j = j0 + jj;
@@ -329,7 +318,7 @@ __global__ __launch_bounds__(TV_THREADS) void batch_horizon_tv_wide_kernel(TvSta
                         lin = part[0][tid] + part[1][tid];
                         prod = cvec[tid] * lin;
                     }
-                    out[g.q0 + (int64_t)p.t * g.q_step + tid] = lin;
+                    out[g.q0 + (int64_t)p.s * g.q_step + tid] = lin;
                 }
                 pr[tid] = 0.0 + prod;
             }
@@ -337,7 +326,7 @@ __global__ __launch_bounds__(TV_THREADS) void batch_horizon_tv_wide_kernel(TvSta
             if (tid < 64) {
                 double t = pr[tid] + pr[tid + 64];
                 for (int h = 32; h > 0; h >>= 1) t = t + __shfl_down(t, h);
-                if (tid == 0) out[g.sc0 + (int64_t)p.t * g.sc_step] = 0.5 * t;
+                if (tid == 0) out[g.sc0 + (int64_t)p.s * g.sc_step] = 0.5 * t;
             }
             // (no barrier here: part and cvec were last read in front of the barrier above, and the next item writes pr only behind its
             // tiles' barriers)
@@ -359,6 +348,7 @@ __global__ __launch_bounds__(TV_THREADS) void batch_horizon_tv_tail_kernel(TvTai
         double dv = 0.0;
         if (g.sign_d && m > 0) dv = g.d[inst * m + (tid < m ? tid : m - 1)];
         // the stage constants in z order, added in S_d's order: 256 chains onto 0.0, then the halving tree
+        // (batch_horizon.hip and batch_horizon_terms.hip hold this sum too: moved into a shared function it compiles to other device code)
         {
             double s = 0.0;
             for (int t = tid; t < ns; t += TV_THREADS) s = s + osc[t];
@@ -370,6 +360,8 @@ __global__ __launch_bounds__(TV_THREADS) void batch_horizon_tv_tail_kernel(TvTai
             }
             if (tid == 0) osc[ns] = red[0];
         }
+        // the constraint block: C_i column-major -> row-major through the tile (rows on the lanes in, columns on the lanes out)
+        // (batch_horizon.hip and batch_horizon_terms.hip hold this block too: moved into a shared function it compiles to other device code)
         if (m > 0) {
             const double *__restrict__ Ci = g.C + inst * m * n;
             double *__restrict__ oc = osc + ns + 1;
@@ -434,7 +426,6 @@ __global__ __launch_bounds__(TV_THREADS) void batch_horizon_tv_expand_kernel(con
                                                                               const int64_t *__restrict__ xvar, const int64_t *__restrict__ varmap,
                                                                               QT *__restrict__ oq, LT *__restrict__ ol, double *__restrict__ oc,
                                                                               VAT *__restrict__ ov, double *__restrict__ ovc) {
-    typedef unsigned long long u64w;
     const int lane = threadIdx.x & 63;
     const int64_t wv = (int64_t)blockIdx.x * TV_WAVES + (threadIdx.x >> 6), nwv = (int64_t)gridDim.x * TV_WAVES;
     const int w = nx + nu, ns = T * (nu ? 2 : 1) + term;
@@ -450,31 +441,12 @@ __global__ __launch_bounds__(TV_THREADS) void batch_horizon_tv_expand_kernel(con
             const int nd = isu ? nu : nx, j = isu ? wi - nx : wi;
             const int64_t zb = u - j;                                            // the stage's first variable in z
             const int64_t at = (int64_t)t * (nqx + nqu) + (isu ? nqx : 0) + tri_pos(nd, j, j);
-            const double *__restrict__ sec = slab + at;
-            const u64w rowvar = (u64w)map_var(varmap, xvar[zb + j]);
-            wave_write_words<3>(reinterpret_cast<u64w *>(oq + at), nd - j, lane, [&](int q) -> u64w {
-                const int e = q / 3, f = q - 3 * e;
-                if (f == 1) return rowvar;
-                if (f == 2) return (u64w)map_var(varmap, xvar[zb + j + e]);
-                return (u64w)__double_as_longlong(sec[e]);
-            });
+            expand_quad_row(slab + at, oq + at, nullptr, nd - j, xvar + zb + j, varmap, lane);
         } else {
             expand_rest(u, u1, u2, u3, n, m, sq, scn, sd, xvar, varmap, ol, ov, ovc, lane);
         }
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) *oc = sq[n + ns];
-}
-
-// the dimension checks both entry points share; `who` words the message
-static int tv_check_dims(const char *who, int64_t T, int64_t nx, int64_t nu, int64_t term, int64_t m) {
-    const std::string w(who);
-    PMT_REQUIRE(T >= 0 && nx >= 0 && nu >= 0 && m >= 0, PMT_DIMENSION_MISMATCH, w + ": negative dimension");
-    PMT_REQUIRE(nx >= 1, PMT_DIMENSION_MISMATCH, w + ": nx < 1");
-    PMT_REQUIRE(nx <= TV_MAX_DIM && nu <= TV_MAX_DIM, PMT_DIMENSION_MISMATCH, w + ": nx or nu above 128");
-    PMT_REQUIRE(T >= 1 && T <= TV_MAX_T, PMT_DIMENSION_MISMATCH, w + ": T outside 1 .. 512");
-    PMT_REQUIRE(term == 0 || term == 1, PMT_DIMENSION_MISMATCH, w + ": term must be 0 or 1");
-    PMT_REQUIRE(m <= (INT64_C(1) << 40), PMT_DIMENSION_MISMATCH, w + ": m beyond 2^40");
-    return PMT_OK;
 }
 
 // a launch of the packed kernel: P items per pass of a workgroup
@@ -512,7 +484,7 @@ extern "C" int pmt_batch_horizon_tv_coeffs_f64(const double *Q, const double *R,
                                                int64_t B, int64_t T, int64_t nx, int64_t nu, int64_t term, int64_t m, int sign_r, int sign_v,
                                                int sign_d, double *out, int64_t out_stride, void *stream) {
     PMT_REQUIRE(B >= 0, PMT_DIMENSION_MISMATCH, "batch_horizon_tv: negative dimension");
-    const int rc = tv_check_dims("batch_horizon_tv", T, nx, nu, term, m);
+    const int rc = check_dims("batch_horizon_tv", T, nx, nu, term, m);
     if (rc != PMT_OK) return rc;
     const int64_t L = pmt_batch_horizon_tv_slab_doubles(T, nx, nu, term, m);
     PMT_REQUIRE(out_stride >= L, PMT_DIMENSION_MISMATCH, "batch_horizon_tv: out_stride smaller than the slab");
@@ -555,15 +527,13 @@ extern "C" int pmt_batch_horizon_tv_coeffs_f64(const double *Q, const double *R,
 extern "C" int pmt_batch_horizon_tv_expand_f64(const double *slab, int64_t T, int64_t nx, int64_t nu, int64_t term, int64_t m, const int64_t *xvar,
                                                const int64_t *varmap, pmt_quadratic_term *out_quad, pmt_linear_term *out_lin, double *out_const,
                                                pmt_vector_affine_term *out_vat, double *out_vconsts, void *stream) {
-    const int rc = tv_check_dims("batch_horizon_tv_expand", T, nx, nu, term, m);
+    const int rc = check_dims("batch_horizon_tv_expand", T, nx, nu, term, m);
     if (rc != PMT_OK) return rc;
     PMT_REQUIRE(slab && xvar && varmap && out_quad && out_lin && out_const && (m == 0 || (out_vat && out_vconsts)), PMT_INVALID_ARGUMENT,
                 "batch_horizon_tv_expand: null pointer");
     const int iT = (int)T, inx = (int)nx, inu = (int)nu, iterm = (int)term;
     return dispatch(stream, [=](hipStream_t s) {
-        const int64_t n = (int64_t)iT * (inx + inu) + (int64_t)iterm * inx;
-        const int64_t units = n + cdiv(n, 64) + cdiv(m * n, 64) + cdiv(m, 64);
-        PMT_LAUNCH(batch_horizon_tv_expand_kernel, dim3((unsigned)std::min<int64_t>(cdiv(units, TV_WAVES), 4096)), dim3(TV_THREADS), 0, s, slab, iT, inx,
+        PMT_LAUNCH(batch_horizon_tv_expand_kernel, expand_grid((int64_t)iT * (inx + inu) + (int64_t)iterm * inx, m), dim3(TV_THREADS), 0, s, slab, iT, inx,
                    inu, iterm, m, xvar, varmap, out_quad, out_lin, out_const, out_vat, out_vconsts);
         return check_launch("batch_horizon_tv_expand_kernel");
     });

@@ -19,7 +19,13 @@
 // weight and its linear word are fetched with its reference word: unconditional on clamped indices, asked for a round ahead, in front of
 // the chains.  A plain stage (sign 0) has no chain: W_s * +0.0 (+ g_s[j]).  Without TERMS the weight is the constant 1.0 and there is no
 // linear vector: the multiplies and adds fold away and the device code is that of the unweighted walk.
+//
+// Beside the walk, what the horizon files share otherwise: the item walk of the kernels whose work item is a stage (HorizonItem), the
+// pieces of the expand kernels (expand_quad_row, expand_rest, and their grid: expand_grid) and the objective entry points' dimension
+// checks (check_dims).  What the two dynamics files share lies in dynamics_tile.h.
 #pragma once
+#include <algorithm>
+
 #include "common.h"
 
 namespace pmt {
@@ -31,6 +37,19 @@ constexpr int HT_MAX_DIM = 128;
 constexpr int HT_MAX_T = 512;
 static_assert(HT_MAX_DIM == PMT_BATCH_HORIZON_MAX_DIM && HT_MAX_T == PMT_BATCH_HORIZON_MAX_T, "the header's bounds are the kernel's");
 static_assert(HT_MAX_DIM <= 2 * HT_TILE, "at most two column blocks: three upper tiles");
+
+// Where the work item is a stage, not an instance (batch_horizon_ltv.hip, batch_horizon_tv.hip): an item's place (item = inst*per + s,
+// `per` items an instance) and its walk in steps of `stride` items without a division per step — (inst, s) follows the item by adding
+// (step_inst, step_s) = (stride / per, stride % per) with one carry
+struct HorizonItem {
+    int64_t item, inst;
+    int s;
+    __device__ __forceinline__ HorizonItem(unsigned first, int per) : item(first), inst(first / (unsigned)per), s((int)(first % (unsigned)per)) {}
+    __device__ __forceinline__ void step(unsigned stride, int step_inst, int step_s, int per) {
+        item += stride; inst += step_inst; s += step_s;
+        if (s >= per) { s -= per; ++inst; }
+    }
+};
 
 template <int NT> struct Tiles { double t[NT == 1 ? 1 : 3][HT_TILE][HT_TILE + 1]; };
 
@@ -246,6 +265,31 @@ __device__ __forceinline__ void stages(Tiles<NT> &tl, double (&cw)[HT_WAVES][NT 
     }
 }
 
+// The quadratic-row unit of an expand kernel: one wave writes row j of a stage, its cnt = nd - j columns k >= j, to `dst`.  Term e takes
+// word e of `sec` (the row's words in the slab's section; times *wt where the stage has a weight, NULL: as it is), the row's variable xv[0]
+// and the column's xv[e] — xv the row's place in xvar (a stage's variables are contiguous in z).  The kernels differ in where sec, dst and
+// the weight lie; each keeps its unit split u1 .. u4 and its decode of row u into (t, isu, nd, j): written once for the three, those
+// change the kernels' register counts.
+__device__ __forceinline__ void expand_quad_row(const double *__restrict__ sec, QT *__restrict__ dst, const double *__restrict__ wt, int cnt,
+                                                const int64_t *__restrict__ xv, const int64_t *__restrict__ varmap, int lane) {
+    typedef unsigned long long u64w;
+    const double wv = wt ? *wt : 1.0;
+    const u64w rowvar = (u64w)map_var(varmap, xv[0]);
+    wave_write_words<3>(reinterpret_cast<u64w *>(dst), cnt, lane, [&](int q) -> u64w {
+        const int e = q / 3, f = q - 3 * e;
+        if (f == 1) return rowvar;
+        if (f == 2) return (u64w)map_var(varmap, xv[e]);
+        return (u64w)__double_as_longlong(wt ? wv * sec[e] : sec[e]);
+    });
+}
+
+// the grid of an expand kernel over n variables and m constraint rows: a wave per unit — the n rows of quadratic terms, then 64 linear
+// terms, 64 vector-affine terms, 64 constants each —, at most 4096 workgroups
+inline dim3 expand_grid(int64_t n, int64_t m) {
+    const int64_t units = n + cdiv(n, 64) + cdiv(m * n, 64) + cdiv(m, 64);
+    return dim3((unsigned)std::min<int64_t>(cdiv(units, HT_WAVES), 4096));
+}
+
 // The units of an expand kernel behind its n rows of quadratic terms, one wave per unit u in [u1, u4): 64 linear terms each up to u2 (q at
 // `sq`), 64 vector-affine terms each up to u3 (the row-major C at `scn`), then 64 constants each (the d-consts at `sd`).
 __device__ __forceinline__ void expand_rest(int64_t u, int64_t u1, int64_t u2, int64_t u3, int64_t n, int64_t m, const double *__restrict__ sq,
@@ -275,6 +319,18 @@ __device__ __forceinline__ void expand_rest(int64_t u, int64_t u1, int64_t u2, i
         const int64_t e = (u - u3) * 64 + lane;
         if (e < m) ovc[e] = sd[e];
     }
+}
+
+// the dimension checks the objective files' entry points share (batch_horizon.hip has no terminal stage: term = 0); `who` words the message
+inline int check_dims(const char *who, int64_t T, int64_t nx, int64_t nu, int64_t term, int64_t m) {
+    const std::string w(who);
+    PMT_REQUIRE(T >= 0 && nx >= 0 && nu >= 0 && m >= 0, PMT_DIMENSION_MISMATCH, w + ": negative dimension");
+    PMT_REQUIRE(nx >= 1, PMT_DIMENSION_MISMATCH, w + ": nx < 1");
+    PMT_REQUIRE(nx <= HT_MAX_DIM && nu <= HT_MAX_DIM, PMT_DIMENSION_MISMATCH, w + ": nx or nu above 128");
+    PMT_REQUIRE(T >= 1 && T <= HT_MAX_T, PMT_DIMENSION_MISMATCH, w + ": T outside 1 .. 512");
+    PMT_REQUIRE(term == 0 || term == 1, PMT_DIMENSION_MISMATCH, w + ": term must be 0 or 1");
+    PMT_REQUIRE(m <= (INT64_C(1) << 40), PMT_DIMENSION_MISMATCH, w + ": m beyond 2^40");
+    return PMT_OK;
 }
 
 }  // namespace pmt

@@ -296,3 +296,44 @@ def test_null_pointers_where_no_data_is_read_and_empty_batches(lib):
         L = H.slab_doubles(T, nx, nu, m)
         lib.call(COEFFS, None, None, None, None, None, None, 0, T, nx, nu, m, -1, 1, -1, None, L, None)
         lib.call(COEFFS, None, None, None, None, None, None, 0, T, nx, nu, m, 0, 0, 0, None, L + 3, None)
+
+
+# ---- 5. the dimension checks the three objective files share: every out-of-range argument, its code and the whole message
+
+# (argument, value) -> the message behind "<who>: ", as the sources worded it when each file had its own copy of the checks; the first
+# failing check speaks, in the order negative, nx < 1, above 128, T, term, m
+DIM_MESSAGES = [("T", -1, "negative dimension"), ("nx", -4, "negative dimension"), ("nu", -1, "negative dimension"), ("m", -2, "negative dimension"),
+                ("nx", 0, "nx < 1"), ("nx", 129, "nx or nu above 128"), ("nu", 129, "nx or nu above 128"), ("nx", 1 << 40, "nx or nu above 128"),
+                ("T", 0, "T outside 1 .. 512"), ("T", 513, "T outside 1 .. 512"), ("T", 1 << 40, "T outside 1 .. 512"),
+                ("term", 2, "term must be 0 or 1"), ("term", -1, "term must be 0 or 1"), ("m", (1 << 40) + 1, "m beyond 2^40")]
+
+
+def _objective_calls(lib):
+    """who -> (call(T, nx, nu, term, m), takes a term): the six entry points with every pointer made up and a stride that is never short"""
+    big = 1 << 62
+    desc = lib.batch_horizon_terms(Q=64, R=64, r=64, v=64, C=64, d=64, sign_r=-1, sign_v=-1, sign_d=-1)      # (no P: term == 0 there)
+    return {
+        "batch_horizon": (lambda T, nx, nu, term, m: lib.call(COEFFS, P, P, P, P, P, P, 1, T, nx, nu, m, -1, -1, -1, P, big, None), False),
+        "batch_horizon_expand": (lambda T, nx, nu, term, m: lib.call(EXPAND, P, T, nx, nu, m, P, P, P, P, P, P, P, None), False),
+        "batch_horizon_terms": (lambda T, nx, nu, term, m: lib.call("pmt_batch_horizon_terms_coeffs_f64", C.byref(desc), 1, T, nx, nu, m, P, big, None), False),
+        "batch_horizon_terms_expand": (lambda T, nx, nu, term, m: lib.call("pmt_batch_horizon_terms_expand_f64", P, T, nx, nu, term, m, P, P, P, P, P, P, P, None), True),
+        "batch_horizon_tv": (lambda T, nx, nu, term, m: lib.call("pmt_batch_horizon_tv_coeffs_f64", P, P, P, P, P, P, 1, T, nx, nu, term, m, -1, -1, -1, P, big, None), True),
+        "batch_horizon_tv_expand": (lambda T, nx, nu, term, m: lib.call("pmt_batch_horizon_tv_expand_f64", P, T, nx, nu, term, m, P, P, P, P, P, P, P, None), True),
+    }
+
+
+@pytest.mark.parametrize("who", ["batch_horizon", "batch_horizon_expand", "batch_horizon_terms", "batch_horizon_terms_expand", "batch_horizon_tv",
+                                 "batch_horizon_tv_expand"])
+def test_every_out_of_range_dimension_keeps_its_code_and_message(lib, who):
+    fn, takes_term = _objective_calls(lib)[who]
+    for arg, value, text in DIM_MESSAGES:
+        if arg == "term" and not takes_term:
+            continue
+        kw = dict(T=3, nx=4, nu=2, term=0, m=2)
+        kw[arg] = value
+        with pytest.raises(lib.DimensionMismatch) as e:
+            fn(**kw)
+        assert str(e.value) == "%s: %s" % (who, text), (arg, value)
+    # the bounds themselves are in range: T, nx and nu at theirs get as far as the null output
+    with pytest.raises(lib.ArgumentError, match="null pointer"):
+        lib.call(COEFFS, P, P, P, P, P, P, 1, H.MAX_T, H.MAX_DIM, H.MAX_DIM, 1, -1, -1, -1, None, 1 << 62, None)
