@@ -674,6 +674,12 @@ int launch_gram_sk(const double *A, int64_t lda, int64_t rows, int64_t cols, con
         if (dma::fault_injection() & 1) { g.flag_value = epoch + 0x40000000u; g.pair_timeout = 2000000LL; }
     }
     if (g.nchunk > 1 && !workspace) return fail(PMT_INVALID_ARGUMENT, "quad_gram: workspace required");
+    // Fewer units than workgroups (U < G: whole tiles in phase A and a short remainder, 257 x 4100: 98 units on 256 workgroups): a workgroup
+    // without a unit writes no partial, but the fix-up kernels add the first slot of EVERY workgroup from a split tile's first owner to its
+    // last, the idle ones between them included — whatever the caller's workspace held there.  Those slots are cleared (+0.0 adds nothing
+    // to a sum that started at +0.0); the workgroups that have a partial overwrite theirs.  On the host, so that the kernels stay as they are.
+    if (g.nchunk > 1 && R > 0 && !fold && g.U < g.G)
+        PMT_HIP_CHECK(hipMemset2DAsync(g.ws, 2 * SLOT * sizeof(double), 0, SLOT * sizeof(double), (size_t)g.G, s));
     const dim3 grid((unsigned)g.G);
     // Two instantiations, plain and ranged.  (The 32-row-stage instantiation used for tall matrices in rounds 1-2 spilled 49 VGPRs — +1 % at r = 16384 when it
     // was introduced — and is gone: all shapes take 16-row stages.  So is the delivery instantiation that counted finished tiles per band

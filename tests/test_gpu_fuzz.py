@@ -1,5 +1,7 @@
-"""-m gpu: randomised shapes through the Gram node (stream-K split, whole-tile and bounds-checked paths, padded / odd leading
-dimensions, 8-byte-misaligned bases) and the dense affine nodes, against numpy — a fixed seed, so failures reproduce."""
+"""-m gpu: randomised shapes through the Gram node (padded / odd leading dimensions, 8-byte-misaligned bases) and the dense affine nodes,
+against numpy — a fixed seed, so failures reproduce.  Since gram_form (csrc/gram.hip) moved these sizes, the shapes here land on the tiny
+node, the one-tile / narrow-panel kernels of gram_tall.hip and the one-launch form of gram_mid.hip; of the stream-K kernel (gram_sk.hip)
+they reach one 1 x 1 CSC call and nothing else — its split, whole-tile and bounds-checked paths are test_gpu_gram_sk.py's."""
 import numpy as np
 import pytest
 
@@ -76,7 +78,9 @@ def _check_gram_node(rows, n, lda, shift, rng):
 def test_gram_node_without_affine_part_and_in_native_form(rows, n, moi):
     """b = null / sign = 0 (the objective (A x) . (A x): q = 0, constant = 0) and the NATIVE canonical form (moi = 0: diagonal coefficient
     (A'A)_jj, off-diagonal 2 (A'A)_jk, model variable indices) across the node's forms — tiny, the 16 / 32 / 64-column panels, one tile,
-    diagonal tiles + strict stream-K up to 2048 columns, the stream-K node beyond — with 8-byte misaligned and odd-pitched A"""
+    the one-launch form from 129 columns on (2049 included) — with 8-byte misaligned and odd-pitched A.  (None of these shapes reaches the
+    stream-K kernel any more, neither its strict launch nor the node beyond 4096 columns: test_gpu_gram_sk.py runs that kernel with
+    b = null and in native form.)"""
     import gpu_util as g
     rng = np.random.default_rng(rows * 31 + n + moi)
     lda = rows + int(rng.integers(0, 4))
