@@ -873,6 +873,51 @@ int pmt_quad_stages_terms_check(const pmt_quad_stage *host_stages, const pmt_qua
 int pmt_quad_stages_terms_f64(const pmt_quad_stage *stages, const pmt_quad_stage_terms *terms, int64_t T,
                               const pmt_quad_stage_const *consts, int64_t nconsts, const int64_t *varmap,
                               pmt_quadratic_term *out_quad, pmt_linear_term *out_lin, double *stage_consts, double *out_const, void *stream);
+/* The same horizon with identity-weighted stage costs — rho*dot(u_t, u_t), dot(x_t - r_t, x_t - r_t), a ridge lam*dot(x_t, x_t) on a vector
+ * that already carries a form — still one launch plus the short constant launch.  A stage is at most one of each over ONE strictly
+ * increasing vector: a dense form with its weight, a diagonal term W_d*dot(x_t (+|-) v_t, x_t (+|-) v_t) (W_d*dot(x_t, x_t) without v), a
+ * linear term W_c*dot(c_t, x_t); at least one of the form and the diagonal term.  `stages` and `terms` are the tables of
+ * pmt_quad_stages_terms_f64, `diags` a DEVICE array of T entries or NULL (no stage has a rider):
+ *   identity stage   Q == NULL: the stage is W_t*dot(x (+|-) v, x (+|-) v) with v = vec, sign = sign (sign == 0: dot(x, x)) and
+ *                    W_t from terms[t].scale / .weight.  It owns n quadratic terms at quad_at — NOT n(n+1)/2 — and n linear terms at
+ *                    lin_at; ldq is ignored; diags[t].present must be 0.
+ *   rider            diags[t].present == 1 on a stage with a Q: the diagonal term W_d*dot(x (+|-) v^d, x (+|-) v^d) beside the form on the
+ *                    same vector, W_d = weight ? scale * *weight : scale (one rounded product); v^d may differ from the form's shift.
+ * The arithmetic is that of pmt_quad_gram_sum_f64 for a PMT_LSQ_DIAG term (D = (2*W_d) on the diagonal; W_d*(2*(0.0 (+|-) v_j)) in lin[j]
+ * behind the blocks and in front of the linear terms; W_d*S_d in the constant; csrc/gram_sum.hip: sum_diag_shift_at, gram_sum_aux,
+ * gram_sum_const).  With c_j = 0.0 (+|-) v_j and S = sum_j c_j*c_j in S_d's order (n <= 256: chain j holds 0.0 + c_j*c_j, then the halving
+ * tree; c_j*c_j and v_j*v_j are the same double), plain multiplies and adds, no fma:
+ *   identity stage   quadratic term j = ((2*W_t), vm[xvar[j]], vm[xvar[j]]).  lin[j] = W_t*(2*c_j) with a v, then + W_c*c_t[j] when lin_vec
+ *                    is given; without v W_c*c_t[j] alone (the first contributor starts the chain: a -0.0 survives); with neither +0.0.
+ *                    stage_consts[t] = W_t*S with a v, +0.0 without.
+ *   rider            every word as pmt_quad_stages_terms_f64 writes it, except: the diagonal coefficient is W_t*(2*Q[j,j]) + (2*W_d);
+ *                    lin[j] = W_t*lin_j, then + W_d*(2*c^d_j) when the rider has a v, then + W_c*c_t[j]; stage_consts[t] = W_t*cc_t,
+ *                    then + W_d*S when the rider has a v.  Word for word what pmt_quad_form_f64 / pmt_quad_form_shift_f64 (moi = 1,
+ *                    alpha = 1.0) leave for the stage alone, followed by pmt_quad_gram_sum_f64 over [block, PMT_LSQ_DIAG, PMT_LSQ_LINEAR].
+ *   other stages     the words of pmt_quad_stages_terms_f64 (with unit terms: of pmt_quad_stages_f64).
+ *   *out_const       unchanged: the chain-then-tree sum of stage_consts, then the scalar constants in table order.
+ * Everything else of pmt_quad_stages_terms_f64's contract holds: every output word written exactly once, nothing outside the slices,
+ * results independent of T, of a stage's position, of launch geometry and of timing; no workgroup waits for another, no atomics, no
+ * workspace.  A NaN weight reaches its own stage's words and *out_const only.
+ * pmt_quad_stages_diag_check is host arithmetic over HOST copies of the tables: everything pmt_quad_stages_terms_check refuses, with its
+ * code, except that a NULL Q is an identity stage (its slice counted as n quadratic terms, its ldq not looked at); an identity stage with
+ * present != 0, a present outside {0, 1}, a rider's sign outside {-1, 0, 1} (an identity stage's: the stage's own check), a rider's NULL
+ * vec with sign != 0: PMT_INVALID_ARGUMENT; overlap or overrun of the slices: PMT_DIMENSION_MISMATCH.  host_diags may be NULL.
+ * pmt_quad_stages_diag_f64 itself rejects null pointers (PMT_INVALID_ARGUMENT; diags may be NULL) and negative counts
+ * (PMT_DIMENSION_MISMATCH) before any device call and does not check the tables again.  Algorithmic bytes: an identity stage reads its
+ * vectors and writes 24 n + 16 n bytes; a rider reads n more doubles. */
+typedef struct {
+    double scale; const double *weight;          /* W_d = weight ? scale * *weight : scale, one rounded product */
+    const double *vec;                           /* v_t (n doubles), or NULL with sign == 0 */
+    int32_t sign, present;                       /* +1 | -1 with vec; present: 1 if stage t has a rider, else 0 */
+} pmt_quad_stage_diag;                           /* 32 bytes, no padding */
+int pmt_quad_stages_diag_check(const pmt_quad_stage *host_stages, const pmt_quad_stage_terms *host_terms,
+                               const pmt_quad_stage_diag *host_diags, int64_t T, const pmt_quad_stage_const *host_consts,
+                               int64_t nconsts, int64_t nterms, int64_t nlin);
+int pmt_quad_stages_diag_f64(const pmt_quad_stage *stages, const pmt_quad_stage_terms *terms, const pmt_quad_stage_diag *diags,
+                             int64_t T, const pmt_quad_stage_const *consts, int64_t nconsts, const int64_t *varmap,
+                             pmt_quadratic_term *out_quad, pmt_linear_term *out_lin, double *stage_consts, double *out_const,
+                             void *stream);
 
 /* Horizon dynamics constraints: the MOI.VectorAffineFunction buffers of T affine records from one launch — x_{t+1} == A*x_t + B*u_t (+ w_t)
  * for every stage of a horizon, the other half of the model whose objective pmt_quad_stages_f64 writes.  A record is a sum

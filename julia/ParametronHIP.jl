@@ -254,6 +254,33 @@ quad_stages_terms!(out_quad, out_lin, stage_consts, out_const, stages::DevPtr, t
                 (DevPtr, DevPtr, Int64, DevPtr, Int64, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
                 stages, terms, T, consts, nconsts, varmap, out_quad, out_lin, stage_consts, out_const, stream))
 
+"pmt_quad_stage_diag (include/parametron_hip.h): the diagonal term W_d*dot(x (+|-) v, x (+|-) v) riding on stage t of
+ pmt_quad_stages_diag_f64 beside its form — W_d = scale * (*weight) (weight C_NULL: scale alone), vec C_NULL with sign 0: W_d*dot(x, x);
+ present 1 | 0 (no rider: the other fields are not read); 32 bytes, no padding"
+struct QuadStageDiag
+    scale::Float64
+    weight::DevPtr
+    vec::DevPtr
+    sign::Int32
+    present::Int32
+end
+
+"quad_stages_terms_check with identity stages (a QuadStage with Q C_NULL: W_t*dot(x (+|-) v, x (+|-) v), n quadratic terms) and riders:
+ `diags` one QuadStageDiag per stage, or nothing when no stage has a rider"
+quad_stages_diag_check(stages::Vector{QuadStage}, terms::Vector{QuadStageTerms}, diags::Union{Vector{QuadStageDiag},Nothing},
+                       consts::Vector{QuadStageConst}, nterms, nlin) =
+    check(ccall((:pmt_quad_stages_diag_check, lib), Cint,
+                (Ptr{QuadStage}, Ptr{QuadStageTerms}, Ptr{QuadStageDiag}, Int64, Ptr{QuadStageConst}, Int64, Int64, Int64),
+                stages, terms, diags === nothing ? C_NULL : diags, length(stages), consts, length(consts), nterms, nlin))
+
+"quad_stages_terms! with identity stages and riders: `stages`, `terms`, `diags` (T entries, or C_NULL: no rider) and `consts` are the DEVICE
+ copies of tables quad_stages_diag_check accepted"
+quad_stages_diag!(out_quad, out_lin, stage_consts, out_const, stages::DevPtr, terms::DevPtr, diags::DevPtr, T, consts::DevPtr, nconsts, varmap,
+                  stream) =
+    check(ccall((:pmt_quad_stages_diag_f64, lib), Cint,
+                (DevPtr, DevPtr, DevPtr, Int64, DevPtr, Int64, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
+                stages, terms, diags, T, consts, nconsts, varmap, out_quad, out_lin, stage_consts, out_const, stream))
+
 "pmt_affine_part (include/parametron_hip.h): one leaf with terms of a record of pmt_affine_stages_f64 — a matrix (column-major, leading
  dimension ld) over `cols` model variables, or mat C_NULL for a Variable vector (cols 1); sign +1 | -1; 32 bytes, no padding"
 struct AffinePart

@@ -90,7 +90,12 @@ class QuadStageConst(C.Structure):
     _fields_ = [("scale", C.c_double), ("weight", C.c_void_p), ("value", C.c_void_p)]
 
 
-assert C.sizeof(QuadStageTerms) == 40 and C.sizeof(QuadStageConst) == 24
+class QuadStageDiag(C.Structure):
+    """pmt_quad_stage_diag: the diagonal term riding on stage t of pmt_quad_stages_diag_f64 (device addresses, or None; present 0: none)."""
+    _fields_ = [("scale", C.c_double), ("weight", C.c_void_p), ("vec", C.c_void_p), ("sign", C.c_int32), ("present", C.c_int32)]
+
+
+assert C.sizeof(QuadStageTerms) == 40 and C.sizeof(QuadStageConst) == 24 and C.sizeof(QuadStageDiag) == 32
 
 
 def _scaled_struct_array(cls, rows, scales):
@@ -111,6 +116,12 @@ def quad_stage_terms(terms):
 def quad_stage_consts(consts):
     """host array of pmt_quad_stage_const from dicts of its fields (missing fields: scale 1.0, pointers None)"""
     return _scaled_struct_array(QuadStageConst, consts, ("scale",))
+
+
+def quad_stage_diags(diags):
+    """host array of pmt_quad_stage_diag from dicts of its fields, an empty dict for a stage without a rider (missing fields: scale 1.0,
+    pointers None, sign 0; present 1 unless the dict is empty or says otherwise)"""
+    return _scaled_struct_array(QuadStageDiag, [dict({"present": 1}, **t) if t else {} for t in diags], ("scale",))
 
 
 PMT_AFFINE_STAGES_MAX_PARTS = 8
@@ -190,11 +201,16 @@ class GroupsLayout:
       ordered               every group's variables are consecutive in z: its function is one slice of the destination
       dst_quad, dst_lin     per group, the slice's first term (meaningful when ordered)
       src_quad, src_lin     per group, its first term in the arena
-      row_src, row_dst      the gather's tables in 8-byte words (row_dst: len(z) + 1 entries);  lin_src: per variable of z, its arena term"""
+      row_src, row_dst      the gather's tables in 8-byte words (row_dst: len(z) + 1 entries);  lin_src: per variable of z, its arena term
+    `diagonal` (one flag per set, or None: no set): a flagged set's function holds its n diagonal terms only (an identity stage of
+    pmt_quad_stages_diag_f64) — n rows of length 1 instead of the triangle's rows of length n .. 1."""
 
-    def __init__(self, sets):
+    def __init__(self, sets, diagonal=None):
         sets = [np.asarray(s, dtype=np.int64).reshape(-1) for s in sets]
         n = np.array([len(s) for s in sets], dtype=np.int64)
+        diag = np.zeros(len(sets), dtype=bool) if diagonal is None else np.asarray(diagonal, dtype=bool).reshape(-1)
+        if len(diag) != len(sets):
+            raise ArgumentError("groups_layout: one diagonal flag per group")
         if len(sets) < 1 or np.any(n < 1) or any(np.any(np.diff(s) <= 0) for s in sets):
             raise ArgumentError("groups_layout: every group needs a non-empty, strictly increasing variable set")
         z = np.concatenate(sets)
@@ -204,11 +220,11 @@ class GroupsLayout:
             raise ArgumentError("groups_layout: the groups' variable sets overlap")
         self.owner = owner = np.repeat(np.arange(len(sets), dtype=np.int64), n)[order]
         local = np.concatenate([np.arange(k, dtype=np.int64) for k in n])[order]          # the variable's position in its group
-        self.src_quad = np.concatenate([[0], np.cumsum(n * (n + 1) // 2)[:-1]]).astype(np.int64)
+        self.src_quad = np.concatenate([[0], np.cumsum(np.where(diag, n, n * (n + 1) // 2))[:-1]]).astype(np.int64)
         self.src_lin = np.concatenate([[0], np.cumsum(n)[:-1]]).astype(np.int64)
-        ng = n[owner]
-        self.row_dst = 3 * np.concatenate([[0], np.cumsum(ng - local)]).astype(np.int64)
-        self.row_src = 3 * (self.src_quad[owner] + local * ng - local * (local - 1) // 2)
+        ng, dg = n[owner], diag[owner]
+        self.row_dst = 3 * np.concatenate([[0], np.cumsum(np.where(dg, 1, ng - local))]).astype(np.int64)
+        self.row_src = 3 * (self.src_quad[owner] + np.where(dg, local, local * ng - local * (local - 1) // 2))
         self.lin_src = self.src_lin[owner] + local
         self.nterms, self.nlin = int(self.row_dst[-1]) // 3, len(self.z)
         self.ordered = int(np.count_nonzero(np.diff(owner))) == len(sets) - 1
@@ -344,6 +360,8 @@ SIGNATURES = {
     "pmt_quad_stages_f64": (_ci, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pmt_quad_stages_terms_check": (_ci, [_vp, _vp, _i64, _vp, _i64, _i64, _i64]),
     "pmt_quad_stages_terms_f64": (_ci, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pmt_quad_stages_diag_check": (_ci, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64]),
+    "pmt_quad_stages_diag_f64": (_ci, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pmt_affine_stages_check": (_ci, [_vp, _i64, _vp, _i64, _i64, _i64]),
     "pmt_affine_stages_f64": (_ci, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "pmt_comm_unique_id": (_ci, [_vp]),

@@ -20,8 +20,10 @@
 //     (form.hip) and sparse_form_kernel do: a slice starts at any 8-byte address.
 // The stages' constants go to stage_consts[t]; a second launch of one workgroup, ordered by the stream alone, adds them in S_d's order.
 // pmt_quad_stages_terms_f64 is the same pair of launches with a weight and a linear term dot(c_t, x_t) per stage and scalar constants
-// beside the stages, from two more device tables: both kernels are templates on TERMS, and the instantiations without it are the device
-// code of pmt_quad_stages_f64 unchanged.
+// beside the stages, from two more device tables.  pmt_quad_stages_diag_f64 adds identity-weighted stage costs: a stage without a matrix
+// (W_t * dot(x_t (+|-) v_t, x_t (+|-) v_t): n quadratic terms, no tile walk) and a diagonal term riding on a form stage, from a third
+// table.  The kernels are templates on MODE; the instantiations QS_PLAIN and QS_TERMS are the device code of the two older entry points
+// unchanged (tools/isa_diff.py).
 // LDS: 33280 (tile) + 8192 (P) + 2048 (c) + 2048 (tree) + 2048 (index words) + 2048 (lin) = 49664 bytes: three workgroups per CU.
 #include <algorithm>
 #include <type_traits>
@@ -42,6 +44,10 @@ static_assert(QS_MAX_N == PMT_QUAD_STAGES_MAX_N, "the header's bound is the kern
 static_assert(QS_MAX_N <= QS_THREADS, "one thread per j adds the blocks; the tree takes one product per thread");
 static_assert(sizeof(pmt_quad_stage) == 56, "pmt_quad_stage: 56 bytes, no padding (the ctypes and Julia mirrors)");
 static_assert(sizeof(pmt_quad_stage_terms) == 40 && sizeof(pmt_quad_stage_const) == 24, "pmt_quad_stage_terms / _const: 40 / 24 bytes, no padding");
+static_assert(sizeof(pmt_quad_stage_diag) == 32, "pmt_quad_stage_diag: 32 bytes, no padding");
+
+// the entry point an instantiation serves: pmt_quad_stages_f64, pmt_quad_stages_terms_f64, pmt_quad_stages_diag_f64
+constexpr int QS_PLAIN = 0, QS_TERMS = 1, QS_DIAG = 2;
 
 struct QuadStagesArgs {
     const pmt_quad_stage *stages; int64_t T;
@@ -55,7 +61,11 @@ struct QuadStagesTermsArgs : QuadStagesArgs {
     const pmt_quad_stage_terms *terms;
     const pmt_quad_stage_const *cterms; int64_t nconsts;
 };
-template <bool TERMS> using QsArgs = std::conditional_t<TERMS, QuadStagesTermsArgs, QuadStagesArgs>;
+// pmt_quad_stages_diag_f64: the stages' riders (NULL: no stage has one)
+struct QuadStagesDiagArgs : QuadStagesTermsArgs {
+    const pmt_quad_stage_diag *diags;
+};
+template <int MODE> using QsArgs = std::conditional_t<MODE == QS_DIAG, QuadStagesDiagArgs, std::conditional_t<MODE == QS_TERMS, QuadStagesTermsArgs, QuadStagesArgs>>;
 
 }  // namespace
 
@@ -63,8 +73,15 @@ template <bool TERMS> using QsArgs = std::conditional_t<TERMS, QuadStagesTermsAr
 // every value word, the linear coefficients and the constant as they are written, W_c * c_t[j] is added to the weighted linear
 // coefficient; the chains (part, cvec, the tree) stay unweighted, so lin_j and cc_t keep the order of the unweighted stage.  No LDS of
 // its own.  The instantiation without TERMS is the kernel of pmt_quad_stages_f64 as it was (tools/isa_diff.py).
-template <bool TERMS>
-__global__ __launch_bounds__(QS_THREADS) void quad_stages_kernel(QsArgs<TERMS> g) {
+// QS_DIAG (pmt_quad_stages_diag_f64) is TERMS with two more kinds of stage, in pmt_quad_gram_sum_f64's order for a PMT_LSQ_DIAG term
+// (gram_sum.hip: sum_diag_shift_at, gram_sum_aux, gram_sum_const):
+//   - an identity stage (Q == NULL) has no tiles: behind the prologue's loads it writes n terms (2*W_t, var_j, var_j), lin[j] =
+//     W_t*(2*c_j) (+ W_c*c_t[j]) — W_c*c_t[j] alone without v, +0.0 with neither — and W_t*S, S = sum_j c_j*c_j from the 256-entry tree;
+//   - a rider (g.diags[t].present) adds (2*W_d) to the stage's n diagonal coefficients as they are written, W_d*(2*c^d_j) to lin[j] between
+//     W_t*lin_j and W_c*c_t[j], and W_d*S to the constant from one more pass of the tree over red[].
+template <int MODE>
+__global__ __launch_bounds__(QS_THREADS, MODE == QS_DIAG ? QS_WG_PER_CU : 1) void quad_stages_kernel(QsArgs<MODE> g) {
+    constexpr bool TERMS = MODE != QS_PLAIN, DIAG = MODE == QS_DIAG;
     typedef unsigned long long u64w;
     __shared__ double tile[QS_TILE][QS_TILE + 1];
     __shared__ double part[QS_MAX_NB][QS_MAX_N];          // P[B][j]
@@ -79,7 +96,12 @@ __global__ __launch_bounds__(QS_THREADS) void quad_stages_kernel(QsArgs<TERMS> g
         const pmt_quad_stage d = g.stages[t];
         [[maybe_unused]] pmt_quad_stage_terms e;          // (asked for with the descriptor: one round trip for both)
         if constexpr (TERMS) e = g.terms[t];
-        const int n = d.n, nt = (n + QS_TILE - 1) / QS_TILE;
+        [[maybe_unused]] pmt_quad_stage_diag dg = {};     // (no table: no stage has a rider)
+        if constexpr (DIAG) {
+            if (g.diags) dg = g.diags[t];
+        }
+        const bool ident = DIAG && d.Q == nullptr, rider = DIAG && dg.present != 0, rider_vec = rider && dg.sign != 0;
+        const int n = d.n, nt = ident ? 0 : (n + QS_TILE - 1) / QS_TILE;
         const int64_t ldq = d.ldq;
         const double *__restrict__ Q = d.Q;
         const bool shift = d.sign != 0;
@@ -100,6 +122,9 @@ __global__ __launch_bounds__(QS_THREADS) void quad_stages_kernel(QsArgs<TERMS> g
             wcv = *(e.lin_weight ? e.lin_weight : own);
             cl = *(e.lin_vec ? e.lin_vec + ct : own);
         }
+        // a rider's weight Parameter likewise (its vector is asked for behind the tiles: the walk has no registers to spare for it)
+        [[maybe_unused]] double wd = 0.0, cd = 0.0, wdv = 0.0;
+        if constexpr (DIAG) wdv = *(rider && dg.weight ? dg.weight : &g.terms[t].scale);
 
         for (int bj = 0; bj < nt; ++bj) {
             for (int bk = bj; bk < nt; ++bk) {
@@ -148,6 +173,10 @@ __global__ __launch_bounds__(QS_THREADS) void quad_stages_kernel(QsArgs<TERMS> g
                         wt = e.weight ? e.scale * wv : e.scale;
                         wc = e.lin_weight ? e.lin_scale * wcv : e.lin_scale;
                     }
+                    if constexpr (DIAG) {               // W_d likewise
+                        asm volatile("" : "+v"(wdv));
+                        wd = dg.weight ? dg.scale * wdv : dg.scale;
+                    }
                     pending = false;
                 }
                 // tile[kk][jj] = Q[j0 + jj, k0 + kk]
@@ -192,6 +221,9 @@ __global__ __launch_bounds__(QS_THREADS) void quad_stages_kernel(QsArgs<TERMS> g
                         if (f == 2) return (u64w)var[k0 + off + e];
                         const double v = tile[jj][off + e];
                         const double c = (diagonal && e == 0) ? 2 * v : v;                        // the row's first term is its diagonal term
+                        if constexpr (DIAG) {
+                            if (rider && diagonal && e == 0) return (u64w)__double_as_longlong(wt * c + 2 * wd);
+                        }
                         return (u64w)__double_as_longlong(TERMS ? wt * c : c);
                     });
                 }
@@ -200,8 +232,32 @@ __global__ __launch_bounds__(QS_THREADS) void quad_stages_kernel(QsArgs<TERMS> g
         }
 
         // lin_j = ((P[0][j] + P[1][j]) + ..) + P[nb-1][j]; T_t by 256 chains onto 0.0 (n <= 256: one product each), then the halving tree
+        if constexpr (DIAG) {
+            if (rider_vec) cd = signed_const(dg.vec[ct], dg.sign);      // c^d = 0.0 (+|-) v^d
+            if (ident) {                                  // no tile in front of which to look at the prologue's loads: here
+                if (tid < n) {
+                    var[tid] = varmap[xv - 1];
+                    if (shift) cvec[tid] = signed_const(pv, d.sign);
+                }
+                wt = e.weight ? e.scale * wv : e.scale;
+                wc = e.lin_weight ? e.lin_scale * wcv : e.lin_scale;
+            }
+        }
         double prod = 0.0;
-        if (tid < n) {
+        if (DIAG && ident) {
+            if (tid < n) {
+                double lin = 0.0;
+                if (shift) {
+                    const double c = cvec[tid];
+                    lin = wt * (2 * c);
+                    if (e.lin_vec) lin = lin + wc * cl;
+                    prod = c * c;
+                } else if (e.lin_vec) {
+                    lin = wc * cl;                        // the first contributor starts the chain: a -0.0 survives
+                }
+                linv[tid] = lin;
+            }
+        } else if (tid < n) {
             double lin = 0.0;
             if (shift) {
                 lin = part[0][tid];
@@ -210,6 +266,9 @@ __global__ __launch_bounds__(QS_THREADS) void quad_stages_kernel(QsArgs<TERMS> g
             }
             if constexpr (TERMS) {                        // W_t * lin_j (a plain stage: W_t * +0.0), then + W_c * c_t[j]
                 lin = wt * lin;
+                if constexpr (DIAG) {
+                    if (rider_vec) lin = lin + wd * (2 * cd);
+                }
                 if (e.lin_vec) lin = lin + wc * cl;
             }
             linv[tid] = lin;
@@ -227,13 +286,41 @@ __global__ __launch_bounds__(QS_THREADS) void quad_stages_kernel(QsArgs<TERMS> g
                     const int e = w0 + (q >> 1);
                     return (q & 1) ? (u64w)var[e] : (u64w)__double_as_longlong(linv[e]);
                 });
+                if (DIAG && ident) {                      // and the terms (2*W_t, var_j, var_j) 64 w .. of an identity stage
+                    const u64w w2 = (u64w)__double_as_longlong(2 * wt);
+                    wave_write_words<3>(reinterpret_cast<u64w *>(oq + w0), cnt, lane, [&](int q) -> u64w {
+                        const int e = q / 3;
+                        return q == 3 * e ? w2 : (u64w)var[w0 + e];
+                    });
+                }
             }
         }
         for (int h = QS_THREADS / 2; h > 0; h >>= 1) {
             if (tid < h) red[tid] = red[tid] + red[tid + h];
             __syncthreads();
         }
-        if (tid == 0) {
+        if constexpr (DIAG) {
+            // an identity stage: W_t * S, or +0.0 without v; a rider with v: W_t * cc_t, then + W_d * S from a second pass of the tree
+            double sc = 0.0;
+            if (ident) {
+                if (shift) sc = wt * red[0];
+            } else {
+                sc = wt * (shift ? 0.5 * red[0] : 0.0);
+            }
+            if (rider_vec) {
+                __syncthreads();                          // every thread has read red[0]
+                double sq = 0.0;
+                if (tid < n) sq = sq + cd * cd;
+                red[tid] = sq;
+                __syncthreads();
+                for (int h = QS_THREADS / 2; h > 0; h >>= 1) {
+                    if (tid < h) red[tid] = red[tid] + red[tid + h];
+                    __syncthreads();
+                }
+                sc = sc + wd * red[0];
+            }
+            if (tid == 0) g.consts[t] = sc;
+        } else if (tid == 0) {
             const double cc = shift ? 0.5 * red[0] : 0.0;
             g.consts[t] = TERMS ? wt * cc : cc;
         }
@@ -245,7 +332,7 @@ __global__ __launch_bounds__(QS_THREADS) void quad_stages_kernel(QsArgs<TERMS> g
 // chain c taking the stages c, c + 256, .. in order, then the halving tree).  T == 0 gives 0.0.  TERMS: one thread then adds the scalar
 // constants in table order, s = s + W_i * (value_i or 1.0).
 template <bool TERMS>
-__global__ __launch_bounds__(QS_THREADS) void quad_stages_const_kernel(QsArgs<TERMS> g) {
+__global__ __launch_bounds__(QS_THREADS) void quad_stages_const_kernel(QsArgs<TERMS ? QS_TERMS : QS_PLAIN> g) {
     __shared__ double red[QS_THREADS];
     const int tid = threadIdx.x;
     const double *__restrict__ c = g.consts;
@@ -284,17 +371,20 @@ static bool qs_slices_ok(std::vector<std::pair<int64_t, int64_t>> &s, int64_t to
 }
 
 // the stage launch (none for T == 0) and the constant's, behind each other on the stream
-template <bool TERMS>
-static int qs_launch(void *stream, const QsArgs<TERMS> &g) {
+// (QS_DIAG adds its constants as QS_TERMS does: the same second kernel)
+template <int MODE>
+static int qs_launch(void *stream, const QsArgs<MODE> &g) {
+    constexpr bool TERMS = MODE != QS_PLAIN;
     return dispatch(stream, [=](hipStream_t s) {
         if (g.T > 0) {
             // three workgroups per CU stay resident (LDS); each walks the stages blockIdx.x, blockIdx.x + G, ..
             const dim3 grid((unsigned)std::min<int64_t>(g.T, (int64_t)QS_WG_PER_CU * cu_count()));
-            PMT_LAUNCH(quad_stages_kernel<TERMS>, grid, dim3(QS_THREADS), 0, s, g);
+            PMT_LAUNCH(quad_stages_kernel<MODE>, grid, dim3(QS_THREADS), 0, s, g);
             const int rc = check_launch("quad_stages_kernel");
             if (rc != PMT_OK) return rc;
         }
-        PMT_LAUNCH(quad_stages_const_kernel<TERMS>, dim3(1), dim3(QS_THREADS), 0, s, g);
+        const QsArgs<TERMS ? QS_TERMS : QS_PLAIN> gc = g;
+        PMT_LAUNCH(quad_stages_const_kernel<TERMS>, dim3(1), dim3(QS_THREADS), 0, s, gc);
         return check_launch("quad_stages_const_kernel");
     });
 }
@@ -303,7 +393,9 @@ static int qs_launch(void *stream, const QsArgs<TERMS> &g) {
 
 using namespace pmt;
 
-extern "C" int pmt_quad_stages_check(const pmt_quad_stage *host_stages, int64_t T, int64_t nterms, int64_t nlin) {
+// pmt_quad_stages_check; `identity` (pmt_quad_stages_diag_check): a stage without a matrix is an identity stage of n quadratic terms, its
+// ldq not looked at
+static int qs_check(const pmt_quad_stage *host_stages, int64_t T, int64_t nterms, int64_t nlin, bool identity) {
     PMT_REQUIRE(T >= 0, PMT_DIMENSION_MISMATCH, "quad_stages: negative stage count");
     PMT_REQUIRE(nterms >= 0 && nlin >= 0, PMT_DIMENSION_MISMATCH, "quad_stages: negative term count");
     if (T == 0) return PMT_OK;
@@ -314,19 +406,23 @@ extern "C" int pmt_quad_stages_check(const pmt_quad_stage *host_stages, int64_t 
     for (int64_t t = 0; t < T; ++t) {
         const pmt_quad_stage &d = host_stages[t];
         const std::string at = " (stage " + std::to_string(t) + ")";
-        PMT_REQUIRE(d.Q, PMT_INVALID_ARGUMENT, "quad_stages: null matrix" + at);
+        PMT_REQUIRE(d.Q || identity, PMT_INVALID_ARGUMENT, "quad_stages: null matrix" + at);
         PMT_REQUIRE(d.xvar, PMT_INVALID_ARGUMENT, "quad_stages: null variable indices" + at);
         PMT_REQUIRE(d.sign >= -1 && d.sign <= 1, PMT_INVALID_ARGUMENT, "quad_stages: sign must be -1, 0 or +1" + at);
         PMT_REQUIRE(d.sign == 0 || d.vec, PMT_INVALID_ARGUMENT, "quad_stages: a shifted stage without its vector" + at);
         PMT_REQUIRE(d.n >= 1 && d.n <= QS_MAX_N, PMT_DIMENSION_MISMATCH, "quad_stages: n outside 1 .. 256" + at);
-        PMT_REQUIRE(d.ldq >= d.n, PMT_DIMENSION_MISMATCH, "quad_stages: ldq < n" + at);
+        PMT_REQUIRE(!d.Q || d.ldq >= d.n, PMT_DIMENSION_MISMATCH, "quad_stages: ldq < n" + at);
         PMT_REQUIRE(d.quad_at >= 0 && d.lin_at >= 0, PMT_DIMENSION_MISMATCH, "quad_stages: a slice starts below 0" + at);
-        quad.emplace_back(d.quad_at, (int64_t)d.n * (d.n + 1) / 2);
+        quad.emplace_back(d.quad_at, d.Q ? (int64_t)d.n * (d.n + 1) / 2 : (int64_t)d.n);
         lin.emplace_back(d.lin_at, (int64_t)d.n);
     }
     PMT_REQUIRE(qs_slices_ok(quad, nterms), PMT_DIMENSION_MISMATCH, "quad_stages: quadratic slices overlap or leave [0, nterms)");
     PMT_REQUIRE(qs_slices_ok(lin, nlin), PMT_DIMENSION_MISMATCH, "quad_stages: linear slices overlap or leave [0, nlin)");
     return PMT_OK;
+}
+
+extern "C" int pmt_quad_stages_check(const pmt_quad_stage *host_stages, int64_t T, int64_t nterms, int64_t nlin) {
+    return qs_check(host_stages, T, nterms, nlin, false);
 }
 
 extern "C" int pmt_quad_stages_f64(const pmt_quad_stage *stages, int64_t T, const int64_t *varmap, pmt_quadratic_term *out_quad,
@@ -339,17 +435,23 @@ extern "C" int pmt_quad_stages_f64(const pmt_quad_stage *stages, int64_t T, cons
     g.varmap = varmap;
     g.quad = out_quad; g.lin = out_lin;
     g.consts = stage_consts; g.cst = out_const;
-    return qs_launch<false>(stream, g);
+    return qs_launch<QS_PLAIN>(stream, g);
 }
 
-extern "C" int pmt_quad_stages_terms_check(const pmt_quad_stage *host_stages, const pmt_quad_stage_terms *host_terms, int64_t T,
-                                           const pmt_quad_stage_const *host_consts, int64_t nconsts, int64_t nterms, int64_t nlin) {
-    const int rc = pmt_quad_stages_check(host_stages, T, nterms, nlin);
+// pmt_quad_stages_terms_check; `identity`: as qs_check
+static int qs_terms_check(const pmt_quad_stage *host_stages, const pmt_quad_stage_terms *host_terms, int64_t T,
+                          const pmt_quad_stage_const *host_consts, int64_t nconsts, int64_t nterms, int64_t nlin, bool identity) {
+    const int rc = qs_check(host_stages, T, nterms, nlin, identity);
     if (rc != PMT_OK) return rc;
     PMT_REQUIRE(T == 0 || host_terms, PMT_INVALID_ARGUMENT, "quad_stages_terms: null table of stage terms");
     PMT_REQUIRE(nconsts >= 0 && nconsts <= PMT_QUAD_STAGES_MAX_CONSTS, PMT_DIMENSION_MISMATCH, "quad_stages_terms: nconsts outside 0 .. 32");
     PMT_REQUIRE(nconsts == 0 || host_consts, PMT_INVALID_ARGUMENT, "quad_stages_terms: null table of constants");
     return PMT_OK;
+}
+
+extern "C" int pmt_quad_stages_terms_check(const pmt_quad_stage *host_stages, const pmt_quad_stage_terms *host_terms, int64_t T,
+                                           const pmt_quad_stage_const *host_consts, int64_t nconsts, int64_t nterms, int64_t nlin) {
+    return qs_terms_check(host_stages, host_terms, T, host_consts, nconsts, nterms, nlin, false);
 }
 
 extern "C" int pmt_quad_stages_terms_f64(const pmt_quad_stage *stages, const pmt_quad_stage_terms *terms, int64_t T,
@@ -369,5 +471,43 @@ extern "C" int pmt_quad_stages_terms_f64(const pmt_quad_stage *stages, const pmt
     g.consts = stage_consts; g.cst = out_const;
     g.terms = terms;
     g.cterms = consts; g.nconsts = nconsts;
-    return qs_launch<true>(stream, g);
+    return qs_launch<QS_TERMS>(stream, g);
+}
+
+extern "C" int pmt_quad_stages_diag_check(const pmt_quad_stage *host_stages, const pmt_quad_stage_terms *host_terms,
+                                          const pmt_quad_stage_diag *host_diags, int64_t T, const pmt_quad_stage_const *host_consts,
+                                          int64_t nconsts, int64_t nterms, int64_t nlin) {
+    const int rc = qs_terms_check(host_stages, host_terms, T, host_consts, nconsts, nterms, nlin, true);
+    if (rc != PMT_OK || !host_diags) return rc;
+    for (int64_t t = 0; t < T; ++t) {
+        const pmt_quad_stage_diag &r = host_diags[t];
+        const std::string at = " (stage " + std::to_string(t) + ")";
+        PMT_REQUIRE(r.present == 0 || r.present == 1, PMT_INVALID_ARGUMENT, "quad_stages_diag: present must be 0 or 1" + at);
+        PMT_REQUIRE(host_stages[t].Q || !r.present, PMT_INVALID_ARGUMENT, "quad_stages_diag: a rider on an identity stage" + at);
+        if (!r.present) continue;
+        PMT_REQUIRE(r.sign >= -1 && r.sign <= 1, PMT_INVALID_ARGUMENT, "quad_stages_diag: sign must be -1, 0 or +1" + at);
+        PMT_REQUIRE(r.sign == 0 || r.vec, PMT_INVALID_ARGUMENT, "quad_stages_diag: a shifted rider without its vector" + at);
+    }
+    return PMT_OK;
+}
+
+extern "C" int pmt_quad_stages_diag_f64(const pmt_quad_stage *stages, const pmt_quad_stage_terms *terms, const pmt_quad_stage_diag *diags,
+                                        int64_t T, const pmt_quad_stage_const *consts, int64_t nconsts, const int64_t *varmap,
+                                        pmt_quadratic_term *out_quad, pmt_linear_term *out_lin, double *stage_consts, double *out_const,
+                                        void *stream) {
+    PMT_REQUIRE(T >= 0, PMT_DIMENSION_MISMATCH, "quad_stages_diag: negative stage count");
+    PMT_REQUIRE(nconsts >= 0 && nconsts <= PMT_QUAD_STAGES_MAX_CONSTS, PMT_DIMENSION_MISMATCH, "quad_stages_diag: nconsts outside 0 .. 32");
+    PMT_REQUIRE(out_const, PMT_INVALID_ARGUMENT, "quad_stages_diag: null constant");
+    PMT_REQUIRE(nconsts == 0 || consts, PMT_INVALID_ARGUMENT, "quad_stages_diag: null table of constants");
+    PMT_REQUIRE(T == 0 || (stages && terms && varmap && out_quad && out_lin && stage_consts), PMT_INVALID_ARGUMENT,
+                "quad_stages_diag: null pointer");
+    QuadStagesDiagArgs g;
+    g.stages = stages; g.T = T;
+    g.varmap = varmap;
+    g.quad = out_quad; g.lin = out_lin;
+    g.consts = stage_consts; g.cst = out_const;
+    g.terms = terms;
+    g.cterms = consts; g.nconsts = nconsts;
+    g.diags = diags;
+    return qs_launch<QS_DIAG>(stream, g);
 }

@@ -517,26 +517,43 @@ class _Record:
         table of descriptors built, checked (pmt_quad_stages_check) and uploaded here once, into the stages' parts of the layout
         (_compile_layout: their slices of the MOI buffers, or the arena and the unchanged gather).  The stages' constants are added by
         the call's own second launch.  With weights, linear terms or constants beside the stages (plan.stage_terms, plan.stage_consts)
-        the one call is pmt_quad_stages_terms_f64 over two more tables, checked by pmt_quad_stages_terms_check.  update! allocates
-        nothing and makes one call, or two with the gather."""
+        the one call is pmt_quad_stages_terms_f64 over two more tables, checked by pmt_quad_stages_terms_check.  With identity stages
+        W_t*dot(x_t (+|-) v_t, x_t (+|-) v_t) (an IdentityStage among plan.stages: n diagonal terms, rows of length 1 in the layout) or
+        diagonal terms riding on form stages (plan.stage_diags) it is pmt_quad_stages_diag_f64 over a third table, checked by
+        pmt_quad_stages_diag_check.  update! allocates nothing and makes one call, or two with the gather."""
         stages = self.plan.stages
-        lay = _lib.GroupsLayout([q.xvars.vars for q in stages])
+        ident = [q.mat is None for q in stages]
+        lay = _lib.GroupsLayout([q.xvars.vars for q in stages], diagonal=ident if any(ident) else None)
         T, n, nq = len(stages), lay.nlin, lay.nterms
         bq, bl, oq, ol, consts, dc, gather = self._compile_layout(ctx, lay, T)
         vs = [_vec_sign(q.vec, q.sign) for q in stages]
-        arr = _lib.quad_stages([{"Q": q.mat.buf, "ldq": q.mat.lda, "xvar": q.xvars.buf, "vec": vec, "n": q.mat.cols, "sign": sign,
+        # (an identity stage's variables may be a host-built term's: their indices get a device buffer here)
+        arr = _lib.quad_stages([{"Q": None, "xvar": ctx.upload_new(np.ascontiguousarray(q.xvars.vars, dtype=np.int64)), "vec": vec,
+                                 "n": len(q.xvars.vars), "sign": sign, "quad_at": int(oq[k]), "lin_at": int(ol[k])} if q.mat is None else
+                                {"Q": q.mat.buf, "ldq": q.mat.lda, "xvar": q.xvars.buf, "vec": vec, "n": q.mat.cols, "sign": sign,
                                  "quad_at": int(oq[k]), "lin_at": int(ol[k])} for k, (q, (vec, sign)) in enumerate(zip(stages, vs))])
-        sterms, sconsts = self.plan.stage_terms, self.plan.stage_consts
-        if sterms is None and not sconsts:
+        sterms, sconsts, sdiags = self.plan.stage_terms, self.plan.stage_consts, self.plan.stage_diags
+        if any(ident) or sdiags is not None:
+            tarr = _lib.quad_stage_terms([self._stage_terms_row(s) for s in sterms or [StageTerms()] * T])
+            rvs = [_vec_sign(r.vec, r.sign) if r is not None else None for r in sdiags or [None] * T]
+            darr = _lib.quad_stage_diags([{} if r is None else {"scale": r.scale, "weight": _buf(r.param), "vec": rv[0], "sign": rv[1]}
+                                          for r, rv in zip(sdiags or [None] * T, rvs)])
+            carr = _lib.quad_stage_consts([{"scale": k.scale, "weight": _buf(k.param), "value": _buf(k.value)} for k in sconsts])
+            nc = len(sconsts)
+            _lib.call("pmt_quad_stages_diag_check", C.addressof(arr), C.addressof(tarr), C.addressof(darr) if sdiags is not None else None, T,
+                      C.addressof(carr), nc, nq, n)
+            table, ttable, ctable = _table(ctx, arr), _table(ctx, tarr), _table(ctx, carr)
+            dtable = _table(ctx, darr) if sdiags is not None else None
+            launch = lambda c: c.call("pmt_quad_stages_diag_f64", P(table), P(ttable), P(dtable), T, P(ctable), nc, P(varmap_buf), P(bq), P(bl),
+                                      P(consts), P(dc))
+        elif sterms is None and not sconsts:
             # no weight, no linear term, no constant: the unweighted entry point, as before
             _lib.call("pmt_quad_stages_check", C.addressof(arr), T, nq, n)
             table = _table(ctx, arr)
             launch = lambda c: c.call("pmt_quad_stages_f64", P(table), T, P(varmap_buf), P(bq), P(bl), P(consts), P(dc))
         else:
             # the weights, the linear terms' vectors and the constants are device mirrors of Parameters, read by the launch at run time
-            tarr = _lib.quad_stage_terms([{"scale": s.scale, "weight": _buf(s.param)} if s.lin is None else
-                                          {"scale": s.scale, "weight": _buf(s.param), "lin_scale": s.lin.scale, "lin_weight": _buf(s.lin.param),
-                                           "lin_vec": s.lin.vec.buf} for s in sterms or [StageTerms()] * T])
+            tarr = _lib.quad_stage_terms([self._stage_terms_row(s) for s in sterms or [StageTerms()] * T])
             carr = _lib.quad_stage_consts([{"scale": k.scale, "weight": _buf(k.param), "value": _buf(k.value)} for k in sconsts])
             nc = len(sconsts)
             _lib.call("pmt_quad_stages_terms_check", C.addressof(arr), C.addressof(tarr), T, C.addressof(carr), nc, nq, n)
@@ -548,6 +565,12 @@ class _Record:
             launch(c)
             gather(c)
         return emit
+
+    @staticmethod
+    def _stage_terms_row(s):                                              # the pmt_quad_stage_terms fields of a StageTerms
+        if s.lin is None:
+            return {"scale": s.scale, "weight": _buf(s.param)}
+        return {"scale": s.scale, "weight": _buf(s.param), "lin_scale": s.lin.scale, "lin_weight": _buf(s.lin.param), "lin_vec": s.lin.vec.buf}
 
     def _compile_sparse_gram(self, ctx, varmap_buf, handoff_varmap):
         """dot(r, r), r = C*x (+|-) d with a sparse C (plan.gram, a DSparseAff): pmt_sparse_gram_f64 streams the pattern's product list
@@ -866,7 +889,17 @@ class StageTerms:
         return self.scale == 1.0 and self.param is None and self.lin is None
 
 
-def _lsq_stages(terms):
+class IdentityStage:
+    """An identity stage of a "canonical-stages" plan, W_t*dot(x_t (+|-) v_t, x_t (+|-) v_t): it stands among plan.stages where a QuadForm
+    stands, without a matrix (mat None); xvars / vec / sign are those of its 'diag' LsqTerm, the weight lies in its StageTerms."""
+    __slots__ = ("xvars", "vec", "sign")
+    mat = None
+
+    def __init__(self, xvars, vec=None, sign=0):
+        self.xvars, self.vec, self.sign = xvars, vec, sign
+
+
+def _lsq_stages(terms, diag=False):
     """(QuadForms, StageTerms per stage or None, 'constant' LsqTerms) of an LsqTerm list that is a horizon of stage costs, or None: more
     than PMT_QUAD_MAX_GROUPS 'form' terms, every one a dense form transpose(x_t)*Q*x_t or transpose(x_t (+|-) v_t)*Q*(x_t (+|-) v_t) over a
     strictly increasing vector of 1 .. PMT_QUAD_STAGES_MAX_N variables, the vectors pairwise disjoint, and at least two stages reading the
@@ -875,45 +908,66 @@ def _lsq_stages(terms):
     forms stand 'linear' terms dot(c_t, x_t), each over exactly the vector of one stage and at most one per stage, and at most
     PMT_QUAD_STAGES_MAX_CONSTS 'constant' terms.  Anything else in the list — a block, a diagonal term, a sparse form, a linear term over
     part of a stage or over other variables, a second one on a stage — leaves the sum to the literal path.  The StageTerms are None when
-    no stage has a weight or a linear term: with no constant either, the record is the unweighted one (pmt_quad_stages_f64)."""
+    no stage has a weight or a linear term: with no constant either, the record is the unweighted one (pmt_quad_stages_f64).
+    `diag` (pmt_quad_stages_diag_f64): 'diag' terms are taken too, host-scaled ones among them (the literal coefficient s of s*u_i*u_i,
+    doubled by the MOI copy, and (2*W_d) are the same word), and the result has a fourth entry.  A diagonal term over exactly the vector of
+    a form is that stage's rider; one over a vector of its own — strictly increasing, 1 .. PMT_QUAD_STAGES_MAX_N variables, disjoint from
+    every other — is a stage, an IdentityStage among the QuadForms at its place in expression order.  At most one diagonal term per
+    vector; one over part of a stage or across two leaves the sum literal.  Stages are counted as vectors: more than PMT_QUAD_MAX_GROUPS
+    of them, at least two FORMS reading one matrix.  The fourth entry holds the rider's 'diag' LsqTerm per stage, or None without a rider."""
     terms = terms or ()
-    forms = [t for t in terms if t.kind == "form"]
+    kinds = ("form", "linear", "constant", "diag") if diag else ("form", "linear", "constant")
+    if any(t.kind not in kinds or (t.host_scaled and not diag) for t in terms):
+        return None
     consts = [t for t in terms if t.kind == "constant"]
-    if len(forms) <= _lib.PMT_QUAD_MAX_GROUPS or len(consts) > _lib.PMT_QUAD_STAGES_MAX_CONSTS:
+    forms = [t for t in terms if t.kind == "form"]
+    # a stage is named by its first variable (disjoint vectors); a diagonal term over a form's own vector rides on it, any other is a stage
+    fvars = {int(t.r.xvars.vars[0]): t.r.xvars.vars for t in forms if isinstance(t.r, QuadForm) and len(t.r.xvars.vars)}
+    riding = lambda t: len(t.xvars.vars) and np.array_equal(fvars.get(int(t.xvars.vars[0]), ()), t.xvars.vars)
+    stages = [t for t in terms if t.kind == "form" or (t.kind == "diag" and not riding(t))]
+    if len(stages) <= _lib.PMT_QUAD_MAX_GROUPS or len(consts) > _lib.PMT_QUAD_STAGES_MAX_CONSTS:
         return None
-    if any(t.kind not in ("form", "linear", "constant") or t.host_scaled for t in terms):
-        return None
-    for t in forms:
-        if not isinstance(t.r, QuadForm):
+    for t in stages:
+        if t.kind == "form" and not isinstance(t.r, QuadForm):
             return None
-        v = t.r.xvars.vars
-        if not 1 <= len(v) <= _lib.PMT_QUAD_STAGES_MAX_N or t.r.mat.cols != len(v) or np.any(np.diff(v) <= 0):
+        v = t.r.xvars.vars if t.kind == "form" else t.xvars.vars
+        if not 1 <= len(v) <= _lib.PMT_QUAD_STAGES_MAX_N or (t.kind == "form" and t.r.mat.cols != len(v)) or np.any(np.diff(v) <= 0):
             return None
-    z = np.concatenate([t.r.xvars.vars for t in forms])
+    svars = [np.asarray(t.r.xvars.vars if t.kind == "form" else t.xvars.vars, dtype=np.int64) for t in stages]
+    z = np.concatenate(svars)
     if len(np.unique(z)) != len(z) or len({id(t.r.mat) for t in forms}) == len(forms):
         return None
-    stage_terms = [StageTerms(t.scale, t.param) for t in forms]
-    first = {int(t.r.xvars.vars[0]): k for k, t in enumerate(forms)}             # (disjoint vectors: a stage is named by its first variable)
+    stage_terms = [StageTerms(t.scale, t.param) for t in stages]
+    first = {int(v[0]): k for k, v in enumerate(svars)}
+    riders = [None] * len(stages)
     for t in terms:
-        if t.kind != "linear":
-            continue
-        v = t.xvars.vars if t.xvars is not None else ()
-        k = first.get(int(v[0])) if len(v) else None
-        if k is None or t.vec is None or stage_terms[k].lin is not None or not np.array_equal(v, forms[k].r.xvars.vars):
-            return None
-        stage_terms[k].lin = t
-    return [t.r for t in forms], None if all(s.plain() for s in stage_terms) else stage_terms, consts
+        if t.kind == "linear":
+            v = t.xvars.vars if t.xvars is not None else ()
+            k = first.get(int(v[0])) if len(v) else None
+            if k is None or t.vec is None or stage_terms[k].lin is not None or not np.array_equal(v, svars[k]):
+                return None
+            stage_terms[k].lin = t
+        elif t.kind == "diag" and riding(t):
+            k = first[int(t.xvars.vars[0])]
+            if riders[k] is not None:
+                return None
+            riders[k] = t
+    out = [t.r if t.kind == "form" else IdentityStage(t.xvars, t.vec, t.sign) for t in stages], \
+        None if all(s.plain() for s in stage_terms) else stage_terms, consts
+    return out + (riders if any(r is not None for r in riders) else None,) if diag else out
 
 
 class QuadPlan:
     """How a quadratic record reaches its MOI function (quad_plan decides; Model.initialize and _Record.compile execute): the mode and what it
     reads — the operand r of dot(r, r) (`gram`), the QuadForm (`form`), the LsqTerm list (`terms`), the QuadGroups of a sum over disjoint
     Variable vectors (`groups`) or the QuadForms of a horizon of stage costs (`stages`, with the StageTerms beside them in `stage_terms` —
-    None: every stage has weight 1 and no linear term — and the 'constant' LsqTerms in `stage_consts`); `canonicalize`: through
+    None: every stage has weight 1 and no linear term —, the 'constant' LsqTerms in `stage_consts` and, per stage, the 'diag' LsqTerm riding
+    on it in `stage_diags` — None: no stage has a rider; an IdentityStage stands among `stages` itself); `canonicalize`: through
     canonicalize! first."""
-    def __init__(self, mode, gram=None, form=None, terms=None, canonicalize=False, groups=None, stages=None, stage_terms=None, stage_consts=()):
+    def __init__(self, mode, gram=None, form=None, terms=None, canonicalize=False, groups=None, stages=None, stage_terms=None, stage_consts=(),
+                 stage_diags=None):
         self.mode, self.gram, self.form, self.terms, self.canonicalize, self.groups = mode, gram, form, terms, canonicalize, groups
-        self.stages, self.stage_terms, self.stage_consts = stages, stage_terms, list(stage_consts)
+        self.stages, self.stage_terms, self.stage_consts, self.stage_diags = stages, stage_terms, list(stage_consts), stage_diags
         # the MOI copy is the canonical least-squares node, bare or the weighted sum of such nodes (model.lane_order: side lane, small-plan order)
         self.gram_record = mode in ("canonical", "canonical-csc", "canonical-sum") or \
             (mode == "canonical-groups" and any(t.kind == "block" for g in groups for t in g.terms))
@@ -924,12 +978,14 @@ class QuadPlan:
         return [r for r in [self.gram] + [t.r for ts in lists for t in ts] + list(self.stages or ()) if r is not None]
 
 
-def quad_plan(terms, bare, kind, nq, is_objective, quadratic_mode, small, handoff, varmap=None, sparse_sums=False, stage_terms=False):
+def quad_plan(terms, bare, kind, nq, is_objective, quadratic_mode, small, handoff, varmap=None, sparse_sums=False, stage_terms=False,
+              stage_diag=False):
     """The QuadPlan of a record over a node described by (terms, bare) = DeviceNode.(lsq_sum, lsq_bare); no mode unless kind == "quad".  `nq`:
     the terms of its literal expansion; `small`: Model._small; `varmap`: the optimizer's index map when it is fixed before the plan is recorded
     (handoff "device" / "host_csc"); `sparse_sums`: weighted sums over sparse blocks take the sparse combine (Model passes True);
     `stage_terms`: a horizon with weights, linear terms or constants beside its stages takes "canonical-stages" (Model passes True; a caller
-    that does not ask gets the row as it was: such a horizon stays literal).  Host data only: nothing is allocated, no stacked matrix is asked for.  First match wins."""
+    that does not ask gets the row as it was: such a horizon stays literal); `stage_diag`: likewise for a horizon with identity-weighted
+    stage costs — rho*dot(u_t, u_t) as a stage, a ridge beside a form (Model passes True).  Host data only: nothing is allocated, no stacked matrix is asked for.  First match wins."""
     one = terms[0] if bare and kind == "quad" else None
     block = one.r if one is not None and one.kind == "block" else None
     if isinstance(block, DSparseAff) and (quadratic_mode == "literal" or handoff == "host_csc"):
@@ -986,10 +1042,14 @@ def quad_plan(terms, bare, kind, nq, is_objective, quadratic_mode, small, handof
                 return QuadPlan("canonical-groups", groups=groups)
             # a horizon of stage costs — more disjoint vectors than the groups hold, every form dense, plain or shifted, two or more of
             # them reading one weight matrix: all stages from one launch (pmt_quad_stages_f64; with weights, linear terms dot(c_t, x_t)
-            # or constants beside the stages pmt_quad_stages_terms_f64)
-            stages = _lsq_stages(terms)
-            if stages and (stage_terms or (stages[1] is None and not stages[2])):
-                return QuadPlan("canonical-stages", stages=stages[0], stage_terms=stages[1], stage_consts=stages[2])
+            # or constants beside the stages pmt_quad_stages_terms_f64; with diagonal terms as stages or beside them
+            # pmt_quad_stages_diag_f64)
+            stages = _lsq_stages(terms, diag=stage_diag)
+            if stages:
+                diags = stages[3] if stage_diag else None
+                has_diag = diags is not None or any(q.mat is None for q in stages[0])
+                if stage_terms or has_diag or (stages[1] is None and not stages[2]):
+                    return QuadPlan("canonical-stages", stages=stages[0], stage_terms=stages[1], stage_consts=stages[2], stage_diags=diags)
     # anything else: the literal function through the generic device canonicalize! (sorted, duplicates combined) before the MOI copy
     return QuadPlan("literal", canonicalize=True)
 

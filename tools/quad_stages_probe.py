@@ -146,7 +146,7 @@ def main():
         old = None
         if T <= a.no_parent_above:
             keep = moi._lsq_stages
-            moi._lsq_stages = lambda terms: None            # the parent commit's decision for this model: the literal function + canonicalize!
+            moi._lsq_stages = lambda terms, diag=False: None         # the parent commit's decision for this model: the literal function + canonicalize!
             try:
                 old = horizon_model(T, nx, nu, st)
                 old.initialize()
