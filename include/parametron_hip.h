@@ -918,6 +918,33 @@ int pmt_quad_stages_diag_f64(const pmt_quad_stage *stages, const pmt_quad_stage_
                              int64_t T, const pmt_quad_stage_const *consts, int64_t nconsts, const int64_t *varmap,
                              pmt_quadratic_term *out_quad, pmt_linear_term *out_lin, double *stage_consts, double *out_const,
                              void *stream);
+/* The same horizon for a device-resident solver: the CSC values of the block-diagonal upper-triangular P instead of quadratic term
+ * structs — 8 bytes per entry, no index words —, from the same launch over the unchanged tables of pmt_quad_stages_diag_f64 (`terms` is
+ * required: unit rows give the unweighted words; `diags` may be NULL; Q == NULL is an identity stage).  quad_at means something else here:
+ * the stage's first double in out_P_values; the slice is n(n+1)/2 doubles, n for an identity stage.
+ *   values           out_P_values[quad_at + k(k+1)/2 + j] = alpha * c(j,k) for j <= k: the layout and meaning of pmt_quad_form_f64's
+ *                    out_P_values.  c(j,k) is the coefficient word pmt_quad_stages_diag_f64 writes at tri(j,k) for the same tables:
+ *                    W_t*(Q[j,k] + Q[k,j]), W_t*(2*Q[j,j]), and + (2*W_d) under a rider.
+ *   identity stage   out_P_values[quad_at + j] = alpha * (2*W_t).
+ *   alpha            with alpha == 1.0 the values equal those coefficient words bit for bit; alpha is one more IEEE multiply (-1.0 flips
+ *                    the sign bit).  Plain multiplies and adds, no fma.
+ *   other outputs    out_lin, stage_consts and *out_const are word for word what pmt_quad_stages_diag_f64 writes; they are NOT scaled by
+ *                    alpha (the hand-off applies the sense to q and r itself, as for pmt_quad_gram_csc_f64 / pmt_quad_form_f64).
+ * Every output word is written exactly once per call and nothing outside the slices is written; a slice may start at any 8-byte address.
+ * Results do not depend on T, on a stage's position in the table, on launch geometry or on timing; no workgroup waits for another, no
+ * atomics, no workspace; persistent workgroups of 256 threads, three per CU, as pmt_quad_stages_diag_f64 (csrc/quad_stages.hip).
+ * pmt_quad_stages_csc_check is host arithmetic over HOST copies of the tables: everything pmt_quad_stages_diag_check refuses for the stage,
+ * terms, diag and const tables, with its codes; value slices that leave [0, nvalues) or overlap (linear slices: [0, nlin)):
+ * PMT_DIMENSION_MISMATCH.  pmt_quad_stages_csc_f64 itself rejects a null stages, terms, varmap, out_P_values, out_lin or stage_consts (with
+ * T > 0), a null out_const and a null consts with nconsts > 0 (PMT_INVALID_ARGUMENT), T < 0 and nconsts outside
+ * 0 .. PMT_QUAD_STAGES_MAX_CONSTS (PMT_DIMENSION_MISMATCH) before any device call and does not check the tables again; T == 0 writes
+ * *out_const only.  Algorithmic bytes: 8 per value and 16 per linear term written; every distinct Q once, the vectors and the tables read. */
+int pmt_quad_stages_csc_check(const pmt_quad_stage *host_stages, const pmt_quad_stage_terms *host_terms,
+                              const pmt_quad_stage_diag *host_diags, int64_t T, const pmt_quad_stage_const *host_consts,
+                              int64_t nconsts, int64_t nvalues, int64_t nlin);
+int pmt_quad_stages_csc_f64(const pmt_quad_stage *stages, const pmt_quad_stage_terms *terms, const pmt_quad_stage_diag *diags,
+                            int64_t T, const pmt_quad_stage_const *consts, int64_t nconsts, const int64_t *varmap, double alpha,
+                            double *out_P_values, pmt_linear_term *out_lin, double *stage_consts, double *out_const, void *stream);
 
 /* Horizon dynamics constraints: the MOI.VectorAffineFunction buffers of T affine records from one launch — x_{t+1} == A*x_t + B*u_t (+ w_t)
  * for every stage of a horizon, the other half of the model whose objective pmt_quad_stages_f64 writes.  A record is a sum

@@ -281,6 +281,22 @@ quad_stages_diag!(out_quad, out_lin, stage_consts, out_const, stages::DevPtr, te
                 (DevPtr, DevPtr, DevPtr, Int64, DevPtr, Int64, DevPtr, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
                 stages, terms, diags, T, consts, nconsts, varmap, out_quad, out_lin, stage_consts, out_const, stream))
 
+"quad_stages_diag_check for the tables of quad_stages_csc!: a stage's quad_at is its first double among the `nvalues` CSC values of P
+ (n(n+1)/2 per form stage, n per identity stage)"
+quad_stages_csc_check(stages::Vector{QuadStage}, terms::Vector{QuadStageTerms}, diags::Union{Vector{QuadStageDiag},Nothing},
+                      consts::Vector{QuadStageConst}, nvalues, nlin) =
+    check(ccall((:pmt_quad_stages_csc_check, lib), Cint,
+                (Ptr{QuadStage}, Ptr{QuadStageTerms}, Ptr{QuadStageDiag}, Int64, Ptr{QuadStageConst}, Int64, Int64, Int64),
+                stages, terms, diags === nothing ? C_NULL : diags, length(stages), consts, length(consts), nvalues, nlin))
+
+"quad_stages_diag! for a device-resident solver: out_P_values[quad_at + k(k+1)/2 + j] = alpha * c(j,k), the CSC values of the block-diagonal
+ upper-triangular P, instead of quadratic term structs; out_lin, stage_consts and out_const as quad_stages_diag! writes them (not scaled)"
+quad_stages_csc!(out_P_values, out_lin, stage_consts, out_const, stages::DevPtr, terms::DevPtr, diags::DevPtr, T, consts::DevPtr, nconsts, varmap,
+                 alpha, stream) =
+    check(ccall((:pmt_quad_stages_csc_f64, lib), Cint,
+                (DevPtr, DevPtr, DevPtr, Int64, DevPtr, Int64, DevPtr, Float64, DevPtr, DevPtr, DevPtr, DevPtr, Ptr{Cvoid}),
+                stages, terms, diags, T, consts, nconsts, varmap, alpha, out_P_values, out_lin, stage_consts, out_const, stream))
+
 "pmt_affine_part (include/parametron_hip.h): one leaf with terms of a record of pmt_affine_stages_f64 — a matrix (column-major, leading
  dimension ld) over `cols` model variables, or mat C_NULL for a Variable vector (cols 1); sign +1 | -1; 32 bytes, no padding"
 struct AffinePart

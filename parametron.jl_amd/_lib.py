@@ -362,6 +362,8 @@ SIGNATURES = {
     "pmt_quad_stages_terms_f64": (_ci, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pmt_quad_stages_diag_check": (_ci, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64]),
     "pmt_quad_stages_diag_f64": (_ci, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pmt_quad_stages_csc_check": (_ci, [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64]),
+    "pmt_quad_stages_csc_f64": (_ci, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _f64, _vp, _vp, _vp, _vp, _vp]),
     "pmt_affine_stages_check": (_ci, [_vp, _i64, _vp, _i64, _i64, _i64]),
     "pmt_affine_stages_f64": (_ci, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "pmt_comm_unique_id": (_ci, [_vp]),

@@ -23,7 +23,8 @@
 // beside the stages, from two more device tables.  pmt_quad_stages_diag_f64 adds identity-weighted stage costs: a stage without a matrix
 // (W_t * dot(x_t (+|-) v_t, x_t (+|-) v_t): n quadratic terms, no tile walk) and a diagonal term riding on a form stage, from a third
 // table.  The kernels are templates on MODE; the instantiations QS_PLAIN and QS_TERMS are the device code of the two older entry points
-// unchanged (tools/isa_diff.py).
+// unchanged (tools/isa_diff.py).  pmt_quad_stages_csc_f64 (QS_CSC) is pmt_quad_stages_diag_f64 with another quadratic epilogue: a device-resident
+// solver's CSC values of the block-diagonal upper-triangular P — 8 bytes per entry, no index words — instead of 24-byte term structs.
 // LDS: 33280 (tile) + 8192 (P) + 2048 (c) + 2048 (tree) + 2048 (index words) + 2048 (lin) = 49664 bytes: three workgroups per CU.
 #include <algorithm>
 #include <type_traits>
@@ -46,8 +47,8 @@ static_assert(sizeof(pmt_quad_stage) == 56, "pmt_quad_stage: 56 bytes, no paddin
 static_assert(sizeof(pmt_quad_stage_terms) == 40 && sizeof(pmt_quad_stage_const) == 24, "pmt_quad_stage_terms / _const: 40 / 24 bytes, no padding");
 static_assert(sizeof(pmt_quad_stage_diag) == 32, "pmt_quad_stage_diag: 32 bytes, no padding");
 
-// the entry point an instantiation serves: pmt_quad_stages_f64, pmt_quad_stages_terms_f64, pmt_quad_stages_diag_f64
-constexpr int QS_PLAIN = 0, QS_TERMS = 1, QS_DIAG = 2;
+// the entry point an instantiation serves: pmt_quad_stages_f64, pmt_quad_stages_terms_f64, pmt_quad_stages_diag_f64, pmt_quad_stages_csc_f64
+constexpr int QS_PLAIN = 0, QS_TERMS = 1, QS_DIAG = 2, QS_CSC = 3;
 
 struct QuadStagesArgs {
     const pmt_quad_stage *stages; int64_t T;
@@ -65,7 +66,11 @@ struct QuadStagesTermsArgs : QuadStagesArgs {
 struct QuadStagesDiagArgs : QuadStagesTermsArgs {
     const pmt_quad_stage_diag *diags;
 };
-template <int MODE> using QsArgs = std::conditional_t<MODE == QS_DIAG, QuadStagesDiagArgs, std::conditional_t<MODE == QS_TERMS, QuadStagesTermsArgs, QuadStagesArgs>>;
+// pmt_quad_stages_csc_f64: P's CSC values (quad is unused) and the sense they are multiplied by
+struct QuadStagesCscArgs : QuadStagesDiagArgs {
+    double *pvalues; double alpha;
+};
+template <int MODE> using QsArgs = std::conditional_t<MODE == QS_CSC, QuadStagesCscArgs, std::conditional_t<MODE == QS_DIAG, QuadStagesDiagArgs, std::conditional_t<MODE == QS_TERMS, QuadStagesTermsArgs, QuadStagesArgs>>>;
 
 }  // namespace
 
@@ -79,9 +84,13 @@ template <int MODE> using QsArgs = std::conditional_t<MODE == QS_DIAG, QuadStage
 //     W_t*(2*c_j) (+ W_c*c_t[j]) — W_c*c_t[j] alone without v, +0.0 with neither — and W_t*S, S = sum_j c_j*c_j from the 256-entry tree;
 //   - a rider (g.diags[t].present) adds (2*W_d) to the stage's n diagonal coefficients as they are written, W_d*(2*c^d_j) to lin[j] between
 //     W_t*lin_j and W_c*c_t[j], and W_d*S to the constant from one more pass of the tree over red[].
+// QS_CSC (pmt_quad_stages_csc_f64) is QS_DIAG with the quadratic epilogue of a CSC hand-off: quad_at counts doubles of g.pvalues, and the
+// coefficient c(j,k) QS_DIAG writes at tri(j,k) goes, times alpha, to k(k+1)/2 + j — column k's rows j0 .. min(j0 + jw - 1, k) of a tile are
+// one contiguous run, a wave per column with the rows on the lanes, two to a lane for the 16-byte stores (tile[jj][kk] with jj = 2 lane,
+// 2 lane + 1: a stride of 130 doubles, lanes l and l + 16 share a bank: two-way at the most); an identity stage writes alpha*(2*W_t) n times.  The index words var[] serve the linear terms alone.
 template <int MODE>
-__global__ __launch_bounds__(QS_THREADS, MODE == QS_DIAG ? QS_WG_PER_CU : 1) void quad_stages_kernel(QsArgs<MODE> g) {
-    constexpr bool TERMS = MODE != QS_PLAIN, DIAG = MODE == QS_DIAG;
+__global__ __launch_bounds__(QS_THREADS, MODE >= QS_DIAG ? QS_WG_PER_CU : 1) void quad_stages_kernel(QsArgs<MODE> g) {
+    constexpr bool TERMS = MODE != QS_PLAIN, DIAG = MODE >= QS_DIAG, CSC = MODE == QS_CSC;
     typedef unsigned long long u64w;
     __shared__ double tile[QS_TILE][QS_TILE + 1];
     __shared__ double part[QS_MAX_NB][QS_MAX_N];          // P[B][j]
@@ -105,7 +114,10 @@ __global__ __launch_bounds__(QS_THREADS, MODE == QS_DIAG ? QS_WG_PER_CU : 1) voi
         const int64_t ldq = d.ldq;
         const double *__restrict__ Q = d.Q;
         const bool shift = d.sign != 0;
-        QT *__restrict__ oq = g.quad + d.quad_at;
+        [[maybe_unused]] QT *__restrict__ oq = nullptr;
+        [[maybe_unused]] double *__restrict__ op = nullptr;
+        if constexpr (CSC) op = g.pvalues + d.quad_at;
+        else oq = g.quad + d.quad_at;
         // v and the index words are asked for now and looked at behind the first tile's loads: no round trip of their own in front of the
         // tiles (every thread loads, thread t >= n the last entry again)
         const int ct = tid < n ? tid : n - 1;
@@ -207,25 +219,40 @@ __global__ __launch_bounds__(QS_THREADS, MODE == QS_DIAG ? QS_WG_PER_CU : 1) voi
                     }
                 }
                 // the quadratic terms: row j holds its columns k >= j; this tile's piece of it, a wave per row segment, 16-byte stores
-                const int ke = k0 + kw;
-                for (int r = 0; r < 16; ++r) {
-                    const int jj = wave * 16 + r, j = j0 + jj;
-                    if (j >= n) break;
-                    const int ks = k0 > j ? k0 : j;
-                    if (ke <= ks) continue;
-                    const int off = ks - k0;
-                    const u64w rowvar = (u64w)var[j];
-                    wave_write_words<3>(reinterpret_cast<u64w *>(oq + tri_pos(n, j, ks)), ke - ks, lane, [&](int q) -> u64w {
-                        const int e = q / 3, f = q - 3 * e;
-                        if (f == 1) return rowvar;
-                        if (f == 2) return (u64w)var[k0 + off + e];
-                        const double v = tile[jj][off + e];
-                        const double c = (diagonal && e == 0) ? 2 * v : v;                        // the row's first term is its diagonal term
-                        if constexpr (DIAG) {
-                            if (rider && diagonal && e == 0) return (u64w)__double_as_longlong(wt * c + 2 * wd);
-                        }
-                        return (u64w)__double_as_longlong(TERMS ? wt * c : c);
-                    });
+                [[maybe_unused]] const int ke = k0 + kw;
+                if constexpr (CSC) {
+                    // P's values: column k holds its rows j <= k; this tile's piece of it, a wave per column, 16-byte stores
+                    for (int r = 0; r < 16; ++r) {
+                        const int kk = wave * 16 + r, k = k0 + kk;
+                        if (k >= n) break;
+                        wave_write_words<1>(reinterpret_cast<u64w *>(op + ((int64_t)k * (k + 1) / 2 + j0)), diagonal ? kk + 1 : jw, lane, [&](int q) -> u64w {
+                            const double v = tile[q][kk];
+                            const bool dj = diagonal && q == kk;                                      // the column's last value is its diagonal one
+                            double c = wt * (dj ? 2 * v : v);
+                            if (rider && dj) c = c + 2 * wd;
+                            return (u64w)__double_as_longlong(g.alpha * c);
+                        });
+                    }
+                } else {
+                    for (int r = 0; r < 16; ++r) {
+                        const int jj = wave * 16 + r, j = j0 + jj;
+                        if (j >= n) break;
+                        const int ks = k0 > j ? k0 : j;
+                        if (ke <= ks) continue;
+                        const int off = ks - k0;
+                        const u64w rowvar = (u64w)var[j];
+                        wave_write_words<3>(reinterpret_cast<u64w *>(oq + tri_pos(n, j, ks)), ke - ks, lane, [&](int q) -> u64w {
+                            const int e = q / 3, f = q - 3 * e;
+                            if (f == 1) return rowvar;
+                            if (f == 2) return (u64w)var[k0 + off + e];
+                            const double v = tile[jj][off + e];
+                            const double c = (diagonal && e == 0) ? 2 * v : v;                        // the row's first term is its diagonal term
+                            if constexpr (DIAG) {
+                                if (rider && diagonal && e == 0) return (u64w)__double_as_longlong(wt * c + 2 * wd);
+                            }
+                            return (u64w)__double_as_longlong(TERMS ? wt * c : c);
+                        });
+                    }
                 }
                 __syncthreads();
             }
@@ -287,11 +314,16 @@ __global__ __launch_bounds__(QS_THREADS, MODE == QS_DIAG ? QS_WG_PER_CU : 1) voi
                     return (q & 1) ? (u64w)var[e] : (u64w)__double_as_longlong(linv[e]);
                 });
                 if (DIAG && ident) {                      // and the terms (2*W_t, var_j, var_j) 64 w .. of an identity stage
-                    const u64w w2 = (u64w)__double_as_longlong(2 * wt);
-                    wave_write_words<3>(reinterpret_cast<u64w *>(oq + w0), cnt, lane, [&](int q) -> u64w {
-                        const int e = q / 3;
-                        return q == 3 * e ? w2 : (u64w)var[w0 + e];
-                    });
+                    if constexpr (CSC) {                  // (P's values: alpha*(2*W_t) 64 w ..)
+                        const u64w w2 = (u64w)__double_as_longlong(g.alpha * (2 * wt));
+                        wave_write_words<1>(reinterpret_cast<u64w *>(op + w0), cnt, lane, [&](int) -> u64w { return w2; });
+                    } else {
+                        const u64w w2 = (u64w)__double_as_longlong(2 * wt);
+                        wave_write_words<3>(reinterpret_cast<u64w *>(oq + w0), cnt, lane, [&](int q) -> u64w {
+                            const int e = q / 3;
+                            return q == 3 * e ? w2 : (u64w)var[w0 + e];
+                        });
+                    }
                 }
             }
         }
@@ -510,4 +542,33 @@ extern "C" int pmt_quad_stages_diag_f64(const pmt_quad_stage *stages, const pmt_
     g.cterms = consts; g.nconsts = nconsts;
     g.diags = diags;
     return qs_launch<QS_DIAG>(stream, g);
+}
+
+// the value slices are the quadratic slices of pmt_quad_stages_diag_check counted in doubles: n(n+1)/2 per form stage, n per identity stage
+extern "C" int pmt_quad_stages_csc_check(const pmt_quad_stage *host_stages, const pmt_quad_stage_terms *host_terms,
+                                         const pmt_quad_stage_diag *host_diags, int64_t T, const pmt_quad_stage_const *host_consts,
+                                         int64_t nconsts, int64_t nvalues, int64_t nlin) {
+    return pmt_quad_stages_diag_check(host_stages, host_terms, host_diags, T, host_consts, nconsts, nvalues, nlin);
+}
+
+extern "C" int pmt_quad_stages_csc_f64(const pmt_quad_stage *stages, const pmt_quad_stage_terms *terms, const pmt_quad_stage_diag *diags,
+                                       int64_t T, const pmt_quad_stage_const *consts, int64_t nconsts, const int64_t *varmap, double alpha,
+                                       double *out_P_values, pmt_linear_term *out_lin, double *stage_consts, double *out_const,
+                                       void *stream) {
+    PMT_REQUIRE(T >= 0, PMT_DIMENSION_MISMATCH, "quad_stages_csc: negative stage count");
+    PMT_REQUIRE(nconsts >= 0 && nconsts <= PMT_QUAD_STAGES_MAX_CONSTS, PMT_DIMENSION_MISMATCH, "quad_stages_csc: nconsts outside 0 .. 32");
+    PMT_REQUIRE(out_const, PMT_INVALID_ARGUMENT, "quad_stages_csc: null constant");
+    PMT_REQUIRE(nconsts == 0 || consts, PMT_INVALID_ARGUMENT, "quad_stages_csc: null table of constants");
+    PMT_REQUIRE(T == 0 || (stages && terms && varmap && out_P_values && out_lin && stage_consts), PMT_INVALID_ARGUMENT,
+                "quad_stages_csc: null pointer");
+    QuadStagesCscArgs g;
+    g.stages = stages; g.T = T;
+    g.varmap = varmap;
+    g.quad = nullptr; g.lin = out_lin;
+    g.consts = stage_consts; g.cst = out_const;
+    g.terms = terms;
+    g.cterms = consts; g.nconsts = nconsts;
+    g.diags = diags;
+    g.pvalues = out_P_values; g.alpha = alpha;
+    return qs_launch<QS_CSC>(stream, g);
 }

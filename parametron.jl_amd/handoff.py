@@ -38,6 +38,25 @@ def _csc_order(rows, cols, nrows, ncols, upper):
     return perm[:n], seg[:k + 1], col_ptr, row_idx[:k]
 
 
+def stage_blocks_pattern(blocks, nvalues):
+    """(rows, cols) of the entries of a "canonical-stages-csc" objective's value buffer, entry i lying 8*i bytes into it, in the index
+    convention _build_matrix takes from MOI terms (1-based optimizer indices).  `blocks`: per stage (idx, at, diagonal) — its strictly
+    increasing optimizer indices, its first double in the buffer, and whether it is an identity stage: then entry at + j is (idx[j], idx[j]),
+    otherwise entry at + k(k+1)/2 + j is (idx[j], idx[k]) for j <= k (moi._Record._compile_stages_csc, pmt_quad_stages_csc_f64).  The slices
+    must tile [0, nvalues).  Host data only."""
+    rows, cols = np.zeros(nvalues, dtype=np.int64), np.zeros(nvalues, dtype=np.int64)
+    for idx, at, diagonal in blocks:
+        idx = np.asarray(idx, dtype=np.int64)
+        j, k = (np.arange(len(idx)),) * 2 if diagonal else np.triu_indices(len(idx))
+        pos = at + (j if diagonal else k * (k + 1) // 2 + j)
+        if len(pos) and (pos[0] < 0 or pos.max() >= nvalues or np.any(rows[pos])):
+            raise ArgumentError("DeviceQP: the stages' value slices overlap or leave the buffer")
+        rows[pos], cols[pos] = idx[j], idx[k]
+    if not np.all(rows):
+        raise ArgumentError("DeviceQP: the stages' value slices leave part of the buffer unnamed")
+    return rows, cols
+
+
 class _Block:
     """One source of matrix entries: a device term buffer (or host values for constant functions) and where its runs go."""
 
@@ -213,7 +232,7 @@ class DeviceQP:
         obj = model.objective
         f = obj.f
         qblocks, lblocks = [], []
-        direct_P = None
+        direct_P = stage_P = None
         if obj.kind == "quad" and not obj.isconstant and "P_values" in obj.dev:
             # the plan was specialised (moi._Record.compile): the Gram epilogue already writes sign * P in CSC order;
             # column c of P belongs to the variable with optimizer index c+1, its rows are the variables before it
@@ -225,6 +244,15 @@ class DeviceQP:
             direct_P = CSC(n, n, col_ptr, pv[np.tril_indices(k)[1]].astype(np.int64), obj.dev["P_values"])
             at = f.affine_terms
             lblocks.append(_Block(at["var"].copy(), None, obj.dev["lin"], 16))
+        elif obj.kind == "quad" and not obj.isconstant and "P_stage_values" in obj.dev:
+            # a horizon of stage costs (moi._Record._compile_stages_csc): the stage launch already wrote sign * P's values, block by block;
+            # with every stage's optimizer indices consecutive the buffer IS P's CSC value array (_build_matrix's shortcut: nothing to
+            # launch), otherwise the gather places them.  q through the generic route, as for a literal objective
+            blocks = obj.dev["P_stage_blocks"]
+            nvalues = sum(len(idx) if diagonal else len(idx) * (len(idx) + 1) // 2 for idx, _, diagonal in blocks)
+            rows, cols = stage_blocks_pattern(blocks, nvalues)
+            stage_P = self._build_matrix([_Block(rows, cols, coeff_ptr=obj.dev["P_stage_values"], stride=8)], n, n, upper=True, alpha=1.0)
+            lblocks.append(_Block(f.affine_terms["var"].copy(), None, obj.dev["lin"], 16))
         elif obj.kind == "quad":
             qt, at = f.quadratic_terms, f.affine_terms
             if obj.isconstant:
@@ -239,7 +267,8 @@ class DeviceQP:
                 lblocks.append(_Block(vm[at["var"] - 1], None, host_coeff=at["coeff"].copy()))
             else:
                 lblocks.append(_Block(at["var"].copy(), None, obj.dev["terms"], 16))
-        self.P = direct_P if direct_P is not None else self._build_matrix(qblocks, n, n, upper=True, alpha=self.sign)
+        self.P = direct_P if direct_P is not None else stage_P if stage_P is not None else \
+            self._build_matrix(qblocks, n, n, upper=True, alpha=self.sign)
         # q, l and u share ONE device block (q | l | u): a host delivery ships them as a single transfer
         mrows = sum(c.nrows for c in model.constraints)
         self._small_ptr = ctx.alloc(8 * max(n + 2 * mrows, 1))

@@ -393,7 +393,8 @@ class Model:
         """the one decision on a quadratic record's form (moi.quad_plan); here: the stacked matrices it reads, canonicalize!"""
         for r in (r for r in self._records if r.kind == "quad"):
             r.plan = plan = moi.quad_plan(r.expr.lsq_sum, r.expr.lsq_bare, r.kind, r.expr.out.nq, r is self.objective, self.quadratic_mode,
-                                          self._small, self.handoff, varmap, sparse_sums=True, stage_terms=True, stage_diag=True)
+                                          self._small, self.handoff, varmap, sparse_sums=True, stage_terms=True, stage_diag=True,
+                                          stage_csc=True)
             for g in (g for g in plan.operands() if hasattr(g, "require_stack")):
                 g.require_stack()
             if plan.canonicalize:

@@ -257,7 +257,7 @@ def _lsq_desc(t):
 
 class _Record:
     """Common part of Objective and Constraint (src/moi_interop.jl:113-129, 141-166)."""
-    mode = property(lambda self: self.plan.mode)                          # "literal" / "canonical" / "canonical-csc" / "-form" / "-sum" / "-groups" / "-stages" / "-sparse" / "-sparse-form" / "-sparse-sum"
+    mode = property(lambda self: self.plan.mode)                          # "literal" / "canonical" / "canonical-csc" / "-form" / "-sum" / "-groups" / "-stages" / "-stages-csc" / "-sparse" / "-sparse-form" / "-sparse-sum"
     lsq_terms = property(lambda self: self.plan.terms)                    # the LsqTerm list a "canonical-sum" record combines, or None
 
     def _setup(self, model, expr):
@@ -526,19 +526,10 @@ class _Record:
         lay = _lib.GroupsLayout([q.xvars.vars for q in stages], diagonal=ident if any(ident) else None)
         T, n, nq = len(stages), lay.nlin, lay.nterms
         bq, bl, oq, ol, consts, dc, gather = self._compile_layout(ctx, lay, T)
-        vs = [_vec_sign(q.vec, q.sign) for q in stages]
-        # (an identity stage's variables may be a host-built term's: their indices get a device buffer here)
-        arr = _lib.quad_stages([{"Q": None, "xvar": ctx.upload_new(np.ascontiguousarray(q.xvars.vars, dtype=np.int64)), "vec": vec,
-                                 "n": len(q.xvars.vars), "sign": sign, "quad_at": int(oq[k]), "lin_at": int(ol[k])} if q.mat is None else
-                                {"Q": q.mat.buf, "ldq": q.mat.lda, "xvar": q.xvars.buf, "vec": vec, "n": q.mat.cols, "sign": sign,
-                                 "quad_at": int(oq[k]), "lin_at": int(ol[k])} for k, (q, (vec, sign)) in enumerate(zip(stages, vs))])
+        arr = self._stage_table(ctx, stages, oq, ol)
         sterms, sconsts, sdiags = self.plan.stage_terms, self.plan.stage_consts, self.plan.stage_diags
         if any(ident) or sdiags is not None:
-            tarr = _lib.quad_stage_terms([self._stage_terms_row(s) for s in sterms or [StageTerms()] * T])
-            rvs = [_vec_sign(r.vec, r.sign) if r is not None else None for r in sdiags or [None] * T]
-            darr = _lib.quad_stage_diags([{} if r is None else {"scale": r.scale, "weight": _buf(r.param), "vec": rv[0], "sign": rv[1]}
-                                          for r, rv in zip(sdiags or [None] * T, rvs)])
-            carr = _lib.quad_stage_consts([{"scale": k.scale, "weight": _buf(k.param), "value": _buf(k.value)} for k in sconsts])
+            tarr, darr, carr = self._stage_side_tables(T)
             nc = len(sconsts)
             _lib.call("pmt_quad_stages_diag_check", C.addressof(arr), C.addressof(tarr), C.addressof(darr) if sdiags is not None else None, T,
                       C.addressof(carr), nc, nq, n)
@@ -565,6 +556,60 @@ class _Record:
             launch(c)
             gather(c)
         return emit
+
+    def _compile_stages_csc(self, ctx, varmap_buf, handoff_varmap):
+        """The horizon of _compile_stages for the device hand-off (plan "canonical-stages-csc"): ONE pmt_quad_stages_csc_f64 writes the
+        solver's CSC values of the block-diagonal upper-triangular P — times the sense — instead of quadratic term structs, and the linear
+        terms and the constant as the MOI entry points do.  The three tables are built, checked (pmt_quad_stages_csc_check) and uploaded
+        here once.  The value slices lie one behind the other in the order of the stages' first optimizer index: when every stage's
+        optimizer indices are consecutive that IS P's CSC order and the hand-off takes the buffer as it is (handoff.stage_blocks_pattern),
+        otherwise its gather places the values.  The linear slices are concatenated in table order — the hand-off orders q itself —, so
+        there is no arena and no gather here.  update! allocates nothing and makes one call."""
+        stages = self.plan.stages
+        T = len(stages)
+        sizes = [len(q.xvars.vars) for q in stages]
+        ident = [q.mat is None for q in stages]
+        idx = [np.asarray(handoff_varmap, dtype=np.int64)[q.xvars.vars - 1] for q in stages]
+        nval = [n if d else n * (n + 1) // 2 for n, d in zip(sizes, ident)]
+        at = np.zeros(T, dtype=np.int64)
+        order = np.argsort([int(i[0]) for i in idx], kind="stable")
+        at[order] = np.cumsum([0] + [nval[k] for k in order])[:-1]
+        ol = np.cumsum([0] + sizes)
+        n, nvalues = int(ol[-1]), int(sum(nval))
+        self.f = ScalarQuadraticFunction(n, 0, alloc=ctx.pinned_array)
+        dp, dl, dc, consts = ctx.alloc(8 * nvalues), ctx.alloc(16 * n), ctx.alloc(8), ctx.alloc(8 * T)
+        self.dev = {"lin": dl, "const": dc, "P_stage_values": dp,
+                    "P_stage_blocks": [(idx[k], int(at[k]), ident[k]) for k in range(T)]}
+        arr = self._stage_table(ctx, stages, at, ol)
+        (tarr, darr, carr), sdiags, nc = self._stage_side_tables(T), self.plan.stage_diags, len(self.plan.stage_consts)
+        _lib.call("pmt_quad_stages_csc_check", C.addressof(arr), C.addressof(tarr), C.addressof(darr) if sdiags is not None else None, T,
+                  C.addressof(carr), nc, nvalues, n)
+        table, ttable, ctable = _table(ctx, arr), _table(ctx, tarr), _table(ctx, carr)
+        dtable = _table(ctx, darr) if sdiags is not None else None
+        alpha = -1.0 if self.model.sense == "Maximize" else 1.0
+        return lambda c: c.call("pmt_quad_stages_csc_f64", P(table), P(ttable), P(dtable), T, P(ctable), nc, P(varmap_buf), alpha, P(dp), P(dl),
+                                P(consts), P(dc))
+
+    @staticmethod
+    def _stage_table(ctx, stages, oq, ol):
+        """the host pmt_quad_stage table of plan.stages, stage k's slices starting at oq[k] / ol[k] (an identity stage's variables may be a
+        host-built term's: their indices get a device buffer here)"""
+        vs = [_vec_sign(q.vec, q.sign) for q in stages]
+        return _lib.quad_stages([{"Q": None, "xvar": ctx.upload_new(np.ascontiguousarray(q.xvars.vars, dtype=np.int64)), "vec": vec,
+                                  "n": len(q.xvars.vars), "sign": sign, "quad_at": int(oq[k]), "lin_at": int(ol[k])} if q.mat is None else
+                                 {"Q": q.mat.buf, "ldq": q.mat.lda, "xvar": q.xvars.buf, "vec": vec, "n": q.mat.cols, "sign": sign,
+                                  "quad_at": int(oq[k]), "lin_at": int(ol[k])} for k, (q, (vec, sign)) in enumerate(zip(stages, vs))])
+
+    def _stage_side_tables(self, T):
+        """the host tables beside the T stages of pmt_quad_stages_diag_f64 / _csc_f64: (terms — unit rows without plan.stage_terms —, riders,
+        constants); nothing is allocated"""
+        sterms, sconsts, sdiags = self.plan.stage_terms, self.plan.stage_consts, self.plan.stage_diags
+        tarr = _lib.quad_stage_terms([self._stage_terms_row(s) for s in sterms or [StageTerms()] * T])
+        rvs = [_vec_sign(r.vec, r.sign) if r is not None else None for r in sdiags or [None] * T]
+        darr = _lib.quad_stage_diags([{} if r is None else {"scale": r.scale, "weight": _buf(r.param), "vec": rv[0], "sign": rv[1]}
+                                      for r, rv in zip(sdiags or [None] * T, rvs)])
+        carr = _lib.quad_stage_consts([{"scale": k.scale, "weight": _buf(k.param), "value": _buf(k.value)} for k in sconsts])
+        return tarr, darr, carr
 
     @staticmethod
     def _stage_terms_row(s):                                              # the pmt_quad_stage_terms fields of a StageTerms
@@ -638,7 +683,8 @@ class _Record:
 
     # the quadratic forms by plan.mode (quad_plan)
     _QUAD_FORMS = {"canonical-sparse": _compile_sparse_gram, "canonical-sparse-form": _compile_sparse_form, "canonical-sparse-sum": _compile_sparse_sum, "literal": _compile_literal, "canonical": _compile_gram, "canonical-csc": _compile_gram, "canonical-form": _compile_form,
-                   "canonical-sum": _compile_lsq_sum, "canonical-groups": _compile_groups, "canonical-stages": _compile_stages}
+                   "canonical-sum": _compile_lsq_sum, "canonical-groups": _compile_groups, "canonical-stages": _compile_stages,
+                   "canonical-stages-csc": _compile_stages_csc}
 
     # ---- Vector{AffineFunction}
     def _compile_vector(self, ctx, varmap_buf, handoff_varmap):
@@ -979,13 +1025,14 @@ class QuadPlan:
 
 
 def quad_plan(terms, bare, kind, nq, is_objective, quadratic_mode, small, handoff, varmap=None, sparse_sums=False, stage_terms=False,
-              stage_diag=False):
+              stage_diag=False, stage_csc=False):
     """The QuadPlan of a record over a node described by (terms, bare) = DeviceNode.(lsq_sum, lsq_bare); no mode unless kind == "quad".  `nq`:
     the terms of its literal expansion; `small`: Model._small; `varmap`: the optimizer's index map when it is fixed before the plan is recorded
     (handoff "device" / "host_csc"); `sparse_sums`: weighted sums over sparse blocks take the sparse combine (Model passes True);
     `stage_terms`: a horizon with weights, linear terms or constants beside its stages takes "canonical-stages" (Model passes True; a caller
     that does not ask gets the row as it was: such a horizon stays literal); `stage_diag`: likewise for a horizon with identity-weighted
-    stage costs — rho*dot(u_t, u_t) as a stage, a ridge beside a form (Model passes True).  Host data only: nothing is allocated, no stacked matrix is asked for.  First match wins."""
+    stage costs — rho*dot(u_t, u_t) as a stage, a ridge beside a form (Model passes True); `stage_csc`: a horizon under handoff "device" takes
+    "canonical-stages-csc", P's CSC values from the stage launch (Model passes True; without it such a horizon stays literal).  Host data only: nothing is allocated, no stacked matrix is asked for.  First match wins."""
     one = terms[0] if bare and kind == "quad" else None
     block = one.r if one is not None and one.kind == "block" else None
     if isinstance(block, DSparseAff) and (quadratic_mode == "literal" or handoff == "host_csc"):
@@ -1050,6 +1097,12 @@ def quad_plan(terms, bare, kind, nq, is_objective, quadratic_mode, small, handof
                 has_diag = diags is not None or any(q.mat is None for q in stages[0])
                 if stage_terms or has_diag or (stages[1] is None and not stages[2]):
                     return QuadPlan("canonical-stages", stages=stages[0], stage_terms=stages[1], stage_consts=stages[2], stage_diags=diags)
+        # the same horizon for the device hand-off: the stage launch writes the solver's CSC values of the block-diagonal P itself
+        # (pmt_quad_stages_csc_f64) — every stage's vector has to keep its order under the optimizer's index map, as canonical-csc asks
+        if stage_csc and is_objective and handoff == "device" and not bare and nq >= GROUPS_MIN_LITERAL_TERMS:
+            stages = _lsq_stages(terms, diag=True)
+            if stages and all(ordered(q.xvars) for q in stages[0]):
+                return QuadPlan("canonical-stages-csc", stages=stages[0], stage_terms=stages[1], stage_consts=stages[2], stage_diags=stages[3])
     # anything else: the literal function through the generic device canonicalize! (sorted, duplicates combined) before the MOI copy
     return QuadPlan("literal", canonicalize=True)
 
