@@ -425,20 +425,30 @@ static int qs_launch(void *stream, const QsArgs<MODE> &g) {
 
 using namespace pmt;
 
-// pmt_quad_stages_check; `identity` (pmt_quad_stages_diag_check): a stage without a matrix is an identity stage of n quadratic terms, its
-// ldq not looked at
-static int qs_check(const pmt_quad_stage *host_stages, int64_t T, int64_t nterms, int64_t nlin, bool identity) {
+// The host side of the four entry points.  They share one check of the host tables (qs_check), the argument checks in front of the launch and
+// the launch itself (qs_run over the most-derived argument struct, of which qs_launch<MODE> takes its slice); the MODE says what an entry has
+// beyond the last:
+//   QS_PLAIN  pmt_quad_stages_f64        the stage table
+//   QS_TERMS  pmt_quad_stages_terms_f64  + the stages' terms and the table of constants
+//   QS_DIAG   pmt_quad_stages_diag_f64   + the riders (the table may be NULL), and a stage without a matrix is an identity stage
+//   QS_CSC    pmt_quad_stages_csc_f64    the same tables; P's CSC values times alpha instead of the quadratic terms
+// A check's message keeps the prefix of the entry that introduced its table, whichever check is called; a launch's says the entry's own name.
+
+// pmt_quad_stages_check .. pmt_quad_stages_csc_check: the counts, the stage table, the slices, the side tables, the riders, in this order.
+// Tables a mode does not have are NULL / 0 and not looked at.  From QS_DIAG on a stage without a matrix is an identity stage of n quadratic
+// terms (QS_CSC: n values; a form stage's n(n+1)/2 likewise count doubles there), its ldq not looked at
+static int qs_check(int mode, const pmt_quad_stage *host_stages, const pmt_quad_stage_terms *host_terms, const pmt_quad_stage_diag *host_diags,
+                    int64_t T, const pmt_quad_stage_const *host_consts, int64_t nconsts, int64_t nterms, int64_t nlin) {
     PMT_REQUIRE(T >= 0, PMT_DIMENSION_MISMATCH, "quad_stages: negative stage count");
     PMT_REQUIRE(nterms >= 0 && nlin >= 0, PMT_DIMENSION_MISMATCH, "quad_stages: negative term count");
-    if (T == 0) return PMT_OK;
-    PMT_REQUIRE(host_stages, PMT_INVALID_ARGUMENT, "quad_stages: null stage table");
+    PMT_REQUIRE(T == 0 || host_stages, PMT_INVALID_ARGUMENT, "quad_stages: null stage table");
     std::vector<std::pair<int64_t, int64_t>> quad, lin;
     quad.reserve((size_t)T);
     lin.reserve((size_t)T);
     for (int64_t t = 0; t < T; ++t) {
         const pmt_quad_stage &d = host_stages[t];
         const std::string at = " (stage " + std::to_string(t) + ")";
-        PMT_REQUIRE(d.Q || identity, PMT_INVALID_ARGUMENT, "quad_stages: null matrix" + at);
+        PMT_REQUIRE(d.Q || mode >= QS_DIAG, PMT_INVALID_ARGUMENT, "quad_stages: null matrix" + at);
         PMT_REQUIRE(d.xvar, PMT_INVALID_ARGUMENT, "quad_stages: null variable indices" + at);
         PMT_REQUIRE(d.sign >= -1 && d.sign <= 1, PMT_INVALID_ARGUMENT, "quad_stages: sign must be -1, 0 or +1" + at);
         PMT_REQUIRE(d.sign == 0 || d.vec, PMT_INVALID_ARGUMENT, "quad_stages: a shifted stage without its vector" + at);
@@ -450,67 +460,11 @@ static int qs_check(const pmt_quad_stage *host_stages, int64_t T, int64_t nterms
     }
     PMT_REQUIRE(qs_slices_ok(quad, nterms), PMT_DIMENSION_MISMATCH, "quad_stages: quadratic slices overlap or leave [0, nterms)");
     PMT_REQUIRE(qs_slices_ok(lin, nlin), PMT_DIMENSION_MISMATCH, "quad_stages: linear slices overlap or leave [0, nlin)");
-    return PMT_OK;
-}
-
-extern "C" int pmt_quad_stages_check(const pmt_quad_stage *host_stages, int64_t T, int64_t nterms, int64_t nlin) {
-    return qs_check(host_stages, T, nterms, nlin, false);
-}
-
-extern "C" int pmt_quad_stages_f64(const pmt_quad_stage *stages, int64_t T, const int64_t *varmap, pmt_quadratic_term *out_quad,
-                                   pmt_linear_term *out_lin, double *stage_consts, double *out_const, void *stream) {
-    PMT_REQUIRE(T >= 0, PMT_DIMENSION_MISMATCH, "quad_stages: negative stage count");
-    PMT_REQUIRE(out_const, PMT_INVALID_ARGUMENT, "quad_stages: null constant");
-    PMT_REQUIRE(T == 0 || (stages && varmap && out_quad && out_lin && stage_consts), PMT_INVALID_ARGUMENT, "quad_stages: null pointer");
-    QuadStagesArgs g;
-    g.stages = stages; g.T = T;
-    g.varmap = varmap;
-    g.quad = out_quad; g.lin = out_lin;
-    g.consts = stage_consts; g.cst = out_const;
-    return qs_launch<QS_PLAIN>(stream, g);
-}
-
-// pmt_quad_stages_terms_check; `identity`: as qs_check
-static int qs_terms_check(const pmt_quad_stage *host_stages, const pmt_quad_stage_terms *host_terms, int64_t T,
-                          const pmt_quad_stage_const *host_consts, int64_t nconsts, int64_t nterms, int64_t nlin, bool identity) {
-    const int rc = qs_check(host_stages, T, nterms, nlin, identity);
-    if (rc != PMT_OK) return rc;
+    if (mode == QS_PLAIN) return PMT_OK;
     PMT_REQUIRE(T == 0 || host_terms, PMT_INVALID_ARGUMENT, "quad_stages_terms: null table of stage terms");
     PMT_REQUIRE(nconsts >= 0 && nconsts <= PMT_QUAD_STAGES_MAX_CONSTS, PMT_DIMENSION_MISMATCH, "quad_stages_terms: nconsts outside 0 .. 32");
     PMT_REQUIRE(nconsts == 0 || host_consts, PMT_INVALID_ARGUMENT, "quad_stages_terms: null table of constants");
-    return PMT_OK;
-}
-
-extern "C" int pmt_quad_stages_terms_check(const pmt_quad_stage *host_stages, const pmt_quad_stage_terms *host_terms, int64_t T,
-                                           const pmt_quad_stage_const *host_consts, int64_t nconsts, int64_t nterms, int64_t nlin) {
-    return qs_terms_check(host_stages, host_terms, T, host_consts, nconsts, nterms, nlin, false);
-}
-
-extern "C" int pmt_quad_stages_terms_f64(const pmt_quad_stage *stages, const pmt_quad_stage_terms *terms, int64_t T,
-                                         const pmt_quad_stage_const *consts, int64_t nconsts, const int64_t *varmap,
-                                         pmt_quadratic_term *out_quad, pmt_linear_term *out_lin, double *stage_consts, double *out_const,
-                                         void *stream) {
-    PMT_REQUIRE(T >= 0, PMT_DIMENSION_MISMATCH, "quad_stages_terms: negative stage count");
-    PMT_REQUIRE(nconsts >= 0 && nconsts <= PMT_QUAD_STAGES_MAX_CONSTS, PMT_DIMENSION_MISMATCH, "quad_stages_terms: nconsts outside 0 .. 32");
-    PMT_REQUIRE(out_const, PMT_INVALID_ARGUMENT, "quad_stages_terms: null constant");
-    PMT_REQUIRE(nconsts == 0 || consts, PMT_INVALID_ARGUMENT, "quad_stages_terms: null table of constants");
-    PMT_REQUIRE(T == 0 || (stages && terms && varmap && out_quad && out_lin && stage_consts), PMT_INVALID_ARGUMENT,
-                "quad_stages_terms: null pointer");
-    QuadStagesTermsArgs g;
-    g.stages = stages; g.T = T;
-    g.varmap = varmap;
-    g.quad = out_quad; g.lin = out_lin;
-    g.consts = stage_consts; g.cst = out_const;
-    g.terms = terms;
-    g.cterms = consts; g.nconsts = nconsts;
-    return qs_launch<QS_TERMS>(stream, g);
-}
-
-extern "C" int pmt_quad_stages_diag_check(const pmt_quad_stage *host_stages, const pmt_quad_stage_terms *host_terms,
-                                          const pmt_quad_stage_diag *host_diags, int64_t T, const pmt_quad_stage_const *host_consts,
-                                          int64_t nconsts, int64_t nterms, int64_t nlin) {
-    const int rc = qs_terms_check(host_stages, host_terms, T, host_consts, nconsts, nterms, nlin, true);
-    if (rc != PMT_OK || !host_diags) return rc;
+    if (mode < QS_DIAG || !host_diags) return PMT_OK;
     for (int64_t t = 0; t < T; ++t) {
         const pmt_quad_stage_diag &r = host_diags[t];
         const std::string at = " (stage " + std::to_string(t) + ")";
@@ -523,52 +477,68 @@ extern "C" int pmt_quad_stages_diag_check(const pmt_quad_stage *host_stages, con
     return PMT_OK;
 }
 
+// An entry point's argument checks under its own `name`, then its launches.  `g` is filled as far as MODE reads it: {{{{stages, T, varmap,
+// out_quad, out_lin, stage_consts, out_const}, terms, consts, nconsts}, diags}, out_P_values, alpha}
+template <int MODE>
+static int qs_run(const char *name, void *stream, const QuadStagesCscArgs &g) {
+    constexpr bool TERMS = MODE != QS_PLAIN;
+    const auto says = [name](const char *what) { return std::string(name) + ": " + what; };
+    PMT_REQUIRE(g.T >= 0, PMT_DIMENSION_MISMATCH, says("negative stage count"));
+    PMT_REQUIRE(!TERMS || (g.nconsts >= 0 && g.nconsts <= PMT_QUAD_STAGES_MAX_CONSTS), PMT_DIMENSION_MISMATCH, says("nconsts outside 0 .. 32"));
+    PMT_REQUIRE(g.cst, PMT_INVALID_ARGUMENT, says("null constant"));
+    PMT_REQUIRE(!TERMS || g.nconsts == 0 || g.cterms, PMT_INVALID_ARGUMENT, says("null table of constants"));
+    const bool out = MODE == QS_CSC ? g.pvalues != nullptr : g.quad != nullptr;
+    PMT_REQUIRE(g.T == 0 || (g.stages && (!TERMS || g.terms) && g.varmap && out && g.lin && g.consts), PMT_INVALID_ARGUMENT, says("null pointer"));
+    return qs_launch<MODE>(stream, g);
+}
+
+extern "C" int pmt_quad_stages_check(const pmt_quad_stage *host_stages, int64_t T, int64_t nterms, int64_t nlin) {
+    return qs_check(QS_PLAIN, host_stages, nullptr, nullptr, T, nullptr, 0, nterms, nlin);
+}
+
+extern "C" int pmt_quad_stages_f64(const pmt_quad_stage *stages, int64_t T, const int64_t *varmap, pmt_quadratic_term *out_quad,
+                                   pmt_linear_term *out_lin, double *stage_consts, double *out_const, void *stream) {
+    return qs_run<QS_PLAIN>("quad_stages", stream,
+                            {{{{stages, T, varmap, out_quad, out_lin, stage_consts, out_const}, nullptr, nullptr, 0}, nullptr}, nullptr, 0.0});
+}
+
+extern "C" int pmt_quad_stages_terms_check(const pmt_quad_stage *host_stages, const pmt_quad_stage_terms *host_terms, int64_t T,
+                                           const pmt_quad_stage_const *host_consts, int64_t nconsts, int64_t nterms, int64_t nlin) {
+    return qs_check(QS_TERMS, host_stages, host_terms, nullptr, T, host_consts, nconsts, nterms, nlin);
+}
+
+extern "C" int pmt_quad_stages_terms_f64(const pmt_quad_stage *stages, const pmt_quad_stage_terms *terms, int64_t T,
+                                         const pmt_quad_stage_const *consts, int64_t nconsts, const int64_t *varmap,
+                                         pmt_quadratic_term *out_quad, pmt_linear_term *out_lin, double *stage_consts, double *out_const,
+                                         void *stream) {
+    return qs_run<QS_TERMS>("quad_stages_terms", stream,
+                            {{{{stages, T, varmap, out_quad, out_lin, stage_consts, out_const}, terms, consts, nconsts}, nullptr}, nullptr, 0.0});
+}
+
+extern "C" int pmt_quad_stages_diag_check(const pmt_quad_stage *host_stages, const pmt_quad_stage_terms *host_terms,
+                                          const pmt_quad_stage_diag *host_diags, int64_t T, const pmt_quad_stage_const *host_consts,
+                                          int64_t nconsts, int64_t nterms, int64_t nlin) {
+    return qs_check(QS_DIAG, host_stages, host_terms, host_diags, T, host_consts, nconsts, nterms, nlin);
+}
+
 extern "C" int pmt_quad_stages_diag_f64(const pmt_quad_stage *stages, const pmt_quad_stage_terms *terms, const pmt_quad_stage_diag *diags,
                                         int64_t T, const pmt_quad_stage_const *consts, int64_t nconsts, const int64_t *varmap,
                                         pmt_quadratic_term *out_quad, pmt_linear_term *out_lin, double *stage_consts, double *out_const,
                                         void *stream) {
-    PMT_REQUIRE(T >= 0, PMT_DIMENSION_MISMATCH, "quad_stages_diag: negative stage count");
-    PMT_REQUIRE(nconsts >= 0 && nconsts <= PMT_QUAD_STAGES_MAX_CONSTS, PMT_DIMENSION_MISMATCH, "quad_stages_diag: nconsts outside 0 .. 32");
-    PMT_REQUIRE(out_const, PMT_INVALID_ARGUMENT, "quad_stages_diag: null constant");
-    PMT_REQUIRE(nconsts == 0 || consts, PMT_INVALID_ARGUMENT, "quad_stages_diag: null table of constants");
-    PMT_REQUIRE(T == 0 || (stages && terms && varmap && out_quad && out_lin && stage_consts), PMT_INVALID_ARGUMENT,
-                "quad_stages_diag: null pointer");
-    QuadStagesDiagArgs g;
-    g.stages = stages; g.T = T;
-    g.varmap = varmap;
-    g.quad = out_quad; g.lin = out_lin;
-    g.consts = stage_consts; g.cst = out_const;
-    g.terms = terms;
-    g.cterms = consts; g.nconsts = nconsts;
-    g.diags = diags;
-    return qs_launch<QS_DIAG>(stream, g);
+    return qs_run<QS_DIAG>("quad_stages_diag", stream,
+                           {{{{stages, T, varmap, out_quad, out_lin, stage_consts, out_const}, terms, consts, nconsts}, diags}, nullptr, 0.0});
 }
 
-// the value slices are the quadratic slices of pmt_quad_stages_diag_check counted in doubles: n(n+1)/2 per form stage, n per identity stage
 extern "C" int pmt_quad_stages_csc_check(const pmt_quad_stage *host_stages, const pmt_quad_stage_terms *host_terms,
                                          const pmt_quad_stage_diag *host_diags, int64_t T, const pmt_quad_stage_const *host_consts,
                                          int64_t nconsts, int64_t nvalues, int64_t nlin) {
-    return pmt_quad_stages_diag_check(host_stages, host_terms, host_diags, T, host_consts, nconsts, nvalues, nlin);
+    return qs_check(QS_CSC, host_stages, host_terms, host_diags, T, host_consts, nconsts, nvalues, nlin);
 }
 
 extern "C" int pmt_quad_stages_csc_f64(const pmt_quad_stage *stages, const pmt_quad_stage_terms *terms, const pmt_quad_stage_diag *diags,
                                        int64_t T, const pmt_quad_stage_const *consts, int64_t nconsts, const int64_t *varmap, double alpha,
                                        double *out_P_values, pmt_linear_term *out_lin, double *stage_consts, double *out_const,
                                        void *stream) {
-    PMT_REQUIRE(T >= 0, PMT_DIMENSION_MISMATCH, "quad_stages_csc: negative stage count");
-    PMT_REQUIRE(nconsts >= 0 && nconsts <= PMT_QUAD_STAGES_MAX_CONSTS, PMT_DIMENSION_MISMATCH, "quad_stages_csc: nconsts outside 0 .. 32");
-    PMT_REQUIRE(out_const, PMT_INVALID_ARGUMENT, "quad_stages_csc: null constant");
-    PMT_REQUIRE(nconsts == 0 || consts, PMT_INVALID_ARGUMENT, "quad_stages_csc: null table of constants");
-    PMT_REQUIRE(T == 0 || (stages && terms && varmap && out_P_values && out_lin && stage_consts), PMT_INVALID_ARGUMENT,
-                "quad_stages_csc: null pointer");
-    QuadStagesCscArgs g;
-    g.stages = stages; g.T = T;
-    g.varmap = varmap;
-    g.quad = nullptr; g.lin = out_lin;
-    g.consts = stage_consts; g.cst = out_const;
-    g.terms = terms;
-    g.cterms = consts; g.nconsts = nconsts;
-    g.diags = diags;
-    g.pvalues = out_P_values; g.alpha = alpha;
-    return qs_launch<QS_CSC>(stream, g);
+    return qs_run<QS_CSC>("quad_stages_csc", stream,
+                          {{{{stages, T, varmap, nullptr, out_lin, stage_consts, out_const}, terms, consts, nconsts}, diags}, out_P_values, alpha});
 }

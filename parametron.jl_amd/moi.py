@@ -520,37 +520,13 @@ class _Record:
         the one call is pmt_quad_stages_terms_f64 over two more tables, checked by pmt_quad_stages_terms_check.  With identity stages
         W_t*dot(x_t (+|-) v_t, x_t (+|-) v_t) (an IdentityStage among plan.stages: n diagonal terms, rows of length 1 in the layout) or
         diagonal terms riding on form stages (plan.stage_diags) it is pmt_quad_stages_diag_f64 over a third table, checked by
-        pmt_quad_stages_diag_check.  update! allocates nothing and makes one call, or two with the gather."""
+        pmt_quad_stages_diag_check.  Which of the three it is says plan.stage_entry; _stage_launch checks and uploads the tables.  update!
+        allocates nothing and makes one call, or two with the gather."""
         stages = self.plan.stages
         ident = [q.mat is None for q in stages]
         lay = _lib.GroupsLayout([q.xvars.vars for q in stages], diagonal=ident if any(ident) else None)
-        T, n, nq = len(stages), lay.nlin, lay.nterms
-        bq, bl, oq, ol, consts, dc, gather = self._compile_layout(ctx, lay, T)
-        arr = self._stage_table(ctx, stages, oq, ol)
-        sterms, sconsts, sdiags = self.plan.stage_terms, self.plan.stage_consts, self.plan.stage_diags
-        if any(ident) or sdiags is not None:
-            tarr, darr, carr = self._stage_side_tables(T)
-            nc = len(sconsts)
-            _lib.call("pmt_quad_stages_diag_check", C.addressof(arr), C.addressof(tarr), C.addressof(darr) if sdiags is not None else None, T,
-                      C.addressof(carr), nc, nq, n)
-            table, ttable, ctable = _table(ctx, arr), _table(ctx, tarr), _table(ctx, carr)
-            dtable = _table(ctx, darr) if sdiags is not None else None
-            launch = lambda c: c.call("pmt_quad_stages_diag_f64", P(table), P(ttable), P(dtable), T, P(ctable), nc, P(varmap_buf), P(bq), P(bl),
-                                      P(consts), P(dc))
-        elif sterms is None and not sconsts:
-            # no weight, no linear term, no constant: the unweighted entry point, as before
-            _lib.call("pmt_quad_stages_check", C.addressof(arr), T, nq, n)
-            table = _table(ctx, arr)
-            launch = lambda c: c.call("pmt_quad_stages_f64", P(table), T, P(varmap_buf), P(bq), P(bl), P(consts), P(dc))
-        else:
-            # the weights, the linear terms' vectors and the constants are device mirrors of Parameters, read by the launch at run time
-            tarr = _lib.quad_stage_terms([self._stage_terms_row(s) for s in sterms or [StageTerms()] * T])
-            carr = _lib.quad_stage_consts([{"scale": k.scale, "weight": _buf(k.param), "value": _buf(k.value)} for k in sconsts])
-            nc = len(sconsts)
-            _lib.call("pmt_quad_stages_terms_check", C.addressof(arr), C.addressof(tarr), T, C.addressof(carr), nc, nq, n)
-            table, ttable, ctable = _table(ctx, arr), _table(ctx, tarr), _table(ctx, carr)
-            launch = lambda c: c.call("pmt_quad_stages_terms_f64", P(table), P(ttable), T, P(ctable), nc, P(varmap_buf), P(bq), P(bl), P(consts),
-                                      P(dc))
+        bq, bl, oq, ol, consts, dc, gather = self._compile_layout(ctx, lay, len(stages))
+        launch = self._stage_launch(ctx, varmap_buf, self._stage_table(ctx, stages, oq, ol), lay.nterms, lay.nlin, (bq, bl, consts, dc))
 
         def emit(c):
             launch(c)
@@ -580,15 +556,30 @@ class _Record:
         dp, dl, dc, consts = ctx.alloc(8 * nvalues), ctx.alloc(16 * n), ctx.alloc(8), ctx.alloc(8 * T)
         self.dev = {"lin": dl, "const": dc, "P_stage_values": dp,
                     "P_stage_blocks": [(idx[k], int(at[k]), ident[k]) for k in range(T)]}
-        arr = self._stage_table(ctx, stages, at, ol)
-        (tarr, darr, carr), sdiags, nc = self._stage_side_tables(T), self.plan.stage_diags, len(self.plan.stage_consts)
-        _lib.call("pmt_quad_stages_csc_check", C.addressof(arr), C.addressof(tarr), C.addressof(darr) if sdiags is not None else None, T,
-                  C.addressof(carr), nc, nvalues, n)
-        table, ttable, ctable = _table(ctx, arr), _table(ctx, tarr), _table(ctx, carr)
-        dtable = _table(ctx, darr) if sdiags is not None else None
-        alpha = -1.0 if self.model.sense == "Maximize" else 1.0
-        return lambda c: c.call("pmt_quad_stages_csc_f64", P(table), P(ttable), P(dtable), T, P(ctable), nc, P(varmap_buf), alpha, P(dp), P(dl),
-                                P(consts), P(dc))
+        return self._stage_launch(ctx, varmap_buf, self._stage_table(ctx, stages, at, ol), nvalues, n, (dp, dl, consts, dc),
+                                  alpha=-1.0 if self.model.sense == "Maximize" else 1.0)
+
+    def _stage_launch(self, ctx, varmap_buf, arr, nq, n, outs, alpha=None):
+        """The one call of the plan's stage entry point (plan.stage_entry: its check and launch symbols in _STAGE_ENTRIES) over the host stage
+        table `arr` (_stage_table), whose slices lie in nq quadratic terms — "csc": values — and n linear terms; `outs`: the device buffers of
+        the quadratic terms or values, the linear terms, the stages' constants and the constant; `alpha` ("csc"): the sense.  The side tables
+        the entry takes are built here (_stage_side_tables: none for "plain"), the entry's check runs on the host arrays, and exactly the
+        arrays it checked are uploaded: the kernel does not re-check, and no stage table reaches the device another way.  Returns the
+        closure that makes the call."""
+        entry = self.plan.stage_entry
+        check, launch = _STAGE_ENTRIES[entry]
+        T, nc = len(self.plan.stages), len(self.plan.stage_consts)
+        tables = [arr]                                                    # in upload order: the stages, their terms, the constants, the riders
+        if entry != "plain":
+            # the weights, the vectors and the constants are device mirrors of Parameters, read by the launch at run time
+            tarr, darr, carr = self._stage_side_tables(T)
+            tables += [tarr, carr] if entry == "terms" else [tarr, carr, darr]
+
+        def lead(stages, terms=None, consts=None, *riders):               # what the check's and the launch's arguments begin with: the tables' addresses
+            return [stages, T] if entry == "plain" else [stages, terms, *riders, T, consts, nc]
+        _lib.call(check, *lead(*[C.addressof(t) if t is not None else None for t in tables]), nq, n)
+        args = lead(*[P(_table(ctx, t)) if t is not None else None for t in tables]) + [P(varmap_buf)] + ([alpha] if entry == "csc" else [])
+        return lambda c: c.call(launch, *args, *map(P, outs))
 
     @staticmethod
     def _stage_table(ctx, stages, oq, ol):
@@ -601,13 +592,13 @@ class _Record:
                                   "quad_at": int(oq[k]), "lin_at": int(ol[k])} for k, (q, (vec, sign)) in enumerate(zip(stages, vs))])
 
     def _stage_side_tables(self, T):
-        """the host tables beside the T stages of pmt_quad_stages_diag_f64 / _csc_f64: (terms — unit rows without plan.stage_terms —, riders,
-        constants); nothing is allocated"""
+        """the host tables beside the T stages of pmt_quad_stages_terms_f64 / _diag_f64 / _csc_f64: (terms — unit rows without
+        plan.stage_terms —, riders — None without plan.stage_diags: no stage has one —, constants); nothing is allocated"""
         sterms, sconsts, sdiags = self.plan.stage_terms, self.plan.stage_consts, self.plan.stage_diags
         tarr = _lib.quad_stage_terms([self._stage_terms_row(s) for s in sterms or [StageTerms()] * T])
-        rvs = [_vec_sign(r.vec, r.sign) if r is not None else None for r in sdiags or [None] * T]
+        rvs = [_vec_sign(r.vec, r.sign) if r is not None else None for r in sdiags or ()]
         darr = _lib.quad_stage_diags([{} if r is None else {"scale": r.scale, "weight": _buf(r.param), "vec": rv[0], "sign": rv[1]}
-                                      for r, rv in zip(sdiags or [None] * T, rvs)])
+                                      for r, rv in zip(sdiags, rvs)]) if sdiags is not None else None
         carr = _lib.quad_stage_consts([{"scale": k.scale, "weight": _buf(k.param), "value": _buf(k.value)} for k in sconsts])
         return tarr, darr, carr
 
@@ -1003,6 +994,11 @@ def _lsq_stages(terms, diag=False):
     return out + (riders if any(r is not None for r in riders) else None,) if diag else out
 
 
+# QuadPlan.stage_entry -> the (check, launch) symbols of the horizon's stage entry point (_Record._stage_launch)
+_STAGE_ENTRIES = {"plain": ("pmt_quad_stages_check", "pmt_quad_stages_f64"), "terms": ("pmt_quad_stages_terms_check", "pmt_quad_stages_terms_f64"),
+                  "diag": ("pmt_quad_stages_diag_check", "pmt_quad_stages_diag_f64"), "csc": ("pmt_quad_stages_csc_check", "pmt_quad_stages_csc_f64")}
+
+
 class QuadPlan:
     """How a quadratic record reaches its MOI function (quad_plan decides; Model.initialize and _Record.compile execute): the mode and what it
     reads — the operand r of dot(r, r) (`gram`), the QuadForm (`form`), the LsqTerm list (`terms`), the QuadGroups of a sum over disjoint
@@ -1017,6 +1013,19 @@ class QuadPlan:
         # the MOI copy is the canonical least-squares node, bare or the weighted sum of such nodes (model.lane_order: side lane, small-plan order)
         self.gram_record = mode in ("canonical", "canonical-csc", "canonical-sum") or \
             (mode == "canonical-groups" and any(t.kind == "block" for g in groups for t in g.terms))
+
+    @property
+    def stage_entry(self):
+        """which of the four stage entry points writes a horizon of stage costs (a key of _STAGE_ENTRIES), each a superset of the one in
+        front of it: "plain" — the stages alone —, "terms" — weights, linear terms or constants beside them —, "diag" — an identity
+        stage among them or a rider —, "csc" — any of these as P's CSC values; None: the plan is no such horizon"""
+        if self.mode == "canonical-stages-csc":
+            return "csc"
+        if self.mode != "canonical-stages":
+            return None
+        if self.stage_diags is not None or any(q.mat is None for q in self.stages):
+            return "diag"
+        return "plain" if self.stage_terms is None and not self.stage_consts else "terms"
 
     def operands(self):
         """what the plan's kernels read: the Gram operand, the forms and blocks of its term lists (Model.initialize: their stacked matrices)"""
@@ -1093,10 +1102,10 @@ def quad_plan(terms, bare, kind, nq, is_objective, quadratic_mode, small, handof
             # pmt_quad_stages_diag_f64)
             stages = _lsq_stages(terms, diag=stage_diag)
             if stages:
-                diags = stages[3] if stage_diag else None
-                has_diag = diags is not None or any(q.mat is None for q in stages[0])
-                if stage_terms or has_diag or (stages[1] is None and not stages[2]):
-                    return QuadPlan("canonical-stages", stages=stages[0], stage_terms=stages[1], stage_consts=stages[2], stage_diags=diags)
+                plan = QuadPlan("canonical-stages", stages=stages[0], stage_terms=stages[1], stage_consts=stages[2],
+                                stage_diags=stages[3] if stage_diag else None)
+                if stage_terms or plan.stage_entry != "terms":                # (the weighted entry only for a caller that asks for it)
+                    return plan
         # the same horizon for the device hand-off: the stage launch writes the solver's CSC values of the block-diagonal P itself
         # (pmt_quad_stages_csc_f64) — every stage's vector has to keep its order under the optimizer's index map, as canonical-csc asks
         if stage_csc and is_objective and handoff == "device" and not bare and nq >= GROUPS_MIN_LITERAL_TERMS:

@@ -363,3 +363,110 @@ def test_record_refuses_tables_the_check_refuses(lib):
     terms[2].r.mat.lda = 3                                                # ldq < n
     with pytest.raises(lib.DimensionMismatch, match="quad_stages"):
         _record(lib, _plan(terms), IDENT)
+
+
+# ---- 5. the entry point of a plan, decided once (QuadPlan.stage_entry), and the check in front of every upload (_Record._stage_launch)
+def _constant(**kw):
+    from parametron_jl_amd.lazyexpression import LsqTerm
+    return LsqTerm("constant", **kw)
+
+
+def test_stage_entry_of_the_plans(lib):
+    from parametron_jl_amd.moi import QuadPlan
+    hz = _horizon()
+    rid = HD._diag(hz[2].r.xvars.vars, scale=2.0, host_scaled=True)
+    plans = {"a plain horizon": (HD._plan(_horizon()), "plain"),
+             "unit weights": (HD._plan([t.scaled(1.0) for t in _horizon()]), "plain"),
+             "built directly": (QuadPlan("canonical-stages", stages=[t.r for t in _horizon()]), "plain"),
+             "weighted stages": (HD._plan([t.scaled(0.5) for t in _horizon()]), "terms"),
+             "constants only": (HD._plan(_horizon() + [_constant(scale=2.0)]), "terms"),
+             "a linear term": (HD._plan(HT._edited("linear")), "terms"),
+             "an identity stage": (HD._plan(HD._rho_horizon()), "diag"),
+             "weighted identity stages": (HD._plan(HD._rho_horizon(rho=HD._Scalar(), scale=0.5)), "diag"),
+             "a rider": (HD._plan(hz + [rid]), "diag"),
+             "the csc horizon": (_plan(_rho_horizon()), "csc"),
+             "the csc horizon of plain forms": (_plan(_horizon()), "csc"),
+             "eight groups": (HD._plan(_horizon(stages=8)), None),
+             "literal": (HD._plan(_horizon(), quadratic_mode="literal"), None),
+             "no mode": (QuadPlan(None), None)}
+    modes = {"plain": "canonical-stages", "terms": "canonical-stages", "diag": "canonical-stages", "csc": "canonical-stages-csc"}
+    assert plans["eight groups"][0].mode == "canonical-groups" and plans["literal"][0].mode == "literal"
+    for name, (plan, entry) in plans.items():
+        assert plan.stage_entry == entry, name
+        assert entry is None or plan.mode == modes[entry], name
+    # a computed property: no constructor argument, nothing to set
+    assert "stage_entry" not in inspect.signature(QuadPlan.__init__).parameters and isinstance(QuadPlan.stage_entry, property)
+    with pytest.raises(AttributeError):
+        plans["a plain horizon"][0].stage_entry = "terms"
+    # a caller of quad_plan that does not ask for the weighted entry keeps the literal row for exactly the plans that would take it
+    for terms in ([t.scaled(0.5) for t in _horizon()], _horizon() + [_constant(scale=2.0)], HT._edited("linear")):
+        assert HD._plan(terms, stage_terms=False).mode == "literal"
+    for terms in (_horizon(), HD._rho_horizon(), hz + [rid]):
+        assert HD._plan(terms, stage_terms=False).mode == "canonical-stages"
+
+
+SYMBOLS = {"plain": ("pmt_quad_stages_check", "pmt_quad_stages_f64"), "terms": ("pmt_quad_stages_terms_check", "pmt_quad_stages_terms_f64"),
+           "diag": ("pmt_quad_stages_diag_check", "pmt_quad_stages_diag_f64"), "csc": ("pmt_quad_stages_csc_check", "pmt_quad_stages_csc_f64")}
+
+
+def _entry_terms(entry, T=9, n=4):
+    """one list per entry point; none has an identity stage, so that compile uploads nothing but the tables"""
+    hz = _horizon(stages=T, n=n)
+    rid = HD._diag(hz[4].r.xvars.vars, scale=0.5, param=HD._Scalar(), vec=_b(n), sign=-1)
+    return {"plain": hz, "terms": [t.scaled(0.5) for t in hz] + [_constant(scale=2.0)], "diag": hz + [rid], "csc": hz + [rid]}[entry]
+
+
+class _Uploads(StubContext):
+    """the stub context, noting every upload beside the allocations"""
+    def __init__(self, lib):
+        super().__init__(lib)
+        self.uploads = []
+
+    def upload_new(self, host):
+        self.uploads.append(np.ascontiguousarray(host).nbytes)
+        return super().upload_new(host)
+
+
+def _compile_spied(lib, monkeypatch, entry, terms):
+    """compile the plan of `terms` on the stub context with _lib.call spied on: (the record, the context, the emitter or the exception, the
+    library calls made through _lib.call with the uploads made before each)"""
+    plan = _plan(terms) if entry == "csc" else HD._plan(terms)
+    assert plan.stage_entry == entry
+    rec = _objective(_model(handoff="device") if entry == "csc" else _model(), _quad_out(7, 7), plan)
+    ctx, seen, real = _Uploads(lib), [], lib.call
+
+    def spy(name, *args):
+        seen.append((name, len(ctx.uploads)))
+        return real(name, *args)
+    monkeypatch.setattr(lib, "call", spy)
+    try:
+        out = rec.compile(ctx, VARMAP_BUF, IDENT if entry == "csc" else None)
+    except Exception as e:                                                # noqa: BLE001 (handed to the caller, which asserts its class)
+        out = e
+    monkeypatch.undo()
+    return rec, ctx, out, seen
+
+
+@pytest.mark.parametrize("entry", ["plain", "terms", "diag", "csc"])
+def test_record_calls_its_entrys_check_and_no_other_before_its_launch(lib, monkeypatch, entry):
+    T, n = 9, 4
+    rec, ctx, emit, seen = _compile_spied(lib, monkeypatch, entry, _entry_terms(entry, T, n))
+    check, launch = SYMBOLS[entry]
+    assert seen == [(check, 0)]                                           # that check alone, and in front of the first upload
+    tables = {"plain": [56 * T], "terms": [56 * T, 40 * T, 24], "diag": [56 * T, 40 * T, 24, 32 * T], "csc": [56 * T, 40 * T, 24, 32 * T]}[entry]
+    assert ctx.uploads == tables and ctx.allocs[-len(tables):] == tables and ctx.calls == []
+    emit(ctx)
+    assert [name for name, _ in ctx.calls] == [launch] and len(ctx.uploads) == len(tables)
+
+
+@pytest.mark.parametrize("entry", ["plain", "terms", "diag", "csc"])
+def test_record_uploads_nothing_when_its_entrys_check_refuses(lib, monkeypatch, entry):
+    T, n = 9, 4
+    terms = _entry_terms(entry, T, n)
+    terms[3].r.mat.lda = 3                                                # ldq < n
+    rec, ctx, err, seen = _compile_spied(lib, monkeypatch, entry, terms)
+    assert type(err) is lib.DimensionMismatch and str(err) == "quad_stages: ldq < n (stage 1)"      # (stages 1 and 3 read one matrix)
+    assert seen == [(SYMBOLS[entry][0], 0)] and ctx.uploads == [] and ctx.calls == []
+    # what is allocated by then are the record's own buffers: the outputs, the constant, the stages' constants
+    nq, nl = T * n * (n + 1) // 2, T * n
+    assert ctx.allocs == [(8 if entry == "csc" else 24) * nq, 16 * nl, 8, 8 * T]
